@@ -16,6 +16,12 @@ CoPER-ConvE, bf16x3 arithmetic; query-sharded across ranks = weak scaling):
   value / ms_per_step     the SURVEY 8(d) region: K passes, each H2D of ids + CSR filters from pinned host buffers + pass + D2H
                           of the int32 ranks to pinned host memory, barrier + synchronize on both sides, MAX over ranks (the
                           driver contract)
+
+A plain run measures that and nothing else: set-up, untimed passes until the clocks have left their idle state (SETTLE_S),
+the W warm-up passes, the K timed ones, the line.  --dump-outputs DIR then writes what the timed path handed its caller in
+its last step as DIR/<name>.npy (float64; inputs are seeded, so two builds can be compared output for output).  Everything
+below comes with --full (and its --no-* switches):
+
   resident_inputs         the same K passes with ids + CSR filters resident in HBM (round 2's headline); `timing` adds
                           median / min per pass (HIP events)
   config.f32_exact        the same pass in the fp32-exact mode; `rank_agreement`: the headline mode's ranks against the fp32
@@ -52,6 +58,11 @@ PEAK_HBM_GBS = 8000.0
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA (same rate); the x3 mode spends 3 hardware MFMAs per algorithmic product
 
 SCALE_WORKLOAD, SCALE_TOPK, HBM_REGIME_QUERIES, SCALE_CHUNKS = "synth10m_cpg", 10, 128, 4
+# A plain run's untimed passes before its W warm-up passes: the device takes tens of milliseconds of load to leave its idle
+# power state (0.588 ms per pass over the first 20 passes after setup, 0.549 over 100, 0.532 over 400), which --full's
+# secondary measurements otherwise provide.  Seconds of back-to-back passes.
+SETTLE_S = 0.5
+DUMP_LIMIT_BYTES = 64 << 20
 # Ranks of the `scale` pass on ONE GPU holding all 10M entities (seed 0, Q = 4096, x3 mode with the scale-invariant fp16 split
 # and the exact band: round 4; entity rows ~ N(0, 0.1^2) as SURVEY 8(d) says, rounds 1 - 3 drew 0.3), measured on MI355X: every
 # entity sharding of the same table must reproduce them bit for bit (integer counts summed across shards).
@@ -146,11 +157,17 @@ def parse_args():
     ap.add_argument("--mode", choices=["query", "entity"], default="query")
     ap.add_argument("--queries", type=int, default=None)
     ap.add_argument("--order", choices=["shuffled", "sorted"], default="shuffled")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement and check: resident-input and per-pass timings, the fp32-exact comparison, "
+                         "the drop-in API timings, per-kernel rooflines, the band audit, the 10M-entity blocks, the training lines, "
+                         "the CPU baseline (the --no-* switches below leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget per thread setting")
     ap.add_argument("--score-mode", choices=["f32", "bf16x3"], default="bf16x3")
     ap.add_argument("--profile-every", type=int, default=10,
-                    help="HIP-event timing of the dominant kernels on every N-th timed step (an event pair around a launch "
+                    help="--full: HIP-event timing of the dominant kernels on every N-th timed step (an event pair around a launch "
                          "costs the stream a few microseconds of pipeline drain; 1 = every step)")
     ap.add_argument("--topk", type=int, default=0,
                     help="entity mode: also select and exchange the per-shard top-k of the filtered rows (SURVEY 8(e) step 3)")
@@ -280,6 +297,44 @@ def timed_passes(ctx, step, steps):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     return dt, out
+
+
+def settle(ctx, step, seconds):
+    """Untimed passes, back to back, until `seconds` have gone by (checked every 8 passes); returns how many ran.  With a
+    process group the ranks stop together: a pass may hold collectives, so every rank must run the same number."""
+    import torch
+    import torch.distributed as dist
+    torch.cuda.synchronize(ctx.device)
+    t0, n = time.perf_counter(), 0
+    while True:
+        for _ in range(8):
+            step()
+        n += 8
+        torch.cuda.synchronize(ctx.device)
+        done = time.perf_counter() - t0 >= seconds
+        if ctx.use_dist:
+            flag = torch.tensor([1 if done else 0], device=ctx.device if ctx.backend == "nccl" else "cpu", dtype=torch.int32)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            done = bool(flag.item())
+        if done:
+            return n
+
+
+def dump_outputs(out_dir, arrays, prefix=""):
+    """`arrays` (name -> tensor / array with one row per query) as out_dir/<prefix><name>.npy in float64 (every value these
+    paths return -- int32 ranks and counts, int64 entity ids, float32 scores -- is exact in it).  Beyond DUMP_LIMIT_BYTES in
+    all, the same seeded sample of rows from every array, its row numbers in <prefix>sample_rows.npy."""
+    arrays = {k: np.asarray(v.cpu() if hasattr(v, "cpu") else v).astype(np.float64) for k, v in arrays.items() if v is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = int(DUMP_LIMIT_BYTES // (total / n + 8))       # (+ 8 bytes a row: its number)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), a)
 
 
 def event_times(ctx, step, steps):
@@ -603,7 +658,7 @@ def main():
         if entity_mode:
             # ids are tiny; the host copies drive the relation split, the device copies feed the kernels
             return ranker.rank(dict(e1=host_q["e1"], rel=host_q["rel"], e2=dev_q["e2"], filt_indptr=dev_q["filt_indptr"],
-                                    filt_idx=dev_q["filt_idx"]), k=args.topk)[:2]
+                                    filt_idx=dev_q["filt_idx"]), k=args.topk)
         # one call per pass, like one session.run of the reference's ranker loop; like ranking_and_hits (and the
         # reference) the pass needs ranks only: tie counts and the embedding itself are not requested
         return model.rank_pass(dev_q["e1"], dev_q["rel"], dev_q["e2"], dev_q["filt_indptr"], dev_q["filt_idx"], filt_nnz=nnz,
@@ -619,16 +674,18 @@ def main():
         return g
 
     step = counted(step)
-    for _ in range(args.warmup):
-        step()
-    model.profile(True)
-    step()                                   # one instrumented untimed pass: fills the library's pool of HIP events
-    torch.cuda.synchronize(device)
-    for k in KERNELS:
-        model.profile_read(k)
-    model.profile(False)
-    extras = not args.no_extras
-    ranks_np = step()[0].cpu().numpy()
+    extras = args.full and not args.no_extras
+    ranks_np = None                          # (--full: the resident path's ranks, which every other path must reproduce)
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        model.profile(True)
+        step()                               # one instrumented untimed pass: fills the library's pool of HIP events
+        torch.cuda.synchronize(device)
+        for k in KERNELS:
+            model.profile_read(k)
+        model.profile(False)
+        ranks_np = step()[0].cpu().numpy()
 
     # The SURVEY 8(d) region (the headline in query mode): ids + CSR filters start in pinned host memory, the ranks end in
     # pinned host memory; copies and kernels of a pass are stream-ordered, passes follow each other on the stream.
@@ -690,11 +747,12 @@ def main():
             return r, None
 
         pcie_step = counted(pcie_step)
-        for _ in range(max(1, args.warmup)):
-            pcie_step()
-        model.post_flush()                                 # (the last pass's ranks: nothing follows that would carry them out)
-        torch.cuda.synchronize(device)
-        assert np.array_equal(out_host.numpy(), ranks_np)
+        if args.full:
+            for _ in range(max(1, args.warmup)):
+                pcie_step()
+            model.post_flush()                             # (the last pass's ranks: nothing follows that would carry them out)
+            torch.cuda.synchronize(device)
+            assert np.array_equal(out_host.numpy(), ranks_np)
         if extras:
             lat = event_times(ctx, pcie_step, args.steps)
             pcie_serial = {"ms_per_pass_median": statistics.median(lat), "ms_per_pass_min": min(lat),
@@ -790,7 +848,7 @@ def main():
     # passes ran before.  Nothing is carried over but the clocks: barrier + synchronize on both sides, EXACTLY K passes,
     # MAX over ranks.
     resident = None
-    if pcie_step is not None:
+    if args.full and pcie_step is not None:
         for _ in range(args.warmup):          # the W warm-up passes of this region, right before it
             step()
         dt_res, _ = timed_passes(ctx, step, args.steps)
@@ -804,15 +862,17 @@ def main():
             model.profile(i % max(1, args.profile_every) == 0)     # per-kernel HIP events on a sample of the timed steps
         return (pcie_step or step)()
 
+    if not args.full:
+        settle(ctx, pcie_step or step, SETTLE_S)
     for _ in range(args.warmup):              # the contract's W untimed warm-up steps, right before its K timed ones
         (pcie_step or step)()
     pre_timed = n_passes[0]
-    dt, res = timed_passes(ctx, profiled_step, args.steps)
+    dt, res = timed_passes(ctx, profiled_step if args.full else (pcie_step or step), args.steps)
     model.profile(False)
     # the run-time audit of the exact band over every audited count launch of this process so far (include/coper_hip.h:
     # coper_band_audit; default period: the first launch and every 8th)
     band_audit = None
-    if args.score_mode == "bf16x3":
+    if args.full and args.score_mode == "bf16x3":
         ratio, n_pairs = model.band_audit(reset=False)
         band_audit = {"max_error_over_allowance": ratio, "pairs_audited": n_pairs,
                       "note": "largest |logit_x3 - logit_fp32chain| / (tau_q / 2) over the pairs the band walks decided; the mode's ranks are "
@@ -820,10 +880,18 @@ def main():
     if pcie_step is not None:
         model.post_flush()
         torch.cuda.synchronize(device)
-        assert np.array_equal(out_host.numpy(), ranks_np)
         assert model.stale_passes() == 0     # (the guard of coper_group_next: no timed pass ran on a sorting its ids had outlived)
-    assert np.array_equal(res[0].cpu().numpy(), ranks_np)
-    kern = {}
+        # what a caller of the timed path holds after its last step: the pass's int32 ranks in pinned host memory
+        outputs = {"ranks": out_host.numpy().copy()}
+    else:
+        outputs = dict(zip(("ranks", "n_equal", "topk_val", "topk_idx"), (t.cpu().numpy() for t in res)))
+    if args.full:
+        assert np.array_equal(outputs["ranks"], ranks_np)
+        assert np.array_equal(res[0].cpu().numpy(), ranks_np)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, prefix="rank%d_" % rank if world > 1 else "")
+    ranks_out = outputs["ranks"]
+    kern = {}                                 # (empty in a plain run, which records no kernel events: no roofline block)
     for k in KERNELS:
         ms, n = model.profile_read(k)
         kern[k] = (ms / n) if n else None
@@ -860,7 +928,7 @@ def main():
                            % pcie_bytes) if pcie_step is not None
                 else "ids + CSR filters resident in HBM before the timed region",
                 "pre_timed_passes": pre_timed,
-                "mean_rank": float(np.mean(ranks_np)), "mrr": float(np.mean(1.0 / ranks_np))},
+                "mean_rank": float(np.mean(ranks_out)), "mrr": float(np.mean(1.0 / ranks_out))},
         }
         if resident:
             out["resident_inputs"] = resident
@@ -940,7 +1008,7 @@ def main():
             if "hbm_regime" in scale and "roofline" in out:
                 out["roofline"]["all_kernels"]["%s@hbm" % scale["hbm_regime"].get("kernel", "k_score_count_bf16x3")] = scale["hbm_regime"]
             out["scale"] = scale["scale"]
-        if not args.no_cpu_baseline and world == 1 and not big:
+        if args.full and not args.no_cpu_baseline and world == 1 and not big:
             host_p = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in cdata.synthetic_params(md, 0).items()}
             out["cpu_baseline"] = cpu_baseline(md, host_p, q, args.cpu_seconds)
             out["config"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

@@ -34,7 +34,7 @@ def _run_bench(extra, timeout=600, world=2):
 
 def test_bench_two_ranks_from_a_plain_shell():
     from bench import SCALE_EXPECTED
-    line, backend = _run_bench([])
+    line, backend = _run_bench(["--full"])
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["value"] > 0
     assert line["config"]["parallelism"] == "query-sharded x2"
     sc = line["scale"]
@@ -78,7 +78,7 @@ def test_bench_scale_block_at_the_target_world_size(world):
     the 8-row (4-row) all-gather layouts -- and the ranks of every chunk must be the single-GPU ranks bit for bit (SHA-1)."""
     from bench import SCALE_EXPECTED
     # (world 4 also with the side stream's collectives on a communicator of their own: the opt-in form)
-    line, backend = _run_bench(["--scale-side-communicator"] if world == 4 else [], timeout=900, world=world)
+    line, backend = _run_bench(["--full"] + (["--scale-side-communicator"] if world == 4 else []), timeout=900, world=world)
     assert line["n_gpus"] == world and line["value"] > 0
     assert line["config"]["parallelism"] == "query-sharded x%d" % world
     sc = line["scale"]

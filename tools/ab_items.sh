@@ -1,5 +1,5 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-X="--no-cpu-baseline --no-extras --workload synth10m_cpg --mode entity --steps 5 --warmup 2"
+X="--full --no-cpu-baseline --no-extras --workload synth10m_cpg --mode entity --steps 5 --warmup 2"
 for R in 0 16 32 64; do
   for T in 0 10; do
     COPER_SC3_ITEM_ROWS=$R timeout 600 python bench.py $X --topk $T > gpurun_out/ab_items_${R}_${T}.json 2>/dev/null

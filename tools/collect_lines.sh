@@ -3,7 +3,7 @@
 TAG=$1
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out
-X="--no-cpu-baseline --no-scale"
+X="--full --no-cpu-baseline --no-scale"
 timeout 600 python bench.py $X --workload wn18rr_cpg > gpurun_out/bench_${TAG}_wn.json 2>/dev/null
 timeout 600 python bench.py $X --workload fb15k237_plain > gpurun_out/bench_${TAG}_plain.json 2>/dev/null
 timeout 600 python bench.py $X --workload nations_cpg > gpurun_out/bench_${TAG}_nations.json 2>/dev/null
