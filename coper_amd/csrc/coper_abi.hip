@@ -180,37 +180,33 @@ static int64_t prod(const std::vector<int64_t>& v) {
   return p;
 }
 
-template <typename T>
-static int dev_alloc(coper_handle* h, T** p, size_t n) {
-  if (*p) { (void)tracked_free(*p); *p = nullptr; }
-  if (n == 0) n = 1;
-  hipError_t e = tracked_malloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    char buf[128];
-    snprintf(buf, sizeof buf, "hipMalloc of %zu bytes failed", n * sizeof(T));
-    return fail(h, COPER_ENOMEM, buf);
-  }
-  return COPER_OK;
-}
-
-template <typename T>
-static void dev_free(T** p) {
-  if (*p) { (void)tracked_free(*p); *p = nullptr; }
+int devbuf_malloc(coper_handle* h, void** p, size_t bytes, const char* what) {
+  *p = nullptr;
+  if (tracked_malloc_impl(p, bytes) == hipSuccess) return COPER_OK;
+  *p = nullptr;
+  (void)hipGetLastError();
+  char buf[160];
+  snprintf(buf, sizeof buf, "hipMalloc of %zu bytes failed (%s)", bytes, what);
+  return fail(h, COPER_ENOMEM, buf);
 }
 
 // ---- grouping sets (coper_group_next) ----
-void group_snapshot_home(coper_handle* h) {
+// the home set's views from its owners (null where an owner is empty)
+void group_home_views(coper_handle* h) {
+  int32_t* c = h->home.counts;
+  const int64_t r2 = h->dm.R + 2;
+  h->rel_count_buf[0] = c;
+  h->rel_count_buf[1] = c ? c + r2 : nullptr;
+  h->rel_cursor = c ? c + 2 * r2 : nullptr;
+  h->group_done = c ? c + 3 * r2 : nullptr;
   coper_handle::GroupSet& g = h->gset[0];
-  g.rel_count = h->rel_count; g.rel_offset = h->rel_offset; g.perm = h->perm; g.inv_perm = h->inv_perm; g.sorted_row = h->sorted_row;
-  g.sorted_rid = h->sorted_rid; g.tiles = h->tiles; g.n_tiles = h->n_tiles; g.x3m = h->x3m; g.fused_fin_dev = h->fused_fin_dev;
-  g.fused_fin_perm = h->fused_fin_perm;
+  g.rel_count = c; g.rel_offset = h->home.rel_offset; g.perm = h->home.perm; g.inv_perm = h->home.inv_perm;
+  g.sorted_row = h->home.sorted_row; g.sorted_rid = h->home.sorted_rid; g.tiles = h->home.tiles; g.n_tiles = h->home.n_tiles;
+  g.x3m = h->home.x3m; g.fused_fin_dev = g.fin;
+  if (h->gcur == 0) group_use_set(h, 0);
 }
 
 void group_use_set(coper_handle* h, int i) {
-  if (h->gcur == i) return;
-  if (h->gcur == 0) group_snapshot_home(h);
   const coper_handle::GroupSet& g = h->gset[i];
   h->rel_count = g.rel_count; h->rel_offset = g.rel_offset; h->perm = g.perm; h->inv_perm = g.inv_perm; h->sorted_row = g.sorted_row;
   h->sorted_rid = g.sorted_rid; h->tiles = g.tiles; h->n_tiles = g.n_tiles; h->x3m = g.x3m; h->fused_fin_dev = g.fused_fin_dev;
@@ -220,12 +216,7 @@ void group_use_set(coper_handle* h, int i) {
 
 void group_sets_free(coper_handle* h) {
   group_use_set(h, 0);
-  for (int i = 1; i < 3; ++i) {
-    coper_handle::GroupSet& g = h->gset[i];
-    if (g.slab) (void)tracked_free(g.slab);
-    if (g.fused_fin_dev) (void)tracked_free(g.fused_fin_dev);
-    g = coper_handle::GroupSet();
-  }
+  for (int i = 1; i < 3; ++i) h->gset[i] = coper_handle::GroupSet();
   h->pipe.invalidate_grouping();
   h->pass_chk = nullptr;
 }
@@ -234,7 +225,7 @@ void group_sets_free(coper_handle* h) {
 int group_sets_ensure(coper_handle* h, hipStream_t s) {
   if (h->gset[1].slab && h->gset[2].slab) return COPER_OK;
   const Dims& dm = h->dm;
-  if (!h->perm || !h->x3m || h->ws_queries <= 0) return fail(h, COPER_ESTATE, "grouping sets: no workspace yet");
+  if (!h->home.x3m || h->ws_queries <= 0) return fail(h, COPER_ESTATE, "grouping sets: no workspace yet");
   const int cur = h->gcur;
   group_use_set(h, 0);
   const size_t cap = (size_t)h->ws_queries, r2 = (size_t)dm.R + 2, nt = 4 * (cap / 32 + (size_t)dm.R + 4);
@@ -243,7 +234,8 @@ int group_sets_ensure(coper_handle* h, hipStream_t s) {
   for (int i = 1; i < 3; ++i) {
     coper_handle::GroupSet& g = h->gset[i];
     if (g.slab) continue;
-    if (tracked_malloc(&g.slab, total * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return fail(h, COPER_ENOMEM, "hipMalloc failed (grouping set)"); }
+    int rc;
+    if ((rc = g.slab.alloc(h, total, "grouping set"))) return rc;
     COPER_HIP_TRY(h, hipMemsetAsync(g.slab, 0, total * sizeof(int32_t), s));
     int32_t* p = g.slab;
     g.rel_count = p; p += up4(r2);
@@ -262,66 +254,62 @@ int group_sets_ensure(coper_handle* h, hipStream_t s) {
   return rc;
 }
 
-static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t s) {
+// the workspace group, all at `cap` queries (the old buffers are freed as the new ones are allocated: no rise of the peak)
+static int alloc_workspace(coper_handle* h, int64_t cap, int ksplit, hipStream_t s) {
   const Dims& dm = h->dm;
+  coper_handle::HomeSet& g = h->home;
+  int rc;
+  // published counts | accumulation buffer (see launch_group_by_relation) | cursors | ticket; zeroed once here, kept zero by the kernels
+  if ((rc = g.counts.alloc(h, 3 * (dm.R + 2) + 4, "relation counts"))) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(g.counts, 0, sizeof(int32_t) * (3 * (dm.R + 2) + 4), s));
+  if ((rc = g.rel_offset.alloc(h, dm.R + 2, "rel_offset")) || (rc = g.perm.alloc(h, cap, "perm")) ||
+      (rc = g.inv_perm.alloc(h, cap, "inv_perm")) || (rc = g.sorted_row.alloc(h, cap, "sorted_row")) ||
+      (rc = g.sorted_rid.alloc(h, cap, "sorted_rid")) || (rc = g.tiles.alloc(h, 4 * (cap / 32 + dm.R + 4), "tiles")) ||
+      (rc = g.n_tiles.alloc(h, 4, "n_tiles")) || (rc = h->blk_off.alloc(h, dm.R + 2, "blk_off")) ||
+      (rc = h->x_sorted.alloc(h, (size_t)cap * dm.F_pad, "x_sorted")) ||
+      (rc = h->z_part.alloc(h, (size_t)ksplit * cap * dm.d_pad16, "z_part")) ||
+      (rc = h->tgt_ws.alloc(h, 2 * cap, "tgt_ws")) ||    // [mode logit | exact-chain logit] (coper_target_scores)
+      (rc = h->cnt_ws.alloc(h, 2 * cap, "cnt_ws")))
+    return rc;
+  if (h->cfg.score_mode == COPER_SCORE_F32) return h->hfrag_ws.alloc(h, (size_t)((cap + 127) / 128) * 128 * dm.d_pad8, "hfrag_ws");
+  const size_t plane = (size_t)((cap + 127) / 128) * 4 * dm.KS16 * 64;          // uint4
+  const size_t f3 = (size_t)((cap + 127) / 128) * 8 * f3_steps(dm.KS16) * 2 * 64;   // the count kernel's query image (uint4)
+  if ((rc = h->hfrag16_hi.alloc(h, plane, "bf16 query planes")) || (rc = h->hfrag16_lo.alloc(h, plane, "bf16 query planes")) ||
+      (rc = h->hrm16_hi.alloc(h, plane, "bf16 query planes")) || (rc = h->hrm16_lo.alloc(h, plane, "bf16 query planes")) ||
+      (rc = h->hf3_ws.alloc(h, f3, "query image")))
+    return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(h->hf3_ws, 0, f3 * sizeof(uint4), s));     // the zero halves of its tail registers are never written again
+  const size_t n_heavy = (size_t)(cap / 32 + 8);
+  if ((rc = h->tband_ws.alloc(h, 2 * (size_t)((cap + 127) / 128 * 128), "tband_ws")) || (rc = h->tgtx_ws.alloc(h, cap, "tgtx_ws")) ||
+      (rc = h->heavy_ws.alloc(h, n_heavy, "heavy_ws")))
+    return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(h->heavy_ws, 0, sizeof(int32_t) * n_heavy, s));   // the excess kernel leaves it zero again
+  return COPER_OK;
+}
+
+static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t s) {
+  int rc;
   if (nnz > h->ws_nnz) h->ws_nnz = nnz;
-  if (h->cfg.score_mode != COPER_SCORE_F32 && nnz > h->row_of_cap) {
+  if (h->cfg.score_mode != COPER_SCORE_F32 && (size_t)nnz > h->row_of_ws.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    int rc0 = dev_alloc(h, &h->row_of_ws, (size_t)nnz);
-    if (rc0) return rc0;
-    h->row_of_cap = nnz;
+    if ((rc = h->row_of_ws.alloc(h, (size_t)nnz, "row_of_ws"))) return rc;
   }
-  if (B <= h->ws_queries && h->perm) return COPER_OK;
+  if (h->ws_queries > 0 && B <= h->ws_queries) return COPER_OK;
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
-  if (h->group_done) {          // (the device counter of coper_stale_passes lives in the slab replaced below)
+  if (h->home.counts) {         // (the device counter of coper_stale_passes lives in the slab replaced below)
     int32_t v = 0;
     COPER_HIP_TRY(h, hipMemcpy(&v, h->group_done + 2, sizeof v, hipMemcpyDeviceToHost));
     h->stale_passes_host += v;
   }
   group_sets_free(h);           // (sized by the workspace; back on the home set before its arrays move)
-  int64_t cap = B < 64 ? 64 : B;
-  int rc;
+  const int64_t cap = B < 64 ? 64 : B;
   const int KSPLIT_MAX = 8;
-  // published counts | accumulation buffer (see launch_group_by_relation) | cursors | ticket; zeroed once here, kept zero by the kernels
-  dev_free(&h->rel_count_buf[0]);
-  if ((rc = dev_alloc(h, &h->rel_count_buf[0], 3 * (dm.R + 2) + 4))) return rc;
-  COPER_HIP_TRY(h, hipMemsetAsync(h->rel_count_buf[0], 0, sizeof(int32_t) * (3 * (dm.R + 2) + 4), s));
-  h->rel_count_buf[1] = h->rel_count_buf[0] + (dm.R + 2);
-  h->rel_cursor = h->rel_count_buf[0] + 2 * (dm.R + 2);
-  h->group_done = h->rel_count_buf[0] + 3 * (dm.R + 2);
-  h->rel_count = h->rel_count_buf[0];
-  if ((rc = dev_alloc(h, &h->rel_offset, dm.R + 2))) return rc;
-  if ((rc = dev_alloc(h, &h->perm, cap))) return rc;
-  if ((rc = dev_alloc(h, &h->inv_perm, cap))) return rc;
-  if ((rc = dev_alloc(h, &h->sorted_row, cap))) return rc;
-  if ((rc = dev_alloc(h, &h->sorted_rid, cap))) return rc;
-  if ((rc = dev_alloc(h, &h->tiles, 4 * (cap / 32 + dm.R + 4)))) return rc;
-  if ((rc = dev_alloc(h, &h->n_tiles, 4))) return rc;
-  if ((rc = dev_alloc(h, &h->blk_off, dm.R + 2))) return rc;
-  if ((rc = dev_alloc(h, &h->x_sorted, (size_t)cap * dm.F_pad))) return rc;
-  if ((rc = dev_alloc(h, &h->z_part, (size_t)KSPLIT_MAX * cap * dm.d_pad16))) return rc;
-  if ((rc = dev_alloc(h, &h->tgt_ws, 2 * cap))) return rc;    // [mode logit | exact-chain logit] (coper_target_scores)
-  if ((rc = dev_alloc(h, &h->cnt_ws, 2 * cap))) return rc;
-  if (h->cfg.score_mode == COPER_SCORE_F32) {
-    if ((rc = dev_alloc(h, &h->hfrag_ws, (size_t)((cap + 127) / 128) * 128 * dm.d_pad8))) return rc;
-  } else {
-    size_t plane = (size_t)((cap + 127) / 128) * 4 * dm.KS16 * 64 * 16;
-    const size_t f3 = (size_t)((cap + 127) / 128) * 8 * f3_steps(dm.KS16) * 2 * 64 * 16;   // the count kernel's query image
-    dev_free((char**)&h->hfrag16_hi); dev_free((char**)&h->hfrag16_lo);
-    dev_free((char**)&h->hrm16_hi); dev_free((char**)&h->hrm16_lo); dev_free((char**)&h->hf3_ws);
-    if (tracked_malloc(&h->hfrag16_hi, plane) != hipSuccess || tracked_malloc(&h->hfrag16_lo, plane) != hipSuccess ||
-        tracked_malloc(&h->hrm16_hi, plane) != hipSuccess || tracked_malloc(&h->hrm16_lo, plane) != hipSuccess ||
-        tracked_malloc(&h->hf3_ws, f3) != hipSuccess)
-      return fail(h, COPER_ENOMEM, "hipMalloc of the bf16 query planes failed");
-    COPER_HIP_TRY(h, hipMemsetAsync(h->hf3_ws, 0, f3, s));     // the zero halves of its tail registers are never written again
-    if ((rc = dev_alloc(h, &h->tband_ws, 2 * (size_t)((cap + 127) / 128 * 128))) || (rc = dev_alloc(h, &h->tgtx_ws, cap))) return rc;
-    const size_t n_heavy = (size_t)(cap / 32 + 8);
-    if ((rc = dev_alloc(h, &h->heavy_ws, n_heavy))) return rc;
-    COPER_HIP_TRY(h, hipMemsetAsync(h->heavy_ws, 0, sizeof(int32_t) * n_heavy, s));   // the excess kernel leaves it zero again
-  }
+  h->ws_queries = 0;            // (until every buffer of the group exists at the new size: a failure leaves the whole group to the next call)
+  rc = alloc_workspace(h, cap, KSPLIT_MAX, s);
+  group_home_views(h);
+  if (rc) return rc;
   h->ws_queries = cap;
   h->ws_ksplit = KSPLIT_MAX;
-  group_snapshot_home(h);
   return fused_fin_update(h, s);        // (perm moved)
 }
 
@@ -331,23 +319,19 @@ static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t
 static int ensure_rank_workspace(coper_handle* h, int64_t B, int64_t nnz, bool need_h, hipStream_t s) {
   int rc;
   if ((rc = ensure_workspace(h, B, nnz, s))) return rc;
-  if (need_h && (!h->h_ws || h->h_ws_rows < B)) {
+  if (need_h && (!h->h_ws || h->h_ws.size() < (size_t)B * h->dm.d)) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
     const int64_t rows = B > h->ws_queries ? B : h->ws_queries;
-    if ((rc = dev_alloc(h, &h->h_ws, (size_t)rows * h->dm.d))) return rc;
-    h->h_ws_rows = rows;
+    if ((rc = h->h_ws.alloc(h, (size_t)rows * h->dm.d, "h_ws"))) return rc;
   }
   if (h->cfg.score_mode == COPER_SCORE_F32) return COPER_OK;
   // the longest count launch any path issues: the mask has the size of the block maxima of the pruned top-k (one bit per logit
   // against one float per 32), so both are cut into the same chunks of queries
   const int64_t qc = topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats);
   const size_t need = score_count3_mask_bytes(h, qc);
-  if (need > h->mask_cap) {
+  if (need > h->mask_ws.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    dev_free((char**)&h->mask_ws);
-    h->mask_cap = 0;
-    if (tracked_malloc(&h->mask_ws, need) != hipSuccess) { (void)hipGetLastError(); return fail(h, COPER_ENOMEM, "hipMalloc of the band mask failed"); }
-    h->mask_cap = need;
+    if ((rc = h->mask_ws.alloc(h, need, "band mask"))) return rc;
   }
   return COPER_OK;
 }
@@ -461,19 +445,6 @@ COPER_API void coper_destroy(coper_handle* h) {
   (void)hipSetDevice(h->cfg.device);
   (void)hipDeviceSynchronize();
   train_destroy(h);
-  group_sets_free(h);
-  dev_free(&h->conv_scale); dev_free(&h->conv_shift); dev_free(&h->fc_scale); dev_free(&h->fc_shift);
-  dev_free(&h->conv_w_rel); dev_free(&h->conv_b_rel); dev_free(&h->fc_b_rel); dev_free(&h->Wf);
-  dev_free(&h->Ef); dev_free(&h->bias_pad); dev_free(&h->ctx_tmp[0]); dev_free(&h->ctx_tmp[1]);
-  dev_free(&h->rel_count_buf[0]); h->rel_count = nullptr; h->rel_count_buf[1] = nullptr; h->group_done = nullptr; dev_free(&h->rel_offset); h->rel_cursor = nullptr; dev_free(&h->perm); dev_free(&h->inv_perm); dev_free(&h->sorted_row); dev_free(&h->sorted_rid);
-  dev_free(&h->tiles); dev_free(&h->n_tiles); dev_free(&h->blk_off); dev_free(&h->x_sorted); dev_free(&h->z_part);
-  dev_free(&h->tgt_ws); dev_free(&h->h_ws); dev_free(&h->cnt_ws); dev_free(&h->hfrag_ws); dev_free(&h->logits_ws); dev_free(&h->row_of_ws);
-  dev_free(&h->tk_coarse_ws); dev_free(&h->gmax_ws); dev_free(&h->cand_blk_ws); dev_free(&h->cand_val_ws); dev_free(&h->cand_q_ws); dev_free(&h->cand_tau_ws); dev_free(&h->cand_sorted_ws); dev_free(&h->blk_cnt_ws); dev_free(&h->blk_off_ws);
-  dev_free((char**)&h->Wf16_hi); dev_free((char**)&h->Wf16_lo);
-  dev_free((char**)&h->Ef16_hi); dev_free((char**)&h->Ef16_lo); dev_free((char**)&h->hfrag16_hi); dev_free((char**)&h->hfrag16_lo);
-  dev_free((char**)&h->Erm16_hi); dev_free((char**)&h->Erm16_lo); dev_free((char**)&h->hrm16_hi); dev_free((char**)&h->hrm16_lo);
-  dev_free((char**)&h->Ef3); dev_free((char**)&h->hf3_ws); dev_free((char**)&h->mask_ws); dev_free(&h->band_consts); dev_free(&h->tband_ws); dev_free(&h->x3s); dev_free(&h->x3m); dev_free(&h->w_exp); dev_free((char**)&h->fused_fin_dev);
-  dev_free(&h->tgtx_ws); dev_free(&h->heavy_ws);
   for (auto& kv : h->timers)
     for (auto& p : kv.second.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   for (auto e : h->event_pool) (void)hipEventDestroy(e);
@@ -574,11 +545,12 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   for (auto& sp : h->specs)
     if (!h->params[sp.name].set) return fail(h, COPER_EMISSING, "coper_prepare: parameter '" + sp.name + "' was never set");
   COPER_HIP_TRY(h, hipSetDevice(cfg.device));
+  h->prepared = false;          // (until every derived buffer below exists again: a prepare that fails leaves a handle that refuses passes)
   int rc;
   group_use_set(h, 0);          // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
   h->pipe.invalidate_grouping();
-  if ((rc = dev_alloc(h, &h->conv_scale, dm.C)) || (rc = dev_alloc(h, &h->conv_shift, dm.C)) ||
-      (rc = dev_alloc(h, &h->fc_scale, dm.d)) || (rc = dev_alloc(h, &h->fc_shift, dm.d)))
+  if ((rc = h->conv_scale.alloc(h, dm.C, "conv_scale")) || (rc = h->conv_shift.alloc(h, dm.C, "conv_shift")) ||
+      (rc = h->fc_scale.alloc(h, dm.d, "fc_scale")) || (rc = h->fc_shift.alloc(h, dm.d, "fc_shift")))
     return rc;
   auto P = [&](const std::string& n) { return h->params[n].ptr; };
   if ((rc = launch_fold_bn(h, P("Conv1BN/gamma"), P("Conv1BN/beta"), P("Conv1BN/moving_mean"),
@@ -590,12 +562,12 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
 
   if (cfg.score_mode != COPER_SCORE_F32) {
     // the shard's maxima (row norm, |pred_bias|: the exact band; |element|: the power of two of the entity planes, split16.h)
-    if ((rc = dev_alloc(h, &h->band_consts, BAND_NCONST)) || (rc = dev_alloc(h, &h->x3s, 4)) ||
-        (rc = dev_alloc(h, &h->x3m, (size_t)X3M_SLOTS)))
-      return rc;
+    const bool bad = (rc = h->band_consts.alloc(h, BAND_NCONST, "band_consts")) || (rc = h->x3s.alloc(h, 4, "x3s")) ||
+                     (rc = h->home.x3m.alloc(h, (size_t)X3M_SLOTS, "x3m"));
+    group_home_views(h);
+    if (bad) return rc;
     COPER_HIP_TRY(h, hipMemsetAsync(h->x3s, 0, 4 * sizeof(int32_t), s));
     COPER_HIP_TRY(h, hipMemsetAsync(h->x3m, 0, X3M_SLOTS * sizeof(float), s));
-    group_snapshot_home(h);
     if ((rc = launch_band_consts(h, P("ent_emb"), P("pred_bias"), s))) return rc;
     {
       unsigned cb[BAND_NCONST];
@@ -627,11 +599,11 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   for (int i = 0; i < cfg.n_ctx_conv; ++i) max_hidden = cfg.ctx_conv[i] > max_hidden ? cfg.ctx_conv[i] : max_hidden;
   for (int i = 0; i < cfg.n_ctx_out; ++i) max_hidden = cfg.ctx_out[i] > max_hidden ? cfg.ctx_out[i] : max_hidden;
   size_t tmp_elems = (size_t)(dm.R + 2) * max_hidden;
-  if ((rc = dev_alloc(h, &h->ctx_tmp[0], tmp_elems)) || (rc = dev_alloc(h, &h->ctx_tmp[1], tmp_elems))) return rc;
+  if ((rc = h->ctx_tmp[0].alloc(h, tmp_elems, "ctx_tmp")) || (rc = h->ctx_tmp[1].alloc(h, tmp_elems, "ctx_tmp"))) return rc;
 
   int64_t nconv = (int64_t)dm.fh * dm.fw * dm.C;
   if (dm.gen_conv) {
-    if ((rc = dev_alloc(h, &h->conv_w_rel, (size_t)dm.R * nconv)) || (rc = dev_alloc(h, &h->conv_b_rel, (size_t)dm.R * dm.C)))
+    if ((rc = h->conv_w_rel.alloc(h, (size_t)dm.R * nconv, "conv_w_rel")) || (rc = h->conv_b_rel.alloc(h, (size_t)dm.R * dm.C, "conv_b_rel")))
       return rc;
     if (dm.lookup) {  // ParameterLookup.generate (models.py:90-94): the table row IS the parameter
       COPER_HIP_TRY(h, hipMemcpyAsync(h->conv_w_rel, P("conv1_weights"), sizeof(float) * dm.R * nconv, hipMemcpyDeviceToDevice, s));
@@ -656,10 +628,10 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   h->w_div = w_div; h->w_rem = w_rem;
   const int64_t n_own = w_div > 1 ? (dm.R > w_rem ? (dm.R - w_rem + w_div - 1) / w_div : 0) : dm.R;
   h->Rw = dm.gen_fc ? (w_div > 1 ? (dm.R + w_div - 1) / w_div : dm.R) : 1;
-  if ((rc = dev_alloc(h, &h->Wf, per_rel * h->Rw))) return rc;
-  float* ctx_sel = nullptr;       // the generator contexts of the held relations, compacted (freed behind the synchronize below)
+  if ((rc = h->Wf.alloc(h, per_rel * h->Rw, "Wf"))) return rc;
+  DevBuf<float> ctx_sel;          // the generator contexts of the held relations, compacted (freed behind the synchronize below)
   if (dm.gen_fc) {
-    if ((rc = dev_alloc(h, &h->fc_b_rel, (size_t)dm.R * dm.d))) return rc;
+    if ((rc = h->fc_b_rel.alloc(h, (size_t)dm.R * dm.d, "fc_b_rel"))) return rc;
     if (dm.lookup) {
       COPER_HIP_TRY(h, hipMemcpyAsync(h->fc_b_rel, P("fc_bias"), sizeof(float) * dm.R * dm.d, hipMemcpyDeviceToDevice, s));
       if ((rc = launch_gen_dense_frag(h, nullptr, dm.R, 0, P("fc_weights"), 1, h->Wf, s))) return rc;
@@ -671,7 +643,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
       if ((rc = run_generator_hidden(h, "fc_weights", cfg.n_ctx_out, cfg.ctx_out, &ctx, &K, s))) return rc;
       snprintf(buf, sizeof buf, "fc_weights/CPG/Projection%d", cfg.n_ctx_out);
       if (w_div > 1) {      // slot i = relation w_rem + i w_div: the same context row, the same sum -- W_r is the same bits at any G
-        if ((rc = dev_alloc(h, &ctx_sel, (size_t)h->Rw * K))) return rc;
+        if ((rc = ctx_sel.alloc(h, (size_t)h->Rw * K, "ctx_sel"))) return rc;
         COPER_HIP_TRY(h, hipMemsetAsync(ctx_sel, 0, sizeof(float) * (size_t)h->Rw * K, s));
         if (n_own > 0)
           COPER_HIP_TRY(h, hipMemcpy2DAsync(ctx_sel, sizeof(float) * K, ctx + (size_t)w_rem * K, sizeof(float) * (size_t)w_div * K, sizeof(float) * K,
@@ -684,64 +656,53 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
     if ((rc = launch_gen_dense_frag(h, nullptr, 1, 0, P("fc_weights"), 1, h->Wf, s))) return rc;
   }
   h->enc_bf16 = cfg.score_mode != COPER_SCORE_F32 && conv_bf16_supported(dm);
-  if (w_div > 1 && !h->enc_bf16) {
-    dev_free(&ctx_sel);
+  if (w_div > 1 && !h->enc_bf16)
     return fail(h, COPER_EUNSUPPORTED, "rel_mod_world > 1: the configuration is not served by the 16-bit encoder");
-  }
   if (h->enc_bf16) {
-    size_t plane = (size_t)h->Rw * dm.nfb * w16_ks_stride(dm) * 64 * 16;
-    dev_free((char**)&h->Wf16_hi); dev_free((char**)&h->Wf16_lo);
-    if (tracked_malloc(&h->Wf16_hi, plane) != hipSuccess || tracked_malloc(&h->Wf16_lo, plane) != hipSuccess)
-      return fail(h, COPER_ENOMEM, "hipMalloc of the bf16 weight planes failed");
+    const size_t plane = (size_t)h->Rw * dm.nfb * w16_ks_stride(dm) * 64;     // uint4
+    if ((rc = h->Wf16_hi.alloc(h, plane, "bf16 weight planes")) || (rc = h->Wf16_lo.alloc(h, plane, "bf16 weight planes"))) return rc;
     // powers of two of the encoder's operands (split16.h): e_W per relation from its own largest |W|, e_x from a bound on x
     if (w_div > 1) {       // e_W is looked up by RELATION ID everywhere; the conversion works on slots: computed there, scattered to the ids
-      int32_t* by_slot = nullptr;
-      if ((rc = dev_alloc(h, &h->w_exp, (size_t)dm.R)) || (rc = dev_alloc(h, &by_slot, (size_t)h->Rw))) return rc;
+      DevBuf<int32_t> by_slot;
+      if ((rc = h->w_exp.alloc(h, (size_t)dm.R, "w_exp")) || (rc = by_slot.alloc(h, (size_t)h->Rw, "w_exp by slot"))) return rc;
       COPER_HIP_TRY(h, hipMemsetAsync(h->w_exp, 0, sizeof(int32_t) * (size_t)dm.R, s));
-      int32_t* by_id = h->w_exp;
-      h->w_exp = by_slot;
-      rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, s);
-      h->w_exp = by_id;
+      rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, by_slot, s);
       if (!rc && n_own > 0 &&
-          hipMemcpy2DAsync(by_id + w_rem, sizeof(int32_t) * (size_t)w_div, by_slot, sizeof(int32_t), sizeof(int32_t), (size_t)n_own,
+          hipMemcpy2DAsync(h->w_exp + w_rem, sizeof(int32_t) * (size_t)w_div, by_slot, sizeof(int32_t), sizeof(int32_t), (size_t)n_own,
                            hipMemcpyDeviceToDevice, s) != hipSuccess)
         rc = fail(h, COPER_EHIP, "hipMemcpy2DAsync (e_W by relation id)");
       hipError_t e = hipStreamSynchronize(s);
-      dev_free(&by_slot);
       if (rc) return rc;
       COPER_HIP_TRY(h, e);
     } else {
-      if ((rc = dev_alloc(h, &h->w_exp, (size_t)h->Rw))) return rc;
-      if ((rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, s))) return rc;
+      if ((rc = h->w_exp.alloc(h, (size_t)h->Rw, "w_exp"))) return rc;
+      if ((rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, h->w_exp, s))) return rc;
     }
     if ((rc = compute_x_exp(h, h->band_consts + 5, s))) return rc;
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    dev_free(&h->Wf);  // the fp32 image was only the staging form
-    dev_free(&ctx_sel);
+    h->Wf.reset();  // the fp32 image was only the staging form
+    ctx_sel.reset();
   }
   }                    // ---- (role_enc)
   // entity table image(s) (a COPER_ROLE_ENCODE handle has none)
   if (!role_score) {
   } else if (cfg.score_mode == COPER_SCORE_F32) {
-    if ((rc = dev_alloc(h, &h->Ef, (size_t)dm.n_eblk * dm.KS * 64 * 4)) || (rc = dev_alloc(h, &h->bias_pad, (size_t)dm.n_eblk * 32)))
+    if ((rc = h->Ef.alloc(h, (size_t)dm.n_eblk * dm.KS * 64 * 4, "Ef")) || (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
       return rc;
     if ((rc = launch_entity_frag(h, P("ent_emb"), P("pred_bias"), s))) return rc;
   } else {
     // bias_pad comes from the (tiny-KS) fp32 image builder run on a 1-k-step view; the table goes to two bf16 planes
-    size_t plane = (size_t)dm.n_eblk * dm.KS16 * 64 * 16;
-    dev_free((char**)&h->Ef16_hi); dev_free((char**)&h->Ef16_lo);
-    dev_free((char**)&h->Erm16_hi); dev_free((char**)&h->Erm16_lo);
-    if (tracked_malloc(&h->Ef16_hi, plane) != hipSuccess || tracked_malloc(&h->Ef16_lo, plane) != hipSuccess ||
-        tracked_malloc(&h->Erm16_hi, plane) != hipSuccess || tracked_malloc(&h->Erm16_lo, plane) != hipSuccess)
-      return fail(h, COPER_ENOMEM, "hipMalloc of the bf16 entity planes failed");
-    if ((rc = dev_alloc(h, &h->bias_pad, (size_t)dm.n_eblk * 32))) return rc;
+    const size_t plane = (size_t)dm.n_eblk * dm.KS16 * 64;     // uint4
+    if ((rc = h->Ef16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Ef16_lo.alloc(h, plane, "bf16 entity planes")) ||
+        (rc = h->Erm16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Erm16_lo.alloc(h, plane, "bf16 entity planes")) ||
+        (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
+      return rc;
     if ((rc = launch_bias_pad(h, P("pred_bias"), s))) return rc;
-    const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64 * 16;    // the count kernel's image (bf16x3_chain.h)
-    dev_free((char**)&h->Ef3);
-    if (tracked_malloc(&h->Ef3, f3) != hipSuccess) { (void)hipGetLastError(); return fail(h, COPER_ENOMEM, "hipMalloc of the entity image failed"); }
-    COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3, s));
-    if ((rc = launch_rows_to_frag_bf16(h, P("ent_emb"), dm.n_local, dm.n_eblk, (uint4*)h->Ef16_hi, (uint4*)h->Ef16_lo,
-                                       (uint4*)h->Erm16_hi, (uint4*)h->Erm16_lo, (uint4*)h->Ef3, false, s)))
+    const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
+    if ((rc = h->Ef3.alloc(h, f3, "entity image"))) return rc;
+    COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3 * sizeof(uint4), s));
+    if ((rc = launch_rows_to_frag_bf16(h, P("ent_emb"), dm.n_local, dm.n_eblk, h->Ef16_hi, h->Ef16_lo, h->Erm16_hi, h->Erm16_lo, h->Ef3,
+                                       false, s)))
       return rc;
     if ((rc = score_bf16_kernels_init(h))) return rc;
   }
@@ -999,33 +960,23 @@ COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float*
     const size_t gneed = (size_t)(topk_gm_rows(h) * topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
     const size_t t64 = (size_t)((int64_t)k * B + filt_nnz), tneed = (size_t)XF * t64;
     const size_t cneed = topk_coarse_bytes(topk_gm_rows(h), topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
-    if (gneed > h->gmax_cap || tneed > h->cand_cap || (size_t)B > h->cand_tau_cap || cneed > h->tk_coarse_cap) {
+    const size_t gv = (size_t)(h->dm.n_eblk * topk_nseg(h->dm.n_eblk));
+    if (gneed > h->gmax_ws.size() || tneed > h->cand_cap || (size_t)B > h->cand_tau_ws.size() || cneed > h->tk_coarse_ws.size() ||
+        !h->blk_cnt_ws || !h->blk_off_ws) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if (cneed > h->tk_coarse_cap) {
-        if ((rc = dev_alloc(h, &h->tk_coarse_ws, cneed))) return rc;
-        h->tk_coarse_cap = cneed;
-      }
-      if (gneed > h->gmax_cap) {
-        if ((rc = dev_alloc(h, &h->gmax_ws, gneed))) return rc;
-        h->gmax_cap = gneed;
-      }
+      if ((rc = h->tk_coarse_ws.ensure(h, cneed, "top-k coarse level")) || (rc = h->gmax_ws.ensure(h, gneed, "block maxima"))) return rc;
       if (tneed > h->cand_cap) {
         h->cand_cap = 0;
         const size_t tlist = tneed + (XF > 1 ? t64 : 0);      // (+ the 64-entity level's own lists, behind the expanded ones)
-        if ((rc = dev_alloc(h, &h->cand_blk_ws, tlist)) || (rc = dev_alloc(h, &h->cand_q_ws, tlist)) ||
-            (rc = dev_alloc(h, &h->cand_val_ws, tneed * 32)) ||
-            (rc = dev_alloc(h, &h->cand_sorted_ws, topk_sorted_cap(h->dm.n_eblk * topk_nseg(h->dm.n_eblk), (int64_t)tneed))))
+        if ((rc = h->cand_blk_ws.alloc(h, tlist, "candidate blocks")) || (rc = h->cand_q_ws.alloc(h, tlist, "candidate queries")) ||
+            (rc = h->cand_val_ws.alloc(h, tneed * 32, "candidate logits")) ||
+            (rc = h->cand_sorted_ws.alloc(h, topk_sorted_cap(gv, (int64_t)tneed), "sorted candidates")))
           return rc;
         h->cand_cap = tneed;
       }
-      if ((size_t)B > h->cand_tau_cap) {
-        if ((rc = dev_alloc(h, &h->cand_tau_ws, (size_t)B))) return rc;
-        h->cand_tau_cap = (size_t)B;
-      }
-      if (!h->blk_cnt_ws) {
-        const size_t gv = (size_t)(h->dm.n_eblk * topk_nseg(h->dm.n_eblk));
-        if ((rc = dev_alloc(h, &h->blk_cnt_ws, 2 * gv)) || (rc = dev_alloc(h, &h->blk_off_ws, gv + 1 + gv / 4096 + 2))) return rc;   // + chunk sums of the scan
-      }
+      if ((rc = h->cand_tau_ws.ensure(h, (size_t)B, "candidate thresholds")) || (rc = h->blk_cnt_ws.ensure(h, 2 * gv, "block counts")) ||
+          (rc = h->blk_off_ws.ensure(h, gv + 1 + gv / 4096 + 2, "block offsets")))   // + chunk sums of the scan
+        return rc;
     }
   }
   if (h->cfg.score_mode != COPER_SCORE_F32) {
@@ -1055,12 +1006,12 @@ COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float*
     int64_t rows = (int64_t)(256ll << 20) / (h->dm.n_local * 4);
     if (rows < 1) rows = 1;
     if (rows > B) rows = B;
-    if (rows > h->logits_ws_rows) {
+    if ((size_t)rows * h->dm.n_local > h->logits_ws.size()) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if ((rc = dev_alloc(h, &h->logits_ws, (size_t)rows * h->dm.n_local))) return rc;
-      h->logits_ws_rows = rows;
+      if ((rc = h->logits_ws.alloc(h, (size_t)rows * h->dm.n_local, "top-k logits"))) return rc;
     }
-    return launch_topk(h, hvec, e2, filt_indptr, filt_idx, B, k, topk_val, topk_idx, h->logits_ws, h->logits_ws_rows, s);
+    return launch_topk(h, hvec, e2, filt_indptr, filt_idx, B, k, topk_val, topk_idx, h->logits_ws,
+                       (int64_t)(h->logits_ws.size() / h->dm.n_local), s);
   }
   return COPER_OK;
 }
@@ -1409,7 +1360,7 @@ COPER_API int coper_stale_passes(coper_handle* h, int64_t* n_passes, void* strea
   if (!h || !n_passes) return COPER_EINVAL;
   *n_passes = h->stale_passes_host;
   h->stale_passes_host = 0;
-  if (!h->group_done) return COPER_OK;
+  if (!h->home.counts) return COPER_OK;
   hipStream_t s = (hipStream_t)stream;
   int32_t v = 0;
   COPER_HIP_TRY(h, hipMemcpyAsync(&v, h->group_done + 2, sizeof v, hipMemcpyDeviceToHost, s));

@@ -61,8 +61,52 @@ namespace coper {
 // the runtime's own scratch and pool decisions)
 hipError_t tracked_malloc_impl(void** p, size_t bytes);
 hipError_t tracked_free(void* p);
+// tracked_malloc_impl of `bytes` for a DevBuf: on failure *p is null, the sticky HIP error is cleared and the handle's error says
+// what failed (COPER_ENOMEM)
+int devbuf_malloc(coper_handle* h, void** p, size_t bytes, const char* what);
+
+// The owner of one device buffer: a pointer and its capacity in elements, freed when the owner is.  Empty (null, capacity 0) until
+// allocated, after reset() and after a failed allocation.  Reads as T* (launch code takes it as the pointer it was before); an
+// explicit cast gives the other pointer types the byte planes are read as.
 template <typename T>
-inline hipError_t tracked_malloc(T** p, size_t bytes) { return tracked_malloc_impl((void**)p, bytes); }
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  // exactly n elements (at least one), replacing the contents: the old buffer is freed first
+  int alloc(coper_handle* h, size_t n, const char* what) {
+    reset();
+    if (n == 0) n = 1;
+    void* p = nullptr;
+    if (int rc = devbuf_malloc(h, &p, n * sizeof(T), what)) return rc;
+    p_ = (T*)p;
+    n_ = n;
+    return COPER_OK;
+  }
+  // at least n elements: nothing happens when they are there
+  int ensure(coper_handle* h, size_t n, const char* what) { return n <= n_ ? COPER_OK : alloc(h, n, what); }
+  void reset() {
+    if (p_) (void)tracked_free(p_);
+    p_ = nullptr;
+    n_ = 0;
+  }
+  size_t size() const { return n_; }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  template <typename U>
+  explicit operator U*() const { return (U*)p_; }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
 
 
 struct Param {
@@ -126,37 +170,44 @@ struct coper_handle {
   bool prepared = false;
 
   // ---- derived device buffers (owned) ----
-  float* conv_scale = nullptr;  // [C]   folded Conv1BN
-  float* conv_shift = nullptr;
-  float* fc_scale = nullptr;    // [d]   folded FCBN
-  float* fc_shift = nullptr;
-  float* conv_w_rel = nullptr;  // [R, fh*fw, C] generated / looked-up conv filters (gen_conv)
-  float* conv_b_rel = nullptr;  // [R, C]
-  float* fc_b_rel = nullptr;    // [R, d]  (gen_fc)
-  float* Wf = nullptr;          // dense weights, fragment-major: [Rw][nfb][F_pad/16][64] float4
-  int64_t Rw = 0;               // R when gen_fc else 1
-  float* Ef = nullptr;          // entity table, fragment-major: [n_eblk][KS][64] float4
-  float* bias_pad = nullptr;    // [n_eblk*32], -inf padded
-  void* Wf16_hi = nullptr;      // COPER_SCORE_BF16X3: dense weights as hi / lo bf16 planes (16x16x32 fragment order)
-  void* Wf16_lo = nullptr;
-  bool enc_bf16 = false;        // encoder runs in bf16x3 (needs 3x3 filters, C % 8 == 0)
-  void* Ef16_hi = nullptr;      // COPER_SCORE_BF16X3: entity table hi / lo bf16 planes, fragment-major
-  void* Ef16_lo = nullptr;      //   [n_eblk][KS16][64] x 16 B
-  void* Erm16_hi = nullptr;     //   row-major twins [n_eblk*32][KS16*16] bf16 (pair kernel gathers)
-  void* Erm16_lo = nullptr;
-  void* Ef3 = nullptr;          //   the count kernel's image (bf16x3_chain.h): [2 n_eblk][NS][2][64] x 16 B, zero-filled first
-  unsigned* band_consts = nullptr;   // [BAND_NCONST] float bits: [0] max |E_e|_2, [1] max |pred_bias| of the shard (exact band), [2] max |E element|,
+  coper::DevBuf<float> conv_scale;  // [C]   folded Conv1BN
+  coper::DevBuf<float> conv_shift;
+  coper::DevBuf<float> fc_scale;    // [d]   folded FCBN
+  coper::DevBuf<float> fc_shift;
+  coper::DevBuf<float> conv_w_rel;  // [R, fh*fw, C] generated / looked-up conv filters (gen_conv)
+  coper::DevBuf<float> conv_b_rel;  // [R, C]
+  coper::DevBuf<float> fc_b_rel;    // [R, d]  (gen_fc)
+  coper::DevBuf<float> Wf;          // dense weights, fragment-major: [Rw][nfb][F_pad/16][64] float4
+  int64_t Rw = 0;                   // R when gen_fc else 1
+  coper::DevBuf<float> Ef;          // entity table, fragment-major: [n_eblk][KS][64] float4
+  coper::DevBuf<float> bias_pad;    // [n_eblk*32], -inf padded
+  coper::DevBuf<uint4> Wf16_hi;     // COPER_SCORE_BF16X3: dense weights as hi / lo bf16 planes (16x16x32 fragment order)
+  coper::DevBuf<uint4> Wf16_lo;
+  bool enc_bf16 = false;            // encoder runs in bf16x3 (needs 3x3 filters, C % 8 == 0)
+  coper::DevBuf<uint4> Ef16_hi;     // COPER_SCORE_BF16X3: entity table hi / lo bf16 planes, fragment-major
+  coper::DevBuf<uint4> Ef16_lo;     //   [n_eblk][KS16][64] x 16 B
+  coper::DevBuf<uint4> Erm16_hi;    //   row-major twins [n_eblk*32][KS16*16] bf16 (pair kernel gathers)
+  coper::DevBuf<uint4> Erm16_lo;
+  coper::DevBuf<uint4> Ef3;         //   the count kernel's image (bf16x3_chain.h): [2 n_eblk][NS][2][64] x 16 B, zero-filled first
+  coper::DevBuf<unsigned> band_consts;   // [BAND_NCONST] float bits: [0] max |E_e|_2, [1] max |pred_bias| of the shard (exact band), [2] max |E element|,
                                      //   [3] the band audit's largest |x3 - chain| / (tau / 2), [4] its pair count (coper_band_audit)
   float band_kappa_mult = 1.f;       // coper_band_policy: a power of two on top of the configured kappa (kept across coper_prepare)
   unsigned band_launches = 0;        // count launches since prepare (which of them the band audit rides on: kernels_score3_bf16.hip)
   int img_exp = 0;                   // e_I: the fused encoder's image planes (compute_x_exp)
   int x3_ent_exp = 0;                // e_E: the entity planes hold E 2^e_E (split16.h; prepare)
   float x3_ent_absmax = 0.f;         //   the maximum it was chosen from (the shard's, or coper_config.x3_ent_absmax)
-  // coper_group_next: grouping arrays in sets.  Set 0 is HOME (the arrays below: every pass that groups itself, and every captured
+  // coper_group_next: grouping arrays in sets.  Set 0 is HOME (the owners in `home`: every pass that groups itself, and every captured
   // graph, uses it); sets 1 and 2 are written by the grouping role of a fused encoder launch for the NEXT pass while the running
   // pass reads its own.  The fields perm / inv_perm / ... / x3m / fused_fin_dev always name the set of the pass being enqueued.
+  struct HomeSet {
+    coper::DevBuf<int32_t> counts;   // [3 (R+2) + 4]: rel_count_buf[0] | rel_count_buf[1] | rel_cursor | group_done (ensure_workspace)
+    coper::DevBuf<int32_t> rel_offset, perm, inv_perm, sorted_row, sorted_rid, tiles, n_tiles;
+    coper::DevBuf<float> x3m;        // (allocated by coper_prepare)
+  } home;
   struct GroupSet {
-    int32_t* slab = nullptr;         // sets 1, 2: one allocation; set 0: unused (a snapshot of the home pointers)
+    coper::DevBuf<int32_t> slab;     // sets 1, 2: one allocation; set 0: empty (its arrays are `home`)
+    coper::DevBuf<char> fin;         // the set's FusedFinConst (fused_fin_update)
+    // views: into slab, or into `home` and fin for set 0 (group_home_views)
     int32_t* rel_count = nullptr; int32_t* rel_offset = nullptr; int32_t* perm = nullptr; int32_t* inv_perm = nullptr;
     int32_t* sorted_row = nullptr; int32_t* sorted_rid = nullptr; int32_t* tiles = nullptr; int32_t* n_tiles = nullptr;
     float* x3m = nullptr; void* fused_fin_dev = nullptr; const int32_t* fused_fin_perm = nullptr;
@@ -198,20 +249,20 @@ struct coper_handle {
   // sorted; the kernels that preset the rank counters read the verdict); nullptr: the pass grouped itself
   int64_t* pass_chk = nullptr;
   int64_t stale_passes_host = 0;     // coper_stale_passes: what the device counter (group_done + 2) held when a growing workspace replaced it
-  void* fused_fin_dev = nullptr;     // FusedFinConst (kernels_dense_fused_bf16.hip): the fused encoder's finalize constants, in device memory
+  void* fused_fin_dev = nullptr;     // view: FusedFinConst (kernels_dense_fused_bf16.hip): the fused encoder's finalize constants, in device memory
   const int32_t* fused_fin_perm = nullptr;   //   the workspace generation they were written for
-  int32_t* w_exp = nullptr;          // [R or 1] e_W per relation id: the dense-weight planes hold W_r 2^e_W (split16.h; prepare)
+  coper::DevBuf<int32_t> w_exp;      // [R or 1] e_W per relation id: the dense-weight planes hold W_r 2^e_W (split16.h; prepare)
   int w_div = 1, w_rem = 0;          // coper_config.rel_mod_*: the weight planes hold the relations r with r % w_div == w_rem, relation r at slot r / w_div
   int x_exp = 0;                     // e_x: the conv activations enter the dense layer as x 2^e_x (from a bound; prepare)
-  int32_t* x3s = nullptr;            // [4] the packed batch's exponents: [0] e_h, [1] e_E + e_h (bf16x3_chain.h)
-  float* x3m = nullptr;              // [X3M_SLOTS] per-block maxima of the h rows being packed (bf16x3_chain.h)
-  float* ctx_tmp[2] = {nullptr, nullptr};  // generator hidden activations
-  size_t ctx_tmp_elems = 0;
+  coper::DevBuf<int32_t> x3s;        // [4] the packed batch's exponents: [0] e_h, [1] e_E + e_h (bf16x3_chain.h)
+  float* x3m = nullptr;              // view: [X3M_SLOTS] per-block maxima of the h rows being packed (bf16x3_chain.h)
+  coper::DevBuf<float> ctx_tmp[2];   // generator hidden activations
 
   // ---- workspace (owned, grown lazily) ----
-  int64_t ws_queries = 0;
+  int64_t ws_queries = 0;         // the capacity of the workspace group of ensure_workspace: 0 while any of it is missing
   int64_t ws_nnz = 0;
   int ws_ksplit = 0;
+  // views of the set being enqueued (gset) and into home.counts
   int32_t* rel_count = nullptr;   // [R+2] counts of the LAST grouping call (+ the out-of-range counter at R+1) = rel_count_buf[0]
   int32_t* rel_count_buf[2] = {nullptr, nullptr};   // [0] the published counts; [1] the accumulation buffer of k_rel_hist_scan (zero between calls)
   int32_t* group_done = nullptr;  // ticket counter of the histogram launch (its last block runs the scan)
@@ -223,56 +274,49 @@ struct coper_handle {
   int32_t* sorted_rid = nullptr;  // [B] sorted position -> validated relation id
   int32_t* tiles = nullptr;       // [T_max*4] (rel, start, n, pad)
   int32_t* n_tiles = nullptr;     // [2] #small tiles, #big 16-query blocks
-  int32_t* blk_off = nullptr;     // [R+1] exclusive scan of the big groups' block counts
-  float* x_sorted = nullptr;      // [B, F_pad]
-  float* z_part = nullptr;        // [ksplit, B, d_pad16]
-  float* tgt_ws = nullptr;        // [B]
-  int32_t* cnt_ws = nullptr;      // [2B]
-  float* h_ws = nullptr;          // internal h of coper_encode_rank when the caller does not want it (fp32 mode)
-  int64_t h_ws_rows = 0;
-  float* logits_ws = nullptr;     // top-k path only: [chunk_rows, n_local]
-  int64_t logits_ws_rows = 0;
+  coper::DevBuf<int32_t> blk_off; // [R+1] exclusive scan of the big groups' block counts
+  coper::DevBuf<float> x_sorted;  // [B, F_pad]
+  coper::DevBuf<float> z_part;    // [ksplit, B, d_pad16]
+  coper::DevBuf<float> tgt_ws;    // [B]
+  coper::DevBuf<int32_t> cnt_ws;  // [2B]
+  coper::DevBuf<float> h_ws;      // internal h of coper_encode_rank when the caller does not want it (fp32 mode)
+  coper::DevBuf<float> logits_ws; // top-k path only: [chunk_rows, n_local]
   // pruned top-k (k <= COPER_TOPK_PRUNED_MAX; kernels_topk_bf16.hip)
   int64_t gmax_max_floats = (int64_t)1 << 28;   // set from the device memory size at prepare
-  float* gmax_ws = nullptr;       // [n_eblk][query chunk]: block maxima written by the count pass
-  size_t gmax_cap = 0;
-  int32_t* cand_blk_ws = nullptr; // [k*B + nnz] candidate blocks, query q's at k*q + indptr[q]
-  float* cand_val_ws = nullptr;   // [k*B + nnz][32] their logits
-  size_t cand_cap = 0;
-  int32_t* cand_q_ws = nullptr;   // [k*B + nnz] the query of every candidate slot
-  char* tk_coarse_ws = nullptr;   // the threshold kernel's coarse level (topk_coarse_bytes)
-  size_t tk_coarse_cap = 0;
-  uint32_t* cand_tau_ws = nullptr; // [B] selection threshold per query (ordered float bits; 0: none)
-  size_t cand_tau_cap = 0;
-  int32_t* cand_sorted_ws = nullptr;  // candidate slots grouped by entity block, 32-padded per block
-  int32_t* blk_cnt_ws = nullptr;  // [2 n_eblk] slots per block | scatter cursors
-  int32_t* blk_off_ws = nullptr;  // [n_eblk + 1] (+ the scan's chunk sums)
-  void* hfrag16_hi = nullptr;     // bf16x3: h hi / lo planes in fragment order
-  void* hfrag16_lo = nullptr;
-  void* hrm16_hi = nullptr;       //   row-major twins
-  void* hrm16_lo = nullptr;
-  void* hf3_ws = nullptr;         //   the count kernel's query image [ceil(B/128) * 8][NS][2][64] x 16 B (zero-filled at allocation)
-  float* tband_ws = nullptr;      // [B] float2 {t_lo, t_hi}: the exact band around the mode's target logit
-  float* tgtx_ws = nullptr;       // [B] exact-chain targets of the two-call flows
-  void* mask_ws = nullptr;        // band bits of one count launch (kernels_score3_bf16.hip)
-  size_t mask_cap = 0;            //   bytes
-  const float* packed_hvec = nullptr;  // what hfrag16 currently holds (only trusted inside coper_rank)
+  coper::DevBuf<float> gmax_ws;         // [n_eblk][query chunk]: block maxima written by the count pass
+  size_t cand_cap = 0;                  // the candidate slots the group of four below holds (0 while any of it is missing)
+  coper::DevBuf<int32_t> cand_blk_ws;   // [k*B + nnz] candidate blocks, query q's at k*q + indptr[q]
+  coper::DevBuf<float> cand_val_ws;     // [k*B + nnz][32] their logits
+  coper::DevBuf<int32_t> cand_q_ws;     // [k*B + nnz] the query of every candidate slot
+  coper::DevBuf<int32_t> cand_sorted_ws;  // candidate slots grouped by entity block, 32-padded per block
+  coper::DevBuf<char> tk_coarse_ws;     // the threshold kernel's coarse level (topk_coarse_bytes)
+  coper::DevBuf<uint32_t> cand_tau_ws;  // [B] selection threshold per query (ordered float bits; 0: none)
+  coper::DevBuf<int32_t> blk_cnt_ws;    // [2 n_eblk] slots per block | scatter cursors
+  coper::DevBuf<int32_t> blk_off_ws;    // [n_eblk + 1] (+ the scan's chunk sums)
+  coper::DevBuf<uint4> hfrag16_hi;      // bf16x3: h hi / lo planes in fragment order
+  coper::DevBuf<uint4> hfrag16_lo;
+  coper::DevBuf<uint4> hrm16_hi;        //   row-major twins
+  coper::DevBuf<uint4> hrm16_lo;
+  coper::DevBuf<uint4> hf3_ws;          //   the count kernel's query image [ceil(B/128) * 8][NS][2][64] x 16 B (zero-filled at allocation)
+  coper::DevBuf<float> tband_ws;        // [B] float2 {t_lo, t_hi}: the exact band around the mode's target logit
+  coper::DevBuf<float> tgtx_ws;         // [B] exact-chain targets of the two-call flows
+  coper::DevBuf<char> mask_ws;          // band bits of one count launch (kernels_score3_bf16.hip)
+  const float* packed_hvec = nullptr;   // view: what hfrag16 currently holds (only trusted inside coper_rank)
   int64_t packed_B = 0;
   bool trust_packed = false;
-  int32_t* row_of_ws = nullptr;   // bf16x3: CSR entry -> query row [nnz]
+  coper::DevBuf<int32_t> row_of_ws;     // bf16x3: CSR entry -> query row [nnz]
   bool excess_pending = false;    // the next band launch also runs the excess role (kernels_score3_bf16.hip), with
   alignas(8) unsigned char excess_args[128] = {};   //   these FilterArgs
-  int32_t* heavy_ws = nullptr;    // fused tail: [0] number of listed blocks, [1] finished workgroups, [2..] 32-query blocks whose CSR entries
-                                  //   exceed what their workgroup corrects itself (k_filter_excess_bf16x3); zero between passes
-  int64_t row_of_cap = 0;
-  float* hfrag_ws = nullptr;      // h re-packed in MFMA-fragment order [ceil(B/128)*4][KS][64] float4
+  coper::DevBuf<int32_t> heavy_ws;      // fused tail: [0] number of listed blocks, [1] finished workgroups, [2..] 32-query blocks whose CSR entries
+                                        //   exceed what their workgroup corrects itself (k_filter_excess_bf16x3); zero between passes
+  coper::DevBuf<float> hfrag_ws;        // h re-packed in MFMA-fragment order [ceil(B/128)*4][KS][64] float4
   int num_cus = 256;
   void* train = nullptr;          // coper::TrainState (coper_train.hip)
   // coper_rank only: the counters accumulate straight into `ranks` (base 1) and are preset by the packing launch
   int32_t count_base = 0;
-  int32_t* preset_cnt = nullptr;  // request: the next pack launch presets these [B] counters (and preset_eq to 0)
+  int32_t* preset_cnt = nullptr;  // view, request: the next pack launch presets these [B] counters (and preset_eq to 0)
   int32_t* preset_eq = nullptr;
-  const int64_t* expand_indptr = nullptr;      // request: the next target pass also writes row_of_ws for this CSR
+  const int64_t* expand_indptr = nullptr;      // view, request: the next target pass also writes row_of_ws for this CSR
   const int64_t* rows_expanded_for = nullptr;  // done: row_of_ws holds the row ids of this CSR
   const int32_t* counts_preset = nullptr;  // done: the next score_count on this buffer skips its own zeroing
   bool dense_attr_done = false;
@@ -429,7 +473,7 @@ int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* t
                               int64_t* topk_idx, hipStream_t s);
 // kernels_encode_bf16.hip
 bool conv_bf16_supported(const Dims& dm);
-int launch_wfrag_to_bf16(coper_handle* h, const float* Wf, int64_t Rw, void* hi, void* lo, hipStream_t s);
+int launch_wfrag_to_bf16(coper_handle* h, const float* Wf, int64_t Rw, void* hi, void* lo, int32_t* w_exp, hipStream_t s);
 int compute_x_exp(coper_handle* h, unsigned* scratch, hipStream_t s);
 // k-steps (of 32) between two feature blocks of the 16-bit dense-weight image Wf16_{hi,lo}: [rel * nfb + fb][stride][64] x 16 B.
 // Round 5: ODD (F / 32 | 1: 145 for 144 at FB15k-237 shapes, +0.7 % memory).  The 26 streams of a workgroup and the 237 workgroups
@@ -449,7 +493,7 @@ int launch_dense_fused_bf16(coper_handle* h, const int64_t* e1, const int64_t* r
 bool dense_fused_finalizes(const coper_handle* h, int nslices, const float* h_out);
 int fused_fin_update(coper_handle* h, hipStream_t s);
 // grouping sets (coper_group_next; coper_abi.hip)
-void group_snapshot_home(coper_handle* h);          // after the home arrays were (re)allocated
+void group_home_views(coper_handle* h);             // after the home arrays were (re)allocated
 void group_use_set(coper_handle* h, int i);         // point the fields at set i
 void group_sets_free(coper_handle* h);              // sets 1, 2 (back to home first)
 int group_sets_ensure(coper_handle* h, hipStream_t s);

@@ -37,10 +37,17 @@ struct TrainParam {
   std::string name;
   float* p = nullptr;   // the caller's variable, updated in place
   int64_t n = 0;
-  float* g = nullptr;   // gradient of the last step
-  float* m = nullptr;   // AMSGrad slots
-  float* v = nullptr;
-  float* vh = nullptr;
+  DevBuf<float> g;      // gradient of the last step
+  DevBuf<float> m;      // AMSGrad slots
+  DevBuf<float> v;
+  DevBuf<float> vh;
+};
+
+// the owner of one operand plane set of the split-16 GEMMs; the GEMM helpers take the TgPlanes it hands out
+struct PlaneSet {
+  DevBuf<uint4> hi, lo;
+  int32_t* exp = nullptr;   // view: its word in TrainState::tg_exps
+  operator TgPlanes() const { return TgPlanes{hi, lo, exp}; }
 };
 
 }  // namespace
@@ -52,61 +59,58 @@ struct TrainState {
   std::vector<TrainParam> tp;
   double b1p = 0, b2p = 0;
   uint32_t step = 0;
-  int64_t capB = 0, capL = 0;
+  int64_t capB = 0, capL = 0;  // the batch and lookup sizes the workspaces hold (0 while any of them is missing)
   // workspaces
-  float *img = nullptr, *y = nullptr, *x = nullptr, *c = nullptr, *dA = nullptr;
-  float *xc = nullptr, *dxc = nullptr;   // concat_rel: [B, F_conv + r] input of the dense layer and its gradient
+  DevBuf<float> img, y, x, c;
+  DevBuf<float> xc, dxc;       // concat_rel: [B, F_conv + r] input of the dense layer and its gradient
   // g_MLP generator chains (models.py:56-70), one for fc_weights (0) and one for fc_bias (1):
   //   v[0] = c;  u[i] = v[i] P_i;  a[i] = relu(BN_i(u[i]));  v[i+1] = dropout(a[i]);  context = v[nh]
   struct Chain {
     int dims[COPER_MAX_CTX + 1];
-    float* v[COPER_MAX_CTX + 1] = {};    // v[0] aliases TrainState::c
-    float* u[COPER_MAX_CTX] = {};
-    float* a[COPER_MAX_CTX] = {};
-    float* dv[COPER_MAX_CTX + 1] = {};   // gradient w.r.t. v[i]
-    float* du[COPER_MAX_CTX] = {};
-    float* st[COPER_MAX_CTX] = {};       // [2][n]: mean | inv_std
+    DevBuf<float> v[COPER_MAX_CTX + 1];  // v[1..]; v[0] is TrainState::c (left empty here)
+    DevBuf<float> u[COPER_MAX_CTX];
+    DevBuf<float> a[COPER_MAX_CTX];
+    DevBuf<float> dv[COPER_MAX_CTX + 1]; // gradient w.r.t. v[i]
+    DevBuf<float> du[COPER_MAX_CTX];
+    DevBuf<float> st[COPER_MAX_CTX];     // [2][n]: mean | inv_std
   } chain[4];                 // 0 fc_weights, 1 fc_bias, 2 conv1_weights, 3 conv1_bias
   int nh = 0;                 // hidden layers of the dense-layer generators
   int nhc = 0;                // hidden layers of the conv generators
-  float *Kt = nullptr, *Kbv = nullptr, *dKs = nullptr, *dkbs = nullptr;   // per-sample conv filters / biases and their gradients
-  float* Sd = nullptr;       // [B, |E|] dense d(loss)/d(logits) when it fits (scorer backward by GEMM)
-  int64_t capS = 0;
-  float* A = nullptr;        // generated dense: T[r][B][d] (forward partials) | dT[r][B][d]
+  DevBuf<float> Kt, Kbv, dKs, dkbs;   // per-sample conv filters / biases and their gradients
+  DevBuf<float> Sd;          // [B, |E|] dense d(loss)/d(logits) when it fits (scorer backward by GEMM)
+  DevBuf<float> A;           // generated dense: T[r][B][d] (forward partials) | dT[r][B][d]
   // generated dense, split-bf16 GEMMs (train_gemm_bf16.hip): operand planes
-  TgPlanes pX, pXt, pP1, pP3, pTn, pTb;   // x rows b | x rows f | P rows (rho,k) | P rows f | dT rows (rho,k) | dT rows b
+  PlaneSet pX, pXt, pP1, pP3, pTn, pTb;   // x rows b | x rows f | P rows (rho,k) | P rows f | dT rows (rho,k) | dT rows b
   // the other products (static dense layer, 1-vs-all scorer, dE of the dense scorer backward): two operand plane sets and
   // the split-K partial sums, grown on demand
-  TgPlanes mmX, mmY;
-  int32_t* tg_exps = nullptr;    // [10 + TR_EXP_CACHE] the exponents of the ten plane sets (train_gemm.h), in the order pX pXt pP1 pP3 pTn pTb mmX mmY mmX2 mmY2,
+  PlaneSet mmX, mmY;
+  DevBuf<int32_t> tg_exps;       // [10 + TR_EXP_CACHE] the exponents of the ten plane sets (train_gemm.h), in the order pX pXt pP1 pP3 pTn pTb mmX mmY mmX2 mmY2,
                                  //   then the words tg_matmul hands out per operand tensor within a step (exp_cache)
   // the largest |W| of the dense weights (the last projection of the fc_weights generator / the static fc_weights), as the OPTIMIZER
   // left it: k_tr_amsgrad folds |p_new| of that leaf into TG_MAX_SLOTS slots while it writes it, the packs of the next step reduce
   // the slots -- the 118 MB pass that used to find the maximum (53 us of a 1.25 ms step) is gone.  Two sets: a step reads [wmax_cur],
   // its optimizer pass writes [wmax_cur ^ 1] (zeroed by the step's zero list).  Valid only from one train step to the next of this
   // handle with no coper_set_param in between (the tensors are the caller's: include/coper_hip.h, coper_train_step)
-  unsigned* xmax = nullptr;      // TG_MAX_SLOTS: max x as k_tr_bn1_fwd wrote it;  dtmax: max |dT| as k_tr_scale_rows wrote it (zeroed per step)
-  unsigned* dtmax = nullptr;
-  unsigned* smax = nullptr;      // TG_MAX_SLOTS: max |S| as k_tr_build_S wrote it
-  unsigned* wmax[2] = {nullptr, nullptr};
+  DevBuf<unsigned> xmax;         // TG_MAX_SLOTS: max x as k_tr_bn1_fwd wrote it;  dtmax: max |dT| as k_tr_scale_rows wrote it (zeroed per step)
+  DevBuf<unsigned> dtmax;
+  DevBuf<unsigned> smax;         // TG_MAX_SLOTS: max |S| as k_tr_build_S wrote it
+  DevBuf<unsigned> wmax[2];
   int wmax_cur = 0;
   bool wmax_valid = false;
   // tg_matmul: the exponent of an operand tensor packed earlier in THIS step (x, the static W, dz and S are each packed for two
   // products): (tensor, its word).  Cleared at the start of a step and where a kernel rewrites a tensor in place.
   std::vector<std::pair<const float*, int32_t*>> exp_cache;
-  unsigned* tg_scratch = nullptr;   // [2] the absmax reduction of tg_pack (zero between packs); [2..3]: the side stream's
+  DevBuf<unsigned> tg_scratch;      // [2] the absmax reduction of tg_pack (zero between packs); [2..3]: the side stream's
   // round 6: a step is not one chain -- the projection's packs do not need the conv, the scorer's backward does not need the dense
   // layer's.  Those stretches run on a side stream of the state's own, forked from and joined to the caller's stream by events
   // (under capture they become branches of the graph).  side[0]: the packs in front, the scorer's backward; side[1]: the dP product.
   hipStream_t side[2] = {nullptr, nullptr};
   hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
-  size_t mmX_cap = 0, mmY_cap = 0, mmP_cap = 0;
-  TgPlanes mmX2, mmY2;               // tg_matmul's operand planes on the side stream (TrainState::side[0])
-  size_t mmX2_cap = 0, mmY2_cap = 0;
-  float* mmP = nullptr;
-  float *z0 = nullptr, *z1 = nullptr, *hv = nullptr, *dh = nullptr, *dz = nullptr, *ds = nullptr, *dx = nullptr, *dc = nullptr;
-  double* red = nullptr;     // reduction scratch: [0] loss, [1] grad sumsq (total, written by the optimizer kernel), [2..] BN sums, then TG_SUMSQ_SLOTS partial sumsq
-  float* bnst = nullptr;     // [4][max(C,d)]: mean1, inv1, mean2, inv2 ... see offsets below
+  PlaneSet mmX2, mmY2;               // tg_matmul's operand planes on the side stream (TrainState::side[0])
+  DevBuf<float> mmP;
+  DevBuf<float> z0, z1, hv, dh, dz, ds, dx, dc;
+  DevBuf<double> red;        // reduction scratch: [0] loss, [1] grad sumsq (total, written by the optimizer kernel), [2..] BN sums, then TG_SUMSQ_SLOTS partial sumsq
+  DevBuf<float> bnst;        // [4][max(C,d)]: mean1, inv1, mean2, inv2 ... see offsets below
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -115,13 +119,6 @@ struct TrainState {
 };
 
 namespace {
-
-template <typename T>
-int talloc(coper_handle* h, T** p, size_t n) {
-  if (*p) { (void)tracked_free(*p); *p = nullptr; }
-  if (tracked_malloc((void**)p, n * sizeof(T)) != hipSuccess) return fail(h, COPER_ENOMEM, "hipMalloc failed (training workspace)");
-  return COPER_OK;
-}
 
 // C(i, j) = sum_k X(i, k) Y(j, k) for two strided fp32 views, on the split-bf16 GEMM of train_gemm_bf16.hip: packs both
 // operands into the state's plane sets (grown on demand), cuts K into slices when the output has few tiles.
@@ -1404,10 +1401,9 @@ static int tg_gemm_split(coper_handle* h, TrainState* T, hipStream_t s, TgPlanes
   const int nsplit = tg_split_k(M, N, K);
   if (slices_left) *slices_left = nsplit > 1 && nsplit <= 8 ? nsplit : 1;
   const size_t np = nsplit > 1 ? (size_t)nsplit * M * N : 0;
-  if (np > T->mmP_cap) {
+  if (np > T->mmP.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = talloc(h, &T->mmP, np))) return rc;
-    T->mmP_cap = np;
+    if ((rc = T->mmP.alloc(h, np, "split-K partial sums"))) return rc;
   }
   return tg_gemm_nt(h, X, M, Y, N, K, C, ci, cj, s, nsplit, T->mmP, nullptr, slices_left && *slices_left > 1);
 }
@@ -1419,25 +1415,15 @@ static int tg_matmul(coper_handle* h, TrainState* T, hipStream_t s, const MmView
   const int nsplit = tg_split_k(M, N, K);
   const size_t np = nsplit > 1 ? (size_t)nsplit * M * N : 0;
   const bool on_side = T->side[0] && s == T->side[0];      // (the caller made sure that no K slices are needed there: one partial-sum pool)
-  TgPlanes& MX = on_side ? T->mmX2 : T->mmX;
-  TgPlanes& MY = on_side ? T->mmY2 : T->mmY;
-  size_t& capX = on_side ? T->mmX2_cap : T->mmX_cap;
-  size_t& capY = on_side ? T->mmY2_cap : T->mmY_cap;
+  PlaneSet& MX = on_side ? T->mmX2 : T->mmX;
+  PlaneSet& MY = on_side ? T->mmY2 : T->mmY;
   if (on_side && nsplit > 1) return fail(h, COPER_ESTATE, "tg_matmul: a product with K slices on the side stream");
-  if (nx > capX || ny > capY || np > T->mmP_cap) {
+  if (nx > MX.hi.size() || nx > MX.lo.size() || ny > MY.hi.size() || ny > MY.lo.size() || np > T->mmP.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if (nx > capX) {
-      if ((rc = talloc(h, &MX.hi, nx)) || (rc = talloc(h, &MX.lo, nx))) return rc;
-      capX = nx;
-    }
-    if (ny > capY) {
-      if ((rc = talloc(h, &MY.hi, ny)) || (rc = talloc(h, &MY.lo, ny))) return rc;
-      capY = ny;
-    }
-    if (np > T->mmP_cap) {
-      if ((rc = talloc(h, &T->mmP, np))) return rc;
-      T->mmP_cap = np;
-    }
+    if ((rc = MX.hi.ensure(h, nx, "GEMM operand planes")) || (rc = MX.lo.ensure(h, nx, "GEMM operand planes")) ||
+        (rc = MY.hi.ensure(h, ny, "GEMM operand planes")) || (rc = MY.lo.ensure(h, ny, "GEMM operand planes")) ||
+        (rc = T->mmP.ensure(h, np, "split-K partial sums")))
+      return rc;
   }
   // an operand tensor packed earlier in this step keeps its power of two (its own word from the pool behind the plane sets' eight):
   // no second pass for the maximum.  A tensor with producer-side maxima (slots) needs no pass at all.
@@ -1472,35 +1458,12 @@ void train_params_changed(coper_handle* h) {
 void train_destroy(coper_handle* h) {
   TrainState* T = (TrainState*)h->train;
   if (!T) return;
-  for (auto& t : T->tp) { (void)tracked_free(t.g); (void)tracked_free(t.m); (void)tracked_free(t.v); (void)tracked_free(t.vh); }
-  for (TgPlanes* pl : {&T->pX, &T->pXt, &T->pP1, &T->pP3, &T->pTn, &T->pTb}) {
-    if (pl->hi) (void)tracked_free(pl->hi);
-    if (pl->lo) (void)tracked_free(pl->lo);
-  }
-  float* bufs[] = {T->Kt, T->Kbv, T->dKs, T->dkbs, T->Sd, T->img, T->y, T->x, T->c, T->A, T->dA, T->z0, T->z1, T->hv, T->dh, T->dz, T->ds, T->dx, T->dc, T->bnst, T->xc, T->dxc};
-  for (float* b : bufs) (void)tracked_free(b);
-  for (auto& ch : T->chain)
-    for (int i = 0; i <= COPER_MAX_CTX; ++i) {
-      if (i > 0) (void)tracked_free(ch.v[i]);
-      (void)tracked_free(ch.dv[i]);
-      if (i < COPER_MAX_CTX) { (void)tracked_free(ch.u[i]); (void)tracked_free(ch.a[i]); (void)tracked_free(ch.du[i]); (void)tracked_free(ch.st[i]); }
-    }
-  (void)tracked_free(T->red);
-  if (T->tg_exps) (void)tracked_free(T->tg_exps);
-  if (T->tg_scratch) (void)tracked_free(T->tg_scratch);
   for (hipStream_t& st : T->side)
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
   for (int i = 0; i < 3; ++i) {
     if (T->ev_fork[i]) (void)hipEventDestroy(T->ev_fork[i]);
     if (T->ev_join[i]) (void)hipEventDestroy(T->ev_join[i]);
   }
-  for (unsigned* w : {T->wmax[0], T->wmax[1], T->xmax, T->dtmax, T->smax})
-    if (w) (void)tracked_free(w);
-  for (TgPlanes* pl : {&T->mmX, &T->mmY, &T->mmX2, &T->mmY2}) {
-    if (pl->hi) (void)tracked_free(pl->hi);
-    if (pl->lo) (void)tracked_free(pl->lo);
-  }
-  if (T->mmP) (void)tracked_free(T->mmP);
   delete T;
   h->train = nullptr;
 }
@@ -1578,25 +1541,25 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
     tp.n = 1;
     for (int64_t s : it->second.shape) tp.n *= s;
     int rc;
-    if ((rc = talloc(h, &tp.g, (size_t)tp.n)) || (rc = talloc(h, &tp.m, (size_t)tp.n)) || (rc = talloc(h, &tp.v, (size_t)tp.n)) ||
-        (rc = talloc(h, &tp.vh, (size_t)tp.n)))
+    if ((rc = tp.g.alloc(h, (size_t)tp.n, "gradient")) || (rc = tp.m.alloc(h, (size_t)tp.n, "AMSGrad slot")) ||
+        (rc = tp.v.alloc(h, (size_t)tp.n, "AMSGrad slot")) || (rc = tp.vh.alloc(h, (size_t)tp.n, "AMSGrad slot")))
       return rc;
     COPER_HIP_TRY(h, hipMemset(tp.m, 0, sizeof(float) * tp.n));
     COPER_HIP_TRY(h, hipMemset(tp.v, 0, sizeof(float) * tp.n));
     COPER_HIP_TRY(h, hipMemset(tp.vh, 0, sizeof(float) * tp.n));
     COPER_HIP_TRY(h, hipMemset(tp.g, 0, sizeof(float) * tp.n));
-    T->tp.push_back(tp);
+    T->tp.push_back(std::move(tp));
   }
   int rc;
   int mx = dm.C > dm.d ? dm.C : dm.d;
   for (int i = 0; i < T->nh; ++i) mx = h->cfg.ctx_out[i] > mx ? h->cfg.ctx_out[i] : mx;
   for (int i = 0; i < T->nhc; ++i) mx = h->cfg.ctx_conv[i] > mx ? h->cfg.ctx_conv[i] : mx;
-  if ((rc = talloc(h, &T->bnst, (size_t)4 * mx))) return rc;
-  if ((rc = talloc(h, &T->red, (size_t)(2 + 2 * mx * TR_COLSUM_SLICES + TG_SUMSQ_SLOTS + 2 * TR_CS_SLOTS * 2 * mx)))) return rc;
-  if ((rc = talloc(h, &T->tg_exps, (size_t)(10 + TR_EXP_CACHE))) || (rc = talloc(h, &T->tg_scratch, (size_t)4)) ||
-      (rc = talloc(h, &T->wmax[0], (size_t)TG_MAX_SLOTS)) || (rc = talloc(h, &T->wmax[1], (size_t)TG_MAX_SLOTS)) ||
-      (rc = talloc(h, &T->xmax, (size_t)TG_MAX_SLOTS)) || (rc = talloc(h, &T->dtmax, (size_t)TG_MAX_SLOTS)) ||
-      (rc = talloc(h, &T->smax, (size_t)TG_MAX_SLOTS)))
+  if ((rc = T->bnst.alloc(h, (size_t)4 * mx, "BN statistics")) ||
+      (rc = T->red.alloc(h, (size_t)(2 + 2 * mx * TR_COLSUM_SLICES + TG_SUMSQ_SLOTS + 2 * TR_CS_SLOTS * 2 * mx), "reductions")) ||
+      (rc = T->tg_exps.alloc(h, (size_t)(10 + TR_EXP_CACHE), "plane exponents")) || (rc = T->tg_scratch.alloc(h, 4, "pack scratch")) ||
+      (rc = T->wmax[0].alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->wmax[1].alloc(h, TG_MAX_SLOTS, "max slots")) ||
+      (rc = T->xmax.alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->dtmax.alloc(h, TG_MAX_SLOTS, "max slots")) ||
+      (rc = T->smax.alloc(h, TG_MAX_SLOTS, "max slots")))
     return rc;
   COPER_HIP_TRY(h, hipMemset(T->tg_exps, 0, (10 + TR_EXP_CACHE) * sizeof(int32_t)));
   COPER_HIP_TRY(h, hipMemset(T->wmax[0], 0, TG_MAX_SLOTS * sizeof(unsigned)));
@@ -1613,7 +1576,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
     }
   }
   {
-    TgPlanes* sets[10] = {&T->pX, &T->pXt, &T->pP1, &T->pP3, &T->pTn, &T->pTb, &T->mmX, &T->mmY, &T->mmX2, &T->mmY2};
+    PlaneSet* sets[10] = {&T->pX, &T->pXt, &T->pP1, &T->pP3, &T->pTn, &T->pTb, &T->mmX, &T->mmY, &T->mmX2, &T->mmY2};
     for (int i = 0; i < 10; ++i) sets[i]->exp = T->tg_exps + i;
   }
   return COPER_OK;
@@ -1695,41 +1658,43 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (B > T->capB || (!one_vs_all && L > T->capL)) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
     int64_t cb = B > T->capB ? B : T->capB, cl = (!one_vs_all && L > T->capL) ? L : (T->capL > 0 ? T->capL : 1);
-    if ((rc = talloc(h, &T->img, (size_t)cb * isz)) || (rc = talloc(h, &T->y, (size_t)cb * F)) ||
-        (rc = talloc(h, &T->x, (size_t)cb * F)) ||
+    T->capB = T->capL = 0;      // (until the last of them exists: a failure leaves the whole group to the next step)
+    auto ws = [&](auto& buf, size_t n) { return buf.alloc(h, n, "training workspace"); };
+    if ((rc = ws(T->img, (size_t)cb * isz)) || (rc = ws(T->y, (size_t)cb * F)) ||
+        (rc = ws(T->x, (size_t)cb * F)) ||
         // (dx doubles as the looked-up dense layer's scratch: TR_LK_NSL partial sums of [B, d] -- more than [B, F] where F < 4 d: a fuzz
         //  shape of round 6, d = 77 with three channels, wrote past the end of it)
-        (rc = talloc(h, &T->dx, (size_t)cb * (size_t)(F > (int64_t)TR_LK_NSL * d ? F : (int64_t)TR_LK_NSL * d))) ||
-        (rc = talloc(h, &T->c, (size_t)cb * r)) || (rc = talloc(h, &T->dc, (size_t)cb * r)) ||
-        (rc = talloc(h, &T->z0, (size_t)cb * d)) || (rc = talloc(h, &T->z1, (size_t)cb * d)) ||
-        (rc = talloc(h, &T->hv, (size_t)cb * d)) || (rc = talloc(h, &T->dh, (size_t)cb * d)) ||
-        (rc = talloc(h, &T->dz, (size_t)cb * d)) || (rc = talloc(h, &T->ds, (size_t)cb * (one_vs_all ? 1 : cl))))
+        (rc = ws(T->dx, (size_t)cb * (size_t)(F > (int64_t)TR_LK_NSL * d ? F : (int64_t)TR_LK_NSL * d))) ||
+        (rc = ws(T->c, (size_t)cb * r)) || (rc = ws(T->dc, (size_t)cb * r)) ||
+        (rc = ws(T->z0, (size_t)cb * d)) || (rc = ws(T->z1, (size_t)cb * d)) ||
+        (rc = ws(T->hv, (size_t)cb * d)) || (rc = ws(T->dh, (size_t)cb * d)) ||
+        (rc = ws(T->dz, (size_t)cb * d)) || (rc = ws(T->ds, (size_t)cb * (one_vs_all ? 1 : cl))))
       return rc;
-    if (cat && ((rc = talloc(h, &T->xc, (size_t)cb * F)) || (rc = talloc(h, &T->dxc, (size_t)cb * F)))) return rc;
+    if (cat && ((rc = ws(T->xc, (size_t)cb * F)) || (rc = ws(T->dxc, (size_t)cb * F)))) return rc;
     if (gen) {
-      if ((rc = talloc(h, &T->A, (size_t)2 * rc_w * cb * d))) return rc;
+      if ((rc = ws(T->A, (size_t)2 * rc_w * cb * d))) return rc;
       const int64_t nrk = (int64_t)rc_w * d;
-      struct { TgPlanes* p; int64_t rows, K; } planes[] = {{&T->pX, cb, F}, {&T->pXt, F, cb}, {&T->pP1, nrk, F}, {&T->pP3, F, nrk},
+      struct { PlaneSet* p; int64_t rows, K; } planes[] = {{&T->pX, cb, F}, {&T->pXt, F, cb}, {&T->pP1, nrk, F}, {&T->pP3, F, nrk},
                                                           {&T->pTn, nrk, cb}, {&T->pTb, cb, nrk}};
       for (auto& pl : planes)
-        if ((rc = talloc(h, &pl.p->hi, tg_plane_elems(pl.rows, pl.K))) || (rc = talloc(h, &pl.p->lo, tg_plane_elems(pl.rows, pl.K)))) return rc;
+        if ((rc = ws(pl.p->hi, tg_plane_elems(pl.rows, pl.K))) || (rc = ws(pl.p->lo, tg_plane_elems(pl.rows, pl.K)))) return rc;
     }
     for (int g = 0; g < 4; ++g) {
       if (g < 2 ? !gen : !genc) continue;
       const int nhx = g < 2 ? nh : nhc;
       TrainState::Chain& ch = T->chain[g];
       for (int i = 0; i <= nhx; ++i) {
-        if (i > 0 && (rc = talloc(h, &ch.v[i], (size_t)cb * ch.dims[i]))) return rc;
-        if ((rc = talloc(h, &ch.dv[i], (size_t)cb * ch.dims[i]))) return rc;
-        if (i < nhx && ((rc = talloc(h, &ch.u[i], (size_t)cb * ch.dims[i + 1])) || (rc = talloc(h, &ch.a[i], (size_t)cb * ch.dims[i + 1])) ||
-                        (rc = talloc(h, &ch.du[i], (size_t)cb * ch.dims[i + 1])) || (rc = talloc(h, &ch.st[i], (size_t)2 * ch.dims[i + 1]))))
+        if (i > 0 && (rc = ws(ch.v[i], (size_t)cb * ch.dims[i]))) return rc;
+        if ((rc = ws(ch.dv[i], (size_t)cb * ch.dims[i]))) return rc;
+        if (i < nhx && ((rc = ws(ch.u[i], (size_t)cb * ch.dims[i + 1])) || (rc = ws(ch.a[i], (size_t)cb * ch.dims[i + 1])) ||
+                        (rc = ws(ch.du[i], (size_t)cb * ch.dims[i + 1])) || (rc = ws(ch.st[i], (size_t)2 * ch.dims[i + 1]))))
           return rc;
       }
     }
-    if (dm.gen_conv && ((rc = talloc(h, &T->Kt, (size_t)cb * NT * C)) || (rc = talloc(h, &T->Kbv, (size_t)cb * C)))) return rc;
+    if (dm.gen_conv && ((rc = ws(T->Kt, (size_t)cb * NT * C)) || (rc = ws(T->Kbv, (size_t)cb * C)))) return rc;
     // per-query filter / bias gradients: what the generators and tables reduce (gen_conv), and -- round 6 -- what the STATIC filters'
     // gradients are summed from (512 workgroups adding to the same 320 addresses were 50 of k_tr_conv_bwd's 60 us)
-    if ((rc = talloc(h, &T->dKs, (size_t)cb * NT * C)) || (rc = talloc(h, &T->dkbs, (size_t)cb * C))) return rc;
+    if ((rc = ws(T->dKs, (size_t)cb * NT * C)) || (rc = ws(T->dkbs, (size_t)cb * C))) return rc;
     T->capB = cb; T->capL = cl;
   }
   auto P_ = [&](const char* n) -> float* { return T->find(n)->p; };
@@ -1757,10 +1722,9 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   // (Round 6 tried the sampled scorer's forward and dh in ONE pass over the gathered rows -- a wave per row, the score a butterfly
   //  sum over its lanes: 242 us against 61 + 45 for the two kernels.  Thirty-two sequential iterations per wave, each with two
   //  dependent round trips and eight six-step cross-lane sums, are latency end to end; removed.)
-  if (!one_vs_all && dense_scorer_bwd && B * dm.E > T->capS) {
+  if (!one_vs_all && dense_scorer_bwd && (size_t)(B * dm.E) > T->Sd.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = talloc(h, &T->Sd, (size_t)(B * dm.E)))) return rc;
-    T->capS = B * dm.E;
+    if ((rc = T->Sd.alloc(h, (size_t)(B * dm.E), "training workspace"))) return rc;
   }
   const std::string wlast = "fc_weights/CPG/Projection" + std::to_string(nh), blast = "fc_bias/CPG/Projection" + std::to_string(nh);
   {
@@ -1799,12 +1763,11 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   // g_MLP generator chain g: context rows c -> v[nhx] (models.py:56-68); g_linear: the context is c itself
   auto chain_forward = [&](int g, int nhx) -> int {
     TrainState::Chain& ch = T->chain[g];
-    ch.v[0] = T->c;
     for (int i = 0; i < nhx; ++i) {
       const int ni = ch.dims[i], nj = ch.dims[i + 1];
       const std::string pn = std::string(kGenNames[g]) + "/CPG/Projection" + std::to_string(i);
       const int64_t tot = B * nj;
-      hipLaunchKernelGGL(k_tr_small_mm, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ch.v[i], P_(pn.c_str()), B, ni, nj, ch.u[i]);
+      hipLaunchKernelGGL(k_tr_small_mm, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, i ? ch.v[i] : T->c, P_(pn.c_str()), B, ni, nj, ch.u[i]);
       const float *ga = nullptr, *be = nullptr;
       if (dm.ctx_bn) {
         double* cs = colsum_slice(3 + 4 * g + i);
@@ -1918,12 +1881,11 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   // a training step over a sampled lookup whose dE goes through the dense S matrix: scores, loss, ds and dh from one pass over the rows
   // (coper_train_forward takes the same kernel: its loss is the step's, bit for bit; the dh it leaves in the workspace is not used)
   const bool score_dh_fused = !one_vs_all && dense_scorer_bwd && (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
-                              (((uintptr_t)ent | (uintptr_t)T->dh | (uintptr_t)T->hv) & 15) == 0;
+                              (((uintptr_t)ent | (uintptr_t)T->dh.get() | (uintptr_t)T->hv.get()) & 15) == 0;
   if (one_vs_all) {
-    if (B * dm.E > T->capS) {
+    if ((size_t)(B * dm.E) > T->Sd.size()) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if ((rc = talloc(h, &T->Sd, (size_t)(B * dm.E)))) return rc;
-      T->capS = B * dm.E;
+      if ((rc = T->Sd.alloc(h, (size_t)(B * dm.E), "training workspace"))) return rc;
     }
     // S[B,E] = h E^T
     if ((rc = tg_matmul(h, T, s, MmView{T->hv, tg_idx(d), tg_idx(1), false}, B, MmView{ent, tg_idx(d), tg_idx(1), false}, dm.E, d, T->Sd,
@@ -1990,7 +1952,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     // dh by the gather (a [d,B] = [d,|E|] x [|E|,B] GEMM has 8 output tiles and a long K: slower than the gather)
     if (score_dh_fused) {
       // (dh came with the scores: k_tr_score_loss_dh)
-    } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh) & 15) == 0)
+    } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
       hipLaunchKernelGGL(k_tr_dh_gather4, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
                          T->ds, dm.E, d, L, T->dh);
     else
@@ -2068,7 +2030,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
       else
         hipLaunchKernelGGL(k_tr_fcbn_bwd, dim3((unsigned)nj), dim3(256), 0, s, ch.u[i], ch.a[i], ch.du[i], (const float*)nullptr,
                            (const float*)nullptr, (const float*)nullptr, B, nj, 0, (float*)nullptr, (float*)nullptr, ch.du[i]);
-      hipLaunchKernelGGL(k_tr_small_mm_tn, dim3((unsigned)(((int64_t)ni * nj + 255) / 256)), dim3(256), 0, s, ch.v[i], ch.du[i], B, ni, nj,
+      hipLaunchKernelGGL(k_tr_small_mm_tn, dim3((unsigned)(((int64_t)ni * nj + 255) / 256)), dim3(256), 0, s, i ? ch.v[i] : T->c, ch.du[i], B, ni, nj,
                          G_(pn.c_str()));
       hipLaunchKernelGGL(k_tr_small_mm_nt, dim3((unsigned)((B * ni + 255) / 256)), dim3(256), 0, s, ch.du[i], P_(pn.c_str()), B, ni, nj, 0,
                          ch.dv[i]);

@@ -868,24 +868,22 @@ static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t
 // the constant part of FusedFin, (re)written when the workspace or the parameters move (ensure_workspace / prepare)
 int fused_fin_update(coper_handle* h, hipStream_t s) {
   const Dims& dm = h->dm;
-  if (!h->enc_bf16 || !h->x3m || !h->perm) return COPER_OK;
-  const int cur = h->gcur;
-  group_use_set(h, 0);
+  if (!h->enc_bf16 || !h->home.x3m || !h->home.perm) return COPER_OK;
   // one block of constants per set of grouping arrays (coper_group_next): perm and x3m are the set's
   for (int i = 0; i < 3; ++i) {
     coper_handle::GroupSet& g = h->gset[i];
     if (i > 0 && !g.slab) continue;
     FusedFinConst c;
-    c.perm = i ? g.perm : h->perm; c.fc_b = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr; c.scale = h->fc_scale; c.shift = h->fc_shift;
-    c.w_exp = h->w_exp; c.x3m = i ? g.x3m : h->x3m; c.per_rel_bias = dm.gen_fc ? 1 : 0; c.x_exp = h->x_exp; c.d = dm.d; c.pad = 0;
-    void** dev = i ? &g.fused_fin_dev : &h->fused_fin_dev;
-    if (!*dev && tracked_malloc(dev, sizeof c) != hipSuccess) return fail(h, COPER_ENOMEM, "hipMalloc failed (fused finalize constants)");
-    COPER_HIP_TRY(h, hipMemcpyAsync(*dev, &c, sizeof c, hipMemcpyHostToDevice, s));
+    c.perm = g.perm; c.fc_b = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr; c.scale = h->fc_scale; c.shift = h->fc_shift;
+    c.w_exp = h->w_exp; c.x3m = g.x3m; c.per_rel_bias = dm.gen_fc ? 1 : 0; c.x_exp = h->x_exp; c.d = dm.d; c.pad = 0;
+    int rc;
+    if ((rc = g.fin.ensure(h, sizeof c, "fused finalize constants"))) return rc;
+    g.fused_fin_dev = g.fin;
+    COPER_HIP_TRY(h, hipMemcpyAsync(g.fin, &c, sizeof c, hipMemcpyHostToDevice, s));
     COPER_HIP_TRY(h, hipStreamSynchronize(s));      // (c is on the stack)
-    if (i) g.fused_fin_perm = g.perm; else h->fused_fin_perm = h->perm;
+    g.fused_fin_perm = g.perm;
   }
-  group_snapshot_home(h);
-  group_use_set(h, cur);
+  group_use_set(h, h->gcur);      // (the fields of the set being enqueued: its constants moved)
   return COPER_OK;
 }
 
@@ -895,7 +893,7 @@ bool dense_fused_finalizes(const coper_handle* h, int nslices, const float* h_ou
   const Dims& dm = h->dm;
   const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params.at("fc_bias").ptr;
   return !off && h_out && nslices == 1 && h->x3m && h->fused_fin_dev && h->fused_fin_perm == h->perm && (dm.d & 3) == 0 &&
-         ((((uintptr_t)h_out) | ((uintptr_t)fcb) | ((uintptr_t)h->fc_scale) | ((uintptr_t)h->fc_shift)) & 15) == 0;
+         ((((uintptr_t)h_out) | ((uintptr_t)fcb) | ((uintptr_t)h->fc_scale.get()) | ((uintptr_t)h->fc_shift.get())) & 15) == 0;
 }
 
 int launch_dense_fused_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,

@@ -76,16 +76,16 @@ __global__ void k_bits_to_exp(int32_t* __restrict__ w_exp, int64_t n) {
   if (i < n) w_exp[i] = x3_exp_for_bits((unsigned)w_exp[i]);
 }
 
-int launch_wfrag_to_bf16(coper_handle* h, const float* Wf, int64_t Rw, void* hi, void* lo, hipStream_t s) {
+int launch_wfrag_to_bf16(coper_handle* h, const float* Wf, int64_t Rw, void* hi, void* lo, int32_t* w_exp, hipStream_t s) {
   const Dims& dm = h->dm;
   int64_t ks32n = dm.F_pad / 32;
   int64_t total = Rw * dm.nfb * ks32n * 64;
   const int64_t per_rel4 = (int64_t)dm.nfb * (dm.F_pad / 16) * 64;
-  COPER_HIP_TRY(h, hipMemsetAsync(h->w_exp, 0, sizeof(int32_t) * Rw, s));
-  hipLaunchKernelGGL(k_w_absmax, dim3(64, (unsigned)Rw), dim3(256), 0, s, (const float4*)Wf, per_rel4, h->w_exp);
-  hipLaunchKernelGGL(k_bits_to_exp, dim3((unsigned)((Rw + 255) / 256)), dim3(256), 0, s, h->w_exp, Rw);
+  COPER_HIP_TRY(h, hipMemsetAsync(w_exp, 0, sizeof(int32_t) * Rw, s));
+  hipLaunchKernelGGL(k_w_absmax, dim3(64, (unsigned)Rw), dim3(256), 0, s, (const float4*)Wf, per_rel4, w_exp);
+  hipLaunchKernelGGL(k_bits_to_exp, dim3((unsigned)((Rw + 255) / 256)), dim3(256), 0, s, w_exp, Rw);
   hipLaunchKernelGGL(k_wfrag_to_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4*)Wf,
-                     Rw * dm.nfb, ks32n, (uint4*)hi, (uint4*)lo, dm.nfb, h->w_exp, w16_ks_stride(dm));
+                     Rw * dm.nfb, ks32n, (uint4*)hi, (uint4*)lo, dm.nfb, w_exp, w16_ks_stride(dm));
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }

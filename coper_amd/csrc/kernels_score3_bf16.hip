@@ -1235,7 +1235,7 @@ size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc) {
 int score_count3_chunk_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s) {
-  if (score_count3_mask_bytes(h, Bc) > h->mask_cap) return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
+  if (score_count3_mask_bytes(h, Bc) > h->mask_ws.size()) return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
   int rc;
   {
     ScopedKernelTimer t(h, "score_count", s);

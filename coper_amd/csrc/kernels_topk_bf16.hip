@@ -869,7 +869,7 @@ static void tk_launch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0, i
   constexpr int64_t SUB = TK_THREADS / QV;
   const int64_t NG = ((G + SUB - 1) / SUB + TK_GRP - 1) / TK_GRP, strips = qs / (4 * QV);
   const size_t cbytes = (size_t)strips * NG * TK_THREADS * sizeof(uint4);
-  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->tk_coarse_ws && cbytes <= h->tk_coarse_cap) ? (uint4*)h->tk_coarse_ws : nullptr;
+  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->tk_coarse_ws && cbytes <= h->tk_coarse_ws.size()) ? (uint4*)h->tk_coarse_ws : nullptr;
   hipLaunchKernelGGL((k_topk_threshold_emit<QV, HCOPY>), dim3((unsigned)(qs / (4 * QV))), dim3(TK_THREADS), lds, s, h->gmax_ws, G, qs, q0, bc,
                      k, indptr, out_blk, out_q, out_cnt, topk_nseg(G), h->cand_tau_ws, tk_pair_xcd() ? 1 : 0, coarse, NG);
 }
@@ -898,7 +898,7 @@ int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* t
   const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
   const int64_t T64 = (int64_t)k * B + nnz;   // candidate blocks: k + (filter entries) per query
   const int64_t T = XF * T64;                 // ... as 32-entity slots
-  if ((size_t)(Gm * qc) > h->gmax_cap || (size_t)T > h->cand_cap)
+  if ((size_t)(Gm * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap)
     return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
   int rc;
   score_count_begin_bf16x3(h, B, ng, ne, s);
@@ -943,7 +943,7 @@ int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt,
   const int64_t G = dm.n_eblk;
   const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
   const int64_t T = (int64_t)k * B + nnz;
-  if ((size_t)(G * qc) > h->gmax_cap || (size_t)T > h->cand_cap)
+  if ((size_t)(G * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap)
     return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
   int rc;
   score_count_begin_f32(h, hvec, B, ng, ne, s);

@@ -690,6 +690,38 @@ def test_one_handle_per_role(mode):
     assert lib.coper_live_device_bytes() == base
 
 
+@pytest.mark.parametrize("mode", ["bf16x3", "f32"])
+def test_refused_workspace_leaves_a_handle_that_regrows(mode):
+    """A workspace the card cannot hold (coper_reserve of 2^40 queries: the query permutation alone is 4 TiB, refused by hipMalloc
+    as an ordinary error before any kernel sees it) is COPER_ENOMEM; the handle holds no more device memory than before, and its
+    next pass regrows the whole workspace and ranks as a fresh handle on the same parameters does, bit for bit."""
+    from coper_amd import _lib
+    from coper_amd.models import ConvE
+    md = cdata.model_descriptors("fb15k237_cpg", num_ent=3000, num_rel=40)
+    p = {k: torch.as_tensor(v).to("cuda:0") for k, v in cdata.synthetic_params(md, 4).items()}
+    q = cdata.synthetic_queries(md, 700, seed=5)
+    args = (q["e1"], q["rel"], q["e2"], q["filt_indptr"], q["filt_idx"])
+    lib = _lib.load()
+    import gc
+    gc.collect()
+    base = lib.coper_live_device_bytes()
+    m = ConvE(md, device="cuda:0", score_mode=mode).load_parameters(p).prepare()
+    first, _ = m.rank_pass(*args, want_equal=False)          # (the workspace exists: every buffer the reserve regrows was there)
+    torch.cuda.synchronize()
+    held = lib.coper_live_device_bytes()
+    with pytest.raises(_lib.CoperError) as e:
+        m.reserve(1 << 40)
+    assert e.value.code == 6, e.value
+    assert lib.coper_live_device_bytes() <= held
+    got, _ = m.rank_pass(*args, want_equal=False)
+    fresh = ConvE(md, device="cuda:0", score_mode=mode).load_parameters(p).prepare()
+    ref, _ = fresh.rank_pass(*args, want_equal=False)
+    assert torch.equal(got, ref) and torch.equal(first, ref)
+    for x in (m, fresh):
+        x.close()
+    assert lib.coper_live_device_bytes() == base
+
+
 @pytest.mark.parametrize("workload,G", [("fb15k237_cpg", 3), ("synth10m_cpg", 8), ("wn18rr_cpg", 4)])
 def test_generated_weights_of_the_held_relations_only(workload, G):
     """coper_config.rel_mod_* (round 6): an encoder handle that holds the generated dense weights of the relations r with
