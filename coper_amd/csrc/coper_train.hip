@@ -97,6 +97,9 @@ struct TrainState {
   DevBuf<unsigned> wmax[2];
   int wmax_cur = 0;
   bool wmax_valid = false;
+  // looked-up dense table: the relation counts of the last step's batch (R + 1), copied out of the grouping workspace behind the
+  // step's grouping -- coper_train_grad hands out the rows of absent relations as zeros by them, whatever has been grouped since
+  DevBuf<int32_t> step_rel_count;
   // tg_matmul: the exponent of an operand tensor packed earlier in THIS step (x, the static W, dz and S are each packed for two
   // products): (tensor, its word).  Cleared at the start of a step and where a kernel rewrites a tensor in place.
   std::vector<std::pair<const float*, int32_t*>> exp_cache;
@@ -1450,9 +1453,16 @@ static int tg_matmul(coper_handle* h, TrainState* T, hipStream_t s, const MmView
 
 }  // namespace
 
-// coper_set_param: whatever the optimizer's last pass knew about the parameters (TrainState::wmax) no longer describes them
+// coper_set_param: whatever the optimizer's last pass knew about the parameters (TrainState::wmax) no longer describes them, and a
+// leaf may now live at another address (a checkpoint loaded between steps): the variables are the registered tensors
 void train_params_changed(coper_handle* h) {
-  if (h->train) ((TrainState*)h->train)->wmax_valid = false;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return;
+  T->wmax_valid = false;
+  for (TrainParam& tp : T->tp) {
+    auto it = h->params.find(tp.name);
+    if (it != h->params.end() && it->second.set) tp.p = const_cast<float*>(it->second.ptr);
+  }
 }
 
 void train_destroy(coper_handle* h) {
@@ -1559,12 +1569,14 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
       (rc = T->tg_exps.alloc(h, (size_t)(10 + TR_EXP_CACHE), "plane exponents")) || (rc = T->tg_scratch.alloc(h, 4, "pack scratch")) ||
       (rc = T->wmax[0].alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->wmax[1].alloc(h, TG_MAX_SLOTS, "max slots")) ||
       (rc = T->xmax.alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->dtmax.alloc(h, TG_MAX_SLOTS, "max slots")) ||
-      (rc = T->smax.alloc(h, TG_MAX_SLOTS, "max slots")))
+      (rc = T->smax.alloc(h, TG_MAX_SLOTS, "max slots")) ||
+      (dm.lookup && dm.gen_fc && (rc = T->step_rel_count.alloc(h, (size_t)dm.R + 1, "relation counts"))))
     return rc;
   COPER_HIP_TRY(h, hipMemset(T->tg_exps, 0, (10 + TR_EXP_CACHE) * sizeof(int32_t)));
   COPER_HIP_TRY(h, hipMemset(T->wmax[0], 0, TG_MAX_SLOTS * sizeof(unsigned)));
   COPER_HIP_TRY(h, hipMemset(T->wmax[1], 0, TG_MAX_SLOTS * sizeof(unsigned)));
   COPER_HIP_TRY(h, hipMemset(T->tg_scratch, 0, 4 * sizeof(unsigned)));
+  if (T->step_rel_count) COPER_HIP_TRY(h, hipMemset(T->step_rel_count, 0, T->step_rel_count.size() * sizeof(int32_t)));
   {
     static const bool one_stream = getenv("COPER_TRAIN_ONE_STREAM") != nullptr;   // A/B switch: the step as one chain
     if (!one_stream) {
@@ -1755,6 +1767,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     if ((rc = coper_reserve(h, B, 0, stream))) return rc;
     group_use_set(h, 0);
     if ((rc = launch_group_by_relation(h, e1, rel, false, B, 32, s))) return rc;
+    if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
   }
 
   // ---- forward
@@ -2161,10 +2174,10 @@ COPER_API int coper_train_grad(coper_handle* h, const char* leaf_name, float* ou
   if (out) {
     if (cap < t->n) return fail(h, COPER_EINVAL, "coper_train_grad: output buffer too small");
     COPER_HIP_TRY(h, hipMemcpyAsync(out, t->g, sizeof(float) * t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (h->dm.lookup && h->dm.gen_fc && t->name == "fc_weights" && h->rel_count && T->step > 0) {
+    if (h->dm.lookup && h->dm.gen_fc && t->name == "fc_weights" && T->step_rel_count && T->step > 0) {
       const int64_t rowlen = h->dm.F * (int64_t)h->dm.d;
       hipLaunchKernelGGL(k_tr_zero_absent_rows, dim3((unsigned)((t->n + 255) / 256 < 4096 ? (t->n + 255) / 256 : 4096)), dim3(256), 0, (hipStream_t)stream, out,
-                         h->rel_count, rowlen, t->n);
+                         T->step_rel_count, rowlen, t->n);
       COPER_HIP_TRY(h, hipGetLastError());
     }
   }

@@ -66,6 +66,14 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _version(t):
+    """torch's version counter of a tensor (every in-place op moves it); -1 for inference-mode tensors, which keep none"""
+    try:
+        return t._version
+    except RuntimeError:
+        return -1
+
+
 def _host(v):
     """A batch field as a host NumPy array (`session.run` returns host arrays); device tensors are copied back."""
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
@@ -122,6 +130,7 @@ class ConvE(object):
             self._lib.coper_param_spec(h, i, C.byref(name), shape, C.byref(nd))
             self._specs[name.value.decode()] = tuple(shape[j] for j in range(nd.value))
         self._tensors: Dict[str, torch.Tensor] = {}
+        self._versions: Dict[str, int] = {}      # torch's version counter of each registered tensor, as it was registered
         self._prepared = False
 
         # fetch handles (models.py:135-190)
@@ -167,12 +176,31 @@ class ConvE(object):
             if t.numel() != int(np.prod(want)):
                 raise ValueError("parameter %s: got shape %s, need %s" % (name, tuple(t.shape), want))
             self._tensors[name] = t
+            self._versions[name] = _version(t)
             shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
             _lib.check(self._h, self._lib.coper_set_param(self._h, name.encode(), _ptr(t), shape, t.dim()))
         if "ent_emb" in params:
             self._ent_absmax_cache = None
         self._prepared = False
         return self
+
+    def parameters_changed(self, names=None):
+        """Registers tensors again whose contents changed in a way torch does not count (raw-pointer writes, a collective into
+        them): the inference caches are rebuilt on the next call, the next training step packs by their new magnitude.  `names`: a
+        leaf name or a list of them (default: every parameter).  In-place torch ops on the tensors (`mul_`, `copy_`, an optimizer
+        of torch's own) need no call: they move the tensor's version counter, and the next call of this model sees it."""
+        names = list(self._tensors) if names is None else [names] if isinstance(names, str) else list(names)
+        return self.load_parameters({n: self._tensors[n] for n in names}, global_rows=False)
+
+    def _sync_parameters(self):
+        """Registers again every tensor whose version counter moved since it was registered: the tensors ARE the variables, and an
+        in-place edit of one leaves the prepared caches, the entity maximum and the training step's record of the dense weights'
+        magnitude stale.  (The library's own writes -- the training step, BN moving statistics -- go through raw pointers and do not
+        move the counters.)"""
+        vs = self._versions
+        changed = [n for n, t in self._tensors.items() if _version(t) != vs[n]]
+        if changed:
+            self.load_parameters({n: self._tensors[n] for n in changed}, global_rows=False)
 
     @property
     def variables(self):
@@ -205,6 +233,7 @@ class ConvE(object):
 
     def prepare(self):
         """coper_prepare: fold BN, evaluate the generators once per relation, build the MFMA images."""
+        self._sync_parameters()
         missing = [n for n in self._specs if n not in self._tensors]
         if missing:
             raise _lib.CoperError(2, "parameters never set: %s" % ", ".join(missing))
@@ -225,6 +254,7 @@ class ConvE(object):
         return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(self.device, non_blocking=True)
 
     def _need_prepared(self):
+        self._sync_parameters()
         if not self._prepared:
             self.prepare()
 
@@ -615,6 +645,7 @@ class ConvE(object):
 
     def ent_absmax(self) -> float:
         """The largest |ent_emb| element of the rows this handle holds (one pass over the shard, kept until the rows change)."""
+        self._sync_parameters()
         c = getattr(self, "_ent_absmax_cache", None)
         if c is None:
             t = self._tensors.get("ent_emb")
@@ -652,6 +683,7 @@ class ConvE(object):
         """coper_set_x3_ent_absmax: the largest |ent_emb| element of the WHOLE table, for a handle that holds a shard of it
         (sharding.py all-reduces it; load_parameters sets it when it is handed the whole table).  No-op in the f32 mode and
         when the value is the one already set; otherwise the handle is prepared again on its next use."""
+        self._sync_parameters()        # (an edit registered later would drop the hint again)
         if self.score_mode != "bf16x3" or getattr(self, "_x3_absmax", None) == float(absmax):
             return
         _lib.check(self._h, self._lib.coper_set_x3_ent_absmax(self._h, float(absmax)))
@@ -747,11 +779,13 @@ class ConvE(object):
         B, L = labels.shape
         if (lookup is not None and tuple(lookup.shape) != (B, L)) or e1.numel() != B or rel.numel() != B:
             raise ValueError("training batch: e1, rel [B]; lookup_values and e2_multi [B, L] (or e2_multi [B, num_ent] alone)")
+        self._sync_parameters()      # (the step packs the dense weights by the magnitude the last step left: include/coper_hip.h)
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_step(self._h, _ptr(e1), _ptr(rel), _ptr(lookup), _ptr(labels), B, L,
                                                            _ptr(self._train_loss), self._stream()))
         self._prepared = False       # caches are stale; the next inference call prepares again
         self._ent_absmax_cache = None
+        self._versions = {n: _version(t) for n, t in self._tensors.items()}
         return self._train_loss
 
     def train_forward(self, batch, want_predictions=False, want_h=False):
@@ -770,6 +804,7 @@ class ConvE(object):
         B, L = labels.shape
         if (lookup is not None and tuple(lookup.shape) != (B, L)) or e1.numel() != B or rel.numel() != B:
             raise ValueError("training batch: e1, rel [B]; lookup_values and e2_multi [B, L] (or e2_multi [B, num_ent] alone)")
+        self._sync_parameters()
         loss = torch.zeros(1, device=self.device, dtype=torch.float32)
         pred = torch.empty((B, L), device=self.device, dtype=torch.float32) if want_predictions else None
         hv = torch.empty((B, self.ent_emb_size), device=self.device, dtype=torch.float32) if want_h else None

@@ -109,7 +109,7 @@ class QueryShardedEvaluator(object):
 class _ChunkPlan(object):
     """Host-side plan of one chunk: who owns which row (step 1), which rank encodes which query (step 2).  Every rank derives
     the same plan from the replicated ids; all index tensors travel to the device in ONE pinned buffer / one copy."""
-    __slots__ = ("B", "cap1", "n_mine", "mine_ids", "cap2", "n_enc", "ints", "off", "dev", "split")
+    __slots__ = ("B", "cap1", "n_mine", "mine_ids", "cap2", "n_enc", "ints", "off", "dev", "split", "slot")
 
 
 class EntityShardedRanker(object):
@@ -161,7 +161,8 @@ class EntityShardedRanker(object):
         self.side_group = group
         if side_communicator and self.overlap and self.world > 1 and not self.emulated:
             self.side_group = dist.new_group(ranks=dist.get_process_group_ranks(group) if group is not None else None)
-        self._pins, self._pin_i = [None] * 4, 0
+        # the plans' pinned ring: slot i is rewritten only after the H2D copy that read it last has run (_pin_ev[i], recorded in _dev)
+        self._pins, self._pin_ev, self._pin_i = [None] * 4, [None] * 4, 0
         # one power of two for the entity planes of every shard (the x3 mode's logits are then the same bits whatever the layout):
         # agreed at construction, and again from the header rows of step 1 on every chunk (a shard whose weights were reloaded)
         self._absmax_ok = hasattr(scorer, "ent_absmax") and hasattr(scorer, "set_x3_ent_absmax")
@@ -252,11 +253,17 @@ class EntityShardedRanker(object):
         for name, a in parts:
             pl.off[name] = (n, n + len(a))
             n += len(a)
-        if self.cuda:       # one pinned buffer (a small ring: the copy of the plan before last may still be in flight), one H2D
+        if self.cuda:       # one pinned buffer (a small ring: the copies of the last plans may still be in flight), one H2D
             i = self._pin_i = (self._pin_i + 1) % len(self._pins)
+            if self._pin_ev[i] is not None:
+                # the copy that read this slot four plans ago: long done unless the host runs far ahead of the device (rank_stream
+                # syncs once per window at most, and not at all when nothing is audited)
+                self._pin_ev[i].synchronize()
+                self._pin_ev[i] = None
             if self._pins[i] is None or self._pins[i].numel() < max(1, n):
+                # (the outgrown buffer goes back to torch's pinned-memory cache, which keeps it until the copies that read it have run)
                 self._pins[i] = torch.empty(max(1, n) * 2, dtype=torch.int64).pin_memory()
-            pl.ints = self._pins[i][:n]
+            pl.ints, pl.slot = self._pins[i][:n], i
             host = pl.ints.numpy()
         else:
             pl.ints = torch.empty(n, dtype=torch.int64)
@@ -269,7 +276,13 @@ class EntityShardedRanker(object):
 
     def _dev(self, pl, name):
         if pl.dev is None:
-            pl.dev = pl.ints.to(self.device, non_blocking=True) if self.cuda else pl.ints
+            if self.cuda:
+                pl.dev = pl.ints.to(self.device, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))     # (the stream the copy went to: main, or the side stream)
+                self._pin_ev[pl.slot] = ev
+            else:
+                pl.dev = pl.ints
         lo, hi = pl.off[name]
         return pl.dev[lo:hi]
 

@@ -460,6 +460,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg);
  * magnitude of the dense weights, noted by the optimizer's pass as it writes them, is what the next step's operand packing scales
  * by).  A caller that changes parameter CONTENTS between steps by other means than this call registers the tensor again
  * (coper_set_param on the same pointer is enough; coper_amd.ConvE.load_parameters does) -- as coper_prepare asks for inference.
+ * coper_set_param with another pointer moves the variable there: later steps read and update the tensor registered last.
  * Ordering: to the caller the step is one sequence of launches on `stream`.  Inside, two stretches that do not depend on the chain
  * beside them (the scorer's backward; the projection gradient's product) run on streams of the training state's own, forked from
  * `stream` and joined to it by events before the call returns -- nothing of the step is left outside `stream`'s order. */
@@ -477,9 +478,10 @@ COPER_API int coper_train_forward(coper_handle* h, const int64_t* e1, const int6
                                   void* stream);
 /* Diagnostics: copies the (unclipped) gradient of the last step for a trainable leaf into `out` (device float
  * buffer of `cap` elements; may be NULL), returns its length in *n, and in *global_norm (optional, host) the
- * global gradient norm of the last step (synchronises).  Call it before anything regroups a batch by relation (an evaluation pass): the
- * looked-up dense table's rows of relations the last batch did not hold are not written by a step -- optimizer and norm skip them by the
- * batch's relation counts -- and are handed out as the zeros they stand for by those same counts. */
+ * global gradient norm of the last step (synchronises).  The looked-up dense table's rows of relations the last batch did not hold are
+ * not written by a step -- optimizer and norm skip them by the batch's relation counts -- and are handed out as the zeros they stand for
+ * by those same counts, which the step keeps a copy of: evaluation passes, coper_encode or coper_reserve in between do not change
+ * what this call returns. */
 COPER_API int coper_train_grad(coper_handle* h, const char* leaf_name, float* out, int64_t cap, int64_t* n,
                                double* global_norm, void* stream);
 

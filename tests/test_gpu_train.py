@@ -158,7 +158,9 @@ def test_train_step_matches_oracle_over_batch_shapes(name, B, L, train_stats):
     _train_step_case(name, train_stats, False, "n0.1", B=B, L=L, steps=2)
 
 
-def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3):
+def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3, edit=None):
+    """`edit(m, ref)`: a change of the variables made to both sides before the last step (tests/test_gpu_between_calls.py); the
+    oracle then restarts from the device's variables before every step, each held to the step-0 bounds."""
     from coper_amd.models import ConvE
     from oracle import coper_train_oracle as T
     md = dict(cdata._COMMON)
@@ -174,9 +176,11 @@ def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3):
     opt = T.AMSGrad(T.trainable_names(md), ref, lr=md["learning_rate"])
     # the wide and the random-shape cases restart the oracle from the device's variables before every step, so that each step is held to the
     # step-0 bounds (the other cases let the two trajectories run free and bound the Adam-amplified drift instead)
-    sync = name.endswith("_wide") or name.startswith("fuzz_")
+    sync = name.endswith("_wide") or name.startswith("fuzz_") or edit is not None
     for step in range(steps):
         batch = _batch(md, B, L, seed=100 + step)
+        if edit is not None and step == steps - 1:
+            edit(m, ref)
         if sync and step > 0:
             for k in ref:
                 ref[k] = m._tensors[k].cpu().numpy().reshape(np.shape(ref[k])).astype(np.float64)
