@@ -193,32 +193,16 @@ int devbuf_malloc(coper_handle* h, void** p, size_t bytes, const char* what) {
 // ---- grouping sets (coper_group_next) ----
 // the home set's views from its owners (null where an owner is empty)
 void group_home_views(coper_handle* h) {
-  int32_t* c = h->home.counts;
-  const int64_t r2 = h->dm.R + 2;
-  h->rel_count_buf[0] = c;
-  h->rel_count_buf[1] = c ? c + r2 : nullptr;
-  h->rel_cursor = c ? c + 2 * r2 : nullptr;
-  h->group_done = c ? c + 3 * r2 : nullptr;
+  const coper_handle::HomeSet& o = h->home;
   coper_handle::GroupSet& g = h->gset[0];
-  g.rel_count = c; g.rel_offset = h->home.rel_offset; g.perm = h->home.perm; g.inv_perm = h->home.inv_perm;
-  g.sorted_row = h->home.sorted_row; g.sorted_rid = h->home.sorted_rid; g.tiles = h->home.tiles; g.n_tiles = h->home.n_tiles;
-  g.x3m = h->home.x3m; g.fused_fin_dev = g.fin;
-  if (h->gcur == 0) group_use_set(h, 0);
-}
-
-void group_use_set(coper_handle* h, int i) {
-  const coper_handle::GroupSet& g = h->gset[i];
-  h->rel_count = g.rel_count; h->rel_offset = g.rel_offset; h->perm = g.perm; h->inv_perm = g.inv_perm; h->sorted_row = g.sorted_row;
-  h->sorted_rid = g.sorted_rid; h->tiles = g.tiles; h->n_tiles = g.n_tiles; h->x3m = g.x3m; h->fused_fin_dev = g.fused_fin_dev;
-  h->fused_fin_perm = g.fused_fin_perm;
-  h->gcur = i;
+  g.rel_count = o.counts; g.rel_offset = o.rel_offset; g.perm = o.perm; g.inv_perm = o.inv_perm;
+  g.sorted_row = o.sorted_row; g.sorted_rid = o.sorted_rid; g.tiles = o.tiles; g.n_tiles = o.n_tiles; g.x3m = o.x3m;
 }
 
 void group_sets_free(coper_handle* h) {
-  group_use_set(h, 0);
+  h->gcur = 0;
   for (int i = 1; i < 3; ++i) h->gset[i] = coper_handle::GroupSet();
   h->pipe.invalidate_grouping();
-  h->pass_chk = nullptr;
 }
 
 // sets 1 and 2 at the capacity of the workspace (which exists: the caller is a pass being enqueued), with their finalize constants
@@ -226,8 +210,6 @@ int group_sets_ensure(coper_handle* h, hipStream_t s) {
   if (h->gset[1].slab && h->gset[2].slab) return COPER_OK;
   const Dims& dm = h->dm;
   if (!h->home.x3m || h->ws_queries <= 0) return fail(h, COPER_ESTATE, "grouping sets: no workspace yet");
-  const int cur = h->gcur;
-  group_use_set(h, 0);
   const size_t cap = (size_t)h->ws_queries, r2 = (size_t)dm.R + 2, nt = 4 * (cap / 32 + (size_t)dm.R + 4);
   auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };      // (16-byte pieces)
   const size_t total = 2 * up4(r2) + 4 * up4(cap) + up4(nt) + 4 + (size_t)X3M_SLOTS + 2 * GROUP_CHK_WORDS;
@@ -249,9 +231,7 @@ int group_sets_ensure(coper_handle* h, hipStream_t s) {
     g.x3m = (float*)p; p += X3M_SLOTS;       // (a multiple of four words: the check words below are 8-byte aligned)
     g.chk = (int64_t*)p;
   }
-  int rc = fused_fin_update(h, s);
-  group_use_set(h, cur);
-  return rc;
+  return fused_fin_update(h, s);
 }
 
 // the workspace group, all at `cap` queries (the old buffers are freed as the new ones are allocated: no rise of the peak)
@@ -298,7 +278,7 @@ static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
   if (h->home.counts) {         // (the device counter of coper_stale_passes lives in the slab replaced below)
     int32_t v = 0;
-    COPER_HIP_TRY(h, hipMemcpy(&v, h->group_done + 2, sizeof v, hipMemcpyDeviceToHost));
+    COPER_HIP_TRY(h, hipMemcpy(&v, h->group_done() + 2, sizeof v, hipMemcpyDeviceToHost));
     h->stale_passes_host += v;
   }
   group_sets_free(h);           // (sized by the workspace; back on the home set before its arrays move)
@@ -547,7 +527,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   COPER_HIP_TRY(h, hipSetDevice(cfg.device));
   h->prepared = false;          // (until every derived buffer below exists again: a prepare that fails leaves a handle that refuses passes)
   int rc;
-  group_use_set(h, 0);          // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
+  h->gcur = 0;                  // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
   h->pipe.invalidate_grouping();
   if ((rc = h->conv_scale.alloc(h, dm.C, "conv_scale")) || (rc = h->conv_shift.alloc(h, dm.C, "conv_shift")) ||
       (rc = h->fc_scale.alloc(h, dm.d, "fc_scale")) || (rc = h->fc_shift.alloc(h, dm.d, "fc_shift")))
@@ -567,7 +547,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
     group_home_views(h);
     if (bad) return rc;
     COPER_HIP_TRY(h, hipMemsetAsync(h->x3s, 0, 4 * sizeof(int32_t), s));
-    COPER_HIP_TRY(h, hipMemsetAsync(h->x3m, 0, X3M_SLOTS * sizeof(float), s));
+    COPER_HIP_TRY(h, hipMemsetAsync(h->home.x3m, 0, X3M_SLOTS * sizeof(float), s));
     if ((rc = launch_band_consts(h, P("ent_emb"), P("pred_bias"), s))) return rc;
     {
       unsigned cb[BAND_NCONST];
@@ -701,7 +681,8 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
     const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
     if ((rc = h->Ef3.alloc(h, f3, "entity image"))) return rc;
     COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3 * sizeof(uint4), s));
-    if ((rc = launch_rows_to_frag_bf16(h, P("ent_emb"), dm.n_local, dm.n_eblk, h->Ef16_hi, h->Ef16_lo, h->Erm16_hi, h->Erm16_lo, h->Ef3,
+    PassCtx none;
+    if ((rc = launch_rows_to_frag_bf16(h, none, P("ent_emb"), dm.n_local, dm.n_eblk, h->Ef16_hi, h->Ef16_lo, h->Erm16_hi, h->Erm16_lo, h->Ef3,
                                        false, s)))
       return rc;
     if ((rc = score_bf16_kernels_init(h))) return rc;
@@ -774,7 +755,6 @@ COPER_API int coper_group_next(coper_handle* h, const int64_t* e1, const int64_t
   auto& g = h->pipe.gnext;
   g.e1 = have_e1_rows ? nullptr : e1; g.rel = rel; g.B = B; g.rows = have_e1_rows ? 1 : 0;
   g.pending = B > 0;
-  g.ride = false;
   return COPER_OK;
 }
 
@@ -794,7 +774,7 @@ static bool stream_is_capturing(hipStream_t s) {
 // grouping, conv and the dense layer up to the K-slice partials in z_part (everything of coper_encode but the finalize)
 // h_x3: where the x3 encoder may write finished h rows when its launch can finalize them itself (dense_fused_finalizes);
 // *finalized says whether it did (the caller then skips its finalize launch)
-static int encode_partials(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, const float* e1_rows, hipStream_t s,
+static int encode_partials(coper_handle* h, PassCtx& ctx, const int64_t* e1, const int64_t* rel, int64_t B, const float* e1_rows, hipStream_t s,
                            int* ksplit_out, float* h_out_f32_path, float* h_x3 = nullptr, bool* finalized = nullptr,
                            bool consume_prepared = false) {
   if (finalized) *finalized = false;
@@ -824,10 +804,9 @@ static int encode_partials(coper_handle* h, const int64_t* e1, const int64_t* re
   {
     int set = 0;
     pre = h->pipe.take_prepared(e1, rel, B, e1_rows ? 1 : 0, &set) && consume_prepared && h->gset[set].slab != nullptr && !stream_is_capturing(s);
-    group_use_set(h, pre ? set : 0);
-    h->pass_chk = pre ? h->gset[set].chk : nullptr;
+    h->gcur = pre ? set : 0;
+    if (pre) ctx.chk = h->gset[set].chk;
   }
-  h->pipe.post.here = false;
   if (!pre) {
     ScopedKernelTimer t(h, "group", s);
     if ((rc = launch_group_by_relation(h, e1, rel, e1_rows != nullptr, B, tq, s))) return rc;
@@ -840,10 +819,10 @@ static int encode_partials(coper_handle* h, const int64_t* e1, const int64_t* re
     h->pipe.gnext.pending = false;
     if (fused && want_group && !stream_is_capturing(s)) {
       if ((rc = group_sets_ensure(h, s))) return rc;
-      h->pipe.gnext.ride = true;
+      ctx.gnext_ride = true;
     }
     if (pre && h->pipe.post.n > 0) {       // the job that rides in the grouping launch otherwise
-      if (fused) h->pipe.post.here = true;
+      if (fused) ctx.post_here = true;
       else if (const int64_t pn = h->pipe.take_post()) {
         if ((rc = launch_copy_i32(h, h->pipe.post.src, pn, h->pipe.post.dst, s))) return rc;
       }
@@ -857,12 +836,12 @@ static int encode_partials(coper_handle* h, const int64_t* e1, const int64_t* re
     if (fused) {   // one launch serves every tile: conv, BN, ReLU and the dense layer (kernels_dense_fused_bf16.hip)
       ScopedKernelTimer t(h, "dense", s);
       if (finalized) *finalized = dense_fused_finalizes(h, ksplit, h_x3);
-      return launch_dense_fused_bf16(h, e1, rel, e1_rows, B, ksplit, h_x3, s);
+      return launch_dense_fused_bf16(h, ctx, e1, rel, e1_rows, B, ksplit, h_x3, s);
     }
-    if ((rc = launch_conv_bf16(h, e1, rel, e1_rows, B, false, s))) return rc;
+    if ((rc = launch_conv_bf16(h, e1, rel, e1_rows, B, s))) return rc;
     {
       ScopedKernelTimer t(h, "dense", s);
-      if ((rc = launch_dense_bf16(h, B, ksplit, false, s))) return rc;
+      if ((rc = launch_dense_bf16(h, B, ksplit, s))) return rc;
     }
     return COPER_OK;
   }
@@ -883,7 +862,8 @@ COPER_API int coper_encode(coper_handle* h, const int64_t* e1, const int64_t* re
   hipStream_t s = (hipStream_t)stream;
   int rc, ksplit = 1;
   bool finalized = false;
-  if ((rc = encode_partials(h, e1, rel, B, e1_rows, s, &ksplit, h_out, h_out, &finalized))) return rc;
+  PassCtx ctx;
+  if ((rc = encode_partials(h, ctx, e1, rel, B, e1_rows, s, &ksplit, h_out, h_out, &finalized))) return rc;
   if (h->enc_bf16 && !finalized) return launch_dense_finalize(h, rel, B, ksplit, h_out, s);
   return COPER_OK;
 }
@@ -912,21 +892,26 @@ COPER_API int coper_score_lookup(coper_handle* h, const float* hvec, const int32
   return launch_score_lookup(h, hvec, lookup, B, L, out, s);
 }
 
-COPER_API int coper_target_scores(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* tgt, void* stream) {
-  COPER_REQUIRE_PREPARED(h);
-  COPER_REQUIRE_SCORER(h);
+// the bodies of coper_target_scores and coper_rank_counts: coper_rank and coper_encode_rank run them with the context of their pass
+static int target_scores_body(coper_handle* h, PassCtx& ctx, const float* hvec, const int64_t* e2, int64_t B, float* tgt, hipStream_t s) {
   if (B == 0) return COPER_OK;
   if (!hvec || !e2 || !tgt || B < 0) return fail(h, COPER_EINVAL, "coper_target_scores: bad argument");
-  hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = ensure_workspace(h, B, 0, s))) return rc;
   if (h->cfg.score_mode != COPER_SCORE_F32) {
-    if ((rc = launch_pair_targets_bf16x3(h, hvec, e2, B, tgt, s))) return rc;
+    if ((rc = launch_pair_targets_bf16x3(h, ctx, hvec, e2, B, tgt, s))) return rc;
     return launch_exact_targets(h, hvec, e2, B, tgt + B, s);     // the fp32-chain logit: what the exact band compares against
   }
   if ((rc = launch_pair_targets(h, hvec, e2, B, tgt, s))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(tgt + B, tgt, sizeof(float) * B, hipMemcpyDeviceToDevice, s));   // the mode's logit IS the chain's
   return COPER_OK;
+}
+
+COPER_API int coper_target_scores(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* tgt, void* stream) {
+  COPER_REQUIRE_PREPARED(h);
+  COPER_REQUIRE_SCORER(h);
+  PassCtx ctx;
+  return target_scores_body(h, ctx, hvec, e2, B, tgt, (hipStream_t)stream);
 }
 
 COPER_API int coper_score_rows(coper_handle* h, const float* hvec, const float* rows, const float* bias, int64_t B, float* out,
@@ -937,18 +922,15 @@ COPER_API int coper_score_rows(coper_handle* h, const float* hvec, const float* 
   return launch_exact_rows(h, hvec, rows, bias, B, out, (hipStream_t)stream);     // (the chain is the f32 mode's own logit)
 }
 
-COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2,
-                      const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
-                      int32_t* n_greater, int32_t* n_equal, float* topk_val, int64_t* topk_idx, void* stream) {
-  COPER_REQUIRE_PREPARED(h);
-  COPER_REQUIRE_SCORER(h);
+static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt, const int64_t* e2,
+                            const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
+                            int32_t* n_greater, int32_t* n_equal, float* topk_val, int64_t* topk_idx, hipStream_t s) {
   if (B == 0) return COPER_OK;
   if (!hvec || !tgt || !e2 || !filt_indptr || !n_greater || B < 0 || filt_nnz < 0 ||
       (filt_nnz > 0 && !filt_idx))
     return fail(h, COPER_EINVAL, "coper_rank_counts: bad argument");
   if (k < 0 || k > 1024 || (k > 0 && (!topk_val || !topk_idx)))
     return fail(h, COPER_EINVAL, "coper_rank_counts: bad top-k arguments (0 <= k <= 1024)");
-  hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, false, s))) return rc;
   // 0 < k <= COPER_TOPK_PRUNED_MAX (128): the count pass also writes block maxima and the top-k is selected from the few blocks that can
@@ -980,17 +962,17 @@ COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float*
     }
   }
   if (h->cfg.score_mode != COPER_SCORE_F32) {
-    if (!(h->trust_packed && h->packed_hvec == hvec && h->packed_B == B) && (rc = launch_pack_h_bf16(h, hvec, B, s))) return rc;
+    if (!(ctx.packed_hvec == hvec && ctx.packed_B == B) && (rc = launch_pack_h_bf16(h, ctx, hvec, B, s))) return rc;
     COPER_DBG_SYNC(h, s, "pack_h");
     // the exact band of every query around the mode's target logit; comparisons inside it are decided against tgt[B ..]
     if ((rc = launch_band_setup(h, hvec, tgt, B, s))) return rc;
     COPER_DBG_SYNC(h, s, "band_setup");
     if (pruned)
-      rc = launch_topk_pruned_bf16x3(h, hvec, tgt + B, e2, filt_indptr, filt_idx, filt_nnz, B, k, n_greater, n_equal, topk_val, topk_idx, s);
+      rc = launch_topk_pruned_bf16x3(h, ctx, hvec, tgt + B, e2, filt_indptr, filt_idx, filt_nnz, B, k, n_greater, n_equal, topk_val, topk_idx, s);
     else
-      rc = launch_score_count_bf16x3(h, hvec, tgt + B, e2, filt_indptr, filt_idx, B, n_greater, n_equal, s);
+      rc = launch_score_count_bf16x3(h, ctx, hvec, tgt + B, e2, filt_indptr, filt_idx, B, n_greater, n_equal, s);
     if (rc) return rc;
-    if ((rc = launch_filter_correct_bf16x3(h, e2, filt_indptr, filt_idx, filt_nnz, B, n_greater, s))) return rc;
+    if ((rc = launch_filter_correct_bf16x3(h, ctx, e2, filt_indptr, filt_idx, filt_nnz, B, n_greater, s))) return rc;
     COPER_DBG_SYNC(h, s, "filter_correct");
   } else {
     if (pruned)
@@ -1016,6 +998,16 @@ COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float*
   return COPER_OK;
 }
 
+COPER_API int coper_rank_counts(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2,
+                      const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
+                      int32_t* n_greater, int32_t* n_equal, float* topk_val, int64_t* topk_idx, void* stream) {
+  COPER_REQUIRE_PREPARED(h);
+  COPER_REQUIRE_SCORER(h);
+  PassCtx ctx;
+  return rank_counts_body(h, ctx, hvec, tgt, e2, filt_indptr, filt_idx, filt_nnz, B, k, n_greater, n_equal, topk_val, topk_idx,
+                          (hipStream_t)stream);
+}
+
 COPER_API int coper_rank(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* filt_indptr,
                const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t* ranks, int32_t* n_equal, void* stream) {
   COPER_REQUIRE_PREPARED(h);
@@ -1027,27 +1019,17 @@ COPER_API int coper_rank(coper_handle* h, const float* hvec, const int64_t* e2, 
   int rc;
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, false, s))) return rc;
   const bool direct = h->cfg.score_mode != COPER_SCORE_F32;
+  PassCtx ctx;
   if (direct) {
     // bf16x3: n_greater accumulates straight into `ranks` started from 1 (no finish launch), preset by the packing
-    // launch of the target pass (no zeroing launch)
-    h->count_base = 1;
-    h->preset_cnt = ranks;
-    h->preset_eq = n_equal;
+    // launch of the target pass (no zeroing launch); the target pass expands the CSR rows for the filter pass.  The count
+    // pass reuses the target pass's query planes: same hvec, same stream, no caller code in between.
+    ctx.cnt = ranks; ctx.eq = n_equal; ctx.base = 1; ctx.csr = filt_indptr;
   }
-  if (direct) h->expand_indptr = filt_indptr;   // the target pass expands the CSR rows for the filter pass
-  rc = coper_target_scores(h, hvec, e2, B, h->tgt_ws, stream);
-  h->expand_indptr = nullptr;
-  h->preset_cnt = nullptr;
-  h->preset_eq = nullptr;
-  if (rc) { h->count_base = 0; h->counts_preset = nullptr; return rc; }
+  if ((rc = target_scores_body(h, ctx, hvec, e2, B, h->tgt_ws, s))) return rc;
   int32_t* ng = direct ? ranks : h->cnt_ws;
   int32_t* ne = n_equal;  // NULL: ties are not counted
-  h->trust_packed = true;  // same hvec, same stream, no caller code in between: the packing of target_scores is valid
-  rc = coper_rank_counts(h, hvec, h->tgt_ws, e2, filt_indptr, filt_idx, filt_nnz, B, 0, ng, ne, nullptr, nullptr, stream);
-  h->trust_packed = false;
-  h->count_base = 0;
-  h->counts_preset = nullptr;
-  if (rc) return rc;
+  if ((rc = rank_counts_body(h, ctx, hvec, h->tgt_ws, e2, filt_indptr, filt_idx, filt_nnz, B, 0, ng, ne, nullptr, nullptr, s))) return rc;
   if (direct) return COPER_OK;
   return launch_finish_ranks(h, ng, B, ranks, s);
 }
@@ -1065,7 +1047,6 @@ COPER_API int coper_encode_rank(coper_handle* h, const int64_t* e1, const int64_
   if (h->dm.n_local != h->dm.E) return fail(h, COPER_ESTATE, "coper_encode_rank needs the whole table (see coper_rank)");
   hipStream_t s = (hipStream_t)stream;
   int rc, ksplit = 1;
-  struct ClearChk { coper_handle* h; ~ClearChk() { h->pass_chk = nullptr; } } clear_chk{h};   // (the guard's verdict belongs to this call's launches only)
   // the embedding is needed in fp32 either way: the fp32-exact mode scores from it, the bf16x3 mode's exact band re-scores from it
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, h_out == nullptr, s))) return rc;
   float* hv = h_out ? h_out : h->h_ws;
@@ -1077,39 +1058,23 @@ COPER_API int coper_encode_rank(coper_handle* h, const int64_t* e1, const int64_
   // bf16x3: the finalize writes h straight into the planes the rank kernels read (and the fp32 rows the exact band needs) and
   // presets the counters, which accumulate into `ranks` from 1: no pack, zero or finish launch
   bool finalized = false;
-  if ((rc = encode_partials(h, e1, rel, B, e1_rows, s, &ksplit, nullptr, hv, &finalized, true))) return rc;
+  PassCtx ctx;
+  if ((rc = encode_partials(h, ctx, e1, rel, B, e1_rows, s, &ksplit, nullptr, hv, &finalized, true))) return rc;
   if (!n_equal && tail_fused_supported(h)) {
     // ranks only (what the reference computes): finalize, targets, the band and the filter correction in ONE launch
     // (kernels_tail_bf16.hip) that leaves ranks = 1 - (known answers above the band); the count kernel and the exact
     // decision of the band add to it
     {
       ScopedKernelTimer t(h, "tail", s);
-      if ((rc = launch_finalize_targets_filter_bf16x3(h, B, finalized ? 0 : ksplit, hv, e2, filt_indptr, filt_idx, filt_nnz, h->tgt_ws, ranks, s))) return rc;
+      if ((rc = launch_finalize_targets_filter_bf16x3(h, ctx, B, finalized ? 0 : ksplit, hv, e2, filt_indptr, filt_idx, filt_nnz, h->tgt_ws, ranks, s))) return rc;
     }
-    h->counts_preset = ranks;
-    h->count_base = 1;
-    rc = launch_score_count_bf16x3(h, hv, nullptr, e2, filt_indptr, filt_idx, B, ranks, nullptr, s);
-    h->count_base = 0;
-    h->counts_preset = nullptr;
-    h->excess_pending = false;     // (consumed by the first band launch; a failed launch must not leave it to a later pass)
-    return rc;
+    return launch_score_count_bf16x3(h, ctx, hv, nullptr, e2, filt_indptr, filt_idx, B, ranks, nullptr, s);
   }
-  if ((rc = launch_dense_finalize_pack(h, B, finalized ? 0 : ksplit, hv, ranks, 1, n_equal, s))) return rc;
-  h->expand_indptr = filt_indptr;
-  rc = launch_pair_targets_packed_bf16x3(h, e2, B, h->tgt_ws, s);
-  h->expand_indptr = nullptr;
-  if (rc) return rc;
+  ctx.cnt = ranks; ctx.eq = n_equal; ctx.base = 1; ctx.csr = filt_indptr;   // (as coper_rank)
+  if ((rc = launch_dense_finalize_pack(h, ctx, B, finalized ? 0 : ksplit, hv, s))) return rc;
+  if ((rc = launch_pair_targets_packed_bf16x3(h, ctx, e2, B, h->tgt_ws, s))) return rc;
   if ((rc = launch_exact_targets(h, hv, e2, B, h->tgt_ws + B, s))) return rc;
-  h->packed_hvec = hv;
-  h->packed_B = B;
-  h->trust_packed = true;
-  h->count_base = 1;
-  h->counts_preset = ranks;
-  rc = coper_rank_counts(h, hv, h->tgt_ws, e2, filt_indptr, filt_idx, filt_nnz, B, 0, ranks, n_equal, nullptr, nullptr, stream);
-  h->trust_packed = false;
-  h->count_base = 0;
-  h->counts_preset = nullptr;
-  return rc;
+  return rank_counts_body(h, ctx, hv, h->tgt_ws, e2, filt_indptr, filt_idx, filt_nnz, B, 0, ranks, n_equal, nullptr, nullptr, s);
 }
 
 COPER_API int coper_band_audit(coper_handle* h, int32_t reset, float* max_ratio, int64_t* n_pairs, void* stream) {
@@ -1363,8 +1328,8 @@ COPER_API int coper_stale_passes(coper_handle* h, int64_t* n_passes, void* strea
   if (!h->home.counts) return COPER_OK;
   hipStream_t s = (hipStream_t)stream;
   int32_t v = 0;
-  COPER_HIP_TRY(h, hipMemcpyAsync(&v, h->group_done + 2, sizeof v, hipMemcpyDeviceToHost, s));
-  COPER_HIP_TRY(h, hipMemsetAsync(h->group_done + 2, 0, sizeof v, s));
+  COPER_HIP_TRY(h, hipMemcpyAsync(&v, h->group_done() + 2, sizeof v, hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(h->group_done() + 2, 0, sizeof v, s));
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
   *n_passes += v;
   return COPER_OK;
@@ -1373,9 +1338,10 @@ COPER_API int coper_stale_passes(coper_handle* h, int64_t* n_passes, void* strea
 COPER_API int coper_check_ids(coper_handle* h, int64_t* n_bad, void* stream) {
   if (!h || !n_bad) return COPER_EINVAL;
   *n_bad = 0;
-  if (!h->rel_count) return COPER_OK;
+  const int32_t* counts = h->grouping().rel_count;
+  if (!counts) return COPER_OK;
   int32_t v = 0;
-  COPER_HIP_TRY(h, hipMemcpyAsync(&v, h->rel_count + h->dm.R + 1, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  COPER_HIP_TRY(h, hipMemcpyAsync(&v, counts + h->dm.R + 1, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
   COPER_HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
   *n_bad = v;
   return COPER_OK;

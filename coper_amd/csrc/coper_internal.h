@@ -198,43 +198,54 @@ struct coper_handle {
   float x3_ent_absmax = 0.f;         //   the maximum it was chosen from (the shard's, or coper_config.x3_ent_absmax)
   // coper_group_next: grouping arrays in sets.  Set 0 is HOME (the owners in `home`: every pass that groups itself, and every captured
   // graph, uses it); sets 1 and 2 are written by the grouping role of a fused encoder launch for the NEXT pass while the running
-  // pass reads its own.  The fields perm / inv_perm / ... / x3m / fused_fin_dev always name the set of the pass being enqueued.
+  // pass reads its own.  grouping() is the set of the pass being enqueued.
   struct HomeSet {
-    coper::DevBuf<int32_t> counts;   // [3 (R+2) + 4]: rel_count_buf[0] | rel_count_buf[1] | rel_cursor | group_done (ensure_workspace)
+    coper::DevBuf<int32_t> counts;   // [3 (R+2) + 4]: rel_count of set 0 | rel_count_acc() | rel_cursor() | group_done() (ensure_workspace)
     coper::DevBuf<int32_t> rel_offset, perm, inv_perm, sorted_row, sorted_rid, tiles, n_tiles;
-    coper::DevBuf<float> x3m;        // (allocated by coper_prepare)
+    coper::DevBuf<float> x3m;        // [X3M_SLOTS] per-block maxima of the h rows being packed (bf16x3_chain.h; allocated by coper_prepare)
   } home;
   struct GroupSet {
     coper::DevBuf<int32_t> slab;     // sets 1, 2: one allocation; set 0: empty (its arrays are `home`)
-    coper::DevBuf<char> fin;         // the set's FusedFinConst (fused_fin_update)
-    // views: into slab, or into `home` and fin for set 0 (group_home_views)
-    int32_t* rel_count = nullptr; int32_t* rel_offset = nullptr; int32_t* perm = nullptr; int32_t* inv_perm = nullptr;
-    int32_t* sorted_row = nullptr; int32_t* sorted_rid = nullptr; int32_t* tiles = nullptr; int32_t* n_tiles = nullptr;
-    float* x3m = nullptr; void* fused_fin_dev = nullptr; const int32_t* fused_fin_perm = nullptr;
+    coper::DevBuf<char> fin;         // the set's FusedFinConst: the fused encoder's finalize constants (fused_fin_update)
+    // views: into slab, or into `home` for set 0 (group_home_views)
+    int32_t* rel_count = nullptr;    // [R+2] counts of the LAST grouping call (+ the out-of-range counter at R+1)
+    int32_t* rel_offset = nullptr;   // [R+1]
+    int32_t* perm = nullptr;         // [B] sorted position -> query
+    int32_t* inv_perm = nullptr;     // [B] query -> sorted position
+    int32_t* sorted_row = nullptr;   // [B] sorted position -> local entity row of e1 (or the e1_rows row), -1 = not on this shard
+    int32_t* sorted_rid = nullptr;   // [B] sorted position -> validated relation id
+    int32_t* tiles = nullptr;        // [T_max*4] (rel, start, n, pad)
+    int32_t* n_tiles = nullptr;      // [2] #small tiles, #big 16-query blocks
+    float* x3m = nullptr;
+    const int32_t* fused_fin_perm = nullptr;   // the perm `fin` was written for (the workspace generation)
     int64_t* chk = nullptr;          // sets 1, 2: [GROUP_CHK_WORDS] what the grouping role sorted (group_body.h: the guard of a prepared grouping)
   } gset[3];
-  int gcur = 0;                      // the set the fields name now
+  int gcur = 0;                      // the set of the pass being enqueued
+  const GroupSet& grouping() const { return gset[gcur]; }
+  // views into home.counts (null until the workspace exists)
+  int32_t* counts_part(int i) const { return home.counts ? home.counts.get() + i * (dm.R + 2) : nullptr; }
+  int32_t* rel_count_acc() const { return counts_part(1); }   // [R+2] the accumulation buffer of k_rel_hist_scan (zero between calls)
+  int32_t* rel_cursor() const { return counts_part(2); }      // [R]
+  int32_t* group_done() const { return counts_part(3); }      // ticket counter of the histogram launch (its last block runs the scan)
   // The jobs a host registers for a LATER launch of this handle, and the grouping a launch prepared ahead: ONE owner, one
   // invalidation rule (the drop rules used to be spread over five places).
   //   stage  (coper_stage_ids_next): a batch to bring in beside the next fused encoder launch            n > 0: pending
   //   post   (coper_post_i32_next):  int32 results to copy out beside the next pass's first launch       n > 0: pending
   //   gnext  (coper_group_next):     id arrays of the pass AFTER the next one, to be sorted inside the next fused encoder launch
   //   gdone: a grouping launched ahead into set `set`; the pass that comes with exactly these pointers consumes it -- and CHECKS it
-  //          on the device against the live ids (pass_chk below)
+  //          on the device against the live ids (PassCtx::chk)
   // Lifetimes: stage / post name buffers the caller owns and stay pending until a launch carries them (an eager pass, or post_flush /
   // a launch of their own where no launch can carry them); gnext is for the NEXT encode / encode_rank call only; gdone is for the
   // call after that only.  invalidate_grouping() -- coper_prepare, a training step, a growing workspace, freed grouping sets -- drops
   // gnext and gdone together; nothing else does.
   struct PassPipeline {
     struct { const int32_t* src = nullptr; int64_t n = 0; int64_t* dst = nullptr; } stage;
-    struct { const int32_t* src = nullptr; int64_t n = 0; int32_t* dst = nullptr;
-             bool here = false; } post;  // here: the pass being enqueued was grouped ahead, its fused encoder launch carries the job
+    struct { const int32_t* src = nullptr; int64_t n = 0; int32_t* dst = nullptr; } post;
     struct { const int64_t* e1 = nullptr; const int64_t* rel = nullptr; int64_t B = 0; int rows = 0;
-             bool pending = false;       // registered, not yet launched
-             bool ride = false; } gnext; // the fused encoder launch being enqueued carries it (sets 1, 2 are allocated)
+             bool pending = false; } gnext;   // pending: registered, not yet launched
     struct { const int64_t* e1 = nullptr; const int64_t* rel = nullptr; int64_t B = 0; int rows = 0;
              bool done = false; int set = 0; } gdone;
-    void invalidate_grouping() { gnext.pending = false; gnext.ride = false; gdone.done = false; }
+    void invalidate_grouping() { gnext.pending = false; gdone.done = false; }
     // the next call's view of a grouping prepared ahead: consumed (true) or dropped -- never kept for a later call
     bool take_prepared(const int64_t* e1, const int64_t* rel, int64_t B, int rows, int* set) {
       const bool hit = gdone.done && gdone.rel == rel && gdone.e1 == (rows ? nullptr : e1) && gdone.B == B && gdone.rows == rows;
@@ -245,35 +256,17 @@ struct coper_handle {
     int64_t take_stage() { const int64_t n = stage.n; stage.n = 0; return n; }
     int64_t take_post() { const int64_t n = post.n; post.n = 0; return n; }
   } pipe;
-  // the pass being enqueued runs on a grouping prepared ahead: the set's check words (its tiles compare the live ids with what was
-  // sorted; the kernels that preset the rank counters read the verdict); nullptr: the pass grouped itself
-  int64_t* pass_chk = nullptr;
-  int64_t stale_passes_host = 0;     // coper_stale_passes: what the device counter (group_done + 2) held when a growing workspace replaced it
-  void* fused_fin_dev = nullptr;     // view: FusedFinConst (kernels_dense_fused_bf16.hip): the fused encoder's finalize constants, in device memory
-  const int32_t* fused_fin_perm = nullptr;   //   the workspace generation they were written for
+  int64_t stale_passes_host = 0;     // coper_stale_passes: what the device counter (group_done() + 2) held when a growing workspace replaced it
   coper::DevBuf<int32_t> w_exp;      // [R or 1] e_W per relation id: the dense-weight planes hold W_r 2^e_W (split16.h; prepare)
   int w_div = 1, w_rem = 0;          // coper_config.rel_mod_*: the weight planes hold the relations r with r % w_div == w_rem, relation r at slot r / w_div
   int x_exp = 0;                     // e_x: the conv activations enter the dense layer as x 2^e_x (from a bound; prepare)
   coper::DevBuf<int32_t> x3s;        // [4] the packed batch's exponents: [0] e_h, [1] e_E + e_h (bf16x3_chain.h)
-  float* x3m = nullptr;              // view: [X3M_SLOTS] per-block maxima of the h rows being packed (bf16x3_chain.h)
   coper::DevBuf<float> ctx_tmp[2];   // generator hidden activations
 
   // ---- workspace (owned, grown lazily) ----
   int64_t ws_queries = 0;         // the capacity of the workspace group of ensure_workspace: 0 while any of it is missing
   int64_t ws_nnz = 0;
   int ws_ksplit = 0;
-  // views of the set being enqueued (gset) and into home.counts
-  int32_t* rel_count = nullptr;   // [R+2] counts of the LAST grouping call (+ the out-of-range counter at R+1) = rel_count_buf[0]
-  int32_t* rel_count_buf[2] = {nullptr, nullptr};   // [0] the published counts; [1] the accumulation buffer of k_rel_hist_scan (zero between calls)
-  int32_t* group_done = nullptr;  // ticket counter of the histogram launch (its last block runs the scan)
-  int32_t* rel_offset = nullptr;  // [R+1]
-  int32_t* rel_cursor = nullptr;  // [R]
-  int32_t* perm = nullptr;        // [B] sorted position -> query
-  int32_t* inv_perm = nullptr;    // [B] query -> sorted position
-  int32_t* sorted_row = nullptr;  // [B] sorted position -> local entity row of e1 (or the e1_rows row), -1 = not on this shard
-  int32_t* sorted_rid = nullptr;  // [B] sorted position -> validated relation id
-  int32_t* tiles = nullptr;       // [T_max*4] (rel, start, n, pad)
-  int32_t* n_tiles = nullptr;     // [2] #small tiles, #big 16-query blocks
   coper::DevBuf<int32_t> blk_off; // [R+1] exclusive scan of the big groups' block counts
   coper::DevBuf<float> x_sorted;  // [B, F_pad]
   coper::DevBuf<float> z_part;    // [ksplit, B, d_pad16]
@@ -301,27 +294,14 @@ struct coper_handle {
   coper::DevBuf<float> tband_ws;        // [B] float2 {t_lo, t_hi}: the exact band around the mode's target logit
   coper::DevBuf<float> tgtx_ws;         // [B] exact-chain targets of the two-call flows
   coper::DevBuf<char> mask_ws;          // band bits of one count launch (kernels_score3_bf16.hip)
-  const float* packed_hvec = nullptr;   // view: what hfrag16 currently holds (only trusted inside coper_rank)
-  int64_t packed_B = 0;
-  bool trust_packed = false;
   coper::DevBuf<int32_t> row_of_ws;     // bf16x3: CSR entry -> query row [nnz]
-  bool excess_pending = false;    // the next band launch also runs the excess role (kernels_score3_bf16.hip), with
-  alignas(8) unsigned char excess_args[128] = {};   //   these FilterArgs
   coper::DevBuf<int32_t> heavy_ws;      // fused tail: [0] number of listed blocks, [1] finished workgroups, [2..] 32-query blocks whose CSR entries
                                         //   exceed what their workgroup corrects itself (k_filter_excess_bf16x3); zero between passes
   coper::DevBuf<float> hfrag_ws;        // h re-packed in MFMA-fragment order [ceil(B/128)*4][KS][64] float4
   int num_cus = 256;
   void* train = nullptr;          // coper::TrainState (coper_train.hip)
-  // coper_rank only: the counters accumulate straight into `ranks` (base 1) and are preset by the packing launch
-  int32_t count_base = 0;
-  int32_t* preset_cnt = nullptr;  // view, request: the next pack launch presets these [B] counters (and preset_eq to 0)
-  int32_t* preset_eq = nullptr;
-  const int64_t* expand_indptr = nullptr;      // view, request: the next target pass also writes row_of_ws for this CSR
-  const int64_t* rows_expanded_for = nullptr;  // done: row_of_ws holds the row ids of this CSR
-  const int32_t* counts_preset = nullptr;  // done: the next score_count on this buffer skips its own zeroing
   bool dense_attr_done = false;
   bool fused_attr_done = false;
-  bool dense_small_only = false;  // set per launch: tiles above 32 queries go to the fused conv + dense kernel
 
   bool profile = false;
   std::map<std::string, coper::Timer> timers;
@@ -329,6 +309,36 @@ struct coper_handle {
 };
 
 namespace coper {
+
+struct FilterArgs {          // the filter role's view of a pass (queries of one count launch: all pointers at its first query)
+  const float* hvec; const uint4* Ehi; const uint4* Elo; const float* bias_pad; const int64_t* e2; const int64_t* indptr;
+  const int64_t* idx; const float2* tband; int32_t* ranks; int32_t* heavy; const int32_t* x3s; int64_t B, n_local; int d;
+};
+
+// What the launches of one API call hand each other.  It lives on the entry point's stack and is passed to the launch helpers of
+// the pass; a helper called outside a ranking pass gets a default one.  coper_handle holds only what outlives a call.
+struct PassCtx {
+  // coper_rank / coper_encode_rank: the pack launch presets the [B] rank counters cnt to base (and eq to 0), so n_greater
+  // accumulates straight into `ranks` from 1; preset: they are, and the count pass on cnt skips its zeroing launch
+  int32_t* cnt = nullptr;
+  int32_t* eq = nullptr;
+  int32_t base = 0;
+  bool preset = false;
+  // the target pass also writes row_of_ws for this CSR; expanded: it did, and the filter correction reads them
+  const int64_t* csr = nullptr;
+  bool expanded = false;
+  // what the query planes were packed from in this call (the count pass of the same call reuses them)
+  const float* packed_hvec = nullptr;
+  int64_t packed_B = 0;
+  // the filter-excess role, deferred to the next band launch (kernels_score3_bf16.hip)
+  bool excess_pending = false;
+  FilterArgs excess = {};
+  // the pass runs on a grouping prepared ahead: the set's check words (its tiles compare the live ids with what was sorted; the
+  // kernels that preset the rank counters read the verdict); nullptr: the pass grouped itself
+  int64_t* chk = nullptr;
+  bool post_here = false;    // pipe.post rides in the fused encoder launch (the pass was grouped ahead: no grouping launch carries it)
+  bool gnext_ride = false;   // pipe.gnext rides in the fused encoder launch (sets 1, 2 are allocated)
+};
 
 int fail(coper_handle* h, int code, const std::string& msg);
 void train_destroy(coper_handle* h);   // coper_train.hip
@@ -386,18 +396,18 @@ int launch_score_lookup(coper_handle* h, const float* hvec, const int32_t* looku
 int launch_finish_ranks(coper_handle* h, const int32_t* ng, int64_t B, int32_t* ranks, hipStream_t s);
 int score_kernels_init(coper_handle* h);
 // kernels_score_bf16.hip (COPER_SCORE_BF16X3)
-int launch_rows_to_frag_bf16(coper_handle* h, const float* src, int64_t n_rows, int64_t n_blk, uint4* hi, uint4* lo,
+int launch_rows_to_frag_bf16(coper_handle* h, PassCtx& ctx, const float* src, int64_t n_rows, int64_t n_blk, uint4* hi, uint4* lo,
                              uint4* rm_hi, uint4* rm_lo, uint4* f3, bool query_side, hipStream_t s);
-int launch_pack_h_bf16(coper_handle* h, const float* hvec, int64_t B, hipStream_t s);
+int launch_pack_h_bf16(coper_handle* h, PassCtx& ctx, const float* hvec, int64_t B, hipStream_t s);
 int launch_absmax_publish(coper_handle* h, const float* src, int64_t n, hipStream_t s);
-int launch_score_count_bf16x3(coper_handle* h, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
+int launch_score_count_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
                               const int64_t* idx, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s);
 int launch_score_all_bf16x3(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s);
-int launch_pair_targets_bf16x3(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* tgt,
+int launch_pair_targets_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const int64_t* e2, int64_t B, float* tgt,
                                hipStream_t s);
 int launch_score_lookup_bf16x3(coper_handle* h, const float* hvec, const int32_t* lookup, int64_t B, int64_t L,
                                float* out, hipStream_t s);
-int launch_filter_correct_bf16x3(coper_handle* h, const int64_t* e2, const int64_t* indptr, const int64_t* idx, int64_t nnz,
+int launch_filter_correct_bf16x3(coper_handle* h, const PassCtx& ctx, const int64_t* e2, const int64_t* indptr, const int64_t* idx, int64_t nnz,
                                  int64_t B, int32_t* ng, hipStream_t s);
 int score_bf16_kernels_init(coper_handle* h);
 // queries whose block maxima are held at a time: at most `cap_floats` (1/32 of the device memory, at least 1 GiB;
@@ -442,9 +452,9 @@ inline int topk_expand(const coper_handle* h) {
 }
 inline int64_t topk_gm_rows(const coper_handle* h) { return h->dm.n_eblk / topk_expand(h); }     // rows of gmax (n_eblk is a multiple of 16)
 inline size_t topk_sorted_cap(int64_t n_eblk, int64_t T) { return (size_t)((T + 31 * (n_eblk < T ? n_eblk : T) + 31) / 32 * 32); }
-void score_count_begin_bf16x3(coper_handle* h, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s);
+void score_count_begin_bf16x3(const PassCtx& ctx, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s);
 // kernels_score3_bf16.hip: the count kernel (16x16x32, software-pipelined, one wave per SIMD) and the exact band
-int score_count3_chunk_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
+int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s);
 size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc);
@@ -455,10 +465,10 @@ int launch_exact_rows(coper_handle* h, const float* hvec, const float* rows, con
 float band_kappa(const coper_handle* h);
 // kernels_tail_bf16.hip: finalize + targets + filter correction of a ranking pass in one launch
 bool tail_fused_supported(const coper_handle* h);
-int launch_finalize_targets_filter_bf16x3(coper_handle* h, int64_t B, int ksplit, float* h_out, const int64_t* e2, const int64_t* indptr,
+int launch_finalize_targets_filter_bf16x3(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, const int64_t* e2, const int64_t* indptr,
                                           const int64_t* idx, int64_t nnz, float* tgt, int32_t* ranks, hipStream_t s);
 int launch_finalize_h_publish(coper_handle* h, int64_t B, int ksplit, float* h_out, hipStream_t s);
-int launch_filter_excess_bf16x3(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
+int launch_filter_excess_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
                                 int64_t nnz, int64_t B, int32_t* ranks, bool defer, hipStream_t s);
 void score_count_begin_f32(coper_handle* h, const float* hvec, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s);
 int score_count_chunk_f32(coper_handle* h, int64_t q0, int64_t Bc, const float* tgt, int32_t* ng, int32_t* ne, float* gmax,
@@ -468,7 +478,7 @@ int launch_topk_score_blocks_f32(coper_handle* h, const float* hvec, int64_t T, 
 int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
                            const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
                            int64_t* topk_idx, hipStream_t s);
-int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
+int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
                               const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
                               int64_t* topk_idx, hipStream_t s);
 // kernels_encode_bf16.hip
@@ -484,23 +494,20 @@ __host__ __device__ inline int64_t w16_ks_stride_n(int64_t ks32n) {
   return ks32n | 1;
 }
 inline int64_t w16_ks_stride(const Dims& dm) { return w16_ks_stride_n(dm.F_pad / 32); }
-int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
-                     bool skip_big, hipStream_t s);
-int launch_dense_bf16(coper_handle* h, int64_t B, int nslices, bool small_only, hipStream_t s);
+int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, hipStream_t s);
+int launch_dense_bf16(coper_handle* h, int64_t B, int nslices, hipStream_t s);
 bool dense_fused_supported(const coper_handle* h, int nslices);
-int launch_dense_fused_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
+int launch_dense_fused_bf16(coper_handle* h, PassCtx& ctx, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
                             int nslices, float* h_fin, hipStream_t s);
 bool dense_fused_finalizes(const coper_handle* h, int nslices, const float* h_out);
 int fused_fin_update(coper_handle* h, hipStream_t s);
 // grouping sets (coper_group_next; coper_abi.hip)
-void group_home_views(coper_handle* h);             // after the home arrays were (re)allocated
-void group_use_set(coper_handle* h, int i);         // point the fields at set i
+void group_home_views(coper_handle* h);             // set 0's views, after the home arrays were (re)allocated
 void group_sets_free(coper_handle* h);              // sets 1, 2 (back to home first)
 int group_sets_ensure(coper_handle* h, hipStream_t s);
 int launch_dense_finalize(coper_handle* h, const int64_t* rel, int64_t B, int ksplit, float* h_out, hipStream_t s);
-int launch_dense_finalize_pack(coper_handle* h, int64_t B, int ksplit, float* h_out, int32_t* cnt, int32_t cnt_base,
-                               int32_t* cnt_eq, hipStream_t s);
-int launch_pair_targets_packed_bf16x3(coper_handle* h, const int64_t* e2, int64_t B, float* tgt, hipStream_t s);
+int launch_dense_finalize_pack(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, hipStream_t s);
+int launch_pair_targets_packed_bf16x3(coper_handle* h, PassCtx& ctx, const int64_t* e2, int64_t B, float* tgt, hipStream_t s);
 int score_all_dispatch(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s);
 int launch_bias_pad(coper_handle* h, const float* bias, hipStream_t s);
 int launch_topk(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,

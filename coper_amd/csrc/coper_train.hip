@@ -1765,9 +1765,9 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     // group the batch by relation (perm / rel_offset / rel_count of the inference path): the table gradient is
     // written per present relation, never zero-filled (1.75 GB at FB15k-237 shapes)
     if ((rc = coper_reserve(h, B, 0, stream))) return rc;
-    group_use_set(h, 0);
+    h->gcur = 0;
     if ((rc = launch_group_by_relation(h, e1, rel, false, B, 32, s))) return rc;
-    if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
+    if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->grouping().rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
   }
 
   // ---- forward
@@ -1981,8 +1981,8 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     hipLaunchKernelGGL(k_tr_lookup_post_bwd, dim3((unsigned)((nBd + 255) / 256)), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o,
                        ks_o, G_("fc_bias"));
     const int rows_per_wg = 32;
-    hipLaunchKernelGGL(k_tr_lookup_dW, dim3((unsigned)((F + rows_per_wg - 1) / rows_per_wg), (unsigned)dm.R), dim3(256), 0, s, T->x, T->dz, h->perm,
-                       h->rel_offset, h->rel_count, F, d, rows_per_wg, G_("fc_weights"));
+    hipLaunchKernelGGL(k_tr_lookup_dW, dim3((unsigned)((F + rows_per_wg - 1) / rows_per_wg), (unsigned)dm.R), dim3(256), 0, s, T->x, T->dz, h->grouping().perm,
+                       h->grouping().rel_offset, h->grouping().rel_count, F, d, rows_per_wg, G_("fc_weights"));
     hipLaunchKernelGGL(k_tr_lookup_dx, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, P_("fc_weights"), rel,
                        dm.R, F, d, T->dx);
   } else {
@@ -2108,7 +2108,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     tt.n[i] = T->tp[i].n;
     const bool table = lk && T->tp[i].name == "fc_weights";
     tt.rowlen[i] = table ? F * d : 1;
-    tt.rowcnt[i] = table ? h->rel_count : nullptr;
+    tt.rowcnt[i] = table ? h->grouping().rel_count : nullptr;
   }
   // the dense weights' largest |p_new| for the next step's packs (k_tr_amsgrad's 16-byte path only: it is the one that carries it)
   tt.wmax = nullptr; tt.wmax_of = -1;

@@ -783,14 +783,15 @@ bool dense_fused_supported(const coper_handle* h, int nslices) {
 }
 
 template <int NFB, bool WNT>
-static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
+static void dense_fused_launch(coper_handle* h, PassCtx& ctx, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
                                int nslices, int zgroups, float* h_fin, hipStream_t s) {
   const Dims& dm = h->dm;
+  const coper_handle::GroupSet& cur = h->grouping();
   FusedFin Fn;
-  Fn.h_out = h_fin; Fn.c = (const FusedFinConst*)h->fused_fin_dev;
+  Fn.h_out = h_fin; Fn.c = (const FusedFinConst*)cur.fin.get();
   int64_t cap_small = (dm.gen_fc ? dm.R : 1) + 1;
   FusedConvArgs A;
-  A.e1_rows = e1_rows; A.sorted_row = h->sorted_row; A.sorted_rid = h->sorted_rid;
+  A.e1_rows = e1_rows; A.sorted_row = cur.sorted_row; A.sorted_rid = cur.sorted_rid;
   A.ent = h->params["ent_emb"].ptr;
   A.rel_emb = dm.lookup ? nullptr : h->params["rel_emb"].ptr;
   A.conv_w = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
@@ -799,8 +800,8 @@ static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t
   A.per_rel_conv = dm.gen_conv ? 1 : 0;
   A.d = dm.d; A.r = dm.r; A.in_w = dm.in_w; A.in_hw = dm.in_h * dm.in_w; A.Wo = dm.Wo;
   A.img_stride = (fused_rows_max(dm, nslices) * dm.in_w) | 1;
-  A.chk = h->pass_chk;
-  A.w_div = h->w_div; A.w_rem = h->w_rem; A.bad = h->rel_count + dm.R + 1;
+  A.chk = ctx.chk;
+  A.w_div = h->w_div; A.w_rem = h->w_rem; A.bad = cur.rel_count + dm.R + 1;
   size_t lds = (size_t)2 * 16 * 64 * sizeof(uint4) + (size_t)128 * A.img_stride * sizeof(float);
   static uint64_t attr_done = 0;   // per instantiation, one bit per device: always the hardware maximum
   const uint64_t bit = 1ull << (h->cfg.device & 63);
@@ -818,19 +819,18 @@ static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t
   // replay would repeat the PCIe read with the pointers recorded at capture time and overwrite whatever staging buffer they name)
   coper_handle::PassPipeline& pp = h->pipe;
   bool capturing = false;
-  if (pp.stage.n > 0 || pp.post.n > 0 || pp.gnext.ride) {
+  if (pp.stage.n > 0 || pp.post.n > 0 || ctx.gnext_ride) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); capturing = true; }
     else capturing = cap != hipStreamCaptureStatusNone;
   }
   const bool stage_now = pp.stage.n > 0 && !capturing;
   // a pass that was grouped ahead has no grouping launch for a pending coper_post_i32_next to ride in: the staging workgroups take it
-  bool post_now = pp.post.n > 0 && pp.post.here && !capturing;
-  pp.post.here = false;
+  const bool post_now = pp.post.n > 0 && ctx.post_here && !capturing;
   // coper_group_next: one more workgroup sorts the next pass's batch into the set this pass does not use
   GroupJob J = {};
   int n_group = 0;
-  if (pp.gnext.ride && !capturing) {
+  if (ctx.gnext_ride && !capturing) {
     const int64_t R = dm.gen_fc ? dm.R : 1;
     const int t = h->gcur == 1 ? 2 : 1;
     const coper_handle::GroupSet& g = h->gset[t];
@@ -844,7 +844,7 @@ static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t
       // the device arrays like any other (one workgroup reading pinned host memory itself manages 0.65 GB/s: measured, 370 us)
       auto in_stage = [&](const int64_t* p) { return stage_now && p && p + J.B > pp.stage.dst && p < pp.stage.dst + pp.stage.n; };
       J.rel64 = pp.gnext.rel; J.e1_64 = pp.gnext.e1;
-      J.ticket = h->group_done + 1;
+      J.ticket = h->group_done() + 1;
       J.wait_for = (in_stage(pp.gnext.rel) || in_stage(pp.gnext.e1)) ? FUSED_STAGE_WGS : 0;
       J.front = 0;
       if (in_stage(pp.gnext.rel)) J.front = (pp.gnext.rel + J.B) - pp.stage.dst;
@@ -855,10 +855,9 @@ static void dense_fused_launch(coper_handle* h, const int64_t* e1, const int64_t
       pp.gdone.done = true; pp.gdone.set = t;
     }
   }
-  pp.gnext.ride = false; pp.gnext.pending = false;
   const int n_stage = (stage_now || post_now) ? FUSED_STAGE_WGS : 0;
   hipLaunchKernelGGL((k_dense_fused_bf16x3<NFB, WNT>), dim3((unsigned)(n_tile_blocks + n_group + n_stage), (unsigned)nslices, (unsigned)zgroups), dim3(512),
-                     lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, A, h->tiles, h->n_tiles, cap_small, dm.nfb,
+                     lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, A, cur.tiles, cur.n_tiles, cap_small, dm.nfb,
                      dm.F_pad / 32, nslices, h->ws_queries, dm.d_pad16, h->z_part, Fn, n_group + n_stage, pp.stage.src,
                      stage_now ? pp.stage.n : 0, pp.stage.dst, w16_ks_stride(dm), J, n_group, pp.post.src, post_now ? pp.post.n : 0, pp.post.dst);
   if (stage_now) pp.take_stage();
@@ -878,12 +877,10 @@ int fused_fin_update(coper_handle* h, hipStream_t s) {
     c.w_exp = h->w_exp; c.x3m = g.x3m; c.per_rel_bias = dm.gen_fc ? 1 : 0; c.x_exp = h->x_exp; c.d = dm.d; c.pad = 0;
     int rc;
     if ((rc = g.fin.ensure(h, sizeof c, "fused finalize constants"))) return rc;
-    g.fused_fin_dev = g.fin;
     COPER_HIP_TRY(h, hipMemcpyAsync(g.fin, &c, sizeof c, hipMemcpyHostToDevice, s));
     COPER_HIP_TRY(h, hipStreamSynchronize(s));      // (c is on the stack)
     g.fused_fin_perm = g.perm;
   }
-  group_use_set(h, h->gcur);      // (the fields of the set being enqueued: its constants moved)
   return COPER_OK;
 }
 
@@ -892,11 +889,12 @@ bool dense_fused_finalizes(const coper_handle* h, int nslices, const float* h_ou
   static const bool off = getenv("COPER_FUSED_NO_FINALIZE") != nullptr;     // A/B switch, read once
   const Dims& dm = h->dm;
   const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params.at("fc_bias").ptr;
-  return !off && h_out && nslices == 1 && h->x3m && h->fused_fin_dev && h->fused_fin_perm == h->perm && (dm.d & 3) == 0 &&
+  const coper_handle::GroupSet& g = h->grouping();
+  return !off && h_out && nslices == 1 && g.x3m && g.fin && g.fused_fin_perm == g.perm && (dm.d & 3) == 0 &&
          ((((uintptr_t)h_out) | ((uintptr_t)fcb) | ((uintptr_t)h->fc_scale.get()) | ((uintptr_t)h->fc_shift.get())) & 15) == 0;
 }
 
-int launch_dense_fused_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
+int launch_dense_fused_bf16(coper_handle* h, PassCtx& ctx, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
                             int nslices, float* h_fin, hipStream_t s) {
   if (!dense_fused_finalizes(h, nslices, h_fin)) h_fin = nullptr;
 #ifndef COPER_FUSED_SPLIT_B
@@ -911,8 +909,8 @@ int launch_dense_fused_bf16(coper_handle* h, const int64_t* e1, const int64_t* r
   const bool wnt = h->dm.gen_fc && B * 2 <= 128 * h->dm.R;
 #define FUSED_GO(NFB_, Z_)                                                             \
   {                                                                                    \
-    if (wnt) dense_fused_launch<NFB_, true>(h, e1, rel, e1_rows, B, nslices, Z_, h_fin, s);   \
-    else dense_fused_launch<NFB_, false>(h, e1, rel, e1_rows, B, nslices, Z_, h_fin, s);      \
+    if (wnt) dense_fused_launch<NFB_, true>(h, ctx, e1, rel, e1_rows, B, nslices, Z_, h_fin, s);   \
+    else dense_fused_launch<NFB_, false>(h, ctx, e1, rel, e1_rows, B, nslices, Z_, h_fin, s);      \
   }
   if (B <= COPER_FUSED_SPLIT_B / 2) FUSED_GO(4, (h->dm.nfb + 3) / 4)
   else if (h->dm.nfb == 13 && B > COPER_FUSED_SPLIT_B) FUSED_GO(13, 1)

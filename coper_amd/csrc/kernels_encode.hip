@@ -284,6 +284,7 @@ static int64_t small_tile_cap(const coper_handle* h) { return (h->dm.gen_fc ? h-
 int launch_group_by_relation(coper_handle* h, const int64_t* e1, const int64_t* rel, bool have_e1_rows, int64_t B, int tq,
                              hipStream_t s) {
   const Dims& dm = h->dm;
+  const coper_handle::GroupSet& g = h->grouping();
   int64_t R = dm.gen_fc ? dm.R : 1;
   bool post_now = h->pipe.post.n > 0;
   if (post_now) {      // (a pass being captured into a hipGraph leaves the job to the next eager call: a replay must not repeat it)
@@ -302,8 +303,8 @@ int launch_group_by_relation(coper_handle* h, const int64_t* e1, const int64_t* 
       h->pipe.take_post();
     }
     hipLaunchKernelGGL(k_rel_group_identity, dim3(nbm + npost), dim3(HIST_BLOCK), 0, s, rel, e1, B, (int64_t)dm.R, have_e1_rows ? 1 : 0,
-                       (int64_t)h->cfg.shard_lo, dm.n_local, small_tile_cap(h), h->rel_count, h->rel_offset, h->tiles, h->n_tiles, h->perm,
-                       h->sorted_row, h->sorted_rid, h->inv_perm, h->x3m, (int)nbm, psrc, pn, pdst);
+                       (int64_t)h->cfg.shard_lo, dm.n_local, small_tile_cap(h), g.rel_count, g.rel_offset, g.tiles, g.n_tiles, g.perm,
+                       g.sorted_row, g.sorted_rid, g.inv_perm, g.x3m, (int)nbm, psrc, pn, pdst);
     (void)tq;
     COPER_HIP_TRY(h, hipGetLastError());
     return COPER_OK;
@@ -313,15 +314,15 @@ int launch_group_by_relation(coper_handle* h, const int64_t* e1, const int64_t* 
     int rc0 = launch_copy_i32(h, h->pipe.post.src, pn, h->pipe.post.dst, s);
     if (rc0) return rc0;
   }
-  // rel_count (= rel_count_buf[0]) holds the counts of the last call; rel_count_buf[1] is the accumulation buffer of the
+  // rel_count holds the counts of the last call; rel_count_acc() is the accumulation buffer of the
   // two-launch path, zero between calls (its last block takes the totals out with atomic exchanges).  No host-side state
   // changes per call: every path below is hipGraph-capturable and replayable, alone or mixed with eager calls.
   if (R <= HIST_LDS_MAX && B <= 4096) {   // a single workgroup is latency-bound beyond a few ids per thread
     // rel_count[R+1] doubles as the out-of-range counter (reset by the kernel)
     hipLaunchKernelGGL(k_rel_group_single, dim3(1), dim3(1024), sizeof(int32_t) * 2 * (size_t)R, s, rel, e1, B, dm.gen_fc ? 1 : 0, R,
-                       dm.R, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, small_tile_cap(h), h->rel_count,
-                       h->rel_count + dm.R + 1, h->rel_offset, h->tiles, h->n_tiles, h->perm, h->sorted_row, h->sorted_rid, h->inv_perm,
-                       h->x3m);
+                       dm.R, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, small_tile_cap(h), g.rel_count,
+                       g.rel_count + dm.R + 1, g.rel_offset, g.tiles, g.n_tiles, g.perm, g.sorted_row, g.sorted_rid, g.inv_perm,
+                       g.x3m);
     (void)tq;
     COPER_HIP_TRY(h, hipGetLastError());
     return COPER_OK;
@@ -338,26 +339,26 @@ int launch_group_by_relation(coper_handle* h, const int64_t* e1, const int64_t* 
       h->pipe.take_post();
     }
     hipLaunchKernelGGL(k_rel_hist_scan, dim3(nb + npost), dim3(HIST_BLOCK), sizeof(int32_t) * (size_t)R, s, rel, B, dm.gen_fc ? 1 : 0, R,
-                       (int64_t)dm.R, h->rel_count_buf[1], h->rel_count, h->group_done, small_tile_cap(h), h->rel_offset, h->tiles,
-                       h->n_tiles, h->rel_cursor, (int)nb, psrc, pn, pdst);
+                       (int64_t)dm.R, h->rel_count_acc(), g.rel_count, h->group_done(), small_tile_cap(h), g.rel_offset, g.tiles,
+                       g.n_tiles, h->rel_cursor(), (int)nb, psrc, pn, pdst);
     hipLaunchKernelGGL(k_rel_scatter, dim3(nb), dim3(HIST_BLOCK), sizeof(int32_t) * (size_t)R, s, rel, B, dm.gen_fc ? 1 : 0, R,
-                       h->rel_offset, h->rel_cursor, h->perm, e1, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, dm.R,
-                       h->sorted_row, h->sorted_rid, h->inv_perm, h->x3m);
+                       g.rel_offset, h->rel_cursor(), g.perm, e1, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, dm.R,
+                       g.sorted_row, g.sorted_rid, g.inv_perm, g.x3m);
     COPER_HIP_TRY(h, hipGetLastError());
     return COPER_OK;
   }
   // relation tables beyond the LDS histogram: memset + three launches
-  COPER_HIP_TRY(h, hipMemsetAsync(h->rel_count, 0, sizeof(int32_t) * (dm.R + 2), s));
-  COPER_HIP_TRY(h, hipMemsetAsync(h->rel_cursor, 0, sizeof(int32_t) * (dm.R + 2), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(g.rel_count, 0, sizeof(int32_t) * (dm.R + 2), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(h->rel_cursor(), 0, sizeof(int32_t) * (dm.R + 2), s));
   size_t hl = 0;
   // rel_count[R+1] doubles as the out-of-range counter (ids are validated on device, never trusted)
-  hipLaunchKernelGGL(k_rel_hist, dim3(nb), dim3(HIST_BLOCK), hl, s, rel, B, dm.gen_fc ? 1 : 0, R, h->rel_count,
-                     h->rel_count + dm.R + 1);
-  hipLaunchKernelGGL(k_rel_scan_tiles, dim3(1), dim3(1024), 0, s, h->rel_count, R, small_tile_cap(h), h->rel_offset,
-                     h->tiles, h->n_tiles);
-  hipLaunchKernelGGL(k_rel_scatter, dim3(nb), dim3(HIST_BLOCK), hl, s, rel, B, dm.gen_fc ? 1 : 0, R, h->rel_offset,
-                     h->rel_cursor, h->perm, e1, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, dm.R,
-                     h->sorted_row, h->sorted_rid, h->inv_perm, h->x3m);
+  hipLaunchKernelGGL(k_rel_hist, dim3(nb), dim3(HIST_BLOCK), hl, s, rel, B, dm.gen_fc ? 1 : 0, R, g.rel_count,
+                     g.rel_count + dm.R + 1);
+  hipLaunchKernelGGL(k_rel_scan_tiles, dim3(1), dim3(1024), 0, s, g.rel_count, R, small_tile_cap(h), g.rel_offset,
+                     g.tiles, g.n_tiles);
+  hipLaunchKernelGGL(k_rel_scatter, dim3(nb), dim3(HIST_BLOCK), hl, s, rel, B, dm.gen_fc ? 1 : 0, R, g.rel_offset,
+                     h->rel_cursor(), g.perm, e1, have_e1_rows ? 1 : 0, (int64_t)h->cfg.shard_lo, dm.n_local, dm.R,
+                     g.sorted_row, g.sorted_rid, g.inv_perm, g.x3m);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -527,13 +528,13 @@ int launch_conv(coper_handle* h, const int64_t* e1, const int64_t* rel, const fl
     constexpr int QPB = 4;
     size_t lds = sizeof(float) * (size_t)QPB * dm.in_h * dm.in_w;
     hipLaunchKernelGGL((k_conv3x3_bn_relu<QPB>), dim3((unsigned)((B + QPB - 1) / QPB)), dim3(256), lds, s, e1, rel,
-                       e1_rows, h->perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
+                       e1_rows, h->grouping().perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                        dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad, dm.R, B,
                        h->x_sorted);
   } else {
     size_t lds = sizeof(float) * ((size_t)dm.in_h * dm.in_w + (size_t)dm.fh * dm.fw * dm.C + 3 * (size_t)dm.C);
-    hipLaunchKernelGGL(k_conv_bn_relu, dim3((unsigned)B), dim3(256), lds, s, e1, rel, e1_rows, h->perm,
+    hipLaunchKernelGGL(k_conv_bn_relu, dim3((unsigned)B), dim3(256), lds, s, e1, rel, e1_rows, h->grouping().perm,
                        h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                        dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.emb_w, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, dm.fh, dm.fw, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad,
@@ -840,12 +841,13 @@ __global__ void k_dense_finalize(const float* __restrict__ z_part, int ksplit, i
 template <int NFB>
 static void dense_launch(coper_handle* h, int64_t B, int nslices, int zgroups, hipStream_t s) {
   const Dims& dm = h->dm;
+  const coper_handle::GroupSet& g = h->grouping();
   int64_t cap_small = small_tile_cap(h);
   int64_t n_small_max = cap_small - 1 < B ? cap_small - 1 : B;
   int64_t n_big_max = B / 33 + 1;
   if (n_small_max > 0)
     hipLaunchKernelGGL((k_dense_small_f32<NFB>), dim3((unsigned)n_small_max, (unsigned)((nslices + 3) / 4), (unsigned)zgroups),
-                       dim3(256), 0, s, (const float4*)h->Wf, h->x_sorted, h->tiles, h->n_tiles, dm.nfb, dm.F_pad / 16,
+                       dim3(256), 0, s, (const float4*)h->Wf, h->x_sorted, g.tiles, g.n_tiles, dm.nfb, dm.F_pad / 16,
                        dm.F_pad, nslices, h->ws_queries, dm.d_pad16, h->z_part);
   if (B > 32) {
     size_t lds = (size_t)COPER_DENSE_NSTAGE * (((NFB + 8 + 3) / 4) * 4) * 64 * sizeof(float4);  // ring, max NB = 8
@@ -854,7 +856,7 @@ static void dense_launch(coper_handle* h, int64_t B, int nslices, int zgroups, h
       h->dense_attr_done = true;
     }
     hipLaunchKernelGGL((k_dense_big_f32<NFB>), dim3((unsigned)n_big_max, (unsigned)nslices, (unsigned)zgroups), dim3(256),
-                       lds, s, (const float4*)h->Wf, h->x_sorted, h->tiles, h->n_tiles, cap_small, dm.nfb, dm.F_pad / 16,
+                       lds, s, (const float4*)h->Wf, h->x_sorted, g.tiles, g.n_tiles, cap_small, dm.nfb, dm.F_pad / 16,
                        dm.F_pad, nslices, h->ws_queries, dm.d_pad16, h->z_part);
   }
 }
@@ -879,7 +881,7 @@ int launch_dense_finalize(coper_handle* h, const int64_t* rel, int64_t B, int ks
   const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr;
   int64_t total = B * (dm.d_pad16 / 4);
   hipLaunchKernelGGL(k_dense_finalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->z_part, ksplit,
-                     h->ws_queries, B, dm.d, dm.d_pad16, h->perm, rel, fcb, dm.gen_fc ? 1 : 0, dm.R, h->fc_scale,
+                     h->ws_queries, B, dm.d, dm.d_pad16, h->grouping().perm, rel, fcb, dm.gen_fc ? 1 : 0, dm.R, h->fc_scale,
                      h->fc_shift, h_out, h->enc_bf16 ? h->w_exp : nullptr, h->enc_bf16 ? h->x_exp : 0);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
@@ -996,8 +998,9 @@ int launch_pack_owned_rows(coper_handle* h, const float* ent, const float* bias,
   const int64_t total = (cap + 1) * (h->dm.d + 1);
   int64_t nb = (total + 255) / 256;
   if (nb > 8192) nb = 8192;
+  int32_t* const counts = h->grouping().rel_count;
   hipLaunchKernelGGL(k_pack_owned_rows, dim3((unsigned)nb), dim3(256), 0, s, ent, bias, loc, n, cap, h->dm.d, h->dm.n_local, hdr0, hdr1, buf,
-                     h->rel_count ? h->rel_count + h->dm.R + 1 : nullptr);
+                     counts ? counts + h->dm.R + 1 : nullptr);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }

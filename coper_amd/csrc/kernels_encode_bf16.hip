@@ -264,8 +264,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_bn_relu_bf16(
 
 bool conv_bf16_supported(const Dims& dm) { return dm.fh == 3 && dm.fw == 3 && dm.C % 8 == 0 && 64 % (dm.C / 8) == 0; }
 
-int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
-                     bool skip_big, hipStream_t s) {
+int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, hipStream_t s) {
   const Dims& dm = h->dm;
   const float* rel_emb = dm.lookup ? nullptr : h->params["rel_emb"].ptr;
   const float* cw = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
@@ -275,14 +274,13 @@ int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, con
   unsigned short* xh = (unsigned short*)h->x_sorted;
   unsigned short* xl = xh + (size_t)h->ws_queries * dm.F_pad;
   ScopedKernelTimer t(h, "conv", s);
-  int64_t cap_small = (dm.gen_fc ? dm.R : 1) + 1;
-  int64_t n_small_max = cap_small - 1 < B ? cap_small - 1 : B;
-  int64_t grid = skip_big ? n_small_max * (32 / QPB) : (B + QPB - 1) / QPB;
+  const coper_handle::GroupSet& g = h->grouping();
+  int64_t grid = (B + QPB - 1) / QPB;
   hipLaunchKernelGGL((k_conv3x3_bn_relu_bf16<QPB>), dim3((unsigned)grid), dim3(256), lds, s, e1, rel,
-                     e1_rows, h->perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
+                     e1_rows, g.perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                      dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.in_h, dm.in_w,
-                     dm.stacked ? 1 : 0, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad, dm.R, B, h->tiles,
-                     h->n_tiles, skip_big ? 1 : 0, xh, xl, h->x_exp);
+                     dm.stacked ? 1 : 0, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad, dm.R, B, g.tiles,
+                     g.n_tiles, /*skip_big=*/0, xh, xl, h->x_exp);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -703,17 +701,17 @@ static void dense_launch_bf16(coper_handle* h, int64_t B, int nslices, int zgrou
   int64_t n_big_max = B / 33 + 1;
   const unsigned short* xh = (const unsigned short*)h->x_sorted;
   const unsigned short* xl = xh + (size_t)h->ws_queries * dm.F_pad;
+  const coper_handle::GroupSet& g = h->grouping();
   if (n_small_max > 0)
     hipLaunchKernelGGL((k_dense_small_bf16x3<NFB>), dim3((unsigned)n_small_max, (unsigned)((nslices + 3) / 4), (unsigned)zgroups),
-                       dim3(256), 0, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, h->tiles, h->n_tiles,
+                       dim3(256), 0, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, g.tiles, g.n_tiles,
                        dm.nfb, dm.F_pad / 32, dm.F_pad, nslices, h->ws_queries, dm.d_pad16, h->z_part);
-  if (h->dense_small_only) return;
 #ifndef COPER_DENSE_RING
   if (B > 32 && NFB >= 8) {
     // x ring only: P stages of (x hi | x lo) for up to 8 query blocks
     size_t lds = (size_t)COPER_DENSE_PF * 16 * 64 * sizeof(uint4);
     hipLaunchKernelGGL((k_dense_reg_bf16x3<NFB>), dim3((unsigned)n_big_max, (unsigned)nslices, (unsigned)zgroups), dim3(256),
-                       lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, h->tiles, h->n_tiles, cap_small,
+                       lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, g.tiles, g.n_tiles, cap_small,
                        dm.nfb, dm.F_pad / 32, dm.F_pad, nslices, h->ws_queries, dm.d_pad16, h->z_part);
     return;
   }
@@ -725,14 +723,13 @@ static void dense_launch_bf16(coper_handle* h, int64_t B, int nslices, int zgrou
       h->dense_attr_done = true;
     }
     hipLaunchKernelGGL((k_dense_big_bf16x3<NFB>), dim3((unsigned)n_big_max, (unsigned)nslices, (unsigned)zgroups), dim3(256),
-                       lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, h->tiles, h->n_tiles, cap_small,
+                       lds, s, (const uint4*)h->Wf16_hi, (const uint4*)h->Wf16_lo, xh, xl, g.tiles, g.n_tiles, cap_small,
                        dm.nfb, dm.F_pad / 32, dm.F_pad, nslices, h->ws_queries, dm.d_pad16, h->z_part);
   }
 }
 
-int launch_dense_bf16(coper_handle* h, int64_t B, int nslices, bool small_only, hipStream_t s) {
+int launch_dense_bf16(coper_handle* h, int64_t B, int nslices, hipStream_t s) {
   const Dims& dm = h->dm;
-  h->dense_small_only = small_only;
   int nfb = dm.nfb;
   if (nfb == 13) dense_launch_bf16<13>(h, B, nslices, 1, s);
   else if (nfb <= 2) dense_launch_bf16<2>(h, B, nslices, 1, s);
@@ -748,19 +745,14 @@ int launch_dense_bf16(coper_handle* h, int64_t B, int nslices, bool small_only, 
 // wrote the planes from the partial sums in one launch; the planes hold h 2^e_h now and e_h is known only when every row is.)
 // The rank counters of the pass are preset by the packing launch.
 // ------------------------------------------------------------------------------------------------
-int launch_dense_finalize_pack(coper_handle* h, int64_t B, int ksplit, float* h_out, int32_t* cnt, int32_t cnt_base,
-                               int32_t* cnt_eq, hipStream_t s) {
+int launch_dense_finalize_pack(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, hipStream_t s) {
   int rc = launch_finalize_h_publish(h, B, ksplit, h_out, s);
   if (rc) return rc;
-  const int32_t base_was = h->count_base;
-  h->preset_cnt = cnt;
-  h->preset_eq = cnt_eq;
-  h->count_base = cnt_base;
   const int64_t n_blk = (B + 127) / 128 * 4;
-  rc = launch_rows_to_frag_bf16(h, h_out, B, n_blk, (uint4*)h->hfrag16_hi, (uint4*)h->hfrag16_lo, (uint4*)h->hrm16_hi, (uint4*)h->hrm16_lo,
-                                (uint4*)h->hf3_ws, true, s);
-  h->count_base = base_was;
-  return rc;
+  ctx.packed_hvec = h_out;
+  ctx.packed_B = B;
+  return launch_rows_to_frag_bf16(h, ctx, h_out, B, n_blk, (uint4*)h->hfrag16_hi, (uint4*)h->hfrag16_lo, (uint4*)h->hrm16_hi,
+                                  (uint4*)h->hrm16_lo, (uint4*)h->hf3_ws, true, s);
 }
 
 }  // namespace coper

@@ -25,7 +25,6 @@
 // tie counts of the mode are therefore those of COPER_SCORE_F32 on the same h, bit for bit, as long as the bf16x3 error
 // stays inside tau (tests measure the margin; coper_config.rank_band_kappa widens it up to the proven worst case).
 #include <algorithm>
-#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -1139,17 +1138,16 @@ static FilterArgs filter_args(coper_handle* h, const float* hvec, const int64_t*
 
 // after a launch whose workgroups listed blocks beyond their own share (the tail kernel's filter phase).  defer: the role
 // joins the band launch of the count pass that follows on the same stream (score_count3_chunk_bf16x3) instead of its own
-int launch_filter_excess_bf16x3(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
+int launch_filter_excess_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
                                 int64_t nnz, int64_t B, int32_t* ranks, bool defer, hipStream_t s) {
-  h->excess_pending = false;
+  ctx.excess_pending = false;
   if (nnz <= TL_OWN_ENTRIES) return COPER_OK;     // no block can exceed its own share
   if (h->dm.KS16 != 13 && h->dm.KS16 != 16) return fail(h, COPER_EUNSUPPORTED, "filter excess: ent_emb_size not served by the fused tail");
   const FilterArgs F = filter_args(h, hvec, e2, indptr, idx, (const float2*)h->tband_ws, B, ranks);
 #ifndef COPER_DBG_SC3_NO_BAND
   if (defer) {
-    static_assert(sizeof(FilterArgs) <= sizeof(h->excess_args), "coper_internal.h: excess_args too small");
-    memcpy(h->excess_args, &F, sizeof F);
-    h->excess_pending = true;
+    ctx.excess = F;
+    ctx.excess_pending = true;
     return COPER_OK;
   }
 #endif
@@ -1232,7 +1230,7 @@ size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc) {
 
 // Count launch over queries [q0, q0 + Bc) (q0 a multiple of 128) of the packed batch + the exact decision of its band.
 // tband_ws / hf3_ws hold the whole batch; hvec (fp32 rows of the whole batch), tgt_x (exact targets of the whole batch or NULL).
-int score_count3_chunk_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
+int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s) {
   if (score_count3_mask_bytes(h, Bc) > h->mask_ws.size()) return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
@@ -1281,16 +1279,14 @@ int score_count3_chunk_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, const flo
     if (rows_per_tile * 4 > 0x7fffffffLL || n_units > 0x7fffffffLL) return fail(h, COPER_EUNSUPPORTED, "band mask beyond 2^31 units");
     const unsigned n_band = (unsigned)((n_units + BE_UPW - 1) / BE_UPW);
     const unsigned long long* summ = (const unsigned long long*)((const char*)h->mask_ws + score_count3_mask_words_bytes(h, Bc));
-    if (h->excess_pending) {
-      FilterArgs F;
-      memcpy(&F, h->excess_args, sizeof F);
-      h->excess_pending = false;
+    if (ctx.excess_pending) {
+      ctx.excess_pending = false;
       if (h->dm.KS16 == 13)
         hipLaunchKernelGGL(k_band_excess_bf16x3<13>, dim3(n_band + FX_GRID), dim3(256), 0, s, (const uint4*)h->mask_ws, summ, n_units,
-                           (unsigned)(rows_per_tile * 4), A, (int)n_band, F);
+                           (unsigned)(rows_per_tile * 4), A, (int)n_band, ctx.excess);
       else
         hipLaunchKernelGGL(k_band_excess_bf16x3<16>, dim3(n_band + FX_GRID), dim3(256), 0, s, (const uint4*)h->mask_ws, summ, n_units,
-                           (unsigned)(rows_per_tile * 4), A, (int)n_band, F);
+                           (unsigned)(rows_per_tile * 4), A, (int)n_band, ctx.excess);
     } else {
 #ifndef COPER_BAND_CB_LARGE
 #define COPER_BAND_CB_LARGE 3

@@ -70,17 +70,16 @@ __global__ __launch_bounds__(256) void k_rows_to_frag_bf16(const float* __restri
   if (f3) f3_store_piece(f3, KS16, row, ks, l >> 5, h4, l4, query_side != 0);
 }
 
-int launch_rows_to_frag_bf16(coper_handle* h, const float* src, int64_t n_rows, int64_t n_blk, uint4* hi, uint4* lo,
+int launch_rows_to_frag_bf16(coper_handle* h, PassCtx& ctx, const float* src, int64_t n_rows, int64_t n_blk, uint4* hi, uint4* lo,
                              uint4* rm_hi, uint4* rm_lo, uint4* f3, bool query_side, hipStream_t s) {
   const Dims& dm = h->dm;
   int64_t total = n_blk * dm.KS16 * 64;
+  int32_t* const done = h->group_done();
   hipLaunchKernelGGL(k_rows_to_frag_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, n_rows, dm.d,
-                     dm.KS16, hi, lo, rm_hi, rm_lo, f3, query_side ? 1 : 0, total, h->preset_cnt, h->count_base, h->preset_eq,
-                     h->x3_ent_exp, query_side ? h->x3m : nullptr, h->x3s,
-                     h->preset_cnt && h->pass_chk ? (const int32_t*)(h->pass_chk + GROUP_CHK_STALE) : nullptr, h->group_done ? h->group_done + 2 : nullptr);
-  if (h->preset_cnt) h->counts_preset = h->preset_cnt;
-  h->preset_cnt = nullptr;
-  h->preset_eq = nullptr;
+                     dm.KS16, hi, lo, rm_hi, rm_lo, f3, query_side ? 1 : 0, total, ctx.cnt, ctx.base, ctx.eq,
+                     h->x3_ent_exp, query_side ? h->grouping().x3m : nullptr, h->x3s,
+                     ctx.cnt && ctx.chk ? (const int32_t*)(ctx.chk + GROUP_CHK_STALE) : nullptr, done ? done + 2 : nullptr);
+  if (ctx.cnt) ctx.preset = true;
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -104,35 +103,36 @@ int launch_absmax_publish(coper_handle* h, const float* src, int64_t n, hipStrea
   int64_t blocks = (n + 256 * 8 - 1) / (256 * 8);
   if (blocks > X3M_SLOTS) blocks = X3M_SLOTS;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_absmax_publish, dim3((unsigned)blocks), dim3(256), 0, s, src, n, h->x3m);
+  hipLaunchKernelGGL(k_absmax_publish, dim3((unsigned)blocks), dim3(256), 0, s, src, n, h->grouping().x3m);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
 
-int launch_pack_h_bf16(coper_handle* h, const float* hvec, int64_t B, hipStream_t s) {
+int launch_pack_h_bf16(coper_handle* h, PassCtx& ctx, const float* hvec, int64_t B, hipStream_t s) {
   int rc0 = launch_absmax_publish(h, hvec, B * h->dm.d, s);
   if (rc0) return rc0;
   int64_t n_blk = (B + 32 * BX_NQ - 1) / (32 * BX_NQ) * BX_NQ;
-  return launch_rows_to_frag_bf16(h, hvec, B, n_blk, (uint4*)h->hfrag16_hi, (uint4*)h->hfrag16_lo, (uint4*)h->hrm16_hi,
+  ctx.packed_hvec = hvec;
+  ctx.packed_B = B;
+  return launch_rows_to_frag_bf16(h, ctx, hvec, B, n_blk, (uint4*)h->hfrag16_hi, (uint4*)h->hfrag16_lo, (uint4*)h->hrm16_hi,
                                   (uint4*)h->hrm16_lo, (uint4*)h->hf3_ws, true, s);
 }
 
-// counters start from count_base unless the caller's pack launch preset them (coper_rank: n_greater accumulates
-// straight into `ranks`, started from 1)
-void score_count_begin_bf16x3(coper_handle* h, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s) {
-  if (h->counts_preset != ng)
-    hipLaunchKernelGGL(k_zero_counts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, ng, ne, h->count_base);
-  h->counts_preset = nullptr;
+// counters start from ctx.base unless the pass preset them (coper_rank: n_greater accumulates straight into `ranks`,
+// started from 1)
+void score_count_begin_bf16x3(const PassCtx& ctx, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s) {
+  if (!(ctx.preset && ctx.cnt == ng))
+    hipLaunchKernelGGL(k_zero_counts, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, ng, ne, ctx.base);
 }
 
 // the whole packed batch in one count launch (+ the exact decision of its band)
-int launch_score_count_bf16x3(coper_handle* h, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
+int launch_score_count_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
                               const int64_t* idx, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s) {
-  score_count_begin_bf16x3(h, B, ng, ne, s);
+  score_count_begin_bf16x3(ctx, B, ng, ne, s);
   // chunks of queries bound the band mask (one bit per logit of a launch): 20,480 queries against 10 M entities would be 25 GB
   const int64_t qc = topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats);
   for (int64_t q0 = 0; q0 < B; q0 += qc) {
-    const int rc = score_count3_chunk_bf16x3(h, q0, B - q0 < qc ? B - q0 : qc, hvec, tgt_x, e2, indptr, idx, ng, ne, nullptr, 0, s);
+    const int rc = score_count3_chunk_bf16x3(h, ctx, q0, B - q0 < qc ? B - q0 : qc, hvec, tgt_x, e2, indptr, idx, ng, ne, nullptr, 0, s);
     if (rc) return rc;
   }
   return COPER_OK;
@@ -237,7 +237,8 @@ __global__ __launch_bounds__(256, 2) void k_score_all_bf16x3(const uint4* __rest
 
 int launch_score_all_bf16x3(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s) {
   const Dims& dm = h->dm;
-  int rc = launch_pack_h_bf16(h, hvec, B, s);
+  PassCtx none;
+  int rc = launch_pack_h_bf16(h, none, hvec, B, s);
   if (rc) return rc;
   int64_t q_groups = (B + 63) / 64;
   int64_t e_groups = (dm.n_eblk + 7) / 8;
@@ -410,31 +411,25 @@ static void pair_launch(coper_handle* h, int mode, int64_t n_pairs, int64_t B, i
                      dm.n_local, out, ng, h->x3s);
 }
 
-int launch_pair_targets_bf16x3(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* tgt,
+int launch_pair_targets_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const int64_t* e2, int64_t B, float* tgt,
                                hipStream_t s) {
-  int rc = launch_pack_h_bf16(h, hvec, B, s);
+  int rc = launch_pack_h_bf16(h, ctx, hvec, B, s);
   if (rc) return rc;
-  h->packed_hvec = hvec;  // coper_rank reuses this packing for the count pass on the same stream
-  h->packed_B = B;
-  pair_launch(h, 0, B, B, 1, e2, nullptr, h->expand_indptr, nullptr, h->expand_indptr ? h->row_of_ws : nullptr, nullptr, tgt, nullptr, s);
-  if (h->expand_indptr) h->rows_expanded_for = h->expand_indptr;
-  h->expand_indptr = nullptr;
-  COPER_HIP_TRY(h, hipGetLastError());
-  return COPER_OK;
+  return launch_pair_targets_packed_bf16x3(h, ctx, e2, B, tgt, s);
 }
 
 // targets of queries whose planes are already in place (coper_encode_rank: written by k_dense_finalize_pack)
-int launch_pair_targets_packed_bf16x3(coper_handle* h, const int64_t* e2, int64_t B, float* tgt, hipStream_t s) {
-  pair_launch(h, 0, B, B, 1, e2, nullptr, h->expand_indptr, nullptr, h->expand_indptr ? h->row_of_ws : nullptr, nullptr, tgt, nullptr, s);
-  if (h->expand_indptr) h->rows_expanded_for = h->expand_indptr;
-  h->expand_indptr = nullptr;
+int launch_pair_targets_packed_bf16x3(coper_handle* h, PassCtx& ctx, const int64_t* e2, int64_t B, float* tgt, hipStream_t s) {
+  pair_launch(h, 0, B, B, 1, e2, nullptr, ctx.csr, nullptr, ctx.csr ? h->row_of_ws : nullptr, nullptr, tgt, nullptr, s);
+  if (ctx.csr) ctx.expanded = true;
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
 
 int launch_score_lookup_bf16x3(coper_handle* h, const float* hvec, const int32_t* lookup, int64_t B, int64_t L,
                                float* out, hipStream_t s) {
-  int rc = launch_pack_h_bf16(h, hvec, B, s);
+  PassCtx none;
+  int rc = launch_pack_h_bf16(h, none, hvec, B, s);
   if (rc) return rc;
   pair_launch(h, 1, B * L, B, L, nullptr, lookup, nullptr, nullptr, nullptr, nullptr, out, nullptr, s);
   COPER_HIP_TRY(h, hipGetLastError());
@@ -442,12 +437,11 @@ int launch_score_lookup_bf16x3(coper_handle* h, const float* hvec, const int32_t
 }
 
 // takes back, for every known answer, what the count kernel counted for it (logit above the band: tband_ws)
-int launch_filter_correct_bf16x3(coper_handle* h, const int64_t* e2, const int64_t* indptr, const int64_t* idx, int64_t nnz,
+int launch_filter_correct_bf16x3(coper_handle* h, const PassCtx& ctx, const int64_t* e2, const int64_t* indptr, const int64_t* idx, int64_t nnz,
                                  int64_t B, int32_t* ng, hipStream_t s) {
   // row ids were written by the target pass of coper_rank / coper_encode_rank; other callers of coper_rank_counts get them
   // from an expansion launch (long rows) -- the pair kernel's bisection of indptr serves short CSRs
-  const int32_t* rows = h->rows_expanded_for == indptr ? h->row_of_ws : nullptr;
-  h->rows_expanded_for = nullptr;
+  const int32_t* rows = ctx.expanded && ctx.csr == indptr ? h->row_of_ws : nullptr;
   if (!rows && nnz > 4096) {
     int64_t threads = B * 16;
     hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, indptr, B, h->row_of_ws);

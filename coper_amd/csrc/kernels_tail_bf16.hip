@@ -398,14 +398,16 @@ int launch_finalize_h_publish(coper_handle* h, int64_t B, int ksplit, float* h_o
   const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr;
   int64_t blocks = (B + 7) / 8;                    // eight rows per block and round
   if (blocks > X3M_SLOTS) blocks = X3M_SLOTS;
+  const coper_handle::GroupSet& g = h->grouping();
   hipLaunchKernelGGL(k_finalize_h_publish, dim3((unsigned)blocks), dim3(256), 0, s, h->z_part, ksplit, h->ws_queries, B, dm.d,
-                     dm.d_pad16, h->inv_perm, h->sorted_rid, fcb, dm.gen_fc ? 1 : 0, h->fc_scale, h->fc_shift, h->w_exp, h->x_exp, h_out,
-                     h->x3m);
+                     dm.d_pad16, g.inv_perm, g.sorted_rid, fcb, dm.gen_fc ? 1 : 0, h->fc_scale, h->fc_shift, h->w_exp, h->x_exp, h_out,
+                     g.x3m);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
 
-int launch_finalize_targets_filter_bf16x3(coper_handle* h, int64_t B, int ksplit, float* h_out, const int64_t* e2, const int64_t* indptr,
+// The launch leaves ranks preset (from 1): the count pass that follows on the same stream skips its zeroing.
+int launch_finalize_targets_filter_bf16x3(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, const int64_t* e2, const int64_t* indptr,
                                           const int64_t* idx, int64_t nnz, float* tgt, int32_t* ranks, hipStream_t s) {
   const Dims& dm = h->dm;
   int rc0 = launch_finalize_h_publish(h, B, ksplit, h_out, s);
@@ -415,14 +417,16 @@ int launch_finalize_targets_filter_bf16x3(coper_handle* h, int64_t B, int ksplit
 #define TL_GO(KS_)                                                                                                                 \
   hipLaunchKernelGGL(k_finalize_targets_filter_bf16x3<KS_>, dim3(grid), dim3(64 * TL_WAVES), 0, s, B, dm.d, (const float*)h_out,   \
                      (uint4*)h->hf3_ws, (const uint4*)h->Erm16_hi, (const uint4*)h->Erm16_lo,                                       \
-                     h->bias_pad, dm.n_local, e2, indptr, idx, tgt, band_kappa(h), h->band_consts, h->x3m, h->x3_ent_exp, h->x3s,   \
-                     (float2*)h->tband_ws, ranks, h->heavy_ws, h->pass_chk ? (const int32_t*)(h->pass_chk + GROUP_CHK_STALE) : nullptr, \
-                     h->group_done + 2)
+                     h->bias_pad, dm.n_local, e2, indptr, idx, tgt, band_kappa(h), h->band_consts, h->grouping().x3m, h->x3_ent_exp,  \
+                     h->x3s, (float2*)h->tband_ws, ranks, h->heavy_ws, ctx.chk ? (const int32_t*)(ctx.chk + GROUP_CHK_STALE) : nullptr, \
+                     h->group_done() + 2)
   if (dm.KS16 == 13) { TL_GO(13); } else { TL_GO(16); }
 #undef TL_GO
   COPER_HIP_TRY(h, hipGetLastError());
+  ctx.cnt = ranks;
+  ctx.preset = true;
   // blocks beyond a workgroup's own share: worked off beside the band walk of the count pass the caller launches next
-  return launch_filter_excess_bf16x3(h, h_out, e2, indptr, idx, nnz, B, ranks, true, s);
+  return launch_filter_excess_bf16x3(h, ctx, h_out, e2, indptr, idx, nnz, B, ranks, true, s);
 }
 
 }  // namespace coper

@@ -889,7 +889,7 @@ static void tk_dispatch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0,
   else tk_launch_emit<4, 4>(h, G, qs, q0, bc, k, indptr, s, out_blk, out_q, out_cnt);
 }
 
-int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
+int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
                               const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
                               int64_t* topk_idx, hipStream_t s) {
   const Dims& dm = h->dm;
@@ -901,7 +901,7 @@ int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* t
   if ((size_t)(Gm * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap)
     return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
   int rc;
-  score_count_begin_bf16x3(h, B, ng, ne, s);
+  score_count_begin_bf16x3(ctx, B, ng, ne, s);
   // slots no query owns (filt_nnz may be a capacity larger than the CSR) must read as unused
   COPER_HIP_TRY(h, hipMemsetAsync(h->cand_blk_ws, 0xFF, sizeof(int32_t) * (T + (XF > 1 ? T64 : 0)), s));
   const int nseg = topk_nseg(G);
@@ -913,7 +913,7 @@ int launch_topk_pruned_bf16x3(coper_handle* h, const float* hvec, const float* t
   for (int64_t q0 = 0; q0 < B; q0 += qc) {
     const int64_t bc = B - q0 < qc ? B - q0 : qc;
     const int64_t qs = (bc + 127) / 128 * 128;
-    if ((rc = score_count3_chunk_bf16x3(h, q0, bc, hvec, tgt_x, e2, indptr, idx, ng, ne, h->gmax_ws, qs, s))) return rc;
+    if ((rc = score_count3_chunk_bf16x3(h, ctx, q0, bc, hvec, tgt_x, e2, indptr, idx, ng, ne, h->gmax_ws, qs, s))) return rc;
     if (XF > 1) tk_dispatch_emit(h, Gm, qs, q0, bc, k, indptr, s, blk64, q64, nullptr);
     else tk_dispatch_emit(h, G, qs, q0, bc, k, indptr, s);
   }

@@ -7,6 +7,7 @@
 
 #include "bf16x3_chain.h"
 #include "conv_fold.h"
+#include "coper_internal.h"
 
 namespace coper {
 
@@ -151,10 +152,5 @@ __device__ __forceinline__ void tail_take_back(const bool hit, const int qi, con
     if (c) atomicSub(&ranks[q0 + qi], c);
   }
 }
-
-struct FilterArgs {          // the filter role's view of a pass (queries of one count launch: all pointers at its first query)
-  const float* hvec; const uint4* Ehi; const uint4* Elo; const float* bias_pad; const int64_t* e2; const int64_t* indptr;
-  const int64_t* idx; const float2* tband; int32_t* ranks; int32_t* heavy; const int32_t* x3s; int64_t B, n_local; int d;
-};
 
 }  // namespace coper
