@@ -52,8 +52,9 @@ def dropout_keep(seed: int, step: int, stage: int, n: int, rate: float) -> np.nd
     return ((x >> np.uint64(8)) >= thr).astype(np.float32)
 
 
-def _generate(p, md, name, c, train_stats, keep_ctx, stats, dtype):
-    """ContextualParameterGenerator.generate (models.py:56-70) in train mode; keep_ctx[(name, i)] = 0/1 dropout mask."""
+def _generate(p, md, name, c, train_stats, keep_ctx, stats, dtype, project=True):
+    """ContextualParameterGenerator.generate (models.py:56-70) in train mode; keep_ctx[(name, i)] = 0/1 dropout mask.
+    project=False: the context in front of the last projection ([B, n_last]), for the factored dense layer."""
     ctx = list(md["context_rel_conv"] if name.startswith("conv1") else md["context_rel_out"])
     use_bn = bool(md.get("context_rel_use_batch_norm", False))
     rate = float(md.get("context_rel_dropout", 0.0))
@@ -71,13 +72,30 @@ def _generate(p, md, name, c, train_stats, keep_ctx, stats, dtype):
             v = (v - m) / torch.sqrt(var + BN_EPS) * p[bn + "/gamma"] + p[bn + "/beta"]
         v = torch.relu(v)
         v = v * torch.as_tensor(keep_ctx[(name, i)].reshape(v.shape)).to(dtype) / (1.0 - rate)
-    return v @ p["%s/CPG/Projection%d" % (name, len(ctx))]
+    return v @ p["%s/CPG/Projection%d" % (name, len(ctx))] if project else v
 
 
-def forward_train(p, md, batch, keep_hidden, keep_out, dtype=torch.float64, keep_ctx=None):
+# Above this many elements (1 GiB of float64) of the per-sample dense weights Wg [B, F, d] or of the gathered rows
+# ent_emb[lookup] [B, L, d], form=None takes the factored evaluation.  Full-size training batches (B = 512, F = 4608, d = 200:
+# 3.8 GB for Wg, twice that under autograd) need it; every small case stays on the form that restates the reference line by line.
+FACTORED_ABOVE = 1 << 27
+
+
+def oracle_form(md, B, F, L):
+    """'dense' or 'factored': the form forward_train(form=None) takes for a batch of B queries, L sampled entities each."""
+    d = int(md["ent_emb_size"])
+    return "factored" if max(B * F * d, B * (L or 0) * d) > FACTORED_ABOVE else "dense"
+
+
+def forward_train(p, md, batch, keep_hidden, keep_out, dtype=torch.float64, keep_ctx=None, form=None):
     """p: dict leaf name -> torch tensor (requires_grad where trainable).  batch: e1, rel int64 [B],
     lookup int64 [B,L], labels float [B,L].  keep_*: 0/1 masks (numpy) for the two dropouts.
-    Returns loss (scalar tensor) and the BN batch statistics dict."""
+    Returns loss (scalar tensor) and the BN batch statistics dict.
+
+    form: 'dense' restates the reference as written: the generated dense layer forms Wg = v P [B, F, d] and the sampled scorer
+    gathers ent_emb[lookup] [B, L, d].  'factored' reassociates both and forms neither: z = sum_rho v[b, rho] (x P_rho)[b, :]
+    with P viewed as [n_last, F, d], and the sampled scores are a gather from h E^T + pred_bias [B, |E|].  The same mathematics in
+    float64 (tests/test_train_oracle.py holds the two to 1e-12).  None: chosen by size (oracle_form)."""
     d, r = int(md["ent_emb_size"]), int(md["rel_emb_size"])
     H = int(md.get("emb_h", 10))
     Wd = d // H
@@ -92,6 +110,11 @@ def forward_train(p, md, batch, keep_hidden, keep_out, dtype=torch.float64, keep
     lookup = None if batch.get("lookup", None) is None else torch.as_tensor(batch["lookup"]).long()
     labels = torch.as_tensor(batch["labels"]).to(dtype)
     B = e1.shape[0]
+    if form is None:
+        Fd = int(p["fc_weights/CPG/Projection%d" % len(ctx_out)].shape[-1]) // d if (ctx_out is not None and not lookup_params) else 0
+        form = oracle_form(md, B, Fd, 0 if lookup is None else lookup.shape[1])
+    if form not in ("dense", "factored"):
+        raise ValueError("form: 'dense', 'factored' or None, not %r" % (form,))
     x0 = p["ent_emb"][e1]
     c = None if lookup_params else p["rel_emb"][rel]          # g_lookup passes the ids through (models.py:180)
     img = x0.reshape(B, H, Wd)
@@ -138,6 +161,12 @@ def forward_train(p, md, batch, keep_hidden, keep_out, dtype=torch.float64, keep
     elif lookup_params:
         Wg = p["fc_weights"][rel].reshape(B, F, d)                       # ParameterLookup.generate (models.py:90-94)
         z = torch.einsum("bf,bfk->bk", x, Wg) + p["fc_bias"][rel]
+    elif form == "factored":
+        v = _generate(p, md, "fc_weights", c, train_stats, keep_ctx, stats, dtype, project=False)
+        Pl = p["fc_weights/CPG/Projection%d" % len(ctx_out)]
+        xP = torch.einsum("bf,rfk->brk", x, Pl.reshape(Pl.shape[0], F, d))   # x P_rho for every rho: [B, n_last, d]
+        bg = _generate(p, md, "fc_bias", c, train_stats, keep_ctx, stats, dtype)
+        z = torch.einsum("br,brk->bk", v, xP) + bg
     else:
         Wg = _generate(p, md, "fc_weights", c, train_stats, keep_ctx, stats, dtype).reshape(B, F, d)   # models.py:70,73
         bg = _generate(p, md, "fc_bias", c, train_stats, keep_ctx, stats, dtype)
@@ -154,6 +183,8 @@ def forward_train(p, md, batch, keep_hidden, keep_out, dtype=torch.float64, keep
     h = torch.relu(z)
     if lookup is None:
         s = h @ p["ent_emb"].T + p["pred_bias"]                                        # models.py:434-437
+    elif form == "factored":
+        s = torch.gather(h @ p["ent_emb"].T + p["pred_bias"], 1, lookup)
     else:
         s = torch.einsum("bk,blk->bl", h, p["ent_emb"][lookup]) + p["pred_bias"][lookup]   # models.py:439-443
     eps_ls = float(md.get("label_smoothing_epsilon", 0.0))
@@ -217,9 +248,9 @@ class AMSGrad(object):
         return gn
 
 
-def train_step(params_np, md, batch, opt: AMSGrad, seed, step, momentum):
+def train_step(params_np, md, batch, opt: AMSGrad, seed, step, momentum, form=None):
     """One reference-semantics step in float64.  Mutates params_np (incl. BN moving statistics).  Returns
-    (loss, grads dict, global grad norm)."""
+    (loss, grads dict, global grad norm).  form: forward_train's."""
     names = trainable_names(md)
     p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=(k in names)) for k, v in params_np.items()}
     B = len(batch["e1"])
@@ -238,7 +269,7 @@ def train_step(params_np, md, batch, opt: AMSGrad, seed, step, momentum):
     for gi, (g, ctx) in enumerate((("fc_weights", ctx_o), ("fc_bias", ctx_o), ("conv1_weights", ctx_c), ("conv1_bias", ctx_c))):
         for i, n in enumerate(ctx):
             kc[(g, i)] = dropout_keep(seed, step, 16 + 8 * gi + i, B * int(n), float(md.get("context_rel_dropout", 0.0)))
-    loss, stats, _, _ = forward_train(p, md, batch, kh, ko, keep_ctx=kc)
+    loss, stats, _, _ = forward_train(p, md, batch, kh, ko, keep_ctx=kc, form=form)
     loss.backward()
     grads = {k: p[k].grad.numpy().copy() for k in names}
     for bn, (mean, var, n) in stats.items():

@@ -158,27 +158,32 @@ def test_train_step_matches_oracle_over_batch_shapes(name, B, L, train_stats):
     _train_step_case(name, train_stats, False, "n0.1", B=B, L=L, steps=2)
 
 
-def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3, edit=None):
+def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3, edit=None, case=None, form=None, clip_norm=5.0,
+                     grads_out=None, batch_seed=100):
     """`edit(m, ref)`: a change of the variables made to both sides before the last step (tests/test_gpu_between_calls.py); the
-    oracle then restarts from the device's variables before every step, each held to the step-0 bounds."""
+    oracle then restarts from the device's variables before every step, each held to the step-0 bounds.
+    `case`: the model's dimensions (else _CASES[name]; a `case` restarts the oracle like `edit`); `form`: the oracle's
+    (coper_train_oracle.forward_train); `clip_norm`: both sides'; `grads_out`: a dict that receives the device's step-0 gradients;
+    step i trains on _batch(seed=batch_seed + i).  Returns the oracle's global gradient norm of every step."""
     from coper_amd.models import ConvE
     from oracle import coper_train_oracle as T
     md = dict(cdata._COMMON)
-    md.update(_CASES[name])
+    md.update(_CASES[name] if case is None else case)
     md.update(batch_norm_train_stats=train_stats, batch_norm_momentum=0.9, hidden_dropout=0.3, output_dropout=0.2,
               label_smoothing_epsilon=0.1, learning_rate=0.003)
     p0 = cdata.synthetic_params(md, seed=21, ent_std=0.1) if init == "n0.1" else cdata.reference_init_params(md, 21)
     seed = 5
     m = ConvE(md, device="cuda:0")
     m.load_parameters({k: torch.as_tensor(np.array(v, np.float32)) for k, v in p0.items()})
-    m.train_init(seed=seed)
+    m.train_init(seed=seed, clip_norm=clip_norm)
     ref = {k: np.array(v, np.float64) for k, v in p0.items()}
-    opt = T.AMSGrad(T.trainable_names(md), ref, lr=md["learning_rate"])
+    opt = T.AMSGrad(T.trainable_names(md), ref, lr=md["learning_rate"], clip=clip_norm)
     # the wide and the random-shape cases restart the oracle from the device's variables before every step, so that each step is held to the
     # step-0 bounds (the other cases let the two trajectories run free and bound the Adam-amplified drift instead)
-    sync = name.endswith("_wide") or name.startswith("fuzz_") or edit is not None
+    sync = name.endswith("_wide") or name.startswith("fuzz_") or edit is not None or case is not None
+    norms = []
     for step in range(steps):
-        batch = _batch(md, B, L, seed=100 + step)
+        batch = _batch(md, B, L, seed=batch_seed + step)
         if edit is not None and step == steps - 1:
             edit(m, ref)
         if sync and step > 0:
@@ -190,13 +195,16 @@ def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3, e
             np.put_along_axis(dense, batch["lookup_values"].astype(np.int64), batch["e2_multi"], axis=1)
             batch = dict(e1=batch["e1"], rel=batch["rel"], e2_multi=dense, lookup_values=np.zeros((B, 0), np.int32))
         ob = dict(e1=batch["e1"], rel=batch["rel"], lookup=None if one_vs_all else batch["lookup_values"], labels=batch["e2_multi"])
-        loss_o, grads_o, gn_o = T.train_step(ref, md, ob, opt, seed=seed, step=step, momentum=md["batch_norm_momentum"])
+        loss_o, grads_o, gn_o = T.train_step(ref, md, ob, opt, seed=seed, step=step, momentum=md["batch_norm_momentum"], form=form)
+        norms.append(gn_o)
         loss = float(m.train_step(batch).cpu()[0])
         assert abs(loss - loss_o) < (2e-5 if tight else 2e-4) * max(1.0, abs(loss_o)), (step, loss, loss_o)
         dg = {}
         for leaf in T.trainable_names(md):
             g, gn = m.train_grad(leaf)
             g = g.cpu().numpy().reshape(grads_o[leaf].shape)
+            if grads_out is not None and step == 0:
+                grads_out[leaf] = g
             err = _rel_err(g, grads_o[leaf], 1e-3 * gn_o)
             # step 0 starts from identical variables; later steps inherit the (bounded, Adam-amplified) differences of the
             # variables themselves, which the gradients see
@@ -230,6 +238,7 @@ def _train_step_case(name, train_stats, one_vs_all, init, B=48, L=37, steps=3, e
     # (the variables carry the Adam-amplified rounding differences bounded above: a sanity check of the rebuild)
     assert np.abs(h - hr).max() < 1e-3
     m.close()
+    return norms
 
 
 def test_train_rejects_unsupported_variants_and_order():

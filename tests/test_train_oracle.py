@@ -124,3 +124,73 @@ def test_inference_oracle_matches_sister_model_scores_incl_mlp_generator(golden_
     out = O.forward({k: np.asarray(v, np.float32) for k, v in p.items()}, md, batch["e1"], batch["rel"], np.float64)
     s = out["h"] @ np.asarray(p["ent_emb"], np.float64).T + np.asarray(p["pred_bias"], np.float64)
     assert np.abs(sigmoid(s) - g[tag + ":S"]).max() < 2e-6
+
+
+_FORM_CASES = {
+    "cpg_linear": dict(context_rel_conv=None, context_rel_out=[]),
+    "cpg_mlp_bn": dict(context_rel_conv=None, context_rel_out=[12], context_rel_use_batch_norm=True, context_rel_dropout=0.2),
+    "cpg_mlp2": dict(context_rel_conv=None, context_rel_out=[9, 7], context_rel_use_batch_norm=False, context_rel_dropout=0.1),
+    "cpg_conv_mlp": dict(context_rel_conv=[5], context_rel_out=[7], context_rel_use_batch_norm=True, context_rel_dropout=0.2),
+    "cpg_linear_concat": dict(context_rel_conv=None, context_rel_out=[], concat_rel=True),
+    "plain": dict(rel_emb_size=40, context_rel_conv=None, context_rel_out=None),
+    "lookup": dict(rel_emb_size=1, context_rel_conv=[], context_rel_out=[], do_parameter_lookup=True),
+}
+
+
+@pytest.mark.parametrize("train_stats,one_vs_all", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("name", sorted(_FORM_CASES))
+def test_factored_form_is_the_dense_form(name, train_stats, one_vs_all):
+    """forward_train(form='factored') -- the generated dense layer as sum_rho v[b, rho] (x P_rho), the sampled scores gathered from
+    h E^T + pred_bias -- against the form that restates the reference (Wg [B, F, d], ent_emb[lookup]): the same loss, gradients,
+    global norm and variables after two AMSGrad steps (BN moving statistics included) to 1e-12.
+
+    What the factored form costs at the shapes of tests/test_gpu_train_large.py (float64 torch on 8 CPU cores, one train_step,
+    dominated by x P_rho and its two backward products; drawing the variables adds 1 - 2 s): fb15k237_cpg dimensions with
+    |E| = 3000 at B = 48 / 300 / 389 / 1000, L = 37: 2.4 / 2.6 / 2.6 / 3.5 s;  fb15k237_cpg at full size, B = 512, L = 1000: 2.7 s,
+    3.6 GB peak;  wn18rr_cpg at full size, B = 512, L = 1000: 1.4 s;  the same 1-vs-all: 2.3 s.  The dense form of the fb15k237_cpg
+    step at B = 512 would need 3.8 GB for Wg alone, twice that under autograd."""
+    md = dict(cdata._COMMON)
+    md.update(num_ent=61, num_rel=5, ent_emb_size=40, rel_emb_size=8, emb_h=10, emb_w=4, conv_num_channels=8)
+    md.update(_FORM_CASES[name])
+    md.update(batch_norm_train_stats=train_stats, batch_norm_momentum=0.9, hidden_dropout=0.3, output_dropout=0.2,
+              label_smoothing_epsilon=0.1)
+    p0 = cdata.synthetic_params(md, seed=6)
+    rng = np.random.default_rng(4)
+    B, L = 12, 9
+    runs = {}
+    for form in ("dense", "factored"):
+        ref = {k: np.array(v, np.float64) for k, v in p0.items()}
+        opt = T.AMSGrad(T.trainable_names(md), ref, lr=0.003, clip=0.05)    # (a clip below the norm: the scale is compared too)
+        out = []
+        for step in range(2):
+            rng = np.random.default_rng(40 + step)
+            lookup = rng.integers(0, 61, (B, L))
+            labels = (rng.random((B, L)) < 0.3).astype(np.float32)
+            if one_vs_all:
+                dense = np.zeros((B, 61), np.float32)
+                np.put_along_axis(dense, lookup, labels, axis=1)
+                lookup, labels = None, dense
+            batch = dict(e1=rng.integers(0, 61, B), rel=rng.integers(0, 5, B), lookup=lookup, labels=labels)
+            out.append(T.train_step(ref, md, batch, opt, seed=3, step=step, momentum=0.9, form=form))
+        runs[form] = (out, ref)
+    (da, ra), (fa, rf) = runs["dense"], runs["factored"]
+    for (l0, g0, n0), (l1, g1, n1) in zip(da, fa):
+        assert n0 > 0.05                                              # (the clip acts)
+        assert abs(l0 - l1) <= 1e-12 * max(1.0, abs(l0))
+        assert abs(n0 - n1) <= 1e-12 * n0
+        for k in g0:
+            assert np.abs(g0[k] - g1[k]).max() <= 1e-12 * max(np.abs(g0[k]).max(), 1e-3 * n0), k
+    for k in ra:
+        assert np.abs(ra[k] - rf[k]).max() <= 1e-12 * max(1.0, np.abs(ra[k]).max()), k
+
+
+def test_oracle_form_is_chosen_by_size():
+    md = dict(ent_emb_size=200)
+    assert T.oracle_form(md, 48, 4608, 37) == "dense"             # (every case of tests/test_gpu_train.py)
+    assert T.oracle_form(md, 512, 4608, 1000) == "factored"
+    assert T.oracle_form(md, 24, 0, 9000) == "dense"
+    assert T.oracle_form(md, 700, 0, 1000) == "factored"
+    with pytest.raises(ValueError):
+        md, p, batch = _setup(True)
+        pt = {k: torch.tensor(np.asarray(v, np.float64)) for k, v in p.items()}
+        T.forward_train(pt, md, batch, np.ones(10 * O.Dims(md).F, np.float32), np.ones(400, np.float32), form="wide")
