@@ -246,8 +246,9 @@ static int alloc_workspace(coper_handle* h, int64_t cap, int ksplit, hipStream_t
       (rc = g.inv_perm.alloc(h, cap, "inv_perm")) || (rc = g.sorted_row.alloc(h, cap, "sorted_row")) ||
       (rc = g.sorted_rid.alloc(h, cap, "sorted_rid")) || (rc = g.tiles.alloc(h, 4 * (cap / 32 + dm.R + 4), "tiles")) ||
       (rc = g.n_tiles.alloc(h, 4, "n_tiles")) || (rc = h->blk_off.alloc(h, dm.R + 2, "blk_off")) ||
-      (rc = h->x_sorted.alloc(h, (size_t)cap * dm.F_pad, "x_sorted")) ||
-      (rc = h->z_part.alloc(h, (size_t)ksplit * cap * dm.d_pad16, "z_part")) ||
+      // (a factored handle has neither fp32 x rows nor per-tile partial sums: its encoder's workspaces are factored_workspace's)
+      (rc = h->x_sorted.alloc(h, h->factored ? 1 : (size_t)cap * dm.F_pad, "x_sorted")) ||
+      (rc = h->z_part.alloc(h, h->factored ? 1 : (size_t)ksplit * cap * dm.d_pad16, "z_part")) ||
       (rc = h->tgt_ws.alloc(h, 2 * cap, "tgt_ws")) ||    // [mode logit | exact-chain logit] (coper_target_scores)
       (rc = h->cnt_ws.alloc(h, 2 * cap, "cnt_ws")))
     return rc;
@@ -273,6 +274,10 @@ static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t
   if (h->cfg.score_mode != COPER_SCORE_F32 && (size_t)nnz > h->row_of_ws.size()) {
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
     if ((rc = h->row_of_ws.alloc(h, (size_t)nnz, "row_of_ws"))) return rc;
+  }
+  if (h->factored && h->fac_chunk > 0 && factored_workspace_short(h, B)) {     // (its own group: bounded by the chunk, not by the batch)
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = factored_workspace(h, B))) return rc;
   }
   if (h->ws_queries > 0 && B <= h->ws_queries) return COPER_OK;
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
@@ -361,6 +366,8 @@ COPER_API int coper_create(const coper_config* cfg, coper_handle** out) {
     return bad("role: COPER_ROLE_BOTH, COPER_ROLE_ENCODE or COPER_ROLE_SCORE");
   if (cfg->rel_mod_world < 0 || (cfg->rel_mod_world > 1 && (cfg->rel_mod_rank < 0 || cfg->rel_mod_rank >= cfg->rel_mod_world)))
     return bad("rel_mod_world >= 0 and 0 <= rel_mod_rank < rel_mod_world");
+  if (cfg->dense_mode != COPER_DENSE_CACHED && cfg->dense_mode != COPER_DENSE_FACTORED)
+    return bad("dense_mode: COPER_DENSE_CACHED or COPER_DENSE_FACTORED");
   // models.py:360: e1 stacked on the reshaped relation only for plain ConvE
   dm.stacked = !dm.gen_conv && !dm.gen_fc && !dm.lookup;
   dm.in_h = dm.emb_h; dm.in_w = dm.emb_w;
@@ -372,6 +379,22 @@ COPER_API int coper_create(const coper_config* cfg, coper_handle** out) {
     return bad("do_parameter_lookup with both contexts None is ill-formed in the reference (models.py:263-264 vs :360)");
   }
   if (dm.lookup && dm.concat_rel) return bad("g_lookup passes relation ids as rel_emb: cannot concat_rel (models.py:180,406)");
+  if (cfg->dense_mode == COPER_DENSE_FACTORED) {
+    // the factored path contracts a generator's context with its last projection: it needs a generator, the 16-bit arithmetic, an
+    // encoder -- and has no cache that could be split by relation
+    const char* why = !dm.gen_fc        ? "the dense layer is not generated (context_rel_out is None)"
+                      : dm.lookup       ? "g_lookup holds every W_r as a table row: there is no projection to factor"
+                      : cfg->score_mode != COPER_SCORE_BF16X3 ? "COPER_SCORE_BF16X3 only (the product runs on the 16-bit matrix cores)"
+                      : cfg->role == COPER_ROLE_SCORE ? "a COPER_ROLE_SCORE handle has no encoder"
+                      : cfg->rel_mod_world > 1 ? "rel_mod_world > 1 splits the weight cache by relation: a factored handle has none"
+                                        : nullptr;
+    if (why) {
+      int rc = fail(nullptr, COPER_EUNSUPPORTED, std::string("coper_create: COPER_DENSE_FACTORED: ") + why);
+      delete h;
+      return rc;
+    }
+    h->factored = true;
+  }
   dm.Ho = dm.in_h - dm.fh + 1; dm.Wo = dm.in_w - dm.fw + 1;
   if (dm.Ho <= 0 || dm.Wo <= 0) return bad("conv filter larger than the image");
   dm.F_conv = (int64_t)dm.Ho * dm.Wo * dm.C;
@@ -608,7 +631,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   h->w_div = w_div; h->w_rem = w_rem;
   const int64_t n_own = w_div > 1 ? (dm.R > w_rem ? (dm.R - w_rem + w_div - 1) / w_div : 0) : dm.R;
   h->Rw = dm.gen_fc ? (w_div > 1 ? (dm.R + w_div - 1) / w_div : dm.R) : 1;
-  if ((rc = h->Wf.alloc(h, per_rel * h->Rw, "Wf"))) return rc;
+  if (!h->factored && (rc = h->Wf.alloc(h, per_rel * h->Rw, "Wf"))) return rc;
   DevBuf<float> ctx_sel;          // the generator contexts of the held relations, compacted (freed behind the synchronize below)
   if (dm.gen_fc) {
     if ((rc = h->fc_b_rel.alloc(h, (size_t)dm.R * dm.d, "fc_b_rel"))) return rc;
@@ -630,12 +653,14 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
                                             (size_t)n_own, hipMemcpyDeviceToDevice, s));
         ctx = ctx_sel;
       }
-      if ((rc = launch_gen_dense_frag(h, ctx, h->Rw, K, P(buf), 0, h->Wf, s))) return rc;
+      if (h->factored) {      // no W_r: the context and the packed projection are the handle's dense layer (e_x first: its device word)
+        if ((rc = compute_x_exp(h, h->band_consts + 5, s)) || (rc = factored_prepare(h, ctx, K, P(buf), s))) return rc;
+      } else if ((rc = launch_gen_dense_frag(h, ctx, h->Rw, K, P(buf), 0, h->Wf, s))) return rc;
     }
   } else {
     if ((rc = launch_gen_dense_frag(h, nullptr, 1, 0, P("fc_weights"), 1, h->Wf, s))) return rc;
   }
-  h->enc_bf16 = cfg.score_mode != COPER_SCORE_F32 && conv_bf16_supported(dm);
+  h->enc_bf16 = !h->factored && cfg.score_mode != COPER_SCORE_F32 && conv_bf16_supported(dm);   // (the CACHED 16-bit encoder)
   if (w_div > 1 && !h->enc_bf16)
     return fail(h, COPER_EUNSUPPORTED, "rel_mod_world > 1: the configuration is not served by the 16-bit encoder");
   if (h->enc_bf16) {
@@ -781,6 +806,23 @@ static int encode_partials(coper_handle* h, PassCtx& ctx, const int64_t* e1, con
   const Dims& dm = h->dm;
   int rc;
   if ((rc = ensure_workspace(h, B, 0, s))) return rc;
+  if (h->factored) {
+    // COPER_DENSE_FACTORED: conv -> x planes, one GEMM with the packed projection, contraction with the relation's context
+    // (kernels_dense_factored_bf16.hip).  Nothing is grouped and nothing rides in its launches: the pending hand-offs are treated as
+    // the non-fused branch below treats them.  h_x3 receives finished rows.
+    if (stream_is_capturing(s)) return fail(h, COPER_EUNSUPPORTED, "COPER_DENSE_FACTORED: the factored encoder cannot be captured into a graph");
+    *ksplit_out = 0;
+    h->gcur = 0;
+    h->pipe.gdone.done = false;
+    h->pipe.gnext.pending = false;
+    if (const int64_t n = h->pipe.take_stage())
+      if ((rc = launch_widen_ids(h, h->pipe.stage.src, n, h->pipe.stage.dst, s))) return rc;
+    if (const int64_t pn = h->pipe.take_post())
+      if ((rc = launch_copy_i32(h, h->pipe.post.src, pn, h->pipe.post.dst, s))) return rc;
+    if ((rc = launch_dense_factored(h, e1, rel, e1_rows, B, h_x3, s))) return rc;
+    if (finalized) *finalized = true;
+    return COPER_OK;
+  }
   const int tq = 32;
   // K-split of the dense layer depends on F only, never on the batch: h[b] is then a pure function of
   // (e1[b], rel[b]) -- bit-identical whatever batch, chunking or rank computes it.
@@ -1051,7 +1093,8 @@ COPER_API int coper_encode_rank(coper_handle* h, const int64_t* e1, const int64_
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, h_out == nullptr, s))) return rc;
   float* hv = h_out ? h_out : h->h_ws;
   if (!h->enc_bf16) {
-    // fp32-exact mode (or a configuration the bf16x3 encoder does not serve): the two-call path
+    // fp32-exact mode, a configuration the bf16x3 encoder does not serve, or COPER_DENSE_FACTORED (whose finish kernel writes fp32 h
+    // rows; coper_rank packs them): the two-call path
     if ((rc = coper_encode(h, e1, rel, B, e1_rows, hv, stream))) return rc;
     return coper_rank(h, hv, e2, filt_indptr, filt_idx, filt_nnz, B, ranks, n_equal, stream);
   }

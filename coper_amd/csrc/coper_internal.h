@@ -262,6 +262,19 @@ struct coper_handle {
   int x_exp = 0;                     // e_x: the conv activations enter the dense layer as x 2^e_x (from a bound; prepare)
   coper::DevBuf<int32_t> x3s;        // [4] the packed batch's exponents: [0] e_h, [1] e_E + e_h (bf16x3_chain.h)
   coper::DevBuf<float> ctx_tmp[2];   // generator hidden activations
+  // ---- COPER_DENSE_FACTORED (kernels_dense_factored_bf16.hip): no W_r cache; built by coper_prepare from the configuration
+  bool factored = false;             // coper_config.dense_mode == COPER_DENSE_FACTORED
+  int fac_K = 0;                     // width of the fc_weights generator's context
+  coper::DevBuf<float> fac_ctx;      // [R, fac_K] that context (rel_emb itself for g_linear)
+  coper::DevBuf<uint4> fac_P_hi;     // the generator's last projection as GEMM operand planes: rows (rho, k), contraction f
+  coper::DevBuf<uint4> fac_P_lo;
+  coper::DevBuf<int32_t> fac_exp;    // [4] device words: [0] e_P, [1] e_x (= x_exp), [2..3] the pack's reduction scratch
+  int64_t fac_chunk = 0;             // queries per GEMM (the slices of T stay within 256 MB)
+  int fac_nsplit = 1;                // K slices of the product
+  int fac_variant = 0;               // TgVariant of the product
+  coper::DevBuf<uint4> fac_x_hi;     // workspace: the chunk's x operand planes
+  coper::DevBuf<uint4> fac_x_lo;
+  coper::DevBuf<float> fac_T;        // workspace: [fac_nsplit][chunk][fac_K d] the product's K slices
 
   // ---- workspace (owned, grown lazily) ----
   int64_t ws_queries = 0;         // the capacity of the workspace group of ensure_workspace: 0 while any of it is missing
@@ -506,6 +519,11 @@ void group_home_views(coper_handle* h);             // set 0's views, after the 
 void group_sets_free(coper_handle* h);              // sets 1, 2 (back to home first)
 int group_sets_ensure(coper_handle* h, hipStream_t s);
 int launch_dense_finalize(coper_handle* h, const int64_t* rel, int64_t B, int ksplit, float* h_out, hipStream_t s);
+// kernels_dense_factored_bf16.hip (COPER_DENSE_FACTORED)
+int factored_prepare(coper_handle* h, const float* ctx, int Kc, const float* P_last, hipStream_t s);
+bool factored_workspace_short(const coper_handle* h, int64_t cap);    // the chunk workspaces do not serve `cap` queries yet
+int factored_workspace(coper_handle* h, int64_t cap);
+int launch_dense_factored(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, float* h_out, hipStream_t s);
 int launch_dense_finalize_pack(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, hipStream_t s);
 int launch_pair_targets_packed_bf16x3(coper_handle* h, PassCtx& ctx, const int64_t* e2, int64_t B, float* tgt, hipStream_t s);
 int score_all_dispatch(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s);

@@ -51,9 +51,13 @@ int tg_pack_both(coper_handle* h, const float* src, TgIdx ri, TgIdx ki, int64_t 
 // nsplit > 1: K is cut into nsplit slices whose partial sums go to `part` ([nsplit][M][N] floats) and are summed in slice order
 // sumsq: when not null, the sum of the squares of the stored C is added by the storing kernel to the TG_SUMSQ_SLOTS device
 // doubles at sumsq (a workgroup adds to slot (its index) % TG_SUMSQ_SLOTS: thousands of atomics on one address serialise)
+// variant: which of the two kernels runs.  TG_AUTO picks from (M, N, K) (the training step); the inference path pins the one it chose
+// from its configuration (tg_variant_for at the full chunk size), so that one element is summed in the same order whatever M arrives
+enum TgVariant { TG_AUTO = 0, TG_FOUR_WAVE = 1, TG_W128 = 2 };
 int tg_gemm_nt(coper_handle* h, TgPlanes X, int64_t M, TgPlanes Y, int64_t N, int64_t K, float* C, TgIdx ci, TgIdx cj, hipStream_t s,
-               int nsplit = 1, float* part = nullptr, double* sumsq = nullptr, bool leave_slices = false);
+               int nsplit = 1, float* part = nullptr, double* sumsq = nullptr, bool leave_slices = false, TgVariant variant = TG_AUTO);
 // (leave_slices: with nsplit > 1 the partial sums stay in `part` and C is not written -- the caller's next kernel adds them, in slice order)
+TgVariant tg_variant_for(int64_t M, int64_t N, int64_t K);   // what TG_AUTO runs for this shape (one-level row views of C)
 // slices that fill the chip when the output has few 128 x 128 tiles and K is long (1: no split)
 int tg_split_k(int64_t M, int64_t N, int64_t K);
 

@@ -510,17 +510,20 @@ int tg_split_k(int64_t M, int64_t N, int64_t K) {
   return sp < 2 ? 1 : (int)sp;
 }
 
+TgVariant tg_variant_for(int64_t M, int64_t N, int64_t K) { return tg_use_w128(M, N, K) ? TG_W128 : TG_FOUR_WAVE; }
+
 void tg_launch_w128(const TgPlanes& X, int64_t M, const TgPlanes& Y, int64_t N, int KS16, int KST, float* C, TgIdx ci, TgIdx cj, hipStream_t s,
                     int nsplit, float* part, double* sumsq);     // (reads X.exp / Y.exp)
 
 int tg_gemm_nt(coper_handle* h, TgPlanes X, int64_t M, TgPlanes Y, int64_t N, int64_t K, float* C, TgIdx ci, TgIdx cj, hipStream_t s,
-               int nsplit, float* part, double* sumsq, bool leave_slices) {
+               int nsplit, float* part, double* sumsq, bool leave_slices, TgVariant variant) {
   const int KS16 = (int)((K + 15) / 16), KST = (int)tg_ks_stride(K);
   if (nsplit < 1 || !part) nsplit = 1;
   // workgroup tiles of 128 x 128 (rows of both plane sets are padded to TG_ROW_PAD).  A 128 x 256 tile (64 x 128 per wave,
   // 512 B of fragments per MFMA instead of 683, two register buffers) measured 165 us against 148 on the dP shape
   // (4608 x 6400 x 512): one k-step of prefetch does not cover the fill latency.
-  if (tg_use_w128(M, N, K) && ci.seg == 0) {   // (two-level row views of C: the four-wave kernel)
+  const bool w128 = variant == TG_AUTO ? tg_use_w128(M, N, K) : variant == TG_W128;
+  if (w128 && ci.seg == 0) {   // (two-level row views of C: the four-wave kernel)
     tg_launch_w128(X, M, Y, N, KS16, KST, C, ci, cj, s, nsplit, part, sumsq);
     if (nsplit > 1 && !leave_slices)
       hipLaunchKernelGGL(k_tg_reduce, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, s, part, nsplit, M, N, C, ci, cj, sumsq);

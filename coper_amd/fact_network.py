@@ -18,7 +18,7 @@ __all__ = ["FactNetworkScorer"]
 
 class FactNetworkScorer(object):
     def __init__(self, state_dict, entity_embeddings, relation_embeddings, emb_2D_d1, emb_2D_d2, cpg, device=None,
-                 score_mode="bf16x3"):
+                 score_mode="bf16x3", dense="cached"):
         """state_dict: of fact_network.ConvE (cpg=False) or CPG_ConvE with cpg_fc_net=[] (cpg=True), tensors or
         arrays; entity / relation embeddings: the KG's tables (`kg.get_all_entity_embeddings()` etc.)."""
         sd = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in state_dict.items()}
@@ -27,7 +27,7 @@ class FactNetworkScorer(object):
         over, params = from_minerva_state_dict(sd, ent, rel, int(emb_2D_d1), int(emb_2D_d2), cpg=bool(cpg))
         md = dict(cdata._COMMON)
         md.update(over)
-        self.model = ConvE(md, device=device, score_mode=score_mode).load_parameters(params).prepare()
+        self.model = ConvE(md, device=device, score_mode=score_mode, dense=dense).load_parameters(params).prepare()
 
     def forward(self, e1, r, kg=None):
         """[B, num_entities] scores of every tail (`fact_network.py:139-167 / 339-391`)."""

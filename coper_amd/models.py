@@ -81,7 +81,7 @@ def _host(v):
 
 class ConvE(object):
     def __init__(self, model_descriptors: dict, device=None, shard=None, score_mode="f32", rank_band_kappa=0.0, band_audit_period=0,
-                 role="both", rel_mod=None):
+                 role="both", rel_mod=None, dense="cached"):
         md = dict(model_descriptors)
         # required keys, as models.py:99-105,119-130 reads them
         for key in ("use_negative_sampling", "label_smoothing_epsilon", "num_ent", "num_rel", "ent_emb_size",
@@ -110,9 +110,13 @@ class ConvE(object):
         if role not in ("both", "encode", "score"):
             raise ValueError("role: 'both', 'encode' (no entity planes; encode only) or 'score' (no generated weights; scoring only)")
         self.role = role
+        if dense not in ("cached", "factored"):
+            raise ValueError("dense: 'cached' (every generated W_r cached at prepare) or 'factored' (no cache: (x P) contracted with the "
+                             "relation's context per batch; cheap prepare, small footprint)")
+        self.dense = dense
         cfg = _lib.make_config(md, device=self.device.index or 0, shard=self.shard, score_mode=mode, rank_band_kappa=rank_band_kappa,
                                band_audit_period=band_audit_period, role={"both": _lib.ROLE_BOTH, "encode": _lib.ROLE_ENCODE, "score": _lib.ROLE_SCORE}[role],
-                               rel_mod=rel_mod)
+                               rel_mod=rel_mod, dense_mode={"cached": _lib.DENSE_CACHED, "factored": _lib.DENSE_FACTORED}[dense])
         self.rel_mod = (int(rel_mod[0]), int(rel_mod[1])) if rel_mod is not None else None
         h = C.c_void_p()
         rc = self._lib.coper_create(C.byref(cfg), C.byref(h))
@@ -602,6 +606,8 @@ class ConvE(object):
         static tensors valid until the next replay.  Every coper_* call inside is allocation-free after
         `reserve`, which is what makes the sequence capturable.  want_equal=False: ranks only (what the reference
         computes) -- in the bf16x3 mode the shorter sequence with the fused tail kernel; n_equal is then None."""
+        if self.dense == "factored":     # (refused before anything is captured; coper_encode_rank says the same on a capturing stream)
+            raise _lib.CoperError(7, "COPER_DENSE_FACTORED: the factored encoder cannot be captured into a graph")
         self._need_prepared()
         self.reserve(B, max_nnz)
         dev = self.device

@@ -41,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--num-labels", type=int, default=100)
     ap.add_argument("--eval-every", type=int, default=200)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--dense", choices=("cached", "factored"), default="cached",
+                    help="generated dense layer at inference: the per-relation weight cache, or the factored path whose prepare after "
+                         "a training step packs one projection instead of rebuilding every W_r (cpg variant only)")
     args = ap.parse_args(argv)
 
     work = args.workdir or tempfile.mkdtemp(prefix="coper_loop_")
@@ -54,7 +57,7 @@ def main(argv=None):
     md.update(num_ent=loader.num_ent, num_rel=loader.num_rel, ent_emb_size=200, learning_rate=0.003,
               label_smoothing_epsilon=0.1, hidden_dropout=0.2, output_dropout=0.2, batch_norm_train_stats=True,
               batch_norm_momentum=0.1)
-    model = ConvE(md, device="cuda:0", score_mode="bf16x3")
+    model = ConvE(md, device="cuda:0", score_mode="bf16x3", dense=args.dense)
     model.load_parameters(cdata.synthetic_params(md, seed=0))      # random init of the named architecture
     model.train_init(seed=0)
 
@@ -85,7 +88,7 @@ def main(argv=None):
     prefix = os.path.join(work, "checkpoints", "model_weights.ckpt")
     slots, powers = model.optimizer_state()
     weights.save_tf_checkpoint(prefix, {k: v.cpu().numpy() for k, v in model._tensors.items()}, slots, powers)
-    restored = ConvE(md, device="cuda:0", score_mode="bf16x3").load_parameters(weights.load_tf_checkpoint(prefix))
+    restored = ConvE(md, device="cuda:0", score_mode="bf16x3", dense=args.dense).load_parameters(weights.load_tf_checkpoint(prefix))
     again = evaluate(restored, test, "test*")
     assert again == final, (again, final)
     print("checkpoint %s.{index,data-00000-of-00001} restored: same test MRR" % prefix)

@@ -125,10 +125,27 @@ typedef struct coper_config {
    * COPER_EUNSUPPORTED from coper_prepare otherwise; no training. */
   int32_t rel_mod_world;
   int32_t rel_mod_rank;
-  int32_t reserved[1];
+  /* How the handle applies a GENERATED dense layer at inference (0 = COPER_DENSE_CACHED = every earlier caller; the field took the
+   * last reserved slot: the struct size and COPER_ABI_VERSION are unchanged).
+   *   COPER_DENSE_CACHED: coper_prepare evaluates the generator once per relation and caches every W_r as MFMA images (R2 F d 4 bytes:
+   *     1.96 GB at FB15k-237 shapes); the encoder streams them.  Right for many queries over frozen weights.
+   *   COPER_DENSE_FACTORED: no W_r is ever formed.  coper_prepare keeps the [R2, K] context of the fc_weights generator and packs its
+   *     last projection P [K, F d] once (2 K d F 2 bytes); an encode computes  T[b] = x[b] P  (one GEMM [B, F] x [F, K d], in chunks of
+   *     a fixed number of queries so that T stays below 256 MB) and  h_pre[b, k] = sum_rho ctx[rel_b, rho] T[b, rho d + k] + fc_b[rel_b, k].
+   *     Right where the weights have just moved (an evaluation between training steps: coper_prepare costs a pack of P, not R2 weight
+   *     sets) or the handle only ever sees small batches.  Everything downstream of h -- coper_score_all, coper_rank, the exact band,
+   *     the audit, top-k -- is the same code.  h[b] stays a pure function of (e1[b], rel[b]) and the parameters (the power of two of x,
+   *     the K slices and the GEMM variant are chosen from the configuration at coper_prepare, never from the batch), but it is NOT
+   *     bit-equal to a cached handle's h: the sums run in another order.  Ranks are the fp32 chain's ranks on the handle's own h.
+   *     Accepted for COPER_SCORE_BF16X3 with context_rel_out set and do_parameter_lookup off, role BOTH or ENCODE; COPER_EUNSUPPORTED from
+   *     coper_create for plain ConvE, g_lookup, COPER_SCORE_F32, COPER_ROLE_SCORE and rel_mod_world > 1 (there is no cache to split).
+   *     coper_encode / coper_encode_rank on a stream that is being captured return COPER_EUNSUPPORTED.  Pending coper_stage_ids_next /
+   *     coper_post_i32_next jobs are served by launches of their own, a pending coper_group_next is dropped. */
+  int32_t dense_mode;           /* coper_dense_mode */
 } coper_config;
 
 typedef enum coper_role { COPER_ROLE_BOTH = 0, COPER_ROLE_ENCODE = 1, COPER_ROLE_SCORE = 2 } coper_role;
+typedef enum coper_dense_mode { COPER_DENSE_CACHED = 0, COPER_DENSE_FACTORED = 1 } coper_dense_mode;
 
 typedef struct coper_handle coper_handle;
 
