@@ -964,6 +964,37 @@ COPER_API int coper_score_rows(coper_handle* h, const float* hvec, const float* 
   return launch_exact_rows(h, hvec, rows, bias, B, out, (hipStream_t)stream);     // (the chain is the f32 mode's own logit)
 }
 
+// the workspaces of the pruned top-k (kernels_topk_bf16.hip) for B queries, k candidate blocks per query beside the filter entries
+static bool topk_pruned_fits(const coper_handle* h, int64_t B, int64_t k, int64_t filt_nnz) {
+  return topk_expand(h) * (k * B + filt_nnz) + 32 * h->dm.n_eblk * topk_nseg(h->dm.n_eblk) < 0x7fffffffLL;   // int32 slot ids
+}
+static int ensure_topk_workspace(coper_handle* h, int64_t B, int32_t k, int64_t filt_nnz, hipStream_t s) {
+  int rc;
+  const int XF = topk_expand(h);      // (2 on large tables: 64-entity candidate blocks, expanded to two 32-entity ones)
+  const size_t gneed = (size_t)(topk_gm_rows(h) * topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
+  const size_t t64 = (size_t)((int64_t)k * B + filt_nnz), tneed = (size_t)XF * t64;
+  const size_t cneed = topk_coarse_bytes(topk_gm_rows(h), topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
+  const size_t gv = (size_t)(h->dm.n_eblk * topk_nseg(h->dm.n_eblk));
+  if (gneed > h->gmax_ws.size() || tneed > h->cand_cap || (size_t)B > h->cand_tau_ws.size() || cneed > h->tk_coarse_ws.size() ||
+      !h->blk_cnt_ws || !h->blk_off_ws) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = h->tk_coarse_ws.ensure(h, cneed, "top-k coarse level")) || (rc = h->gmax_ws.ensure(h, gneed, "block maxima"))) return rc;
+    if (tneed > h->cand_cap) {
+      h->cand_cap = 0;
+      const size_t tlist = tneed + (XF > 1 ? t64 : 0);      // (+ the 64-entity level's own lists, behind the expanded ones)
+      if ((rc = h->cand_blk_ws.alloc(h, tlist, "candidate blocks")) || (rc = h->cand_q_ws.alloc(h, tlist, "candidate queries")) ||
+          (rc = h->cand_val_ws.alloc(h, tneed * 32, "candidate logits")) ||
+          (rc = h->cand_sorted_ws.alloc(h, topk_sorted_cap(gv, (int64_t)tneed), "sorted candidates")))
+        return rc;
+      h->cand_cap = tneed;
+    }
+    if ((rc = h->cand_tau_ws.ensure(h, (size_t)B, "candidate thresholds")) || (rc = h->blk_cnt_ws.ensure(h, 2 * gv, "block counts")) ||
+        (rc = h->blk_off_ws.ensure(h, gv + 1 + gv / 4096 + 2, "block offsets")))   // + chunk sums of the scan
+      return rc;
+  }
+  return COPER_OK;
+}
+
 static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt, const int64_t* e2,
                             const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
                             int32_t* n_greater, int32_t* n_equal, float* topk_val, int64_t* topk_idx, hipStream_t s) {
@@ -977,32 +1008,8 @@ static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, co
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, false, s))) return rc;
   // 0 < k <= COPER_TOPK_PRUNED_MAX (128): the count pass also writes block maxima and the top-k is selected from the few blocks that can
   // hold it (kernels_topk_bf16.hip): no logits workspace
-  const int XF = topk_expand(h);      // (2 on large tables: 64-entity candidate blocks, expanded to two 32-entity ones)
-  const bool pruned = k > 0 && k <= COPER_TOPK_PRUNED_MAX &&
-                      XF * ((int64_t)k * B + filt_nnz) + 32 * h->dm.n_eblk * topk_nseg(h->dm.n_eblk) < 0x7fffffffLL;   // int32 slot ids
-  if (pruned) {
-    const size_t gneed = (size_t)(topk_gm_rows(h) * topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
-    const size_t t64 = (size_t)((int64_t)k * B + filt_nnz), tneed = (size_t)XF * t64;
-    const size_t cneed = topk_coarse_bytes(topk_gm_rows(h), topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
-    const size_t gv = (size_t)(h->dm.n_eblk * topk_nseg(h->dm.n_eblk));
-    if (gneed > h->gmax_ws.size() || tneed > h->cand_cap || (size_t)B > h->cand_tau_ws.size() || cneed > h->tk_coarse_ws.size() ||
-        !h->blk_cnt_ws || !h->blk_off_ws) {
-      COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if ((rc = h->tk_coarse_ws.ensure(h, cneed, "top-k coarse level")) || (rc = h->gmax_ws.ensure(h, gneed, "block maxima"))) return rc;
-      if (tneed > h->cand_cap) {
-        h->cand_cap = 0;
-        const size_t tlist = tneed + (XF > 1 ? t64 : 0);      // (+ the 64-entity level's own lists, behind the expanded ones)
-        if ((rc = h->cand_blk_ws.alloc(h, tlist, "candidate blocks")) || (rc = h->cand_q_ws.alloc(h, tlist, "candidate queries")) ||
-            (rc = h->cand_val_ws.alloc(h, tneed * 32, "candidate logits")) ||
-            (rc = h->cand_sorted_ws.alloc(h, topk_sorted_cap(gv, (int64_t)tneed), "sorted candidates")))
-          return rc;
-        h->cand_cap = tneed;
-      }
-      if ((rc = h->cand_tau_ws.ensure(h, (size_t)B, "candidate thresholds")) || (rc = h->blk_cnt_ws.ensure(h, 2 * gv, "block counts")) ||
-          (rc = h->blk_off_ws.ensure(h, gv + 1 + gv / 4096 + 2, "block offsets")))   // + chunk sums of the scan
-        return rc;
-    }
-  }
+  const bool pruned = k > 0 && k <= COPER_TOPK_PRUNED_MAX && topk_pruned_fits(h, B, k, filt_nnz);
+  if (pruned && (rc = ensure_topk_workspace(h, B, k, filt_nnz, s))) return rc;
   if (h->cfg.score_mode != COPER_SCORE_F32) {
     if (!(ctx.packed_hvec == hvec && ctx.packed_B == B) && (rc = launch_pack_h_bf16(h, ctx, hvec, B, s))) return rc;
     COPER_DBG_SYNC(h, s, "pack_h");
@@ -1118,6 +1125,87 @@ COPER_API int coper_encode_rank(coper_handle* h, const int64_t* e1, const int64_
   if ((rc = launch_pair_targets_packed_bf16x3(h, ctx, e2, B, h->tgt_ws, s))) return rc;
   if ((rc = launch_exact_targets(h, hv, e2, B, h->tgt_ws + B, s))) return rc;
   return rank_counts_body(h, ctx, hv, h->tgt_ws, e2, filt_indptr, filt_idx, filt_nnz, B, 0, ranks, n_equal, nullptr, nullptr, s);
+}
+
+// ---- answering a query: the exact, filtered top-k of (e1, rel, ?) without a target (kernels_topk_bf16.hip: the predict section) ----
+COPER_API int coper_predict_topk(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const float* hvec,
+                                 const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
+                                 float* topk_val, int64_t* topk_idx, void* stream) {
+  if (!h) return COPER_EINVAL;
+  const bool by_ids = rel != nullptr || e1 != nullptr || e1_rows != nullptr;
+  const bool raw = !filt_indptr && !filt_idx && filt_nnz == 0;
+  if (k <= 0 || B < 0 || filt_nnz < 0) return fail(h, COPER_EINVAL, "coper_predict_topk: k >= 1, B >= 0, filt_nnz >= 0");
+  // (an empty batch names no arrays: B == 0 is COPER_OK on a prepared handle whichever form the NULL pointers suggest)
+  if (B > 0 && by_ids == (hvec != nullptr)) return fail(h, COPER_EINVAL, "coper_predict_topk: give either (e1 / e1_rows, rel) or hvec");
+  if (B > 0 && by_ids && (!rel || (!e1 && !e1_rows))) return fail(h, COPER_EINVAL, "coper_predict_topk: rel and one of e1 / e1_rows are needed");
+  if (!raw && (!filt_indptr || (filt_nnz > 0 && !filt_idx)))
+    return fail(h, COPER_EINVAL, "coper_predict_topk: half-given filter (indptr, idx and nnz together, or all NULL / 0)");
+  if (B > 0 && (!topk_val || !topk_idx)) return fail(h, COPER_EINVAL, "coper_predict_topk: no output buffers");
+  if (!h->prepared) return fail(h, COPER_ESTATE, "coper_prepare has not been called");
+  if (h->cfg.role == COPER_ROLE_ENCODE) return fail(h, COPER_EUNSUPPORTED, "coper_predict_topk: a COPER_ROLE_ENCODE handle has no entity table");
+  if (by_ids) COPER_REQUIRE_ENCODER(h);
+  if (B == 0) return COPER_OK;
+  if (B > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_predict_topk: batch too large");
+  const bool x3 = h->cfg.score_mode != COPER_SCORE_F32;
+  const int32_t kb = x3 ? k + PREDICT_SLACK : k;      // candidate blocks per query beside the filter entries
+  if (k > COPER_TOPK_PRUNED_MAX || !topk_pruned_fits(h, B, kb, filt_nnz))
+    return fail(h, COPER_EUNSUPPORTED, "coper_predict_topk: k <= 128 and (k + 4) B + filt_nnz candidate slots within int32 (split the batch)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = ensure_rank_workspace(h, B, filt_nnz, by_ids, s)) || (rc = ensure_topk_workspace(h, B, kb, filt_nnz, s))) return rc;
+  const size_t n_rows = x3 ? (size_t)(predict_rows_workgroups(h, B) * h->dm.n_local) : 0;
+  if ((size_t)(2 * B + 1) > h->pred_ids_ws.size() || (x3 && ((size_t)(3 * B) > h->pred_q_ws.size() || !h->pred_stats || n_rows > h->pred_rows_ws.size()))) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = h->pred_ids_ws.ensure(h, (size_t)(2 * B + 1), "predict ids"))) return rc;
+    if (x3) {
+      if ((rc = h->pred_q_ws.ensure(h, (size_t)(3 * B), "predict per-query words")) || (rc = h->pred_rows_ws.ensure(h, n_rows, "predict rows")))
+        return rc;
+      if (!h->pred_stats) {
+        if ((rc = h->pred_stats.alloc(h, 8, "predict statistics"))) return rc;
+        COPER_HIP_TRY(h, hipMemsetAsync(h->pred_stats, 0, 8 * sizeof(uint32_t), s));
+      }
+    }
+  }
+  // "no target" for the kernels that exempt one from the filter, and the empty CSR of a raw call
+  int64_t* no_target = h->pred_ids_ws;
+  COPER_HIP_TRY(h, hipMemsetAsync(no_target, 0xFF, sizeof(int64_t) * B, s));
+  if (raw) {
+    COPER_HIP_TRY(h, hipMemsetAsync(no_target + B, 0, sizeof(int64_t) * (B + 1), s));
+    filt_indptr = no_target + B;
+    filt_idx = no_target + B;      // (never read: every row is empty)
+  }
+  const float* hv = hvec;
+  if (by_ids) {
+    if ((rc = coper_encode(h, e1, rel, B, e1_rows, h->h_ws, stream))) return rc;
+    hv = h->h_ws;
+  }
+  h->pred_queries += B;
+  if (x3) {
+    PassCtx ctx;
+    if ((rc = launch_pack_h_bf16(h, ctx, hv, B, s))) return rc;
+    return launch_predict_topk_bf16x3(h, hv, no_target, filt_indptr, filt_idx, filt_nnz, B, k, topk_val, topk_idx, s);
+  }
+  // fp32 mode: block maxima and candidates ARE chain values; the counters of the count pass go to scratch, against targets no logit reaches
+  COPER_HIP_TRY(h, hipMemsetAsync(h->tgt_ws, 0x7f, sizeof(float) * 2 * B, s));
+  return launch_topk_pruned_f32(h, hv, h->tgt_ws, no_target, filt_indptr, filt_idx, filt_nnz, B, k, h->cnt_ws, nullptr, topk_val, topk_idx, s);
+}
+
+COPER_API int coper_predict_stats(coper_handle* h, int32_t reset, int64_t* n_queries, int64_t* n_unresolved, int64_t* n_rescored,
+                                  float* max_ratio, void* stream) {
+  if (!h) return COPER_EINVAL;
+  uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipStream_t s = (hipStream_t)stream;
+  if (h->pred_stats) {
+    COPER_HIP_TRY(h, hipMemcpyAsync(v, h->pred_stats, sizeof v, hipMemcpyDeviceToHost, s));
+    if (reset) COPER_HIP_TRY(h, hipMemsetAsync(h->pred_stats, 0, sizeof v, s));
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  }
+  if (n_queries) *n_queries = h->pred_queries;
+  if (n_unresolved) *n_unresolved = (int64_t)v[0];
+  if (n_rescored) { uint64_t r; memcpy(&r, &v[6], sizeof r); *n_rescored = (int64_t)r; }
+  if (max_ratio) memcpy(max_ratio, &v[2], sizeof(float));
+  if (reset) h->pred_queries = 0;
+  return COPER_OK;
 }
 
 COPER_API int coper_band_audit(coper_handle* h, int32_t reset, float* max_ratio, int64_t* n_pairs, void* stream) {

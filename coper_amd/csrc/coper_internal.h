@@ -299,6 +299,13 @@ struct coper_handle {
   coper::DevBuf<uint32_t> cand_tau_ws;  // [B] selection threshold per query (ordered float bits; 0: none)
   coper::DevBuf<int32_t> blk_cnt_ws;    // [2 n_eblk] slots per block | scatter cursors
   coper::DevBuf<int32_t> blk_off_ws;    // [n_eblk + 1] (+ the scan's chunk sums)
+  // coper_predict_topk (kernels_topk_bf16.hip: the predict section)
+  coper::DevBuf<int64_t> pred_ids_ws;   // [B] -1: "no target" for the kernels that exempt e2 from the filter | [B + 1] zeros: the raw call's CSR
+  coper::DevBuf<int32_t> pred_q_ws;     // [B] chain re-scores of the query (-1: unresolved) | [B] its audit ratio's float bits | [B] unresolved queries
+  coper::DevBuf<uint32_t> pred_stats;   // [8] since the last reset: [0] unresolved queries, [2] largest audit ratio (float bits), [4] unresolved of the
+                                        //   running call, [6..7] chain re-scores (64 bit); zeroed when allocated
+  coper::DevBuf<float> pred_rows_ws;    // [workgroups][n_local] chain logits of the unresolved queries being served
+  int64_t pred_queries = 0;             // queries answered since the last reset (host count)
   coper::DevBuf<uint4> hfrag16_hi;      // bf16x3: h hi / lo planes in fragment order
   coper::DevBuf<uint4> hfrag16_lo;
   coper::DevBuf<uint4> hrm16_hi;        //   row-major twins
@@ -491,6 +498,13 @@ int launch_topk_score_blocks_f32(coper_handle* h, const float* hvec, int64_t T, 
 int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
                            const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
                            int64_t* topk_idx, hipStream_t s);
+// coper_predict_topk: blocks emitted beyond the k + (filter entries) that hold the x3 top-k, so that the chain's top-k provably sits in
+// emitted blocks (kernels_topk_bf16.hip); the candidate workspaces are sized for k + PREDICT_SLACK
+constexpr int PREDICT_SLACK = 4;
+int64_t predict_rows_workgroups(const coper_handle* h, int64_t B);
+int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t* no_target, const int64_t* indptr, const int64_t* idx, int64_t nnz,
+                               int64_t B, int k, float* topk_val, int64_t* topk_idx, hipStream_t s);
+int score_count3_maxima_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s);
 int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
                               const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
                               int64_t* topk_idx, hipStream_t s);

@@ -1305,4 +1305,22 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
   return COPER_OK;
 }
 
+// The count kernel for its block maxima alone (coper_predict_topk): the caller has filled tband_ws with a band no logit reaches, so
+// no counter moves, no mask bit is set and there is nothing for k_band_exact to decide -- it is not launched, and the launch is not
+// one of those the audit period counts (band_launches: a prediction between two ranking passes leaves their audit schedule alone).
+int score_count3_maxima_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s) {
+  if (score_count3_mask_bytes(h, Bc) > h->mask_ws.size()) return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
+  if (!gmax) return fail(h, COPER_EINVAL, "score_count3_maxima: no block maxima buffer");
+  int rc;
+  ScopedKernelTimer t(h, "predict_maxima", s);
+  switch (h->dm.KS16) {
+#define SC3_CASE(KS_) case KS_: rc = sc3_gm<(KS_) / 2, (KS_) & 1>(h, q0, Bc, ng, gmax, gm_stride, s); break;
+    SC3_CASE(1) SC3_CASE(2) SC3_CASE(3) SC3_CASE(4) SC3_CASE(5) SC3_CASE(6) SC3_CASE(7) SC3_CASE(8) SC3_CASE(9) SC3_CASE(10)
+    SC3_CASE(11) SC3_CASE(12) SC3_CASE(13) SC3_CASE(14) SC3_CASE(15) SC3_CASE(16) SC3_CASE(17) SC3_CASE(18) SC3_CASE(19) SC3_CASE(20)
+#undef SC3_CASE
+    default: rc = fail(h, COPER_EUNSUPPORTED, "score_count3: ent_emb_size beyond 320");
+  }
+  return rc;
+}
+
 }  // namespace coper

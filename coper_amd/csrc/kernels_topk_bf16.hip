@@ -962,4 +962,282 @@ int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt,
   return COPER_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// coper_predict_topk, COPER_SCORE_BF16X3: the top-k of a query WITHOUT a target, exact by the fp32 chain.
+//
+// The matrix-core logits only prune.  Steps 1 - 3 are the pruned top-k above with two changes: the count kernel runs for its block
+// maxima alone (a band no logit reaches: score_count3_maxima_bf16x3), and the threshold kernel is asked for k + PREDICT_SLACK, so it
+// emits m + s blocks (m = k + filter entries) and leaves t_last, the smallest emitted maximum, in cand_tau.  Every listed id is masked:
+// the kernels that exempt a target read one that no entity has (-1).  Then, one workgroup per query (k_predict_select_x3):
+//   u_k   = the k-th largest x3 logit among the unmasked entities of the emitted blocks;
+//   tau_q = the band's bound for the query (x3_band_tau: a function of |h_q| and the table's constants), so every x3 logit is within
+//           tau_q / 2 of its chain value -- what the band audit checks, and what this kernel audits on every pair it re-scores;
+//   kept  = the candidates with x3 logit >= u_k - tau_q.  With v_k the chain's k-th largest value: u_k >= v_k - tau_q / 2 (the chain's
+//           top k have x3 logits that large) and v_k >= u_k - tau_q / 2 (the x3 top k have chain values that large), so every member
+//           of the chain's top-k has an x3 logit >= v_k - tau_q / 2 >= u_k - tau_q: it is kept, PROVIDED it was emitted.  An entity
+//           of a block that was not emitted has an x3 logit <= t_last; the query is RESOLVED when t_last < u_k - tau_q.
+//   The kept candidates are re-scored by the chain (exact_chain_pair on the registered fp32 rows) and the k largest by
+//   (chain value desc, id asc) are the answer.
+// A query that is not resolved (near-ties beyond the slack, more survivors than the LDS list holds) is listed on the device and
+// served by k_predict_rows in the same call: the chain logits of its whole row into a scratch row, k rounds of arg-max.  No host
+// synchronisation on either route.  (-inf thresholds / every block emitted: nothing is un-emitted, the query is resolved.)
+// ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float tk_unkey(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+constexpr int PS_CAP = 2048;   // survivors (candidates >= t_last) per query held in LDS
+
+struct PredictArgs {
+  const float* cand_val; const int32_t* cand_blk; const uint32_t* cand_tau; const int64_t* indptr;
+  const float* hvec; const float* ent; const float* bias; const unsigned* consts; const int32_t* x3s;
+  float* out_val; int64_t* out_idx; int32_t* q_kept; uint32_t* q_ratio;
+  int64_t B, lo; int k, ks, xf, d; float kappa;
+};
+
+__global__ __launch_bounds__(256) void k_predict_select_x3(const PredictArgs A) {
+  __shared__ float s_v[PS_CAP];     // x3 logit of the survivor (accumulator units: x 2^(e_E + e_h))
+  __shared__ int s_id[PS_CAP];      // its local row
+  __shared__ float s_c[PS_CAP];     // its chain logit; -inf: not kept
+  __shared__ float s_red[4];
+  __shared__ int s_n, s_nk;
+  __shared__ float s_uk;
+  __shared__ uint32_t s_ratio;
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const int k = A.k, d = A.d;
+  const int sexp = A.x3s[1];
+  const float* hr = A.hvec + q * d;
+  if (tid == 0) { s_n = 0; s_nk = 0; s_uk = -INFINITY; s_ratio = 0u; }
+  // |h_q|^2 -> tau_q
+  float s2 = 0.f;
+  for (int i = tid; i < d; i += 256) { const float v = hr[i]; s2 = fmaf(v, v, s2); }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s2 += __shfl_xor(s2, o);
+  if ((tid & 63) == 0) s_red[tid >> 6] = s2;
+  __syncthreads();
+  s2 = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  // (rounded up: a wider bound can only keep more candidates and resolve fewer queries)
+  const float tau = x3_band_tau(s2 * 1.00001f, A.kappa, A.consts, d, A.x3s) * 1.0001f;
+  const float tau_s = x3_scale(tau, sexp);
+  const int64_t beg = A.indptr[q] - A.indptr[0];
+  const int64_t off = A.xf * ((int64_t)A.ks * q + beg);
+  const int n = A.xf * (int)((int64_t)A.ks + (A.indptr[q + 1] - A.indptr[0] - beg)) * 32;
+  const float* val = A.cand_val + off * 32;
+  const int32_t* blk = A.cand_blk + off;
+  const uint32_t tkey = A.cand_tau[q];
+  for (int j = tid; j < n; j += 256) {
+    const int32_t b = blk[j >> 5];
+    if (b < 0) continue;               // unused slot
+    const float v = val[j];
+    if (!(v > -INFINITY) || tk_key(v) < tkey) continue;
+    const int pos = atomicAdd(&s_n, 1);
+    if (pos < PS_CAP) { s_v[pos] = v; s_id[pos] = b * 32 + (j & 31); }
+  }
+  __syncthreads();
+  const int S = s_n;
+  float* ov = A.out_val + q * k;
+  int64_t* oi = A.out_idx + q * k;
+  bool resolved = S <= PS_CAP;
+  if (resolved && S >= k) {
+    for (int i = tid; i < S; i += 256) {
+      const float v = s_v[i];
+      const int id = s_id[i];
+      int ahead = 0;
+      for (int t = 0; t < S; ++t) {
+        const float v2 = s_v[t];
+        ahead += (v2 > v || (v2 == v && s_id[t] < id)) ? 1 : 0;
+      }
+      if (ahead == k - 1) s_uk = v;
+    }
+  }
+  __syncthreads();
+  float thr = -INFINITY;
+  if (resolved && S >= k) {
+    thr = s_uk - tau_s;
+    thr -= fabsf(thr) * 2.4e-7f;       // (the subtraction's own rounding, downwards)
+    resolved = tkey == 0u || tk_unkey(tkey) < thr;
+  } else if (resolved) {
+    resolved = tkey == 0u;             // fewer than k survivors: only when everything was emitted
+  }
+  if (!resolved) {                     // (workgroup-uniform)
+    if (tid == 0) { A.q_kept[q] = -1; A.q_ratio[q] = 0u; }
+    return;
+  }
+  float rmax = 0.f;
+  for (int i = tid; i < S; i += 256) {
+    float c = -INFINITY;
+    if (s_v[i] >= thr) {
+      const int64_t row = s_id[i];
+      float unused = 0.f;
+      exact_chain_pair(A.ent + row * d, nullptr, hr, A.bias[row], 0.f, d, c, unused);
+      rmax = fmaxf(rmax, fabsf(x3_scale(s_v[i], -sexp) - c) / (0.5f * tau));
+      atomicAdd(&s_nk, 1);
+    }
+    s_c[i] = c;
+  }
+  if (rmax > 0.f) atomicMax(&s_ratio, __float_as_uint(rmax));     // (non-negative floats order as their bits; NaN bits are largest: seen)
+  __syncthreads();
+  const int C = s_nk;
+  for (int i = tid; i < S; i += 256) {
+    const float c = s_c[i];
+    if (!(c > -INFINITY)) continue;
+    const int id = s_id[i];
+    int ahead = 0;
+    for (int t = 0; t < S; ++t) {
+      const float c2 = s_c[t];
+      ahead += (c2 > c || (c2 == c && s_id[t] < id)) ? 1 : 0;
+    }
+    if (ahead < k) { ov[ahead] = c; oi[ahead] = A.lo + id; }
+  }
+  for (int r = C + tid; r < k; r += 256) { ov[r] = -INFINITY; oi[r] = -1; }
+  if (tid == 0) { A.q_kept[q] = C; A.q_ratio[q] = s_ratio; }
+}
+
+// one workgroup: the per-query words of the select kernel into the list of unresolved queries and the statistics
+__global__ __launch_bounds__(1024) void k_predict_reduce(const int32_t* __restrict__ q_kept, const uint32_t* __restrict__ q_ratio, int64_t B,
+                                                         int32_t* __restrict__ unres, uint32_t* __restrict__ stats) {
+  __shared__ int s_cnt;
+  __shared__ unsigned long long s_sum;
+  __shared__ uint32_t s_max;
+  if (threadIdx.x == 0) { s_cnt = 0; s_sum = 0ull; s_max = 0u; }
+  __syncthreads();
+  unsigned long long sum = 0ull;
+  uint32_t mx = 0u;
+  for (int64_t q = threadIdx.x; q < B; q += 1024) {
+    const int32_t c = q_kept[q];
+    if (c < 0) unres[atomicAdd(&s_cnt, 1)] = (int32_t)q;
+    else { sum += (unsigned long long)c; const uint32_t r = q_ratio[q]; mx = r > mx ? r : mx; }
+  }
+  if (sum) atomicAdd(&s_sum, sum);
+  if (mx) atomicMax(&s_max, mx);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    stats[4] = (uint32_t)s_cnt;
+    stats[0] += (uint32_t)s_cnt;
+    stats[2] = s_max > stats[2] ? s_max : stats[2];
+    *(unsigned long long*)(stats + 6) += s_sum;
+  }
+}
+
+// The unconditional route: workgroup w serves the unresolved queries w, w + grid, ...: the chain logit of every unfiltered entity of
+// the shard into the workgroup's scratch row (a known answer: -inf; the CSR rows are ascending: binary search), then k rounds of a
+// workgroup-wide arg-max in (value desc, id asc) order.
+__global__ __launch_bounds__(256) void k_predict_rows(const int32_t* __restrict__ unres, const uint32_t* __restrict__ stats,
+                                                      const float* __restrict__ hvec, const float* __restrict__ ent,
+                                                      const float* __restrict__ bias, const int64_t* __restrict__ indptr,
+                                                      const int64_t* __restrict__ idx, int64_t lo, int64_t n_local, int d, int k,
+                                                      float* __restrict__ rows, float* __restrict__ out_val, int64_t* __restrict__ out_idx) {
+  __shared__ float s_val[256];
+  __shared__ int s_idx[256];
+  const int n_unres = (int)stats[4];
+  float* row = rows + (int64_t)blockIdx.x * n_local;
+  for (int u = blockIdx.x; u < n_unres; u += gridDim.x) {
+    const int64_t q = unres[u];
+    const float* hr = hvec + q * d;
+    const int64_t fb = indptr[q], fe = indptr[q + 1];
+    for (int64_t j = threadIdx.x; j < n_local; j += 256) {
+      const int64_t gid = lo + j;
+      int64_t a = fb, b = fe;
+      while (a < b) { const int64_t m = (a + b) >> 1; if (idx[m] < gid) a = m + 1; else b = m; }
+      float v = -INFINITY, unused = 0.f;
+      if (!(a < fe && idx[a] == gid)) exact_chain_pair(ent + j * d, nullptr, hr, bias[j], 0.f, d, v, unused);
+      row[j] = v;
+    }
+    __syncthreads();
+    for (int round = 0; round < k; ++round) {
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int64_t j = threadIdx.x; j < n_local; j += 256) {
+        const float v = row[j];
+        if (v > best || (v == best && v > -INFINITY && (int)j < bi)) { best = v; bi = (int)j; }
+      }
+      s_val[threadIdx.x] = best;
+      s_idx[threadIdx.x] = bi;
+      __syncthreads();
+      for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+          const float v2 = s_val[threadIdx.x + o];
+          const int i2 = s_idx[threadIdx.x + o];
+          if (v2 > s_val[threadIdx.x] || (v2 == s_val[threadIdx.x] && i2 < s_idx[threadIdx.x])) { s_val[threadIdx.x] = v2; s_idx[threadIdx.x] = i2; }
+        }
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) {
+        const float v = s_val[0];
+        const int i = s_idx[0];
+        const bool ok = i != 0x7fffffff && v > -INFINITY;
+        out_val[q * k + round] = ok ? v : -INFINITY;
+        out_idx[q * k + round] = ok ? lo + i : -1;
+        if (ok) row[i] = -INFINITY;   // taken
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// workgroups (= scratch rows) of k_predict_rows: at most 64 MiB of rows, 256 workgroups, one per query
+int64_t predict_rows_workgroups(const coper_handle* h, int64_t B) {
+  int64_t w = ((int64_t)64 << 20) / (h->dm.n_local * 4);
+  if (w > 256) w = 256;
+  if (w > B) w = B;
+  return w < 1 ? 1 : w;
+}
+
+int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t* no_target, const int64_t* indptr, const int64_t* idx, int64_t nnz,
+                               int64_t B, int k, float* topk_val, int64_t* topk_idx, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const int ks = k + PREDICT_SLACK;
+  const int XF = topk_expand(h);
+  const int64_t G = dm.n_eblk, Gm = G / XF;
+  const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
+  const int64_t T64 = (int64_t)ks * B + nnz;
+  const int64_t T = XF * T64;
+  const int64_t W = predict_rows_workgroups(h, B);
+  if ((size_t)(Gm * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap || (size_t)(3 * B) > h->pred_q_ws.size() || !h->pred_stats ||
+      (size_t)(W * dm.n_local) > h->pred_rows_ws.size())
+    return fail(h, COPER_ESTATE, "predict top-k: workspace not reserved");
+  int rc;
+  // a band no logit reaches (0x7f7f7f7f = 3.4e38 on both ends): the count kernel counts nothing and marks nothing
+  COPER_HIP_TRY(h, hipMemsetAsync(h->tband_ws, 0x7f, sizeof(float) * h->tband_ws.size(), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_blk_ws, 0xFF, sizeof(int32_t) * (T + (XF > 1 ? T64 : 0)), s));
+  const int nseg = topk_nseg(G);
+  const int64_t GV = G * nseg;
+  COPER_HIP_TRY(h, hipMemsetAsync(h->blk_cnt_ws, 0, sizeof(int32_t) * 2 * GV, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_sorted_ws, 0xFF, sizeof(int32_t) * topk_sorted_cap(GV, T), s));
+  int32_t* blk64 = XF > 1 ? h->cand_blk_ws + T : nullptr;
+  int32_t* q64 = XF > 1 ? h->cand_q_ws + T : nullptr;
+  for (int64_t q0 = 0; q0 < B; q0 += qc) {
+    const int64_t bc = B - q0 < qc ? B - q0 : qc;
+    const int64_t qs = (bc + 127) / 128 * 128;
+    if ((rc = score_count3_maxima_bf16x3(h, q0, bc, h->cnt_ws, h->gmax_ws, qs, s))) return rc;
+    if (XF > 1) tk_dispatch_emit(h, Gm, qs, q0, bc, ks, indptr, s, blk64, q64, nullptr);
+    else tk_dispatch_emit(h, G, qs, q0, bc, ks, indptr, s);
+  }
+  if (XF > 1)
+    hipLaunchKernelGGL(k_topk_expand64, dim3((unsigned)((T64 + 255) / 256)), dim3(256), 0, s, blk64, q64, T64, h->cand_blk_ws, h->cand_q_ws,
+                       h->blk_cnt_ws, nseg);
+  tk_launch_blk_scan(h->blk_cnt_ws, GV, h->blk_off_ws, h->blk_off_ws + GV + 1, GV / TK_SCAN_CHUNK + 2, s);
+  hipLaunchKernelGGL(k_topk_blk_scatter, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, h->cand_blk_ws, T, h->blk_off_ws,
+                     h->blk_cnt_ws + GV, nseg, h->cand_sorted_ws);
+  const int64_t waves = topk_sorted_cap(GV, T) / 32;
+  hipLaunchKernelGGL(k_topk_score_blocks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)h->Ef16_hi,
+                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, GV, no_target,
+                     indptr, idx, h->cand_blk_ws, h->cand_q_ws, h->blk_off_ws, h->cand_sorted_ws, (int64_t)h->cfg.shard_lo,
+                     h->cand_val_ws, h->x3s);
+  PredictArgs A;
+  A.cand_val = h->cand_val_ws; A.cand_blk = h->cand_blk_ws; A.cand_tau = h->cand_tau_ws; A.indptr = indptr;
+  A.hvec = hvec; A.ent = h->params["ent_emb"].ptr; A.bias = h->params["pred_bias"].ptr; A.consts = h->band_consts; A.x3s = h->x3s;
+  A.out_val = topk_val; A.out_idx = topk_idx; A.q_kept = h->pred_q_ws; A.q_ratio = (uint32_t*)(h->pred_q_ws + B);
+  A.B = B; A.lo = (int64_t)h->cfg.shard_lo; A.k = k; A.ks = ks; A.xf = XF; A.d = dm.d; A.kappa = band_kappa(h);
+  hipLaunchKernelGGL(k_predict_select_x3, dim3((unsigned)B), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(k_predict_reduce, dim3(1), dim3(1024), 0, s, (const int32_t*)h->pred_q_ws, (const uint32_t*)(h->pred_q_ws + B), B,
+                     h->pred_q_ws + 2 * B, (uint32_t*)h->pred_stats);
+  hipLaunchKernelGGL(k_predict_rows, dim3((unsigned)W), dim3(256), 0, s, (const int32_t*)(h->pred_q_ws + 2 * B), (const uint32_t*)h->pred_stats,
+                     hvec, A.ent, A.bias, indptr, idx, A.lo, dm.n_local, dm.d, k, h->pred_rows_ws, topk_val, topk_idx);
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
+}
+
 }  // namespace coper

@@ -39,5 +39,15 @@ class FactNetworkScorer(object):
         e2 = np.asarray(e2.detach().cpu() if hasattr(e2, "detach") else e2).reshape(-1, 1).astype(np.int32)
         return torch.sigmoid(self.model.score_lookup(h, e2))
 
+    def predict_topk(self, e1, r, k, filt_indptr=None, filt_idx=None, kg=None):
+        """(scores f32 [B, k], entity ids int64 [B, k]): the top of `forward(e1, r)` -- with the CSR of known answers masked --
+        without the [B, num_entities] matrix: what the callers of `EmbeddingBasedMethod.predict` take on the host afterwards.
+        The sigmoid is monotonic, so the order is the logits' (coper_predict_topk: exact by the fp32 chain); padding stays
+        (sigmoid(-inf) = 0, -1)."""
+        e1 = e1.detach().cpu().numpy() if hasattr(e1, "detach") else np.asarray(e1)
+        r = r.detach().cpu().numpy() if hasattr(r, "detach") else np.asarray(r)
+        val, idx = self.model.predict_topk(e1.reshape(-1), r.reshape(-1), k, filt_indptr, filt_idx)
+        return torch.sigmoid(val), idx
+
     def close(self):
         self.model.close()

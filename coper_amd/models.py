@@ -598,6 +598,51 @@ class ConvE(object):
                                                         nnz, B, _ptr(h), _ptr(ranks), _ptr(ne), self._stream()))
         return (ranks, ne, h) if want_h else (ranks, ne)
 
+    def predict_topk(self, e1, rel, k, filt_indptr=None, filt_idx=None, e1_rows=None, h=None):
+        """Which entities complete (e1, rel, ?): (val f32 [B, k], idx int64 [B, k]) -- the k unfiltered entities of this shard with the
+        largest logit, (score desc, global id asc), padded with (-inf, -1) (coper_predict_topk).  Exact in both score modes: values,
+        set and order are those of the fp32 chain.  The filter is a CSR of known answers (global ids ascending per row; None = raw);
+        no entity is exempt.  Either (e1, rel[, e1_rows]) or h = finished embeddings [B, d]."""
+        self._need_prepared()
+        if (h is None) == (rel is None):
+            raise ValueError("predict_topk: give either (e1, rel) or h")
+        if (filt_indptr is None) != (filt_idx is None):
+            raise ValueError("predict_topk: filt_indptr and filt_idx together, or neither")
+        if h is None and e1 is not None and not any(isinstance(a, torch.Tensor) for a in (e1, rel, filt_indptr, filt_idx)):
+            if filt_indptr is not None:       # host batch: one pinned int32 buffer, one widening launch (as rank_pass)
+                e1, rel, filt_indptr, filt_idx = self.stage_batch(e1, rel, filt_indptr, filt_idx)
+            else:
+                e1, rel = self.stage_batch(e1, rel)
+        ip = self._ids(filt_indptr) if filt_indptr is not None else None
+        ix = self._ids(filt_idx) if filt_idx is not None else None
+        if h is not None:
+            h = h.to(device=self.device, dtype=torch.float32).contiguous()
+            B = int(h.shape[0])
+            e1 = rel = e1_rows = None
+        else:
+            rel = self._ids(rel)
+            e1 = self._ids(e1) if e1 is not None else None
+            B = rel.numel()
+            if e1_rows is not None:
+                e1_rows = e1_rows.to(device=self.device, dtype=torch.float32).contiguous()
+        if ip is not None and ip.numel() != B + 1:
+            raise ValueError("predict_topk: filt_indptr needs B + 1 entries")
+        nnz = int(ix.numel()) if ix is not None else 0
+        k = int(k)
+        tv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32)
+        ti = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.int64)
+        _lib.check(self._h, self._lib.coper_predict_topk(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), _ptr(h), _ptr(ip),
+                                                         _ptr(ix) if ip is not None else None, nnz, B, k, _ptr(tv), _ptr(ti), self._stream()))
+        return tv, ti
+
+    def predict_stats(self, reset=True):
+        """coper_predict_stats since the last reset: dict(queries, unresolved, rescored, max_ratio) -- queries answered, those served
+        by the whole-row route, candidates re-scored by the fp32 chain, and the largest |x3 - chain| / (tau_q / 2) among them."""
+        nq, nu, nr, ratio = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0.0)
+        _lib.check(self._h, self._lib.coper_predict_stats(self._h, 1 if reset else 0, C.byref(nq), C.byref(nu), C.byref(nr), C.byref(ratio),
+                                                          self._stream()))
+        return {"queries": int(nq.value), "unresolved": int(nu.value), "rescored": int(nr.value), "max_ratio": float(ratio.value)}
+
     def capture_rank_pass(self, B, max_nnz, want_equal=True):
         """hipGraph capture of one encode -> fused-rank pass for batches of exactly B queries (the reference's
         per-`session.run` batch, B = 512, is launch-bound: ~14 kernel launches per batch).  Returns

@@ -428,6 +428,35 @@ class EntityShardedRanker(object):
             raise RuntimeError("bf16x3 band audit: still above the band's allowance after 4 re-counted chunks")
         return self._merge(allrec, B, k)
 
+    # ------------------------------------------------------------------------------------------------ answering queries
+    def predict_topk(self, chunk, k):
+        """The global answer to (e1, rel, ?) for a chunk without targets: (val f32 [B, k], idx int64 [B, k]), the k unfiltered
+        entities with the largest fp32-chain logit in (score desc, id asc) order.  Steps 1 - 2 of the exchange give every rank the
+        chunk's h; the scorer handle answers for its rows (coper_predict_topk: exact per shard); ONE all-gather of [B, 2 k] words
+        and `merge_topk` give the same bits as an unsharded handle.  chunk: e1, rel and optionally filt_indptr / filt_idx."""
+        chunk = dict(chunk)
+        chunk.setdefault("e2", chunk["e1"])                # (the plan gathers target rows too; a prediction has none: any held id serves)
+        if chunk.get("filt_indptr") is None:
+            B0 = len(self._host_ids(chunk["rel"]))
+            chunk["filt_indptr"], chunk["filt_idx"] = np.zeros(B0 + 1, np.int64), np.zeros(0, np.int64)
+            raw = True
+        else:
+            raw = False
+        pl = self.plan(chunk)
+        B = pl.B
+        h = self._steps12(pl, chunk, self.group)[0]
+        val, idx = self.scorer.predict_topk(None, None, k, None if raw else chunk["filt_indptr"], None if raw else chunk["filt_idx"], h=h)
+        rec = torch.cat([val.contiguous().view(torch.int32).to(torch.int64), idx], dim=1).contiguous()      # [B, 2 k]
+        if self.dist:
+            allrec = torch.empty((self.world * B, 2 * k), dtype=torch.int64, device=rec.device)
+            self._all_gather(allrec, rec, self.group)
+            allrec = allrec.view(self.world, B, 2 * k)
+        else:
+            allrec = rec.view(1, B, 2 * k)
+        vals = allrec[:, :, :k].to(torch.int32).view(torch.float32).permute(1, 0, 2).reshape(B, self.world * k)
+        ids = allrec[:, :, k:].permute(1, 0, 2).reshape(B, self.world * k)
+        return merge_topk(vals.contiguous(), ids.contiguous(), k)
+
     # ------------------------------------------------------------------------------------------------ the evaluation loop
     def rank_stream(self, chunks, k=0, window=8):
         """Generator over `chunks` (an iterable of chunk dicts: e1 / rel / e2 host arrays, the CSR filter on the host or the

@@ -324,6 +324,36 @@ COPER_API int coper_encode_rank(coper_handle* h, const int64_t* e1, const int64_
                                 const int64_t* e2, const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz,
                                 int64_t B, float* h_out, int32_t* ranks, int32_t* n_equal, void* stream);
 
+/* Answering a query: which entities complete (e1, rel, ?).  The reference has no such entry point -- its callers take the top of
+ * `predictions` (models.py:183-192) on the host; coper_rank_counts' k > 0 side output needs a target and exempts it from the filter.
+ * For every query b, over the entities j of the handle's shard that are NOT in the query's filter row (no entity is exempt: there is
+ * no target), the k entries with the largest logit in (score desc, global id asc) order: topk_idx [B, k] global ids, topk_val [B, k]
+ * logits; rows with fewer than k unfiltered entities are padded with (-inf, -1) like coper_rank_counts.
+ *   query:   either (e1, rel, e1_rows) as coper_encode_rank takes them (hvec NULL), or hvec = finished h rows [B, d] (the others NULL);
+ *   filter:  CSR of known answers, GLOBAL ids ascending per row, filt_nnz = filt_indptr[B]; all NULL / 0 = raw (unfiltered).
+ * EXACT in both score modes: topk_val[b, i] is the logit of (b, topk_idx[b, i]) by the fp32 chain of COPER_SCORE_F32 -- the value
+ * coper_score_all of an f32 handle writes for that element from the same h -- and the selected set and its order are that chain's,
+ * bit for bit.  In COPER_SCORE_BF16X3 the matrix-core logits only PRUNE: block maxima select k + 4 + (filter entries) candidate
+ * blocks, the candidates within tau_q (rank_band_kappa above) of the k-th largest x3 logit are re-scored by the chain and selected by
+ * it; a query whose near-ties reach beyond the emitted blocks is served, in the same call, from chain logits of its whole row
+ * (counted: coper_predict_stats).  h is what the handle's encoder produces, as for ranks.  No logits are materialised on the common
+ * route (workspace: the block maxima of coper_rank_counts + 32 floats per (k + 4 + filter entries) and query + at most 64 MiB of rows
+ * for unresolved queries); stream-ordered, no host synchronisation once the workspace has its size.
+ * 1 <= k <= 128; larger k: COPER_EUNSUPPORTED (use coper_score_all).  k <= 0, B < 0, a half-given CSR, both or neither of
+ * (e1 / rel, hvec): COPER_EINVAL.  B == 0: COPER_OK, nothing launched.  Not prepared: COPER_ESTATE.  COPER_ROLE_ENCODE handles have
+ * no entity table: COPER_EUNSUPPORTED.  Out-of-range e1 / rel are clamped and counted (coper_check_ids).  Entity shards return the
+ * top-k of THEIR rows with global ids: coper_amd.sharding.merge_topk over the shards is the global answer.  Not for hipGraph capture. */
+COPER_API int coper_predict_topk(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const float* hvec,
+                                 const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
+                                 float* topk_val, int64_t* topk_idx, void* stream);
+/* What coper_predict_topk did since the last reset (synchronises the stream): queries answered; of those (COPER_SCORE_BF16X3) the
+ * UNRESOLVED ones, served from chain logits of their whole row; candidates re-scored by the fp32 chain on the common route; and the
+ * largest |logit_x3 - logit_chain| / (tau_q / 2) over those re-scored candidates -- every one is an audit sample of the bound the
+ * selection rests on (below 1 is what makes it exact; the library's tests assert <= 0.5, like coper_band_audit).  Any output may be
+ * NULL.  COPER_SCORE_F32 handles report their queries and zeros. */
+COPER_API int coper_predict_stats(coper_handle* h, int32_t reset, int64_t* n_queries, int64_t* n_unresolved, int64_t* n_rescored,
+                                  float* max_ratio, void* stream);
+
 /* COPER_SCORE_BF16X3: the run-time audit of the exact band.  An AUDITED count launch (coper_config.band_audit_period: by default
  * the first after coper_prepare and every 8th, a sample of its workgroups, 128 pairs per round) re-scores pairs its band walk
  * decides (the competitors closest to each target) with the mode's own arithmetic as well and keeps the largest
