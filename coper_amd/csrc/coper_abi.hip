@@ -494,8 +494,7 @@ COPER_API int coper_set_param(coper_handle* h, const char* leaf_name, const void
   it->second.shape = got;
   it->second.set = true;
   h->prepared = false;
-  train_params_changed(h);
-  return COPER_OK;
+  return train_params_changed(h);
 }
 
 // Evaluate one generator for every relation id: ctx chain through the hidden layers (BN folded, ReLU),

@@ -260,6 +260,8 @@ def train_step(params_np, md, batch, opt: AMSGrad, seed, step, momentum, form=No
     in_h = H * 2 if (md.get("context_rel_out", None) is None and md.get("context_rel_conv", None) is None) else H
     fh, fw = int(md.get("conv_filter_height", 3)), int(md.get("conv_filter_width", 3))
     F = (in_h - fh + 1) * (d // H - fw + 1) * C
+    # the stage ids are those of coper_amd/csrc/train_common.h (DROPOUT_STAGE_HIDDEN, DROPOUT_STAGE_OUTPUT, dropout_stage_chain): change neither
+    # side alone
     kh = dropout_keep(seed, step, 1, B * F, float(md.get("hidden_dropout", 0.0)))
     ko = dropout_keep(seed, step, 2, B * d, float(md.get("output_dropout", 0.0)))
     kc = {}

@@ -167,6 +167,46 @@ def test_train_step_after_the_dense_weights_changed(name, how):
     _train_step_case(name, True, False, "n0.1", steps=3, edit=_edit(how))
 
 
+def test_train_step_after_the_moving_statistics_were_registered_elsewhere():
+    """BN moving statistics are variables like the trainable leaves: registered at another address between two steps (a checkpoint
+    loaded into fresh tensors), the next step updates the NEW tensors -- by what a twin handle that never registered anything again
+    moves its own, to the bound _train_step_case holds a moving statistic to -- and leaves the old ones bit for bit alone."""
+    from coper_amd.models import ConvE
+    md = dict(cdata._COMMON)
+    md.update(_CASES["cpg_mlp_bn"])
+    md.update(batch_norm_train_stats=True, batch_norm_momentum=0.9, hidden_dropout=0.3, output_dropout=0.2, label_smoothing_epsilon=0.1,
+              learning_rate=0.003)
+    moved = ["Conv1BN/moving_mean", "FCBN/moving_variance", "fc_weights/CPG/Projection0/BatchNorm/moving_mean",
+             "fc_weights/CPG/Projection0/BatchNorm/moving_variance"]
+    p0 = cdata.synthetic_params(md, seed=21, ent_std=0.1)
+    pair = []
+    for _ in range(2):
+        m = ConvE(md, device=DEV).load_parameters({k: torch.as_tensor(np.array(v, np.float32)) for k, v in p0.items()})
+        m.train_init(seed=5)
+        m.train_step(_batch(md, 48, 37, seed=100))
+        pair.append(m)
+    m, twin = pair
+    torch.cuda.synchronize()
+    old = {k: m._tensors[k] for k in moved}
+    kept = {k: t.clone() for k, t in old.items()}
+    m.load_parameters({k: t.clone() for k, t in old.items()})
+    for k in moved:
+        assert m._tensors[k].data_ptr() != old[k].data_ptr()
+    for x in pair:
+        x.train_step(_batch(md, 48, 37, seed=101))
+    torch.cuda.synchronize()
+    for k in moved:
+        got, want = m._tensors[k].cpu().numpy(), twin._tensors[k].cpu().numpy()
+        tol = 2e-5 + 1e-5 * np.abs(want).max()
+        if k == "Conv1BN/moving_mean":       # (mean(conv) carries conv1_bias, whose steps under batch statistics are rounding noise)
+            tol += float((m._tensors["conv1_bias"] - twin._tensors["conv1_bias"]).abs().max())
+        assert np.abs(got - want).max() < tol, (k, np.abs(got - want).max(), tol)
+        assert np.abs(got - kept[k].cpu().numpy()).max() > 0, k      # (the step did move it)
+        assert _same(old[k], kept[k]), k
+    m.close()
+    twin.close()
+
+
 def _edit_inference(T, ent=True):
     with torch.no_grad():
         if ent:
