@@ -405,7 +405,7 @@ COPER_API int coper_create(const coper_config* cfg, coper_handle** out) {
   dm.KS16 = (dm.d + 15) / 16;
   dm.n_local = cfg->shard_hi - cfg->shard_lo;
   dm.n_eblk = ((dm.n_local + 31) / 32 + EBLK_ALIGN - 1) / EBLK_ALIGN * EBLK_ALIGN;
-  if (dm.KS * 4 * 64 * 16 > 160 * 1024) return bad("ent_emb_size too large for the LDS query tile (d <= 320)");
+  if (dm.d > COPER_MAX_ENT_EMB) return bad("ent_emb_size too large for the LDS query tile in two halves of K (d <= 640)");
   if ((int64_t)dm.in_h * dm.in_w + (int64_t)dm.fh * dm.fw * dm.C + 3 * dm.C > 40000) return bad("conv stage too large for LDS");
 
   // parameter specs (models.py:203-336)
@@ -719,6 +719,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
     h->gmax_max_floats = share > ((int64_t)1 << 28) ? share : ((int64_t)1 << 28);
   }
   if (role_score && cfg.score_mode == COPER_SCORE_F32 && (rc = score_kernels_init(h))) return rc;
+  if (role_score && cfg.score_mode == COPER_SCORE_BF16X3 && h->dm.KS16 > X3_KS16_LDS && (rc = score_count3_wide_init(h))) return rc;
   if ((rc = fused_fin_update(h, s))) return rc;       // (parameters / exponents moved)
   h->prepared = true;
   return COPER_OK;

@@ -478,6 +478,16 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s);
 size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc);
+// The count kernels hold the fragments of a 128-query tile in the CU's 160 KiB of LDS: whole up to KS16 = 20 / KS = 40
+// (ent_emb_size <= 320), in two halves of K beyond that (kernels_score3_wide_bf16.hip, k_score_count_wide_f32) -- up to
+// ent_emb_size = 640, the bound coper_create enforces.
+constexpr int X3_TILE_Q = 128;        // queries per tile of either count kernel
+constexpr int X3_KS16_LDS = 20;       // k-steps of 16 whose f3 tile fits LDS (x3 mode)
+constexpr int F32_KS_LDS = 40;        // k-steps of 8 whose fp32 tile fits LDS (f32 mode)
+constexpr int COPER_MAX_ENT_EMB = 16 * 2 * X3_KS16_LDS;
+int score_count3_wide_init(coper_handle* h);      // per handle, at prepare: the launch's dynamic-LDS limit on the handle's device
+int score_count3_wide_launch(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, uint4* mask, unsigned long long* summ, float* gmax,
+                             int64_t gm_stride, hipStream_t s);
 int launch_band_consts(coper_handle* h, const float* ent, const float* bias, hipStream_t s);
 int launch_band_setup(coper_handle* h, const float* hvec, const float* tgt, int64_t B, hipStream_t s);
 int launch_exact_targets(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* out, hipStream_t s);

@@ -194,6 +194,9 @@ __global__ __launch_bounds__(256) void k_entity_frag(const float* __restrict__ e
 int launch_entity_frag(coper_handle* h, const float* ent, const float* bias, hipStream_t s) {
   const Dims& dm = h->dm;
   size_t lds = (size_t)32 * (8 * dm.KS + 4) * sizeof(float);
+  // (beyond ent_emb_size = 508 a block's rows pass the 64 KiB a launch may ask for without saying so: 82,432 bytes at 640)
+  if (lds > (size_t)64 * 1024)
+    COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_entity_frag, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * (8 * (COPER_MAX_ENT_EMB / 8) + 4) * (int)sizeof(float)));
   hipLaunchKernelGGL(k_entity_frag, dim3((unsigned)dm.n_eblk), dim3(256), lds, s, ent, bias, dm.n_local, dm.d,
                      dm.KS, (float4*)h->Ef, h->bias_pad);
   COPER_HIP_TRY(h, hipGetLastError());

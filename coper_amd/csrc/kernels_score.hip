@@ -214,6 +214,90 @@ __global__ __launch_bounds__(512, 2) void k_score_count_f32(const float4* __rest
 #undef FLUSH_COUNTS
 }
 
+// ent_emb_size beyond 320 (KS = 41 .. 80): the packed 128-query tile no longer fits the CU's 160 KiB, so it is held in TWO
+// HALVES OF K: a unit runs k-steps [0, KCH) from the first half, the workgroup swaps the second half in, and the accumulators
+// are carried across (a half is re-read from L2 once per unit, and the counters are flushed per unit: 101 - 105 TFLOP/s algorithmic
+// at d = 400 .. 640 against 122 for k_score_count_f32 at d = 320).  Same tile, same hfrag / Ef images, same chain -- k-steps ascending, pred_bias first -- same epilogue and
+// block maxima as k_score_count_f32, which is not touched.
+template <bool EQ, bool GM>
+__global__ __launch_bounds__(512, 1) void k_score_count_wide_f32(const float4* __restrict__ Ef, const float* __restrict__ bias_pad,
+                                                                 const float4* __restrict__ hfrag, const float* __restrict__ tgt,
+                                                                 int64_t B, int KS, int KCH, int64_t iters, int64_t units,
+                                                                 int32_t* __restrict__ ng, int32_t* __restrict__ ne,
+                                                                 float* __restrict__ gmax, int64_t gm_stride) {
+  constexpr int NQ = SC_NQ;
+  extern __shared__ float4 hl[];  // [NQ][KCH][64]
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t u_begin = units * blockIdx.x / gridDim.x;
+  const int64_t u_end = units * (blockIdx.x + 1) / gridDim.x;
+  for (int64_t u = u_begin; u < u_end; ++u) {
+    const int64_t tile = u / iters;
+    const int64_t eb = (u % iters) * SC_WAVES + wave;
+    const float4* src = hfrag + tile * ((int64_t)NQ * KS * 64);
+    const float4* ep = Ef + eb * KS * 64 + lane;
+    f32x16 acc[NQ];
+    {
+      // accumulator row of reg r: (r&3) + 8(r>>2) + 4(lane>>5): the chain starts from pred_bias
+      const float4* bp = (const float4*)(bias_pad + eb * 32 + 4 * (lane >> 5));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 bq = bp[2 * j];
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) {
+          acc[b][4 * j + 0] = bq.x; acc[b][4 * j + 1] = bq.y;
+          acc[b][4 * j + 2] = bq.z; acc[b][4 * j + 3] = bq.w;
+        }
+      }
+    }
+    float4 a0 = ep[0];
+    for (int k0 = 0; k0 < KS; k0 += KCH) {   // workgroup-uniform
+      const int nk = KS - k0 < KCH ? KS - k0 : KCH;
+      __syncthreads();                       // every wave has read the previous half
+      for (int j = threadIdx.x; j < NQ * nk * 64; j += 512) {
+        const int b = j / (nk * 64), o = j - b * (nk * 64);
+        hl[b * (KCH * 64) + o] = src[((int64_t)b * KS + k0) * 64 + o];
+      }
+      __syncthreads();
+      for (int kl = 0; kl < nk; ++kl) {
+        const int ks = k0 + kl;
+        const float4 a1 = ep[(int64_t)(ks + 1 < KS ? ks + 1 : ks) * 64];    // one k-step ahead
+        float4 bv[NQ];
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) bv[b] = hl[(b * KCH + kl) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+          for (int b = 0; b < NQ; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(F4C(a0, tt), F4C(bv[b], tt), acc[b], 0, 0, 0);
+        a0 = a1;
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) {
+      const int64_t q = tile * (32 * NQ) + b * 32 + (lane & 31);
+      const float t = q < B ? tgt[q] : INFINITY;
+      int cg = 0, ce = 0;
+      float mx = acc[b][0];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float sc = acc[b][r];
+        cg += (sc > t) ? 1 : 0;
+        if (EQ) ce += (sc == t) ? 1 : 0;
+        if (GM) mx = fmaxf(mx, sc);
+      }
+      const int g = cg + __shfl_xor(cg, 32);
+      const int e = EQ ? ce + __shfl_xor(ce, 32) : 0;
+      if (lane < 32 && q < B) {
+        if (g) atomicAdd(&ng[q], g);
+        if (EQ && e) atomicAdd(&ne[q], e);
+      }
+      if (GM) {
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        if (lane < 32) gmax[eb * gm_stride + tile * (32 * NQ) + b * 32 + lane] = mx;
+      }
+    }
+  }
+}
+
 // packs h for the whole batch and zeroes the counters
 void score_count_begin_f32(coper_handle* h, const float* hvec, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s) {
   const Dims& dm = h->dm;
@@ -235,6 +319,18 @@ int score_count_chunk_f32(coper_handle* h, int64_t q0, int64_t Bc, const float* 
   size_t lds = (size_t)SC_NQ * dm.KS * 64 * sizeof(float4);
   const float4* hf = (const float4*)h->hfrag_ws + (q0 / 32) * dm.KS * 64;
   ScopedKernelTimer t(h, "score_count", s);
+  if (dm.KS > F32_KS_LDS) {      // the tile in two halves of K
+    const int KCH = (dm.KS + 1) / 2;
+    lds = (size_t)SC_NQ * KCH * 64 * sizeof(float4);
+#define SCW_LAUNCH(EQ_, GM_)                                                                                                          \
+  hipLaunchKernelGGL((k_score_count_wide_f32<EQ_, GM_>), dim3((unsigned)grid), dim3(512), lds, s, (const float4*)h->Ef, h->bias_pad, \
+                     hf, tgt + q0, Bc, dm.KS, KCH, iters, units, ng + q0, ne ? ne + q0 : nullptr, gmax, gm_stride)
+    if (gmax) { if (ne) SCW_LAUNCH(true, true); else SCW_LAUNCH(false, true); }
+    else      { if (ne) SCW_LAUNCH(true, false); else SCW_LAUNCH(false, false); }
+#undef SCW_LAUNCH
+    COPER_HIP_TRY(h, hipGetLastError());
+    return COPER_OK;
+  }
 #define SC_LAUNCH(EQ_, GM_)                                                                                                    \
   hipLaunchKernelGGL((k_score_count_f32<EQ_, GM_>), dim3((unsigned)grid), dim3(512), lds, s, (const float4*)h->Ef, h->bias_pad, \
                      hf, tgt + q0, Bc, dm.KS, iters, units, ng + q0, ne ? ne + q0 : nullptr, gmax, gm_stride)
@@ -253,6 +349,14 @@ int launch_score_count(coper_handle* h, const float* hvec, const float* tgt, int
 
 int score_kernels_init(coper_handle* h) {
   const Dims& dm = h->dm;
+  if (dm.KS > F32_KS_LDS) {
+    const int ldw = 160 * 1024;    // (an attribute of the function, shared by every handle of the process: the largest half-tile)
+    COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_wide_f32<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ldw));
+    COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_wide_f32<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ldw));
+    COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_wide_f32<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldw));
+    COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_wide_f32<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldw));
+    return COPER_OK;
+  }
   int lds = (int)((size_t)SC_NQ * dm.KS * 64 * sizeof(float4));
   COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_f32<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_score_count_f32<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));

@@ -1242,7 +1242,9 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
       SC3_CASE(1) SC3_CASE(2) SC3_CASE(3) SC3_CASE(4) SC3_CASE(5) SC3_CASE(6) SC3_CASE(7) SC3_CASE(8) SC3_CASE(9) SC3_CASE(10)
       SC3_CASE(11) SC3_CASE(12) SC3_CASE(13) SC3_CASE(14) SC3_CASE(15) SC3_CASE(16) SC3_CASE(17) SC3_CASE(18) SC3_CASE(19) SC3_CASE(20)
 #undef SC3_CASE
-      default: rc = fail(h, COPER_EUNSUPPORTED, "score_count3: ent_emb_size beyond 320");
+      // KS16 = 21 .. 40: the tile in two halves of K (kernels_score3_wide_bf16.hip); same mask, summaries and block maxima
+      default: rc = score_count3_wide_launch(h, q0, Bc, ng, (uint4*)h->mask_ws,
+                                             (unsigned long long*)((char*)h->mask_ws + score_count3_mask_words_bytes(h, Bc)), gmax, gm_stride, s);
     }
   }
   if (rc) return rc;
@@ -1318,7 +1320,8 @@ int score_count3_maxima_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, int32_t*
     SC3_CASE(1) SC3_CASE(2) SC3_CASE(3) SC3_CASE(4) SC3_CASE(5) SC3_CASE(6) SC3_CASE(7) SC3_CASE(8) SC3_CASE(9) SC3_CASE(10)
     SC3_CASE(11) SC3_CASE(12) SC3_CASE(13) SC3_CASE(14) SC3_CASE(15) SC3_CASE(16) SC3_CASE(17) SC3_CASE(18) SC3_CASE(19) SC3_CASE(20)
 #undef SC3_CASE
-    default: rc = fail(h, COPER_EUNSUPPORTED, "score_count3: ent_emb_size beyond 320");
+    default: rc = score_count3_wide_launch(h, q0, Bc, ng, (uint4*)h->mask_ws,
+                                           (unsigned long long*)((char*)h->mask_ws + score_count3_mask_words_bytes(h, Bc)), gmax, gm_stride, s);
   }
   return rc;
 }

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_finalize_h_publish(const float* __restr
   const int p = threadIdx.x & 31, r = threadIdx.x >> 5;
   const int k0 = 8 * p;
   float m = 0.f;
-  for (int p0 = 0; p0 < np; p0 += 32) {       // (d <= 256: one round)
+  for (int p0 = 0; p0 < np; p0 += 32) {       // (d <= 256: one round; 640: three)
     const int kp = k0 + 8 * p0;
     const bool mine = p + p0 < np && kp < d;
     const bool vec = mine && kp + 8 <= d && (d & 3) == 0 &&

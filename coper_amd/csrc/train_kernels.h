@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256) void k_tr_score_bwd(const float* __restrict__ 
                                                       int64_t E, int d, int64_t L, float* __restrict__ dh,
                                                       float* __restrict__ dE, float* __restrict__ dbias) {
   const int64_t b = blockIdx.x;
-  for (int k0 = 0; k0 < d; k0 += 256) {   // a thread per feature, 256 features at a time (d <= 256: one trip)
+  for (int k0 = 0; k0 < d; k0 += 256) {   // a thread per feature, 256 features at a time (d <= 256: one trip; 640: three)
   const int k = k0 + threadIdx.x;
   const float hk = k < d ? hv[b * d + k] : 0.f;
   float acc = 0.f;

@@ -65,7 +65,8 @@ typedef struct coper_config {
   int32_t device;               /* HIP device ordinal */
   int64_t num_ent;              /* |E| (global)                          models.py:102 */
   int64_t num_rel;              /* R2 = 2|R| incl. _reverse relations    models.py:103 */
-  int32_t ent_emb_size;         /* d                                     models.py:104 */
+  int32_t ent_emb_size;         /* d <= 640 (COPER_EINVAL beyond: the count kernels hold a 128-query tile in LDS, whole up to
+                                 * d = 320, in two halves of K up to 640)      models.py:104 */
   int32_t rel_emb_size;         /* r                                     models.py:105 */
   int32_t emb_h, emb_w;         /* image reshape, emb_h * emb_w == d     models.py:355 */
   int32_t conv_filter_height;   /* default 3                             models.py:109 */
