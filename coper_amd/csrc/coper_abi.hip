@@ -148,30 +148,52 @@ ScopedKernelTimer::~ScopedKernelTimer() {
   h->timers[name].pending.emplace_back(e0, e1);
 }
 
-static void add_spec(coper_handle* h, const std::string& name, std::vector<int64_t> shape) {
-  h->specs.push_back({name, shape});
-  h->params[name] = Param();
-}
-
-static void add_bn_specs(coper_handle* h, const std::string& prefix, int64_t n) {
-  add_spec(h, prefix + "/gamma", {n});
-  add_spec(h, prefix + "/beta", {n});
-  add_spec(h, prefix + "/moving_mean", {n});
-  add_spec(h, prefix + "/moving_variance", {n});
-}
-
-// ContextualParameterGenerator.__init__ (models.py:44-54): projections [in, n] over context_size[1:] + [num_elements]
-static void add_generator_specs(coper_handle* h, const std::string& name, int n_hidden, const int32_t* hidden,
-                                int64_t num_elements) {
-  int64_t in = h->dm.r;
-  for (int i = 0; i <= n_hidden; ++i) {
-    int64_t n = i < n_hidden ? hidden[i] : num_elements;
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s/CPG/Projection%d", name.c_str(), i);
-    add_spec(h, buf, {in, n});
-    if (i < n_hidden && h->dm.ctx_bn) add_bn_specs(h, std::string(buf) + "/BatchNorm", n);
-    in = n;
-  }
+// The leaves of the configuration (models.py:203-336) in the order coper_param_spec reports them: appends each to h->leaves and files
+// it in h->lv.  The only place that spells a leaf's name; everything else goes through h->lv (coper_set_param: through the name it is given).
+static void enumerate_leaves(coper_handle* h) {
+  const Dims& dm = h->dm;
+  const coper_config& cfg = h->cfg;
+  Leaves& lv = h->lv;
+  auto add = [&](const std::string& name, std::vector<int64_t> shape) {
+    h->leaves.emplace_back();
+    h->leaves.back().name = name;
+    h->leaves.back().spec_shape = std::move(shape);
+    return &h->leaves.back();
+  };
+  auto bn = [&](const std::string& prefix, int64_t n) {
+    Leaves::Bn b;
+    b.gamma = add(prefix + "/gamma", {n});
+    b.beta = add(prefix + "/beta", {n});
+    b.moving_mean = add(prefix + "/moving_mean", {n});
+    b.moving_variance = add(prefix + "/moving_variance", {n});
+    return b;
+  };
+  // one of the four parameters a relation can generate, [.., n] values each: a g_MLP chain (ContextualParameterGenerator.__init__,
+  // models.py:44-54: projections [in, n] over context_size[1:] + [n]), a g_lookup table with a row per relation, or the static tensor
+  auto param = [&](GenId g, const char* name, Leaf*& single, int n_hidden, const int32_t* hidden, int64_t n, std::vector<int64_t> static_shape) {
+    if (n_hidden < 0 || dm.lookup) {
+      single = add(name, n_hidden < 0 ? std::move(static_shape) : std::vector<int64_t>{dm.R, n});
+      return;
+    }
+    lv.gen[g].n_hidden = n_hidden;
+    int64_t in = dm.r;
+    for (int i = 0; i <= n_hidden; ++i) {
+      const int64_t out = i < n_hidden ? hidden[i] : n;
+      const std::string pn = std::string(name) + "/CPG/Projection" + std::to_string(i);
+      lv.gen[g].proj[i] = add(pn, {in, out});
+      if (i < n_hidden && dm.ctx_bn) lv.gen[g].bn[i] = bn(pn + "/BatchNorm", out);
+      in = out;
+    }
+  };
+  lv.ent_emb = add("ent_emb", {dm.n_local, dm.d});
+  lv.pred_bias = add("pred_bias", {dm.n_local});
+  if (!dm.lookup) lv.rel_emb = add("rel_emb", {dm.R, dm.r});      // g_lookup has no relation embedding (models.py:210)
+  param(GEN_CONV1_WEIGHTS, "conv1_weights", lv.conv1_weights, cfg.n_ctx_conv, cfg.ctx_conv, (int64_t)dm.fh * dm.fw * dm.C, {dm.fh, dm.fw, 1, dm.C});
+  param(GEN_CONV1_BIAS, "conv1_bias", lv.conv1_bias, cfg.n_ctx_conv, cfg.ctx_conv, dm.C, {dm.C});
+  param(GEN_FC_WEIGHTS, "fc_weights", lv.fc_weights, cfg.n_ctx_out, cfg.ctx_out, dm.F * dm.d, {dm.F, dm.d});
+  param(GEN_FC_BIAS, "fc_bias", lv.fc_bias, cfg.n_ctx_out, cfg.ctx_out, dm.d, {dm.d});
+  lv.Conv1BN = bn("Conv1BN", dm.C);
+  lv.FCBN = bn("FCBN", dm.d);
 }
 
 static int64_t prod(const std::vector<int64_t>& v) {
@@ -408,37 +430,7 @@ COPER_API int coper_create(const coper_config* cfg, coper_handle** out) {
   if (dm.d > COPER_MAX_ENT_EMB) return bad("ent_emb_size too large for the LDS query tile in two halves of K (d <= 640)");
   if ((int64_t)dm.in_h * dm.in_w + (int64_t)dm.fh * dm.fw * dm.C + 3 * dm.C > 40000) return bad("conv stage too large for LDS");
 
-  // parameter specs (models.py:203-336)
-  add_spec(h, "ent_emb", {dm.n_local, dm.d});
-  add_spec(h, "pred_bias", {dm.n_local});
-  if (!dm.lookup) add_spec(h, "rel_emb", {dm.R, dm.r});
-  int64_t nconv = (int64_t)dm.fh * dm.fw * dm.C;
-  if (dm.gen_conv) {
-    if (dm.lookup) {
-      add_spec(h, "conv1_weights", {dm.R, nconv});
-      add_spec(h, "conv1_bias", {dm.R, dm.C});
-    } else {
-      add_generator_specs(h, "conv1_weights", cfg->n_ctx_conv, cfg->ctx_conv, nconv);
-      add_generator_specs(h, "conv1_bias", cfg->n_ctx_conv, cfg->ctx_conv, dm.C);
-    }
-  } else {
-    add_spec(h, "conv1_weights", {dm.fh, dm.fw, 1, dm.C});
-    add_spec(h, "conv1_bias", {dm.C});
-  }
-  if (dm.gen_fc) {
-    if (dm.lookup) {
-      add_spec(h, "fc_weights", {dm.R, dm.F * dm.d});
-      add_spec(h, "fc_bias", {dm.R, dm.d});
-    } else {
-      add_generator_specs(h, "fc_weights", cfg->n_ctx_out, cfg->ctx_out, dm.F * dm.d);
-      add_generator_specs(h, "fc_bias", cfg->n_ctx_out, cfg->ctx_out, dm.d);
-    }
-  } else {
-    add_spec(h, "fc_weights", {dm.F, dm.d});
-    add_spec(h, "fc_bias", {dm.d});
-  }
-  add_bn_specs(h, "Conv1BN", dm.C);
-  add_bn_specs(h, "FCBN", dm.d);
+  enumerate_leaves(h);
   *out = h;
   return COPER_OK;
 }
@@ -463,73 +455,37 @@ COPER_API int coper_get_dims(const coper_handle* h, int64_t* F, int32_t* Ho, int
   return COPER_OK;
 }
 
-COPER_API int coper_num_params(const coper_handle* h) { return h ? (int)h->specs.size() : 0; }
+COPER_API int coper_num_params(const coper_handle* h) { return h ? (int)h->leaves.size() : 0; }
 
 COPER_API int coper_param_spec(const coper_handle* h, int index, const char** leaf_name, int64_t* shape_out, int* ndim_out) {
-  if (!h || index < 0 || index >= (int)h->specs.size()) return COPER_EINVAL;
-  const ParamSpec& sp = h->specs[index];
-  if (leaf_name) *leaf_name = sp.name.c_str();
-  if (ndim_out) *ndim_out = (int)sp.shape.size();
+  if (!h || index < 0 || index >= (int)h->leaves.size()) return COPER_EINVAL;
+  const Leaf& lf = h->leaves[index];
+  if (leaf_name) *leaf_name = lf.name.c_str();
+  if (ndim_out) *ndim_out = (int)lf.spec_shape.size();
   if (shape_out)
-    for (size_t i = 0; i < sp.shape.size() && i < 4; ++i) shape_out[i] = sp.shape[i];
+    for (size_t i = 0; i < lf.spec_shape.size() && i < 4; ++i) shape_out[i] = lf.spec_shape[i];
   return COPER_OK;
 }
 
 COPER_API int coper_set_param(coper_handle* h, const char* leaf_name, const void* dev_ptr, const int64_t* shape, int ndim) {
   if (!h || !leaf_name || !dev_ptr || !shape || ndim <= 0) return fail(h, COPER_EINVAL, "coper_set_param: null argument");
-  auto it = h->params.find(leaf_name);
-  if (it == h->params.end())
+  Leaf* lf = nullptr;      // (the one lookup by name: h->lv points at the leaf itself, so the inference side resolves nothing again)
+  for (Leaf& l : h->leaves)
+    if (l.name == leaf_name) lf = &l;
+  if (!lf)
     return fail(h, COPER_EINVAL, std::string("coper_set_param: '") + leaf_name + "' is not a parameter of this configuration");
-  const ParamSpec* sp = nullptr;
-  for (auto& s : h->specs)
-    if (s.name == leaf_name) sp = &s;
   std::vector<int64_t> got(shape, shape + ndim);
-  if (prod(got) != prod(sp->shape)) {
+  if (prod(got) != prod(lf->spec_shape)) {
     char buf[256];
     snprintf(buf, sizeof buf, "coper_set_param: '%s' has %lld elements, configuration needs %lld", leaf_name,
-             (long long)prod(got), (long long)prod(sp->shape));
+             (long long)prod(got), (long long)prod(lf->spec_shape));
     return fail(h, COPER_ESHAPE, buf);
   }
-  it->second.ptr = (const float*)dev_ptr;
-  it->second.shape = got;
-  it->second.set = true;
+  lf->ptr = (const float*)dev_ptr;
+  lf->shape = got;
+  lf->set = true;
   h->prepared = false;
   return train_params_changed(h);
-}
-
-// Evaluate one generator for every relation id: ctx chain through the hidden layers (BN folded, ReLU),
-// returns the final context and its width.  (models.py:56-70)
-static int run_generator_hidden(coper_handle* h, const std::string& name, int n_hidden, const int32_t* hidden,
-                                const float** ctx_out, int* K_out, hipStream_t s) {
-  const Dims& dm = h->dm;
-  const float* cur = h->params["rel_emb"].ptr;
-  int K = dm.r;
-  for (int i = 0; i < n_hidden; ++i) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s/CPG/Projection%d", name.c_str(), i);
-    int n = hidden[i];
-    float* dst = h->ctx_tmp[i & 1];
-    const float* sc = nullptr;
-    const float* sh = nullptr;
-    float* scb = nullptr;
-    if (dm.ctx_bn) {
-      // fold this layer's BN into a scratch (scale | shift) placed after the activations
-      scb = h->ctx_tmp[i & 1] + (size_t)dm.R * n;
-      std::string bn = std::string(buf) + "/BatchNorm";
-      int rc = launch_fold_bn(h, h->params[bn + "/gamma"].ptr, h->params[bn + "/beta"].ptr,
-                              h->params[bn + "/moving_mean"].ptr, h->params[bn + "/moving_variance"].ptr, n,
-                              h->cfg.bn_epsilon, scb, scb + n, s);
-      if (rc) return rc;
-      sc = scb; sh = scb + n;
-    }
-    int rc = launch_gen_small(h, cur, dm.R, K, h->params[buf].ptr, n, sc, sh, true, dst, s);
-    if (rc) return rc;
-    cur = dst;
-    K = n;
-  }
-  *ctx_out = cur;
-  *K_out = K;
-  return COPER_OK;
 }
 
 COPER_API int coper_set_x3_ent_absmax(coper_handle* h, float absmax) {
@@ -539,187 +495,268 @@ COPER_API int coper_set_x3_ent_absmax(coper_handle* h, float absmax) {
   return COPER_OK;
 }
 
-COPER_API int coper_prepare(coper_handle* h, void* stream) {
-  if (!h) return COPER_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
+// ---- coper_prepare: its phases, in the order coper_prepare runs them ----
+static int prepare_check_set(coper_handle* h) {
+  for (const Leaf& lf : h->leaves)
+    if (!lf.set) return fail(h, COPER_EMISSING, "coper_prepare: parameter '" + lf.name + "' was never set");
+  return COPER_OK;
+}
+
+static int fold_bn(coper_handle* h, const Leaves::Bn& b, int n, float* scale, float* shift, hipStream_t s) {
+  return launch_fold_bn(h, b.gamma->ptr, b.beta->ptr, b.moving_mean->ptr, b.moving_variance->ptr, n, h->cfg.bn_epsilon, scale, shift, s);
+}
+
+static int prepare_bn_folds(coper_handle* h, hipStream_t s) {
   const Dims& dm = h->dm;
-  const coper_config& cfg = h->cfg;
-  for (auto& sp : h->specs)
-    if (!h->params[sp.name].set) return fail(h, COPER_EMISSING, "coper_prepare: parameter '" + sp.name + "' was never set");
-  COPER_HIP_TRY(h, hipSetDevice(cfg.device));
-  h->prepared = false;          // (until every derived buffer below exists again: a prepare that fails leaves a handle that refuses passes)
   int rc;
-  h->gcur = 0;                  // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
-  h->pipe.invalidate_grouping();
   if ((rc = h->conv_scale.alloc(h, dm.C, "conv_scale")) || (rc = h->conv_shift.alloc(h, dm.C, "conv_shift")) ||
       (rc = h->fc_scale.alloc(h, dm.d, "fc_scale")) || (rc = h->fc_shift.alloc(h, dm.d, "fc_shift")))
     return rc;
-  auto P = [&](const std::string& n) { return h->params[n].ptr; };
-  if ((rc = launch_fold_bn(h, P("Conv1BN/gamma"), P("Conv1BN/beta"), P("Conv1BN/moving_mean"),
-                           P("Conv1BN/moving_variance"), dm.C, cfg.bn_epsilon, h->conv_scale, h->conv_shift, s)))
-    return rc;
-  if ((rc = launch_fold_bn(h, P("FCBN/gamma"), P("FCBN/beta"), P("FCBN/moving_mean"), P("FCBN/moving_variance"),
-                           dm.d, cfg.bn_epsilon, h->fc_scale, h->fc_shift, s)))
-    return rc;
+  if ((rc = fold_bn(h, h->lv.Conv1BN, dm.C, h->conv_scale, h->conv_shift, s))) return rc;
+  return fold_bn(h, h->lv.FCBN, dm.d, h->fc_scale, h->fc_shift, s);
+}
 
-  if (cfg.score_mode != COPER_SCORE_F32) {
-    // the shard's maxima (row norm, |pred_bias|: the exact band; |element|: the power of two of the entity planes, split16.h)
-    const bool bad = (rc = h->band_consts.alloc(h, BAND_NCONST, "band_consts")) || (rc = h->x3s.alloc(h, 4, "x3s")) ||
-                     (rc = h->home.x3m.alloc(h, (size_t)X3M_SLOTS, "x3m"));
-    group_home_views(h);
-    if (bad) return rc;
-    COPER_HIP_TRY(h, hipMemsetAsync(h->x3s, 0, 4 * sizeof(int32_t), s));
-    COPER_HIP_TRY(h, hipMemsetAsync(h->home.x3m, 0, X3M_SLOTS * sizeof(float), s));
-    if ((rc = launch_band_consts(h, P("ent_emb"), P("pred_bias"), s))) return rc;
-    {
-      unsigned cb[BAND_NCONST];
-      COPER_HIP_TRY(h, hipMemcpyAsync(cb, h->band_consts, sizeof cb, hipMemcpyDeviceToHost, s));
-      COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      float xmax;
-      memcpy(&xmax, &cb[2], sizeof xmax);
-      // shards of one table agree on the exponent through the hint (the mode's logits are then the same bits on every shard
-      // layout); a hint below the shard's own maximum could overflow fp16: refused
-      if (cfg.x3_ent_absmax > 0.f) {
-        if (!(cfg.x3_ent_absmax >= xmax)) return fail(h, COPER_EINVAL, "coper_prepare: x3_ent_absmax is below the largest |ent_emb| element of the shard");
-        xmax = cfg.x3_ent_absmax;
-      }
-      unsigned xb;
-      memcpy(&xb, &xmax, sizeof xb);
-      h->x3_ent_absmax = xmax;
-      h->x3_ent_exp = x3_exp_for_bits(xb);
-    }
+// COPER_SCORE_BF16X3: the shard's maxima (row norm, |pred_bias|: the exact band; |element|: the power of two of the entity planes, split16.h)
+static int prepare_x3_scale(coper_handle* h, hipStream_t s) {
+  const coper_config& cfg = h->cfg;
+  int rc;
+  const bool bad = (rc = h->band_consts.alloc(h, BAND_NCONST, "band_consts")) || (rc = h->x3s.alloc(h, 4, "x3s")) ||
+                   (rc = h->home.x3m.alloc(h, (size_t)X3M_SLOTS, "x3m"));
+  group_home_views(h);
+  if (bad) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(h->x3s, 0, 4 * sizeof(int32_t), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(h->home.x3m, 0, X3M_SLOTS * sizeof(float), s));
+  if ((rc = launch_band_consts(h, h->lv.ent_emb->ptr, h->lv.pred_bias->ptr, s))) return rc;
+  unsigned cb[BAND_NCONST];
+  COPER_HIP_TRY(h, hipMemcpyAsync(cb, h->band_consts, sizeof cb, hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  float xmax;
+  memcpy(&xmax, &cb[2], sizeof xmax);
+  // shards of one table agree on the exponent through the hint (the mode's logits are then the same bits on every shard
+  // layout); a hint below the shard's own maximum could overflow fp16: refused
+  if (cfg.x3_ent_absmax > 0.f) {
+    if (!(cfg.x3_ent_absmax >= xmax)) return fail(h, COPER_EINVAL, "coper_prepare: x3_ent_absmax is below the largest |ent_emb| element of the shard");
+    xmax = cfg.x3_ent_absmax;
   }
+  unsigned xb;
+  memcpy(&xb, &xmax, sizeof xb);
+  h->x3_ent_absmax = xmax;
+  h->x3_ent_exp = x3_exp_for_bits(xb);
+  return COPER_OK;
+}
 
-  const bool role_enc = cfg.role != COPER_ROLE_SCORE, role_score = cfg.role != COPER_ROLE_ENCODE;
-  h->enc_bf16 = false;
-  h->x_exp = 0;
-  h->band_launches = 0;
-  h->Rw = 0;
-  if (role_enc) {      // ---- the encoder's derived state (a COPER_ROLE_SCORE handle has none: no generator evaluated, no W_r cached)
-  // scratch for generator hidden activations: R * max_hidden (+ 2 * max_hidden for the folded BN)
-  int max_hidden = 1;
-  for (int i = 0; i < cfg.n_ctx_conv; ++i) max_hidden = cfg.ctx_conv[i] > max_hidden ? cfg.ctx_conv[i] : max_hidden;
-  for (int i = 0; i < cfg.n_ctx_out; ++i) max_hidden = cfg.ctx_out[i] > max_hidden ? cfg.ctx_out[i] : max_hidden;
-  size_t tmp_elems = (size_t)(dm.R + 2) * max_hidden;
-  if ((rc = h->ctx_tmp[0].alloc(h, tmp_elems, "ctx_tmp")) || (rc = h->ctx_tmp[1].alloc(h, tmp_elems, "ctx_tmp"))) return rc;
-
-  int64_t nconv = (int64_t)dm.fh * dm.fw * dm.C;
-  if (dm.gen_conv) {
-    if ((rc = h->conv_w_rel.alloc(h, (size_t)dm.R * nconv, "conv_w_rel")) || (rc = h->conv_b_rel.alloc(h, (size_t)dm.R * dm.C, "conv_b_rel")))
-      return rc;
-    if (dm.lookup) {  // ParameterLookup.generate (models.py:90-94): the table row IS the parameter
-      COPER_HIP_TRY(h, hipMemcpyAsync(h->conv_w_rel, P("conv1_weights"), sizeof(float) * dm.R * nconv, hipMemcpyDeviceToDevice, s));
-      COPER_HIP_TRY(h, hipMemcpyAsync(h->conv_b_rel, P("conv1_bias"), sizeof(float) * dm.R * dm.C, hipMemcpyDeviceToDevice, s));
-    } else {
-      const float* ctx; int K; char buf[256];
-      if ((rc = run_generator_hidden(h, "conv1_weights", cfg.n_ctx_conv, cfg.ctx_conv, &ctx, &K, s))) return rc;
-      snprintf(buf, sizeof buf, "conv1_weights/CPG/Projection%d", cfg.n_ctx_conv);
-      if ((rc = launch_gen_small(h, ctx, dm.R, K, P(buf), nconv, nullptr, nullptr, false, h->conv_w_rel, s))) return rc;
-      if ((rc = run_generator_hidden(h, "conv1_bias", cfg.n_ctx_conv, cfg.ctx_conv, &ctx, &K, s))) return rc;
-      snprintf(buf, sizeof buf, "conv1_bias/CPG/Projection%d", cfg.n_ctx_conv);
-      if ((rc = launch_gen_small(h, ctx, dm.R, K, P(buf), dm.C, nullptr, nullptr, false, h->conv_b_rel, s))) return rc;
+// Evaluate one generator for every relation id: ctx chain through the hidden layers (BN folded, ReLU),
+// returns the final context and its width.  (models.py:56-70)
+static int run_generator_hidden(coper_handle* h, const Leaves::Gen& g, const int32_t* hidden, const float** ctx_out, int* K_out, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const float* cur = h->lv.rel_emb->ptr;
+  int K = dm.r, rc;
+  for (int i = 0; i < g.n_hidden; ++i) {
+    const int n = hidden[i];
+    float* dst = h->ctx_tmp[i & 1];
+    const float* sc = nullptr;
+    const float* sh = nullptr;
+    if (dm.ctx_bn) {
+      // fold this layer's BN into a scratch (scale | shift) placed after the activations
+      float* scb = h->ctx_tmp[i & 1] + (size_t)dm.R * n;
+      if ((rc = fold_bn(h, g.bn[i], n, scb, scb + n, s))) return rc;
+      sc = scb; sh = scb + n;
     }
+    if ((rc = launch_gen_small(h, cur, dm.R, K, g.proj[i]->ptr, n, sc, sh, true, dst, s))) return rc;
+    cur = dst;
+    K = n;
   }
-  int64_t ksteps = dm.F_pad / 16;
-  size_t per_rel = (size_t)dm.nfb * ksteps * 64 * 4;  // floats
+  *ctx_out = cur;
+  *K_out = K;
+  return COPER_OK;
+}
+
+// out[rel, N] of a generator with a small output (conv filters / biases, dense bias): the context times the last projection
+static int run_generator_small(coper_handle* h, const Leaves::Gen& g, const int32_t* hidden, int64_t N, float* out, hipStream_t s) {
+  const float* ctx; int K, rc;
+  if ((rc = run_generator_hidden(h, g, hidden, &ctx, &K, s))) return rc;
+  return launch_gen_small(h, ctx, h->dm.R, K, g.proj[g.n_hidden]->ptr, N, nullptr, nullptr, false, out, s);
+}
+
+static int prepare_conv_filters(coper_handle* h, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const coper_config& cfg = h->cfg;
+  const Leaves& lv = h->lv;
+  if (!dm.gen_conv) return COPER_OK;
+  const int64_t nconv = (int64_t)dm.fh * dm.fw * dm.C;
+  int rc;
+  if ((rc = h->conv_w_rel.alloc(h, (size_t)dm.R * nconv, "conv_w_rel")) || (rc = h->conv_b_rel.alloc(h, (size_t)dm.R * dm.C, "conv_b_rel")))
+    return rc;
+  if (dm.lookup) {  // ParameterLookup.generate (models.py:90-94): the table row IS the parameter
+    COPER_HIP_TRY(h, hipMemcpyAsync(h->conv_w_rel, lv.conv1_weights->ptr, sizeof(float) * dm.R * nconv, hipMemcpyDeviceToDevice, s));
+    COPER_HIP_TRY(h, hipMemcpyAsync(h->conv_b_rel, lv.conv1_bias->ptr, sizeof(float) * dm.R * dm.C, hipMemcpyDeviceToDevice, s));
+    return COPER_OK;
+  }
+  if ((rc = run_generator_small(h, lv.gen[GEN_CONV1_WEIGHTS], cfg.ctx_conv, nconv, h->conv_w_rel, s))) return rc;
+  return run_generator_small(h, lv.gen[GEN_CONV1_BIAS], cfg.ctx_conv, dm.C, h->conv_b_rel, s);
+}
+
+// coper_config.rel_mod_*: the relations r with r % w_div == w_rem this handle holds weights of
+static int64_t rel_mod_owned(const coper_handle* h) {
+  const int64_t R = h->dm.R;
+  return h->w_div > 1 ? (R > h->w_rem ? (R - h->w_rem + h->w_div - 1) / h->w_div : 0) : R;
+}
+
+// The dense layer: its bias per relation where it is generated, and W_r -- fragment-major fp32 in Wf, or (COPER_DENSE_FACTORED) the
+// context and the packed projection.  ctx_sel: the generator contexts of the held relations, compacted (rel_mod_world > 1); the
+// caller frees it behind a synchronize.
+static int prepare_dense(coper_handle* h, DevBuf<float>& ctx_sel, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const coper_config& cfg = h->cfg;
+  const Leaves& lv = h->lv;
+  int rc;
+  const size_t per_rel = (size_t)dm.nfb * (dm.F_pad / 16) * 64 * 4;  // floats
   // coper_config.rel_mod_*: weight sets of the relations r with r % G == g only, relation r at slot r / G (ceil(R / G) slots on
   // every rank: a relation id the handle does not hold still indexes inside the planes; it is counted, kernels_dense_fused_bf16.hip)
   const int w_div = cfg.rel_mod_world > 1 ? cfg.rel_mod_world : 1, w_rem = w_div > 1 ? cfg.rel_mod_rank : 0;
   if (w_div > 1 && (!dm.gen_fc || dm.lookup || cfg.score_mode == COPER_SCORE_F32))
     return fail(h, COPER_EUNSUPPORTED, "rel_mod_world > 1: COPER_SCORE_BF16X3 with generated dense weights (context_rel_out) only");
   h->w_div = w_div; h->w_rem = w_rem;
-  const int64_t n_own = w_div > 1 ? (dm.R > w_rem ? (dm.R - w_rem + w_div - 1) / w_div : 0) : dm.R;
+  const int64_t n_own = rel_mod_owned(h);
   h->Rw = dm.gen_fc ? (w_div > 1 ? (dm.R + w_div - 1) / w_div : dm.R) : 1;
   if (!h->factored && (rc = h->Wf.alloc(h, per_rel * h->Rw, "Wf"))) return rc;
-  DevBuf<float> ctx_sel;          // the generator contexts of the held relations, compacted (freed behind the synchronize below)
-  if (dm.gen_fc) {
-    if ((rc = h->fc_b_rel.alloc(h, (size_t)dm.R * dm.d, "fc_b_rel"))) return rc;
-    if (dm.lookup) {
-      COPER_HIP_TRY(h, hipMemcpyAsync(h->fc_b_rel, P("fc_bias"), sizeof(float) * dm.R * dm.d, hipMemcpyDeviceToDevice, s));
-      if ((rc = launch_gen_dense_frag(h, nullptr, dm.R, 0, P("fc_weights"), 1, h->Wf, s))) return rc;
-    } else {
-      const float* ctx; int K; char buf[256];
-      if ((rc = run_generator_hidden(h, "fc_bias", cfg.n_ctx_out, cfg.ctx_out, &ctx, &K, s))) return rc;
-      snprintf(buf, sizeof buf, "fc_bias/CPG/Projection%d", cfg.n_ctx_out);
-      if ((rc = launch_gen_small(h, ctx, dm.R, K, P(buf), dm.d, nullptr, nullptr, false, h->fc_b_rel, s))) return rc;
-      if ((rc = run_generator_hidden(h, "fc_weights", cfg.n_ctx_out, cfg.ctx_out, &ctx, &K, s))) return rc;
-      snprintf(buf, sizeof buf, "fc_weights/CPG/Projection%d", cfg.n_ctx_out);
-      if (w_div > 1) {      // slot i = relation w_rem + i w_div: the same context row, the same sum -- W_r is the same bits at any G
-        if ((rc = ctx_sel.alloc(h, (size_t)h->Rw * K, "ctx_sel"))) return rc;
-        COPER_HIP_TRY(h, hipMemsetAsync(ctx_sel, 0, sizeof(float) * (size_t)h->Rw * K, s));
-        if (n_own > 0)
-          COPER_HIP_TRY(h, hipMemcpy2DAsync(ctx_sel, sizeof(float) * K, ctx + (size_t)w_rem * K, sizeof(float) * (size_t)w_div * K, sizeof(float) * K,
-                                            (size_t)n_own, hipMemcpyDeviceToDevice, s));
-        ctx = ctx_sel;
-      }
-      if (h->factored) {      // no W_r: the context and the packed projection are the handle's dense layer (e_x first: its device word)
-        if ((rc = compute_x_exp(h, h->band_consts + 5, s)) || (rc = factored_prepare(h, ctx, K, P(buf), s))) return rc;
-      } else if ((rc = launch_gen_dense_frag(h, ctx, h->Rw, K, P(buf), 0, h->Wf, s))) return rc;
-    }
-  } else {
-    if ((rc = launch_gen_dense_frag(h, nullptr, 1, 0, P("fc_weights"), 1, h->Wf, s))) return rc;
+  if (!dm.gen_fc) return launch_gen_dense_frag(h, nullptr, 1, 0, lv.fc_weights->ptr, 1, h->Wf, s);
+  if ((rc = h->fc_b_rel.alloc(h, (size_t)dm.R * dm.d, "fc_b_rel"))) return rc;
+  if (dm.lookup) {
+    COPER_HIP_TRY(h, hipMemcpyAsync(h->fc_b_rel, lv.fc_bias->ptr, sizeof(float) * dm.R * dm.d, hipMemcpyDeviceToDevice, s));
+    return launch_gen_dense_frag(h, nullptr, dm.R, 0, lv.fc_weights->ptr, 1, h->Wf, s);
   }
-  h->enc_bf16 = !h->factored && cfg.score_mode != COPER_SCORE_F32 && conv_bf16_supported(dm);   // (the CACHED 16-bit encoder)
-  if (w_div > 1 && !h->enc_bf16)
-    return fail(h, COPER_EUNSUPPORTED, "rel_mod_world > 1: the configuration is not served by the 16-bit encoder");
-  if (h->enc_bf16) {
-    const size_t plane = (size_t)h->Rw * dm.nfb * w16_ks_stride(dm) * 64;     // uint4
-    if ((rc = h->Wf16_hi.alloc(h, plane, "bf16 weight planes")) || (rc = h->Wf16_lo.alloc(h, plane, "bf16 weight planes"))) return rc;
-    // powers of two of the encoder's operands (split16.h): e_W per relation from its own largest |W|, e_x from a bound on x
-    if (w_div > 1) {       // e_W is looked up by RELATION ID everywhere; the conversion works on slots: computed there, scattered to the ids
-      DevBuf<int32_t> by_slot;
-      if ((rc = h->w_exp.alloc(h, (size_t)dm.R, "w_exp")) || (rc = by_slot.alloc(h, (size_t)h->Rw, "w_exp by slot"))) return rc;
-      COPER_HIP_TRY(h, hipMemsetAsync(h->w_exp, 0, sizeof(int32_t) * (size_t)dm.R, s));
-      rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, by_slot, s);
-      if (!rc && n_own > 0 &&
-          hipMemcpy2DAsync(h->w_exp + w_rem, sizeof(int32_t) * (size_t)w_div, by_slot, sizeof(int32_t), sizeof(int32_t), (size_t)n_own,
-                           hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = fail(h, COPER_EHIP, "hipMemcpy2DAsync (e_W by relation id)");
-      hipError_t e = hipStreamSynchronize(s);
-      if (rc) return rc;
-      COPER_HIP_TRY(h, e);
-    } else {
-      if ((rc = h->w_exp.alloc(h, (size_t)h->Rw, "w_exp"))) return rc;
-      if ((rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, h->w_exp, s))) return rc;
-    }
+  if ((rc = run_generator_small(h, lv.gen[GEN_FC_BIAS], cfg.ctx_out, dm.d, h->fc_b_rel, s))) return rc;
+  const Leaves::Gen& gw = lv.gen[GEN_FC_WEIGHTS];
+  const float* ctx; int K;
+  if ((rc = run_generator_hidden(h, gw, cfg.ctx_out, &ctx, &K, s))) return rc;
+  if (w_div > 1) {      // slot i = relation w_rem + i w_div: the same context row, the same sum -- W_r is the same bits at any G
+    if ((rc = ctx_sel.alloc(h, (size_t)h->Rw * K, "ctx_sel"))) return rc;
+    COPER_HIP_TRY(h, hipMemsetAsync(ctx_sel, 0, sizeof(float) * (size_t)h->Rw * K, s));
+    if (n_own > 0)
+      COPER_HIP_TRY(h, hipMemcpy2DAsync(ctx_sel, sizeof(float) * K, ctx + (size_t)w_rem * K, sizeof(float) * (size_t)w_div * K, sizeof(float) * K,
+                                        (size_t)n_own, hipMemcpyDeviceToDevice, s));
+    ctx = ctx_sel;
+  }
+  const float* P_last = gw.proj[gw.n_hidden]->ptr;
+  if (h->factored) {      // no W_r: the context and the packed projection are the handle's dense layer (e_x first: its device word)
     if ((rc = compute_x_exp(h, h->band_consts + 5, s))) return rc;
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    h->Wf.reset();  // the fp32 image was only the staging form
-    ctx_sel.reset();
+    return factored_prepare(h, ctx, K, P_last, s);
   }
-  }                    // ---- (role_enc)
-  // entity table image(s) (a COPER_ROLE_ENCODE handle has none)
-  if (!role_score) {
-  } else if (cfg.score_mode == COPER_SCORE_F32) {
+  return launch_gen_dense_frag(h, ctx, h->Rw, K, P_last, 0, h->Wf, s);
+}
+
+// the CACHED 16-bit encoder: Wf as hi / lo bf16 planes, with the powers of two of the encoder's operands (split16.h): e_W per
+// relation from its own largest |W|, e_x from a bound on x.  Frees the fp32 staging image and ctx_sel.
+static int prepare_weight_planes(coper_handle* h, DevBuf<float>& ctx_sel, hipStream_t s) {
+  const Dims& dm = h->dm;
+  int rc;
+  const size_t plane = (size_t)h->Rw * dm.nfb * w16_ks_stride(dm) * 64;     // uint4
+  if ((rc = h->Wf16_hi.alloc(h, plane, "bf16 weight planes")) || (rc = h->Wf16_lo.alloc(h, plane, "bf16 weight planes"))) return rc;
+  if (h->w_div > 1) {       // e_W is looked up by RELATION ID everywhere; the conversion works on slots: computed there, scattered to the ids
+    const int64_t n_own = rel_mod_owned(h);
+    DevBuf<int32_t> by_slot;
+    if ((rc = h->w_exp.alloc(h, (size_t)dm.R, "w_exp")) || (rc = by_slot.alloc(h, (size_t)h->Rw, "w_exp by slot"))) return rc;
+    COPER_HIP_TRY(h, hipMemsetAsync(h->w_exp, 0, sizeof(int32_t) * (size_t)dm.R, s));
+    rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, by_slot, s);
+    if (!rc && n_own > 0 &&
+        hipMemcpy2DAsync(h->w_exp + h->w_rem, sizeof(int32_t) * (size_t)h->w_div, by_slot, sizeof(int32_t), sizeof(int32_t), (size_t)n_own,
+                         hipMemcpyDeviceToDevice, s) != hipSuccess)
+      rc = fail(h, COPER_EHIP, "hipMemcpy2DAsync (e_W by relation id)");
+    hipError_t e = hipStreamSynchronize(s);      // (by_slot is freed below: not before the copy has read it)
+    if (rc) return rc;
+    COPER_HIP_TRY(h, e);
+  } else {
+    if ((rc = h->w_exp.alloc(h, (size_t)h->Rw, "w_exp"))) return rc;
+    if ((rc = launch_wfrag_to_bf16(h, h->Wf, h->Rw, h->Wf16_hi, h->Wf16_lo, h->w_exp, s))) return rc;
+  }
+  if ((rc = compute_x_exp(h, h->band_consts + 5, s))) return rc;
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  h->Wf.reset();  // the fp32 image was only the staging form
+  ctx_sel.reset();
+  return COPER_OK;
+}
+
+// the encoder's derived state (a COPER_ROLE_SCORE handle has none: no generator evaluated, no W_r cached)
+static int prepare_encoder(coper_handle* h, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const coper_config& cfg = h->cfg;
+  int rc;
+  // scratch for generator hidden activations: R * max_hidden (+ 2 * max_hidden for the folded BN)
+  int max_hidden = 1;
+  for (int i = 0; i < cfg.n_ctx_conv; ++i) max_hidden = cfg.ctx_conv[i] > max_hidden ? cfg.ctx_conv[i] : max_hidden;
+  for (int i = 0; i < cfg.n_ctx_out; ++i) max_hidden = cfg.ctx_out[i] > max_hidden ? cfg.ctx_out[i] : max_hidden;
+  const size_t tmp_elems = (size_t)(dm.R + 2) * max_hidden;
+  if ((rc = h->ctx_tmp[0].alloc(h, tmp_elems, "ctx_tmp")) || (rc = h->ctx_tmp[1].alloc(h, tmp_elems, "ctx_tmp"))) return rc;
+  if ((rc = prepare_conv_filters(h, s))) return rc;
+  DevBuf<float> ctx_sel;
+  if ((rc = prepare_dense(h, ctx_sel, s))) return rc;
+  h->enc_bf16 = !h->factored && cfg.score_mode != COPER_SCORE_F32 && conv_bf16_supported(dm);
+  if (h->w_div > 1 && !h->enc_bf16)
+    return fail(h, COPER_EUNSUPPORTED, "rel_mod_world > 1: the configuration is not served by the 16-bit encoder");
+  return h->enc_bf16 ? prepare_weight_planes(h, ctx_sel, s) : COPER_OK;
+}
+
+// the entity table image(s) of the score mode (a COPER_ROLE_ENCODE handle has none)
+static int prepare_entity_images(coper_handle* h, hipStream_t s) {
+  const Dims& dm = h->dm;
+  const Leaves& lv = h->lv;
+  int rc;
+  if (h->cfg.score_mode == COPER_SCORE_F32) {
     if ((rc = h->Ef.alloc(h, (size_t)dm.n_eblk * dm.KS * 64 * 4, "Ef")) || (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
       return rc;
-    if ((rc = launch_entity_frag(h, P("ent_emb"), P("pred_bias"), s))) return rc;
-  } else {
-    // bias_pad comes from the (tiny-KS) fp32 image builder run on a 1-k-step view; the table goes to two bf16 planes
-    const size_t plane = (size_t)dm.n_eblk * dm.KS16 * 64;     // uint4
-    if ((rc = h->Ef16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Ef16_lo.alloc(h, plane, "bf16 entity planes")) ||
-        (rc = h->Erm16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Erm16_lo.alloc(h, plane, "bf16 entity planes")) ||
-        (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
-      return rc;
-    if ((rc = launch_bias_pad(h, P("pred_bias"), s))) return rc;
-    const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
-    if ((rc = h->Ef3.alloc(h, f3, "entity image"))) return rc;
-    COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3 * sizeof(uint4), s));
-    PassCtx none;
-    if ((rc = launch_rows_to_frag_bf16(h, none, P("ent_emb"), dm.n_local, dm.n_eblk, h->Ef16_hi, h->Ef16_lo, h->Erm16_hi, h->Erm16_lo, h->Ef3,
-                                       false, s)))
-      return rc;
-    if ((rc = score_bf16_kernels_init(h))) return rc;
+    return launch_entity_frag(h, lv.ent_emb->ptr, lv.pred_bias->ptr, s);
   }
-  {
-    hipDeviceProp_t prop;
-    COPER_HIP_TRY(h, hipGetDeviceProperties(&prop, cfg.device));
-    h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const int64_t share = (int64_t)(prop.totalGlobalMem / 32 / sizeof(float));
-    h->gmax_max_floats = share > ((int64_t)1 << 28) ? share : ((int64_t)1 << 28);
-  }
-  if (role_score && cfg.score_mode == COPER_SCORE_F32 && (rc = score_kernels_init(h))) return rc;
-  if (role_score && cfg.score_mode == COPER_SCORE_BF16X3 && h->dm.KS16 > X3_KS16_LDS && (rc = score_count3_wide_init(h))) return rc;
+  // bias_pad comes from the (tiny-KS) fp32 image builder run on a 1-k-step view; the table goes to two bf16 planes
+  const size_t plane = (size_t)dm.n_eblk * dm.KS16 * 64;     // uint4
+  if ((rc = h->Ef16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Ef16_lo.alloc(h, plane, "bf16 entity planes")) ||
+      (rc = h->Erm16_hi.alloc(h, plane, "bf16 entity planes")) || (rc = h->Erm16_lo.alloc(h, plane, "bf16 entity planes")) ||
+      (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
+    return rc;
+  if ((rc = launch_bias_pad(h, lv.pred_bias->ptr, s))) return rc;
+  const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
+  if ((rc = h->Ef3.alloc(h, f3, "entity image"))) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3 * sizeof(uint4), s));
+  PassCtx none;
+  if ((rc = launch_rows_to_frag_bf16(h, none, lv.ent_emb->ptr, dm.n_local, dm.n_eblk, h->Ef16_hi, h->Ef16_lo, h->Erm16_hi, h->Erm16_lo, h->Ef3,
+                                     false, s)))
+    return rc;
+  return score_bf16_kernels_init(h);
+}
+
+// what the launches size themselves by, and the scorer's kernel attributes on the handle's device
+static int prepare_device(coper_handle* h, bool role_score) {
+  hipDeviceProp_t prop;
+  COPER_HIP_TRY(h, hipGetDeviceProperties(&prop, h->cfg.device));
+  h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  const int64_t share = (int64_t)(prop.totalGlobalMem / 32 / sizeof(float));
+  h->gmax_max_floats = share > ((int64_t)1 << 28) ? share : ((int64_t)1 << 28);
+  int rc;
+  if (role_score && h->cfg.score_mode == COPER_SCORE_F32 && (rc = score_kernels_init(h))) return rc;
+  if (role_score && h->cfg.score_mode == COPER_SCORE_BF16X3 && h->dm.KS16 > X3_KS16_LDS && (rc = score_count3_wide_init(h))) return rc;
+  return COPER_OK;
+}
+
+COPER_API int coper_prepare(coper_handle* h, void* stream) {
+  if (!h) return COPER_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const coper_config& cfg = h->cfg;
+  const bool role_enc = cfg.role != COPER_ROLE_SCORE, role_score = cfg.role != COPER_ROLE_ENCODE;
+  int rc;
+  if ((rc = prepare_check_set(h))) return rc;
+  COPER_HIP_TRY(h, hipSetDevice(cfg.device));
+  h->prepared = false;          // (until every derived buffer below exists again: a prepare that fails leaves a handle that refuses passes)
+  h->gcur = 0;                  // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
+  h->pipe.invalidate_grouping();
+  if ((rc = prepare_bn_folds(h, s))) return rc;
+  if (cfg.score_mode != COPER_SCORE_F32 && (rc = prepare_x3_scale(h, s))) return rc;
+  h->enc_bf16 = false;
+  h->x_exp = 0;
+  h->band_launches = 0;
+  h->Rw = 0;
+  if (role_enc && (rc = prepare_encoder(h, s))) return rc;
+  if (role_score && (rc = prepare_entity_images(h, s))) return rc;
+  if ((rc = prepare_device(h, role_score))) return rc;
   if ((rc = fused_fin_update(h, s))) return rc;       // (parameters / exponents moved)
   h->prepared = true;
   return COPER_OK;
@@ -1244,10 +1281,9 @@ COPER_API int coper_post_ranks_audit(coper_handle* h, const int32_t* ranks, int6
 COPER_API int coper_pack_owned_rows(coper_handle* h, const int64_t* local_rows, int64_t n, int64_t cap, float hdr0, float hdr1, float* buf,
                                     void* stream) {
   if (!h || n < 0 || cap < n || !buf || (n > 0 && !local_rows)) return fail(h, COPER_EINVAL, "coper_pack_owned_rows: bad argument");
-  auto e = h->params.find("ent_emb"), b = h->params.find("pred_bias");
-  if (e == h->params.end() || b == h->params.end() || !e->second.set || !b->second.set)
-    return fail(h, COPER_EMISSING, "coper_pack_owned_rows: ent_emb / pred_bias were never set");
-  return launch_pack_owned_rows(h, e->second.ptr, b->second.ptr, local_rows, n, cap, hdr0, hdr1, buf, (hipStream_t)stream);
+  const Leaves& lv = h->lv;
+  if (!lv.ent_emb->set || !lv.pred_bias->set) return fail(h, COPER_EMISSING, "coper_pack_owned_rows: ent_emb / pred_bias were never set");
+  return launch_pack_owned_rows(h, lv.ent_emb->ptr, lv.pred_bias->ptr, local_rows, n, cap, hdr0, hdr1, buf, (hipStream_t)stream);
 }
 
 COPER_API int coper_unpack_rows(coper_handle* h, const float* gathered, const int64_t* take1, const int64_t* take2, int64_t B, float* rows1,

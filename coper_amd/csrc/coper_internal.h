@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <stdint.h>
+#include <deque>
 #include <map>
 #include <string>
 #include <vector>
@@ -109,16 +110,31 @@ class DevBuf {
 };
 
 
-struct Param {
+// One parameter of the configuration: what coper_param_spec reports (name, spec_shape) and what coper_set_param registered.
+struct Leaf {
+  std::string name;
+  std::vector<int64_t> spec_shape;
   const float* ptr = nullptr;
   std::vector<int64_t> shape;
   bool set = false;
 };
 
-struct ParamSpec {
-  std::string name;
-  std::vector<int64_t> shape;
+// The leaves of a handle by role, resolved once (enumerate_leaves in coper_abi.hip, at coper_create): launch code reads
+// h->lv.<leaf>->ptr and never looks a name up.  A leaf the configuration does not have is null.
+struct Leaves {
+  struct Bn { Leaf *gamma = nullptr, *beta = nullptr, *moving_mean = nullptr, *moving_variance = nullptr; };
+  struct Gen {              // a g_MLP generator: proj[0 .. n_hidden], the last one multiplies the context; bn[i] behind proj[i], i < n_hidden
+    int n_hidden = 0;
+    Leaf* proj[COPER_MAX_CTX + 1] = {};
+    Bn bn[COPER_MAX_CTX];
+  };
+  Leaf *ent_emb = nullptr, *pred_bias = nullptr, *rel_emb = nullptr /* none under g_lookup */;
+  Leaf *conv1_weights = nullptr, *conv1_bias = nullptr;   // static filters or g_lookup tables (none where they are generated)
+  Leaf *fc_weights = nullptr, *fc_bias = nullptr;         // static dense layer or g_lookup tables (none where it is generated)
+  Bn Conv1BN, FCBN;
+  Gen gen[4];               // GenId; empty where the parameter is not generated by a g_MLP
 };
+enum GenId { GEN_FC_WEIGHTS = 0, GEN_FC_BIAS = 1, GEN_CONV1_WEIGHTS = 2, GEN_CONV1_BIAS = 3 };
 
 // Derived sizes, exactly as ConvE._create_variables derives them (models.py:261-271).
 struct Dims {
@@ -164,8 +180,8 @@ struct Timer {
 struct coper_handle {
   coper_config cfg;
   coper::Dims dm;
-  std::vector<coper::ParamSpec> specs;
-  std::map<std::string, coper::Param> params;
+  std::deque<coper::Leaf> leaves;    // one per parameter, in spec order; a deque: the elements (and the names handed out) never move
+  coper::Leaves lv;                  // the same leaves by role
   std::string err;
   bool prepared = false;
 
@@ -330,7 +346,14 @@ struct coper_handle {
 
 namespace coper {
 
-struct FilterArgs {          // the filter role's view of a pass (queries of one count launch: all pointers at its first query)
+// what the encoder's launches read: the per-relation buffers coper_prepare derived where the parameter is generated or looked up,
+// the registered tensor where it is static; rel_emb is null under g_lookup
+inline const float* conv_w(const coper_handle* h) { return h->dm.gen_conv ? h->conv_w_rel.get() : h->lv.conv1_weights->ptr; }
+inline const float* conv_b(const coper_handle* h) { return h->dm.gen_conv ? h->conv_b_rel.get() : h->lv.conv1_bias->ptr; }
+inline const float* fc_b(const coper_handle* h) { return h->dm.gen_fc ? h->fc_b_rel.get() : h->lv.fc_bias->ptr; }
+inline const float* rel_emb_or_null(const coper_handle* h) { return h->lv.rel_emb ? h->lv.rel_emb->ptr : nullptr; }
+
+struct FilterArgs {         // the filter role's view of a pass (queries of one count launch: all pointers at its first query)
   const float* hvec; const uint4* Ehi; const uint4* Elo; const float* bias_pad; const int64_t* e2; const int64_t* indptr;
   const int64_t* idx; const float2* tband; int32_t* ranks; int32_t* heavy; const int32_t* x3s; int64_t B, n_local; int d;
 };

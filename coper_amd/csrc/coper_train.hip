@@ -51,9 +51,10 @@ struct PlaneSet {
   operator TgPlanes() const { return TgPlanes{hi, lo, exp}; }
 };
 
-// What the step reads and writes, resolved ONCE (resolve_leaves: at coper_train_init and behind every coper_set_param): the step never
-// looks a name up.  Trainable leaves by their TrainParam, BN moving statistics by where they are registered now.
-struct Leaves {
+// What the step reads and writes: the handle's leaves (coper::Leaves, h->lv) as the step sees them, resolved ONCE (resolve_leaves: at
+// coper_train_init and behind every coper_set_param).  Trainable leaves by their TrainParam, BN moving statistics by where they are
+// registered now.
+struct TrainLeaves {
   TrainParam *ent_emb = nullptr, *rel_emb = nullptr /* none under g_lookup */, *pred_bias = nullptr;
   TrainParam *conv1_weights = nullptr, *conv1_bias = nullptr;   // static filters or g_lookup tables (none where they are generated)
   TrainParam *fc_weights = nullptr, *fc_bias = nullptr;         // static dense layer or g_lookup tables (none where it is generated)
@@ -61,7 +62,7 @@ struct Leaves {
   struct Gen {              // generator chain g: proj[0 .. nh], the last one multiplies the context; bn[i] behind proj[i], i < nh
     TrainParam* proj[COPER_MAX_CTX + 1] = {};
     Bn bn[COPER_MAX_CTX];
-  } gen[4];                 // 0 fc_weights, 1 fc_bias, 2 conv1_weights, 3 conv1_bias
+  } gen[4];                 // GenId
 };
 
 // The one description of TrainState::red, the step's reduction scratch in double (zeroed whole by the step's zero list): [0] loss,
@@ -83,8 +84,6 @@ struct RedLayout {
 enum BnRow { BN1_MEAN, BN1_INV, FCBN_MEAN, FCBN_INV, BN_ROWS };
 
 }  // namespace
-
-static const char* const kGenNames[4] = {"fc_weights", "fc_bias", "conv1_weights", "conv1_bias"};
 
 struct TrainState {
   coper_train_config cfg;
@@ -149,7 +148,7 @@ struct TrainState {
   int mx = 0;                // the widest BN layer: both are sized by it
   RedLayout red_layout() const { return RedLayout{red, (size_t)mx}; }
   float* bn_row(BnRow k) const { return bnst + (size_t)k * mx; }
-  Leaves lv;                 // where the variables are (resolve_leaves)
+  TrainLeaves lv;            // where the variables are (resolve_leaves)
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -221,65 +220,64 @@ static int tg_matmul(coper_handle* h, TrainState* T, hipStream_t s, const MmView
   return tg_gemm_nt(h, px, M, py, N, K, C, ci, cj, s, nsplit, T->mmP, sumsq);
 }
 
-// Fills TrainState::lv: the only place that spells a leaf's name or asks the handle where a variable lives.  `create` (coper_train_init):
-// the trainable leaves become the TrainParams of T->tp (the optimizer's tensor table follows their order); otherwise each is found again.
+// Fills TrainState::lv from the handle's leaves (h->lv, which spells the names): the only place that asks where a variable lives.
+// `create` (coper_train_init): the trainable leaves become the TrainParams of T->tp (the optimizer's tensor table follows their order:
+// the order of the calls here); otherwise each is found again.
 static int resolve_leaves(coper_handle* h, TrainState* T, bool create) {
-  const Dims& dm = h->dm;
-  Leaves& lv = T->lv;
-  lv = Leaves();
+  const Leaves& hl = h->lv;
+  TrainLeaves& lv = T->lv;
+  lv = TrainLeaves();
   int rc = COPER_OK;
-  // where a registered variable lives now; `trainable`: into its TrainParam (created at init, in the order of the calls here)
-  auto var = [&](const std::string& name, TrainParam** trainable) -> float* {
-    auto it = h->params.find(name);
-    if (it == h->params.end() || !it->second.set) {
-      if (!rc) rc = fail(h, COPER_EINVAL, "coper_train: missing parameter " + name);
-      return nullptr;
-    }
-    float* const p = const_cast<float*>(it->second.ptr);
-    if (!trainable) return p;
-    TrainParam* t = T->find(name.c_str());
+  // where a registered BN moving statistic lives now
+  auto stat = [&](const Leaf* lf) -> float* {
+    if (lf && lf->set) return const_cast<float*>(lf->ptr);
+    if (!rc) rc = fail(h, COPER_EINVAL, "coper_train: missing parameter " + (lf ? lf->name : std::string("(not of this configuration)")));
+    return nullptr;
+  };
+  // a trainable leaf: its TrainParam (created at init), pointed at where the variable lives now
+  auto leaf = [&](const Leaf* lf) -> TrainParam* {
+    float* const p = stat(lf);
+    if (!p) return nullptr;
+    TrainParam* t = T->find(lf->name.c_str());
     if (!t && create && (int)T->tp.size() < TR_MAX_PARAMS) {      // (T->tp is reserved: the TrainParams handed out stay where they are)
       T->tp.emplace_back();
       t = &T->tp.back();
-      t->name = name;
+      t->name = lf->name;
       t->n = 1;
-      for (int64_t s : it->second.shape) t->n *= s;
+      for (int64_t s : lf->shape) t->n *= s;
     }
     if (t) t->p = p;
     else if (!rc) rc = create ? fail(h, COPER_EUNSUPPORTED, "coper_train_init: too many trainable tensors")
-                              : fail(h, COPER_EINVAL, "coper_train: not a trainable leaf: " + name);
-    *trainable = t;
-    return p;
+                              : fail(h, COPER_EINVAL, "coper_train: not a trainable leaf: " + lf->name);
+    return t;
   };
-  auto stat = [&](const std::string& name) { return var(name, nullptr); };
-  auto leaf = [&](const std::string& name) { TrainParam* t = nullptr; var(name, &t); return t; };
-  auto bn = [&](const std::string& prefix) {
-    TrainParam *const gamma = leaf(prefix + "/gamma"), *const beta = leaf(prefix + "/beta");
-    return Leaves::Bn{gamma, beta, stat(prefix + "/moving_mean"), stat(prefix + "/moving_variance")};
+  auto bn = [&](const Leaves::Bn& b) {
+    TrainParam *const gamma = leaf(b.gamma), *const beta = leaf(b.beta);
+    return TrainLeaves::Bn{gamma, beta, stat(b.moving_mean), stat(b.moving_variance)};
   };
-  auto chain = [&](int g, int nhx) {
-    for (int i = 0; i <= nhx; ++i) {
-      const std::string pn = std::string(kGenNames[g]) + "/CPG/Projection" + std::to_string(i);
-      lv.gen[g].proj[i] = leaf(pn);
-      if (i < nhx && dm.ctx_bn) lv.gen[g].bn[i] = bn(pn + "/BatchNorm");
+  auto chain = [&](int g) {
+    const Leaves::Gen& hg = hl.gen[g];
+    for (int i = 0; i <= hg.n_hidden; ++i) {
+      lv.gen[g].proj[i] = leaf(hg.proj[i]);
+      if (i < hg.n_hidden && h->dm.ctx_bn) lv.gen[g].bn[i] = bn(hg.bn[i]);
     }
   };
-  lv.ent_emb = leaf("ent_emb");
-  lv.pred_bias = leaf("pred_bias");
-  lv.bn1 = bn("Conv1BN");
-  lv.fcbn = bn("FCBN");
-  if (!dm.lookup) lv.rel_emb = leaf("rel_emb");      // g_lookup has no relation embedding (models.py:210)
-  if (dm.gen_conv && !dm.lookup) {
-    for (int g : {2, 3}) chain(g, T->nhc);
+  lv.ent_emb = leaf(hl.ent_emb);
+  lv.pred_bias = leaf(hl.pred_bias);
+  lv.bn1 = bn(hl.Conv1BN);
+  lv.fcbn = bn(hl.FCBN);
+  if (hl.rel_emb) lv.rel_emb = leaf(hl.rel_emb);      // g_lookup has no relation embedding (models.py:210)
+  if (hl.conv1_weights) {
+    lv.conv1_weights = leaf(hl.conv1_weights);   // static [3,3,1,C], or the [R, 9C] table of g_lookup
+    lv.conv1_bias = leaf(hl.conv1_bias);
   } else {
-    lv.conv1_weights = leaf("conv1_weights");   // static [3,3,1,C], or the [R, 9C] table of g_lookup
-    lv.conv1_bias = leaf("conv1_bias");
+    for (int g : {GEN_CONV1_WEIGHTS, GEN_CONV1_BIAS}) chain(g);
   }
-  if (dm.gen_fc && !dm.lookup) {
-    for (int g : {0, 1}) chain(g, T->nh);
+  if (hl.fc_weights) {
+    lv.fc_weights = leaf(hl.fc_weights);   // static [F, d], or the [R, F*d] table of g_lookup
+    lv.fc_bias = leaf(hl.fc_bias);         // [d], or the [R, d] table
   } else {
-    lv.fc_weights = leaf("fc_weights");   // static [F, d], or the [R, F*d] table of g_lookup
-    lv.fc_bias = leaf("fc_bias");         // [d], or the [R, d] table
+    for (int g : {GEN_FC_WEIGHTS, GEN_FC_BIAS}) chain(g);
   }
   return rc;
 }
@@ -326,8 +324,8 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   if (!(cfg->learning_rate > 0) || cfg->hidden_dropout < 0 || cfg->hidden_dropout >= 1 || cfg->output_dropout < 0 ||
       cfg->output_dropout >= 1)
     return fail(h, COPER_EINVAL, "coper_train_init: bad hyper-parameter");
-  for (auto& sp : h->specs)
-    if (!h->params[sp.name].set) return fail(h, COPER_EINVAL, "coper_train_init: parameter not set: " + sp.name);
+  for (const Leaf& lf : h->leaves)
+    if (!lf.set) return fail(h, COPER_EINVAL, "coper_train_init: parameter not set: " + lf.name);
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   train_destroy(h);
   TrainState* T = new TrainState();
@@ -413,7 +411,7 @@ struct SideJoin {
 struct Step {
   coper_handle* const h;
   TrainState* const T;
-  const Dims& dm; const coper_train_config& tc; const Leaves& lv;
+  const Dims& dm; const coper_train_config& tc; const TrainLeaves& lv;
   hipStream_t const s;
   const int64_t *const e1, *const rel; const int32_t* const lookup; const float* const labels; const int64_t B, L;
   float *const loss_out, *const pred_out, *const h_out;
@@ -547,7 +545,7 @@ struct Step {
     TrainState::Chain& ch = T->chain[g];
     for (int i = 0; i < nhx; ++i) {
       const int ni = ch.dims[i], nj = ch.dims[i + 1];
-      const Leaves::Bn& b = lv.gen[g].bn[i];
+      const TrainLeaves::Bn& b = lv.gen[g].bn[i];
       const int64_t tot = B * nj;
       hipLaunchKernelGGL(k_tr_small_mm, grid1d(tot), dim3(256), 0, s, i ? ch.v[i] : T->c, lv.gen[g].proj[i]->p, B, ni, nj, ch.u[i]);
       const float *ga = nullptr, *be = nullptr;
@@ -802,7 +800,7 @@ struct Step {
     TrainState::Chain& ch = T->chain[g];
     for (int i = nhx - 1; i >= 0; --i) {
       const int ni = ch.dims[i], nj = ch.dims[i + 1];
-      const Leaves::Bn& b = lv.gen[g].bn[i];
+      const TrainLeaves::Bn& b = lv.gen[g].bn[i];
       const TrainParam* const proj = lv.gen[g].proj[i];
       const int64_t tot = B * nj;
       hipLaunchKernelGGL(k_tr_chain_drop_bwd, grid1d(tot), dim3(256), 0, s, ch.dv[i + 1], tot, tc.seed, step, dropout_stage_chain(g, i), thr_c, ks_c,

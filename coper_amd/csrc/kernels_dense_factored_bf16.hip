@@ -216,10 +216,10 @@ int launch_dense_factored(coper_handle* h, const int64_t* e1, const int64_t* rel
   int32_t* bad = h->gset[0].rel_count + dm.R + 1;
   COPER_HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   FacXArgs A;
-  A.ent = h->params["ent_emb"].ptr; A.shard_lo = h->cfg.shard_lo; A.n_local = dm.n_local; A.E = dm.E; A.R = dm.R;
-  A.rel_emb = h->params["rel_emb"].ptr;
-  A.conv_w = dm.gen_conv ? h->conv_w_rel.get() : h->params["conv1_weights"].ptr;
-  A.conv_b = dm.gen_conv ? h->conv_b_rel.get() : h->params["conv1_bias"].ptr;
+  A.ent = h->lv.ent_emb->ptr; A.shard_lo = h->cfg.shard_lo; A.n_local = dm.n_local; A.E = dm.E; A.R = dm.R;
+  A.rel_emb = h->lv.rel_emb->ptr;
+  A.conv_w = conv_w(h);
+  A.conv_b = conv_b(h);
   A.per_rel_conv = dm.gen_conv ? 1 : 0;
   A.scale = h->conv_scale; A.shift = h->conv_shift;
   A.d = dm.d; A.r = dm.r; A.in_w = dm.in_w; A.fh = dm.fh; A.fw = dm.fw; A.C = dm.C; A.Wo = dm.Wo;

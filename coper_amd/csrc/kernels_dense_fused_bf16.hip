@@ -792,10 +792,10 @@ static void dense_fused_launch(coper_handle* h, PassCtx& ctx, const int64_t* e1,
   int64_t cap_small = (dm.gen_fc ? dm.R : 1) + 1;
   FusedConvArgs A;
   A.e1_rows = e1_rows; A.sorted_row = cur.sorted_row; A.sorted_rid = cur.sorted_rid;
-  A.ent = h->params["ent_emb"].ptr;
-  A.rel_emb = dm.lookup ? nullptr : h->params["rel_emb"].ptr;
-  A.conv_w = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
-  A.conv_b = dm.gen_conv ? h->conv_b_rel : h->params["conv1_bias"].ptr;
+  A.ent = h->lv.ent_emb->ptr;
+  A.rel_emb = rel_emb_or_null(h);
+  A.conv_w = conv_w(h);
+  A.conv_b = conv_b(h);
   A.scale = h->conv_scale; A.shift = h->conv_shift; A.x_exp = h->x_exp; A.img_exp = h->img_exp;
   A.per_rel_conv = dm.gen_conv ? 1 : 0;
   A.d = dm.d; A.r = dm.r; A.in_w = dm.in_w; A.in_hw = dm.in_h * dm.in_w; A.Wo = dm.Wo;
@@ -873,7 +873,7 @@ int fused_fin_update(coper_handle* h, hipStream_t s) {
     coper_handle::GroupSet& g = h->gset[i];
     if (i > 0 && !g.slab) continue;
     FusedFinConst c;
-    c.perm = g.perm; c.fc_b = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr; c.scale = h->fc_scale; c.shift = h->fc_shift;
+    c.perm = g.perm; c.fc_b = fc_b(h); c.scale = h->fc_scale; c.shift = h->fc_shift;
     c.w_exp = h->w_exp; c.x3m = g.x3m; c.per_rel_bias = dm.gen_fc ? 1 : 0; c.x_exp = h->x_exp; c.d = dm.d; c.pad = 0;
     int rc;
     if ((rc = g.fin.ensure(h, sizeof c, "fused finalize constants"))) return rc;
@@ -888,7 +888,7 @@ int fused_fin_update(coper_handle* h, hipStream_t s) {
 bool dense_fused_finalizes(const coper_handle* h, int nslices, const float* h_out) {
   static const bool off = getenv("COPER_FUSED_NO_FINALIZE") != nullptr;     // A/B switch, read once
   const Dims& dm = h->dm;
-  const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params.at("fc_bias").ptr;
+  const float* fcb = fc_b(h);
   const coper_handle::GroupSet& g = h->grouping();
   return !off && h_out && nslices == 1 && g.x3m && g.fin && g.fused_fin_perm == g.perm && (dm.d & 3) == 0 &&
          ((((uintptr_t)h_out) | ((uintptr_t)fcb) | ((uintptr_t)h->fc_scale.get()) | ((uintptr_t)h->fc_shift.get())) & 15) == 0;

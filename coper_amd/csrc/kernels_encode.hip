@@ -520,22 +520,22 @@ __global__ __launch_bounds__(256) void k_conv3x3_bn_relu(
 int launch_conv(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
                 hipStream_t s) {
   const Dims& dm = h->dm;
-  const float* rel_emb = dm.lookup ? nullptr : h->params["rel_emb"].ptr;
-  const float* cw = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
-  const float* cb = dm.gen_conv ? h->conv_b_rel : h->params["conv1_bias"].ptr;
+  const float* rel_emb = rel_emb_or_null(h);
+  const float* cw = conv_w(h);
+  const float* cb = conv_b(h);
   ScopedKernelTimer t(h, "conv", s);
   if (dm.fh == 3 && dm.fw == 3 && dm.C % 32 == 0) {
     constexpr int QPB = 4;
     size_t lds = sizeof(float) * (size_t)QPB * dm.in_h * dm.in_w;
     hipLaunchKernelGGL((k_conv3x3_bn_relu<QPB>), dim3((unsigned)((B + QPB - 1) / QPB)), dim3(256), lds, s, e1, rel,
-                       e1_rows, h->grouping().perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
+                       e1_rows, h->grouping().perm, h->lv.ent_emb->ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                        dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad, dm.R, B,
                        h->x_sorted);
   } else {
     size_t lds = sizeof(float) * ((size_t)dm.in_h * dm.in_w + (size_t)dm.fh * dm.fw * dm.C + 3 * (size_t)dm.C);
     hipLaunchKernelGGL(k_conv_bn_relu, dim3((unsigned)B), dim3(256), lds, s, e1, rel, e1_rows, h->grouping().perm,
-                       h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
+                       h->lv.ent_emb->ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                        dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.emb_w, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, dm.fh, dm.fw, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad,
                        dm.R, h->x_sorted);
@@ -878,7 +878,7 @@ int launch_dense(coper_handle* h, const int64_t* rel, int64_t B, int tq, int ksp
 
 int launch_dense_finalize(coper_handle* h, const int64_t* rel, int64_t B, int ksplit, float* h_out, hipStream_t s) {
   const Dims& dm = h->dm;
-  const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr;
+  const float* fcb = fc_b(h);
   int64_t total = B * (dm.d_pad16 / 4);
   hipLaunchKernelGGL(k_dense_finalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->z_part, ksplit,
                      h->ws_queries, B, dm.d, dm.d_pad16, h->grouping().perm, rel, fcb, dm.gen_fc ? 1 : 0, dm.R, h->fc_scale,
@@ -1102,7 +1102,7 @@ int launch_gather_entities(coper_handle* h, const int64_t* ids, int64_t B, float
   const Dims& dm = h->dm;
   int64_t total = B * dm.d;
   hipLaunchKernelGGL(k_gather_entities, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     h->params["ent_emb"].ptr, ids, B, dm.d, (int64_t)h->cfg.shard_lo, dm.n_local, out);
+                     h->lv.ent_emb->ptr, ids, B, dm.d, (int64_t)h->cfg.shard_lo, dm.n_local, out);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }

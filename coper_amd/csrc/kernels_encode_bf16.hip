@@ -117,12 +117,12 @@ __global__ void k_absmax_bits(const float* __restrict__ src, int64_t n, unsigned
 // e_x of the handle (synchronises: prepare).  scratch: two device words.
 int compute_x_exp(coper_handle* h, unsigned* scratch, hipStream_t s) {
   const Dims& dm = h->dm;
-  const float* cw = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
-  const float* cb = dm.gen_conv ? h->conv_b_rel : h->params["conv1_bias"].ptr;
+  const float* cw = conv_w(h);
+  const float* cb = conv_b(h);
   COPER_HIP_TRY(h, hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned), s));
   float rel_max = 0.f;
   if ((dm.stacked || dm.concat_rel) && !dm.lookup) {
-    hipLaunchKernelGGL(k_absmax_bits, dim3(64), dim3(256), 0, s, h->params["rel_emb"].ptr, dm.R * (int64_t)dm.r, scratch + 1);
+    hipLaunchKernelGGL(k_absmax_bits, dim3(64), dim3(256), 0, s, h->lv.rel_emb->ptr, dm.R * (int64_t)dm.r, scratch + 1);
     COPER_HIP_TRY(h, hipMemcpyAsync(&rel_max, scratch + 1, sizeof(float), hipMemcpyDeviceToHost, s));
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
   }
@@ -266,9 +266,9 @@ bool conv_bf16_supported(const Dims& dm) { return dm.fh == 3 && dm.fw == 3 && dm
 
 int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, hipStream_t s) {
   const Dims& dm = h->dm;
-  const float* rel_emb = dm.lookup ? nullptr : h->params["rel_emb"].ptr;
-  const float* cw = dm.gen_conv ? h->conv_w_rel : h->params["conv1_weights"].ptr;
-  const float* cb = dm.gen_conv ? h->conv_b_rel : h->params["conv1_bias"].ptr;
+  const float* rel_emb = rel_emb_or_null(h);
+  const float* cw = conv_w(h);
+  const float* cb = conv_b(h);
   constexpr int QPB = 4;
   size_t lds = sizeof(float) * (size_t)QPB * dm.in_h * dm.in_w;
   unsigned short* xh = (unsigned short*)h->x_sorted;
@@ -277,7 +277,7 @@ int launch_conv_bf16(coper_handle* h, const int64_t* e1, const int64_t* rel, con
   const coper_handle::GroupSet& g = h->grouping();
   int64_t grid = (B + QPB - 1) / QPB;
   hipLaunchKernelGGL((k_conv3x3_bn_relu_bf16<QPB>), dim3((unsigned)grid), dim3(256), lds, s, e1, rel,
-                     e1_rows, g.perm, h->params["ent_emb"].ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
+                     e1_rows, g.perm, h->lv.ent_emb->ptr, (int64_t)h->cfg.shard_lo, dm.n_local, rel_emb, cw, cb,
                      dm.gen_conv ? 1 : 0, h->conv_scale, h->conv_shift, dm.d, dm.r, dm.in_h, dm.in_w,
                      dm.stacked ? 1 : 0, dm.C, dm.Ho, dm.Wo, dm.concat_rel ? 1 : 0, dm.F, dm.F_pad, dm.R, B, g.tiles,
                      g.n_tiles, /*skip_big=*/0, xh, xl, h->x_exp);

@@ -497,8 +497,8 @@ __global__ void k_pair_targets(const float* __restrict__ ent, const float* __res
 int launch_pair_targets(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* tgt,
                         hipStream_t s) {
   const Dims& dm = h->dm;
-  hipLaunchKernelGGL(k_pair_targets, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->params["ent_emb"].ptr,
-                     h->params["pred_bias"].ptr, hvec, e2, B, dm.d, (int64_t)h->cfg.shard_lo, dm.n_local, tgt);
+  hipLaunchKernelGGL(k_pair_targets, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->lv.ent_emb->ptr,
+                     h->lv.pred_bias->ptr, hvec, e2, B, dm.d, (int64_t)h->cfg.shard_lo, dm.n_local, tgt);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -585,7 +585,7 @@ int launch_filter_correct(coper_handle* h, const float* hvec, const float* tgt, 
   (void)nnz;
   int64_t threads = B * 16;
   hipLaunchKernelGGL(k_filter_correct, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
-                     h->params["ent_emb"].ptr, h->params["pred_bias"].ptr, hvec, tgt, e2, indptr, idx, B, dm.d,
+                     h->lv.ent_emb->ptr, h->lv.pred_bias->ptr, hvec, tgt, e2, indptr, idx, B, dm.d,
                      (int64_t)h->cfg.shard_lo, dm.n_local, ng, ne);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
@@ -606,7 +606,7 @@ int launch_score_lookup(coper_handle* h, const float* hvec, const int32_t* looku
   const Dims& dm = h->dm;
   int64_t total = B * L;
   hipLaunchKernelGGL(k_score_lookup, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     h->params["ent_emb"].ptr, h->params["pred_bias"].ptr, hvec, lookup, B, L, dm.d,
+                     h->lv.ent_emb->ptr, h->lv.pred_bias->ptr, hvec, lookup, B, L, dm.d,
                      (int64_t)h->cfg.shard_lo, dm.n_local, out);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
@@ -807,8 +807,8 @@ __global__ __launch_bounds__(256) void k_topk_score_blocks_f32(const float* __re
 int launch_topk_score_blocks_f32(coper_handle* h, const float* hvec, int64_t T, const int64_t* e2, const int64_t* indptr,
                                  const int64_t* idx, hipStream_t s) {
   const Dims& dm = h->dm;
-  hipLaunchKernelGGL(k_topk_score_blocks_f32, dim3((unsigned)((T * 32 + 255) / 256)), dim3(256), 0, s, h->params["ent_emb"].ptr,
-                     h->params["pred_bias"].ptr, hvec, dm.d, T, e2, indptr, idx, h->cand_blk_ws, h->cand_q_ws, (int64_t)h->cfg.shard_lo,
+  hipLaunchKernelGGL(k_topk_score_blocks_f32, dim3((unsigned)((T * 32 + 255) / 256)), dim3(256), 0, s, h->lv.ent_emb->ptr,
+                     h->lv.pred_bias->ptr, hvec, dm.d, T, e2, indptr, idx, h->cand_blk_ws, h->cand_q_ws, (int64_t)h->cfg.shard_lo,
                      dm.n_local, h->cand_val_ws);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;

@@ -761,7 +761,7 @@ int launch_exact_rows(coper_handle* h, const float* hvec, const float* rows, con
 }
 
 int launch_exact_targets(coper_handle* h, const float* hvec, const int64_t* e2, int64_t B, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_exact_targets, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->params["ent_emb"].ptr, h->params["pred_bias"].ptr,
+  hipLaunchKernelGGL(k_exact_targets, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->lv.ent_emb->ptr, h->lv.pred_bias->ptr,
                      hvec, e2, B, h->dm.d, (int64_t)h->cfg.shard_lo, h->dm.n_local, out);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
@@ -1254,7 +1254,7 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
     ScopedKernelTimer t(h, "band_exact", s);
     const int64_t rows_per_tile = h->dm.n_eblk * 2 / SC3_MB / 8;
     BandArgs A;
-    A.hvec = hvec + q0 * h->dm.d; A.ent = h->params["ent_emb"].ptr; A.bias = h->params["pred_bias"].ptr;
+    A.hvec = hvec + q0 * h->dm.d; A.ent = h->lv.ent_emb->ptr; A.bias = h->lv.pred_bias->ptr;
     A.e2 = e2 + q0; A.indptr = indptr + q0; A.idx = idx; A.tgt_x = tgt_x ? tgt_x + q0 : nullptr;
     A.ng = ng + q0; A.ne = ne ? ne + q0 : nullptr; A.Bc = Bc; A.n_local = h->dm.n_local; A.shard_lo = (int64_t)h->cfg.shard_lo; A.d = h->dm.d;
     { static const int dbg = getenv("COPER_DBG_BAND") ? atoi(getenv("COPER_DBG_BAND")) : 0; A.dbg = dbg; }

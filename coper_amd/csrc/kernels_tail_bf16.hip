@@ -395,7 +395,7 @@ bool tail_fused_supported(const coper_handle* h) {
 int launch_finalize_h_publish(coper_handle* h, int64_t B, int ksplit, float* h_out, hipStream_t s) {
   if (ksplit == 0) return COPER_OK;      // the fused encoder finalized in its own epilogue (kernels_dense_fused_bf16.hip: FusedFin)
   const Dims& dm = h->dm;
-  const float* fcb = dm.gen_fc ? h->fc_b_rel : h->params["fc_bias"].ptr;
+  const float* fcb = fc_b(h);
   int64_t blocks = (B + 7) / 8;                    // eight rows per block and round
   if (blocks > X3M_SLOTS) blocks = X3M_SLOTS;
   const coper_handle::GroupSet& g = h->grouping();

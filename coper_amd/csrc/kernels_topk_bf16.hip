@@ -1228,7 +1228,7 @@ int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t
                      h->cand_val_ws, h->x3s);
   PredictArgs A;
   A.cand_val = h->cand_val_ws; A.cand_blk = h->cand_blk_ws; A.cand_tau = h->cand_tau_ws; A.indptr = indptr;
-  A.hvec = hvec; A.ent = h->params["ent_emb"].ptr; A.bias = h->params["pred_bias"].ptr; A.consts = h->band_consts; A.x3s = h->x3s;
+  A.hvec = hvec; A.ent = h->lv.ent_emb->ptr; A.bias = h->lv.pred_bias->ptr; A.consts = h->band_consts; A.x3s = h->x3s;
   A.out_val = topk_val; A.out_idx = topk_idx; A.q_kept = h->pred_q_ws; A.q_ratio = (uint32_t*)(h->pred_q_ws + B);
   A.B = B; A.lo = (int64_t)h->cfg.shard_lo; A.k = k; A.ks = ks; A.xf = XF; A.d = dm.d; A.kappa = band_kappa(h);
   hipLaunchKernelGGL(k_predict_select_x3, dim3((unsigned)B), dim3(256), 0, s, A);

@@ -4,7 +4,8 @@ ranker; these run the same kernels against the same references after the sequenc
 A. EntityShardedRanker.rank_stream with the host far ahead of the device: every chunk's plan travels through a ring of four pinned
    buffers, and a slot must not be rewritten before the copy that reads it has run.
 B. Parameters edited between training steps and between inference passes: the registered tensors ARE the variables, so an in-place
-   torch edit must reach the training step's packing scale and the prepared inference caches.
+   torch edit must reach the training step's packing scale and the prepared inference caches -- and a leaf registered again at
+   another address must be read there by every launch, never where it was first registered.
 C. coper_train_grad after an evaluation pass, an encode or a reserve: the looked-up dense table's absent rows are zeroed by the
    relation counts of the STEP, not by whatever batch was grouped since."""
 import numpy as np
@@ -216,11 +217,69 @@ def _edit_inference(T, ent=True):
             T["fc_weights"].mul_(-3.0)
         else:
             T["fc_weights/CPG/Projection0"].mul_(-3.0)
-        T["rel_emb"].mul_(0.5).add_(0.01)
+        if "rel_emb" in T:                   # (g_lookup has none)
+            T["rel_emb"].mul_(0.5).add_(0.01)
 
 
 def _same(a, b):
     return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+_MOVED = {"cpg": ("fb15k237_cpg", {}),
+          "cpg_hidden_bn": ("fb15k237_cpg", dict(context_rel_out=[64], context_rel_conv=[16])),
+          "plain": ("fb15k237_plain", {}),
+          "lookup": ("fb15k237_cpg", dict(do_parameter_lookup=True, context_rel_conv=[]))}
+_MOVED_CASES = [(c, mode, "cached") for c in _MOVED for mode in ("f32", "bf16x3")] + [("cpg", "bf16x3", "factored")]
+
+
+def _every_route(m, q, lookup):
+    """name -> tensor of every inference route that reads a registered leaf at launch time"""
+    h = m.encode(q["e1"], q["rel"])
+    out = {"encode": h}
+    out["rank"], out["rank n_equal"] = m.rank(h, q["e2"], q["filt_indptr"], q["filt_idx"])
+    out["rank_pass"], out["rank_pass n_equal"] = m.rank_pass(q["e1"], q["rel"], q["e2"], q["filt_indptr"], q["filt_idx"])
+    out["score_all"] = m.score_all(h)
+    out["score_lookup"] = m.score_lookup(h, lookup)
+    out["target_scores"] = m.target_scores(h, q["e2"])
+    out["gather_entities"] = m.gather_entities(q["e2"])
+    out["predict_topk val"], out["predict_topk idx"] = m.predict_topk(q["e1"], q["rel"], 5, q["filt_indptr"], q["filt_idx"])
+    return out
+
+
+@pytest.mark.parametrize("case,mode,dense", _MOVED_CASES, ids=["-".join(c) for c in _MOVED_CASES])
+def test_inference_after_every_parameter_was_registered_at_a_new_address(case, mode, dense):
+    """encode + rank, then EVERY leaf registered again from an edited clone (a checkpoint loaded into fresh tensors) while the old
+    tensors stay alive full of NaN: after prepare every inference route is a fresh model's of the same values, bit for bit, and free
+    of NaN -- no launch site reads a pointer it kept from the first registration."""
+    from coper_amd.models import ConvE
+    name, over = _MOVED[case]
+    md = cdata.model_descriptors(name, num_ent=3000, num_rel=40, **over)
+    p = {k: torch.as_tensor(v).to(DEV) for k, v in cdata.synthetic_params(md, 9).items()}
+    q = cdata.synthetic_queries(md, 300, seed=10)
+    lookup = np.random.default_rng(3).integers(0, md["num_ent"], (300, 8)).astype(np.int32)
+    m = ConvE(md, device=DEV, score_mode=mode, dense=dense).load_parameters(p).prepare()
+    h0 = m.encode(q["e1"], q["rel"])
+    m.rank(h0, q["e2"], q["filt_indptr"], q["filt_idx"])
+    torch.cuda.synchronize()
+    old = dict(m._tensors)
+    assert set(old) == set(m.parameter_specs)
+    clones = {k: t.clone() for k, t in old.items()}
+    _edit_inference(clones)
+    m.load_parameters(clones)
+    for k, t in old.items():
+        assert m._tensors[k].data_ptr() != t.data_ptr(), k
+        t.fill_(float("nan"))          # (kept alive: the allocator cannot hand these addresses to the clones or to `fresh`)
+    m.prepare()
+    fresh = ConvE(md, device=DEV, score_mode=mode, dense=dense).load_parameters({k: t.clone() for k, t in clones.items()}).prepare()
+    got, want = _every_route(m, q, lookup), _every_route(fresh, q, lookup)
+    for k, w in want.items():
+        g = got[k]
+        assert g.dtype == w.dtype and (_same(g, w) if g.dtype == torch.float32 else torch.equal(g, w)), k
+        assert not (g.dtype == torch.float32 and bool(torch.isnan(g).any())), k
+    assert not _same(got["encode"], h0)
+    assert all(bool(torch.isnan(t).all()) for t in old.values())
+    m.close()
+    fresh.close()
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16x3"])
