@@ -462,19 +462,26 @@ inline int64_t topk_chunk_queries(int64_t n_eblk, int64_t B, int64_t cap_floats)
   const int64_t Bpad = (B + 127) / 128 * 128;
   return qc > Bpad ? Bpad : qc;
 }
-// The coarse level of the top-k threshold kernel (kernels_topk_bf16.hip: TK_GRP; round 5): one key per 16 visits of a thread, i.e.
-// 1/16 of the block maxima of a query chunk -- bytes of the scratch for G blocks x qs queries, for either strip width (4 x QV
-// queries, 512 / QV sub-ranges); 0: the block axis is too short for the route to pay.
-constexpr int64_t TK_COARSE_MIN_BLOCKS = 16384;
+// Geometry of the top-k threshold kernel (kernels_topk_bf16.hip): a workgroup of TK_THREADS threads per strip of 4 x QV queries
+// (QV = 4 or 8), the block axis divided among TK_THREADS / QV sub-ranges.
+constexpr int TK_THREADS = 512;
+constexpr int tk_strip_queries(int QV) { return 4 * QV; }
+constexpr int tk_sub_ranges(int QV) { return TK_THREADS / QV; }
+inline int64_t tk_strips(int64_t qs, int QV) { return (qs + tk_strip_queries(QV) - 1) / tk_strip_queries(QV); }
+// Its coarse level (round 5): one key per TK_GRP visits of a thread, i.e. 1/16 of the block maxima of a query chunk.
+constexpr int TK_GRP = 16;
+constexpr int64_t TK_COARSE_MIN_BLOCKS = 16384;       // below: the block axis is too short for the route to pay
+inline int64_t tk_coarse_groups(int64_t G, int QV) {  // coarse keys a thread writes
+  return ((G + tk_sub_ranges(QV) - 1) / tk_sub_ranges(QV) + TK_GRP - 1) / TK_GRP;
+}
+inline size_t tk_coarse_bytes(int64_t G, int64_t qs, int QV) {   // four keys (a thread's four queries) per thread, group and strip
+  return (size_t)tk_strips(qs, QV) * tk_coarse_groups(G, QV) * TK_THREADS * sizeof(uint4);
+}
+// bytes of the scratch for G blocks x qs queries, for either strip width; 0: no coarse route
 inline size_t topk_coarse_bytes(int64_t G, int64_t qs) {
   if (G < TK_COARSE_MIN_BLOCKS) return 0;
-  size_t need = 0;
-  for (int QV : {4, 8}) {
-    const int64_t SUB = 512 / QV, NG = ((G + SUB - 1) / SUB + 15) / 16, strips = (qs + 4 * QV - 1) / (4 * QV);
-    const size_t b = (size_t)strips * NG * 512 * 16;
-    need = b > need ? b : need;
-  }
-  return need;
+  const size_t b4 = tk_coarse_bytes(G, qs, 4), b8 = tk_coarse_bytes(G, qs, 8);
+  return b4 > b8 ? b4 : b8;
 }
 // size of the block-grouped slot list: every block with candidates is padded to a multiple of 32
 // counters per block for the grouping of candidate slots: few blocks = many slots per block = contended atomics

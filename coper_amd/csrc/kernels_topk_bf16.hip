@@ -32,7 +32,6 @@ __device__ __forceinline__ uint32_t tk_key(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-constexpr int TK_THREADS = 512;
 #ifndef COPER_TK_DEPTH
 #define COPER_TK_DEPTH 4
 #endif
@@ -99,20 +98,20 @@ constexpr int TK_BIN = 64;   // block maxima per query that may share the thresh
 // largest COARSE key tau_c on that level (four passes over 1/16), and then only the groups whose coarse key reaches tau_c are
 // read again: the m-th largest maximum tau is >= tau_c (the m largest coarse keys are m maxima >= tau_c), so every block with a
 // maximum >= tau lies in such a group -- about m groups per query.  Their maxima >= tau_c go to an LDS list (TK_CL entries per
-// query) that is ranked (key desc, block asc) exactly as the bin list of the fast path was; a list that overflows (queries with
+// query) that is ranked (key desc, block asc) exactly as the bin list of the fast path is; a list that overflows (queries with
 // hundreds of known answers: m = k + their number) sends the strip down the three-sweep route.
-constexpr int TK_GRP = 16;   // visits per coarse key
 constexpr int TK_CL = 128;   // candidate-list entries per query on the coarse route (>= TK_BIN: the two routes share the lists)
 
 // Threshold + candidate blocks of a strip of NQS = 4 * QV queries (QV = 8: 32 queries; QV = 4: 16).
 // thread = (sub-range of the block axis, 4 queries); HCOPY histogram copies (sub-range % HCOPY) thin out same-bank
-// LDS atomics.  Three sweeps over the strip's block maxima in the common case:
-//   1, 2  radix-select the upper 16 bits of the m-th largest (two 8-bit digits);
-//   3     blocks above that 16-bit bin are candidates (slot by an LDS counter), blocks inside it go to a short LDS
-//         list; the list is ranked in LDS ((key desc, block asc): exact ties go to the lowest-numbered blocks) and
-//         its first `rem` entries complete the m candidates.
-// A bin with more than TK_BIN blocks (heavy ties, clustered maxima) takes the general route instead: two more radix
-// digits, a counting sweep and an ordered emission sweep, rewriting the strip's slots.
+// LDS atomics.  A strip takes the first of three routes that finishes it (k_topk_threshold_emit):
+//   coarse   (long block axes, see above) one sweep, a select on the coarse level, a ranked list;
+//   fast     three sweeps: 1, 2 radix-select the upper 16 bits of the m-th largest (two 8-bit digits); 3: blocks above that
+//            16-bit bin are candidates (slot by an LDS counter), blocks inside it go to a short LDS list; the list is ranked in
+//            LDS ((key desc, block asc): exact ties go to the lowest-numbered blocks) and its first `rem` entries complete the
+//            m candidates;
+//   general  a bin with more than TK_BIN blocks (heavy ties, clustered maxima): two more radix digits, a counting sweep and
+//            an ordered emission sweep, rewriting the strip's slots.
 #ifdef COPER_DBG_TK_OVER
 // diagnostic build: strips that left the fast path (a query of the strip has more than TK_BIN maxima in its threshold bin)
 __device__ int g_tk_over;
@@ -147,280 +146,312 @@ __device__ __forceinline__ void tk_coarse_walk(const uint4* __restrict__ my, int
   }
 }
 
+// The strip's dynamic LDS: the kernel's views are its members, the launch asks for its size.
 template <int QV, int HCOPY>
-__global__ __launch_bounds__(TK_THREADS) void k_topk_threshold_emit(const float* __restrict__ gmax, int64_t G, int64_t Qs, int64_t q0,
-                                                                    int64_t Bc, int k, const int64_t* __restrict__ indptr,
-                                                                    int32_t* __restrict__ cand_blk, int32_t* __restrict__ cand_q,
-                                                                    int32_t* __restrict__ blk_cnt, int nseg,
-                                                                    uint32_t* __restrict__ cand_tau, int pair_xcd,
-                                                                    uint4* __restrict__ coarse, int64_t NG) {
-  constexpr int NQS = 4 * QV, SUB = TK_THREADS / QV;
-  extern __shared__ uint32_t tk_lds[];
-  uint32_t* hist = tk_lds;                               // [HCOPY][256 digits][NQS]
-  uint32_t* s_prefix = hist + HCOPY * 256 * NQS;         // [NQS]
-  uint32_t* s_rem = s_prefix + NQS;                      // [NQS]
-  uint32_t* s_slot = s_rem + NQS;                        // [NQS] fast path: candidates emitted so far
-  uint32_t* s_bn = s_slot + NQS;                         // [NQS] fast path: entries of the bin list
-  uint32_t* s_cgt = s_bn + NQS;                          // [SUB][NQS]   (general route)
-  uint32_t* s_ceq = s_cgt + SUB * NQS;                   // [SUB][NQS]
-  uint32_t* s_bkey = s_ceq + SUB * NQS;                  // [NQS][TK_CL]   (fast path: TK_BIN of them)
-  int32_t* s_bg = (int32_t*)(s_bkey + NQS * TK_CL);      // [NQS][TK_CL]
-  const int qv = threadIdx.x % QV, sr = threadIdx.x / QV;
-  // 16-query strips are 64 B of a 128-B line of gmax: the two strips of a line go to workgroups 8 apart, i.e. to the same
-  // XCD (workgroup w runs on XCD w % 8) -- one L2 then fetches the line once, where neighbouring workgroups (two XCDs)
-  // fetched it twice
-  int64_t strip = blockIdx.x;
-  if (QV == 4 && pair_xcd && (gridDim.x & 15) == 0) strip = (((int64_t)blockIdx.x >> 4) * 8 + (blockIdx.x & 7)) * 2 + ((blockIdx.x >> 3) & 1);
-  const int64_t qs0 = strip * NQS;                       // first query of the strip within the chunk
-  const int64_t gs = (G + SUB - 1) / SUB;
-  const int64_t g_lo = sr * gs < G ? sr * gs : G;
-  const int64_t g_hi = g_lo + gs < G ? g_lo + gs : G;
-  const float4* col = (const float4*)(gmax + qs0) + qv;  // + g * (Qs / 4)
-  const int64_t qs4 = Qs >> 2;
-  const uint32_t kinf = tk_key(-INFINITY);
-  if (threadIdx.x < NQS) {
-    const int64_t ql = qs0 + threadIdx.x;
-    int64_t m64 = 0;
-    if (ql < Bc) {
-      m64 = (int64_t)k + (indptr[q0 + ql + 1] - indptr[q0 + ql]);
-      if (m64 > G) m64 = G;
-    }
-    s_prefix[threadIdx.x] = 0;
-    s_rem[threadIdx.x] = (uint32_t)m64;
-    s_slot[threadIdx.x] = 0;
-    s_bn[threadIdx.x] = 0;
-  }
-  // this thread's four queries: slot range and validity
-  int64_t off[4], slots[4];
+struct TkLds {
+  static constexpr int NQS = tk_strip_queries(QV), SUB = tk_sub_ranges(QV);
+  uint32_t hist[HCOPY * 256 * NQS];           // [HCOPY][256 digits][NQS]
+  uint32_t prefix[NQS], rem[NQS];             // digits of the m-th largest key found so far, its rank among the keys that share them
+  uint32_t slot[NQS], bn[NQS];                // fast path: candidates emitted so far; entries of the query's list
+  uint32_t cgt[SUB * NQS], ceq[SUB * NQS];    // [SUB][NQS]   (general route)
+  uint32_t bkey[NQS * TK_CL];                 // [NQS][TK_CL]   (fast path: TK_BIN of them)
+  int32_t bg[NQS * TK_CL];                    // [NQS][TK_CL]
+};
+template <int QV, int HCOPY>
+constexpr size_t tk_emit_lds() { return sizeof(TkLds<QV, HCOPY>); }
+
+// What the phases of a strip share: its LDS, the launch's arguments, and the thread's place in the strip.
+template <int QV, int HCOPY>
+struct TkStrip {
+  static constexpr int NQS = tk_strip_queries(QV), SUB = tk_sub_ranges(QV);
+  TkLds<QV, HCOPY>& lds;
+  uint32_t* myhist;              // this thread's histogram copy, at its four queries
+  // the launch
+  int64_t G, q0, Bc;
+  int k;
+  const int64_t* __restrict__ indptr;
+  int32_t *__restrict__ cand_blk, *__restrict__ cand_q;
+  uint32_t* __restrict__ cand_tau;
+  // the thread: queries 4 qv .. 4 qv + 3 of the strip, sub-range sr of the block axis
+  int qv, sr;
+  int64_t strip, qs0;            // qs0: first query of the strip within the chunk
+  const float4* __restrict__ col;   // + g * qs4: the four queries' maxima of block g
+  int64_t qs4, g_lo, g_hi;       // [g_lo, g_hi): the thread's share of the sweeps that go in block order
   bool valid[4];
+  int64_t off[4], slots[4];      // the queries' slot ranges in cand_blk / cand_q
+
+  __device__ __forceinline__ TkStrip(TkLds<QV, HCOPY>& L, const float* __restrict__ gmax, int64_t G_, int64_t Qs, int64_t q0_, int64_t Bc_, int k_,
+                                     const int64_t* __restrict__ indptr_, int32_t* __restrict__ cand_blk_, int32_t* __restrict__ cand_q_,
+                                     uint32_t* __restrict__ cand_tau_, int pair_xcd)
+      : lds(L), G(G_), q0(q0_), Bc(Bc_), k(k_), indptr(indptr_), cand_blk(cand_blk_), cand_q(cand_q_), cand_tau(cand_tau_) {
+    qv = threadIdx.x % QV; sr = threadIdx.x / QV;
+    myhist = L.hist + (sr % HCOPY) * 256 * NQS + 4 * qv;
+    // 16-query strips are 64 B of a 128-B line of gmax: the two strips of a line go to workgroups 8 apart, i.e. to the same
+    // XCD (workgroup w runs on XCD w % 8) -- one L2 then fetches the line once, where neighbouring workgroups (two XCDs)
+    // fetched it twice
+    strip = blockIdx.x;
+    if (QV == 4 && pair_xcd && (gridDim.x & 15) == 0) strip = (((int64_t)blockIdx.x >> 4) * 8 + (blockIdx.x & 7)) * 2 + ((blockIdx.x >> 3) & 1);
+    qs0 = strip * NQS;
+    const int64_t gs = (G + SUB - 1) / SUB;
+    g_lo = sr * gs < G ? sr * gs : G;
+    g_hi = g_lo + gs < G ? g_lo + gs : G;
+    col = (const float4*)(gmax + qs0) + qv;
+    qs4 = Qs >> 2;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t ql = qs0 + 4 * qv + c;
+      valid[c] = ql < Bc;
+      off[c] = slots[c] = 0;
+      if (valid[c]) {
+        const int64_t qg = q0 + ql;
+        const int64_t beg = indptr[qg] - indptr[0];
+        off[c] = (int64_t)k * qg + beg;
+        slots[c] = (int64_t)k + (indptr[qg + 1] - indptr[0] - beg);
+      }
+    }
+  }
+};
+
+// Every query starts as "the m-th largest of all keys", m = k + its filter entries, clamped to the number of blocks; no
+// candidate emitted, the lists empty.
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_strip_reset(const TkStrip<QV, HCOPY>& st) {
+  if (threadIdx.x < st.NQS) {
+    const int64_t ql = st.qs0 + threadIdx.x;
+    int64_t m64 = 0;
+    if (ql < st.Bc) {
+      m64 = (int64_t)st.k + (st.indptr[st.q0 + ql + 1] - st.indptr[st.q0 + ql]);
+      if (m64 > st.G) m64 = st.G;
+    }
+    st.lds.prefix[threadIdx.x] = 0;
+    st.lds.rem[threadIdx.x] = (uint32_t)m64;
+    st.lds.slot[threadIdx.x] = 0;
+    st.lds.bn[threadIdx.x] = 0;
+  }
+}
+
+// From the histogram of one radix digit (complete: the caller's sweep has ended) the digit of the rem-th largest among the keys
+// that share the prefix; prefix and rem move on to the next pass.
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_pick_digit(const TkStrip<QV, HCOPY>& st, int shift) {
+  __syncthreads();
+  if (threadIdx.x < st.NQS) {
+    const int qi = threadIdx.x;
+    const uint32_t rem = st.lds.rem[qi];
+    if (rem > 0) {
+      uint32_t cum = 0;
+      int dg = 255;
+      for (; dg > 0; --dg) {
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int hc = 0; hc < HCOPY; ++hc) cnt += st.lds.hist[(hc * 256 + dg) * st.NQS + qi];
+        if (cum + cnt >= rem) break;
+        cum += cnt;
+      }
+      st.lds.prefix[qi] |= (uint32_t)dg << shift;
+      st.lds.rem[qi] = rem - cum;
+    }
+  }
+  __syncthreads();
+}
+
+// One 8-bit digit of the m-th largest block maximum: a histogram sweep over the keys that share the digits found so far.
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_radix_pass(const TkStrip<QV, HCOPY>& st, int pass) {
+  const int shift = 24 - 8 * pass;
+  const uint32_t mask = pass ? ~0u << (32 - 8 * pass) : 0u;   // the digits found so far
+  for (int j = threadIdx.x; j < HCOPY * 256 * st.NQS; j += TK_THREADS) st.lds.hist[j] = 0;
+  __syncthreads();
+  uint32_t prefix[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) prefix[c] = st.lds.prefix[4 * st.qv + c];
+  // block maxima cluster: consecutive values of a query mostly share the digit (in the first pass -- sign and the upper
+  // exponent bits -- nearly all of them), so a thread counts runs in registers and adds a run at once; one LDS atomic per
+  // value on a handful of addresses was what the sweep spent its time on
+  uint32_t run_d[4] = {0, 0, 0, 0}, run_n[4] = {0, 0, 0, 0};
+  tk_sweep_strided(st.col, st.qs4, (int64_t)st.sr, (int64_t)st.SUB, st.G, [&](int64_t, const float4& v4) {
+    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const uint32_t key = tk_key(vv[c]);
+      if ((key & mask) == prefix[c]) {
+        const uint32_t dgt = (key >> shift) & 255;
+        if (dgt != run_d[c]) {
+          if (run_n[c]) atomicAdd(&st.myhist[run_d[c] * st.NQS + c], run_n[c]);
+          run_d[c] = dgt;
+          run_n[c] = 0;
+        }
+        ++run_n[c];
+      }
+    }
+  });
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (run_n[c]) atomicAdd(&st.myhist[run_d[c] * st.NQS + c], run_n[c]);
+  tk_pick_digit(st, shift);
+}
+
+// Ranks the queries' LDS lists (STRIDE entries each, lds.bn of them used) by (key desc, block asc) and writes the first `want`
+// entries of each to the candidate slots from `base` on.  whole: the list holds every block that can be a candidate (coarse
+// route): base 0, want m; otherwise it is the threshold bin's (fast path): lds.slot candidates precede it, lds.rem are wanted.
+// The entry that completes the m candidates carries tau, what the selection may discard unseen: logits below tau, when tau is
+// a real m-th largest (at least k unmasked logits >= tau exist then); with every block a candidate (m clamped to G) or a -inf
+// tau nothing is discarded.
+template <int STRIDE, int QV, int HCOPY>
+__device__ __forceinline__ void tk_rank_list(const TkStrip<QV, HCOPY>& st, bool whole) {
+  const uint32_t kinf = tk_key(-INFINITY);
+  for (int t = threadIdx.x; t < st.NQS * STRIDE; t += TK_THREADS) {
+    const int qi = t / STRIDE, e = t % STRIDE;
+    const int64_t ql = st.qs0 + qi;
+    const uint32_t nb = st.lds.bn[qi];
+    if (ql >= st.Bc || (uint32_t)e >= nb) continue;
+    const int64_t qg = st.q0 + ql;
+    const int64_t beg = st.indptr[qg] - st.indptr[0];
+    const int64_t nslots = (int64_t)st.k + (st.indptr[qg + 1] - st.indptr[0] - beg);
+    const uint32_t base = whole ? 0u : st.lds.slot[qi];
+    const uint32_t want = whole ? (uint32_t)(nslots < st.G ? nslots : st.G) : st.lds.rem[qi];
+    const uint32_t key = st.lds.bkey[qi * STRIDE + e];
+    const int32_t g = st.lds.bg[qi * STRIDE + e];
+    uint32_t ahead = 0;
+    for (uint32_t t2 = 0; t2 < nb; ++t2) {
+      const uint32_t k2 = st.lds.bkey[qi * STRIDE + t2];
+      ahead += (k2 > key || (k2 == key && st.lds.bg[qi * STRIDE + t2] < g)) ? 1u : 0u;
+    }
+    if (ahead >= want) continue;
+    const int64_t o = (int64_t)st.k * qg + beg;
+    st.cand_blk[o + base + ahead] = key > kinf ? g : -1;   // blocks whose maximum is -inf hold nothing: their slots stay unused
+    if (ahead == want - 1) st.cand_tau[qg] = (nslots <= st.G && key > kinf) ? key : 0u;
+  }
+}
+
+// Query ids of all slots of the thread's query c; slots past the `used` candidates are unused.
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_fill_slots(const TkStrip<QV, HCOPY>& st, int c, int64_t used) {
+  if (!st.valid[c]) return;
+  for (int64_t j = st.sr; j < st.slots[c]; j += st.SUB) {
+    st.cand_q[st.off[c] + j] = (int32_t)(st.q0 + st.qs0 + 4 * st.qv + c);
+    if (j >= used) st.cand_blk[st.off[c] + j] = -1;
+  }
+}
+
+// Candidates are scored block by block: how many slots want block g (nseg counters per block thin out the same-address
+// atomics when there are few blocks).
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_count_blocks(const TkStrip<QV, HCOPY>& st, int32_t* __restrict__ blk_cnt, int nseg) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const int64_t ql = qs0 + 4 * qv + c;
-    valid[c] = ql < Bc;
-    off[c] = slots[c] = 0;
-    if (valid[c]) {
-      const int64_t qg = q0 + ql;
-      const int64_t beg = indptr[qg] - indptr[0];
-      off[c] = (int64_t)k * qg + beg;
-      slots[c] = (int64_t)k + (indptr[qg + 1] - indptr[0] - beg);
+    if (!st.valid[c] || !blk_cnt) continue;      // (blk_cnt == NULL: 64-entity candidates, counted after their expansion: k_topk_expand64)
+    for (int64_t j = st.sr; j < st.slots[c]; j += st.SUB) {
+      const int32_t g = st.cand_blk[st.off[c] + j];
+      if (g >= 0) atomicAdd(&blk_cnt[(int64_t)g * nseg + ((st.off[c] + j) & (nseg - 1))], 1);
     }
   }
-  // a sweep whose result does not depend on the visiting order (contiguous ranges were the A/B form of round 4)
-  auto sweep_any_order = [&](auto&& f) {
-    tk_sweep_strided(col, qs4, (int64_t)sr, (int64_t)SUB, G, f);
-  };
-  uint32_t* myhist = hist + (sr % HCOPY) * 256 * NQS + 4 * qv;
-  uint32_t mask = 0;
-  auto radix_pass = [&](int pass) {
+}
+
+// ---- the coarse route (see TK_CL above).  false: a list overflowed, and the strip is reset for the three-sweep route.
+template <int QV, int HCOPY>
+__device__ __forceinline__ bool tk_route_coarse(const TkStrip<QV, HCOPY>& st, uint4* __restrict__ coarse, int64_t NG) {
+  const int qv = st.qv, sr = st.sr;
+  const int64_t G = st.G;
+  uint4* my = coarse + ((int64_t)st.strip * NG) * TK_THREADS + threadIdx.x;      // my group jg: my[jg * TK_THREADS]
+  const int64_t n_vis = (int64_t)sr < G ? (G - sr + st.SUB - 1) / st.SUB : 0;     // my visits: blocks sr, sr + SUB, ...
+  const int64_t n_grp = (n_vis + TK_GRP - 1) / TK_GRP;
+  {   // sweep 1: the largest key of every TK_GRP visits
+    uint32_t gm[4] = {0u, 0u, 0u, 0u};
+    int64_t gj = 0;
+    tk_sweep_strided(st.col, st.qs4, (int64_t)st.sr, (int64_t)st.SUB, st.G, [&](int64_t g, const float4& v4) {
+      const int64_t jg = ((g - sr) / st.SUB) / TK_GRP;
+      if (jg != gj) { my[gj * TK_THREADS] = make_uint4(gm[0], gm[1], gm[2], gm[3]); gm[0] = gm[1] = gm[2] = gm[3] = 0u; gj = jg; }
+      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { const uint32_t key = tk_key(vv[c]); gm[c] = key > gm[c] ? key : gm[c]; }
+    });
+    if (n_vis > 0) my[gj * TK_THREADS] = make_uint4(gm[0], gm[1], gm[2], gm[3]);
+  }
+  // the m-th largest coarse key of every query: four radix digits over the keys this thread wrote itself
+  for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
-    for (int j = threadIdx.x; j < HCOPY * 256 * NQS; j += TK_THREADS) hist[j] = 0;
+    const uint32_t cmask = pass ? ~0u << (32 - 8 * pass) : 0u;
+    for (int j = threadIdx.x; j < HCOPY * 256 * st.NQS; j += TK_THREADS) st.lds.hist[j] = 0;
     __syncthreads();
     uint32_t prefix[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) prefix[c] = s_prefix[4 * qv + c];
-    // block maxima cluster: consecutive values of a query mostly share the digit (in the first pass -- sign and the upper
-    // exponent bits -- nearly all of them), so a thread counts runs in registers and adds a run at once; one LDS atomic per
-    // value on a handful of addresses was what the sweep spent its time on
-    uint32_t run_d[4] = {0, 0, 0, 0}, run_n[4] = {0, 0, 0, 0};
-    sweep_any_order([&](int64_t, const float4& v4) {
-      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+    for (int c = 0; c < 4; ++c) prefix[c] = st.lds.prefix[4 * qv + c];
+    tk_coarse_walk(my, n_grp, [&](int64_t, const uint4& k4) {
+      const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t key = tk_key(vv[c]);
-        if ((key & mask) == prefix[c]) {
-          const uint32_t dgt = (key >> shift) & 255;
-          if (dgt != run_d[c]) {
-            if (run_n[c]) atomicAdd(&myhist[run_d[c] * NQS + c], run_n[c]);
-            run_d[c] = dgt;
-            run_n[c] = 0;
-          }
-          ++run_n[c];
-        }
-      }
+      for (int c = 0; c < 4; ++c)
+        if ((kk[c] & cmask) == prefix[c]) atomicAdd(&st.myhist[((kk[c] >> shift) & 255) * st.NQS + c], 1u);
     });
+    tk_pick_digit(st, shift);
+  }
+  // the groups that reach tau_c: their maxima >= tau_c into the query's list
+  {
+    uint32_t tauc[4];
+    bool live[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (run_n[c]) atomicAdd(&myhist[run_d[c] * NQS + c], run_n[c]);
-    __syncthreads();
-    if (threadIdx.x < NQS) {
-      const int qi = threadIdx.x;
-      const uint32_t rem = s_rem[qi];
-      if (rem > 0) {   // the digit of the rem-th largest among the keys that share the prefix
-        uint32_t cum = 0;
-        int dg = 255;
-        for (; dg > 0; --dg) {
-          uint32_t cnt = 0;
+    for (int c = 0; c < 4; ++c) { tauc[c] = st.lds.prefix[4 * qv + c]; live[c] = st.valid[c]; }
+    tk_coarse_walk(my, n_grp, [&](int64_t jg, const uint4& k4) {
+      const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
+      bool q_[4], any = false;
 #pragma unroll
-          for (int hc = 0; hc < HCOPY; ++hc) cnt += hist[(hc * 256 + dg) * NQS + qi];
-          if (cum + cnt >= rem) break;
-          cum += cnt;
+      for (int c = 0; c < 4; ++c) { q_[c] = live[c] && kk[c] >= tauc[c]; any |= q_[c]; }
+      if (!any) return;
+      for (int u0 = 0; u0 < TK_GRP; u0 += 8) {      // the group's maxima again, eight loads in flight
+        float4 f8[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int64_t g = sr + (jg * TK_GRP + u0 + u) * (int64_t)st.SUB;
+          f8[u] = st.col[(g < G ? g : (int64_t)sr) * st.qs4];
         }
-        s_prefix[qi] |= (uint32_t)dg << shift;
-        s_rem[qi] = rem - cum;
-      }
-    }
-    mask |= 0xFFu << shift;
-    __syncthreads();
-  };
-  // ---- the coarse route (see TK_GRP above)
-  bool coarse_done = false;
-  if (coarse) {
-    uint4* my = coarse + ((int64_t)strip * NG) * TK_THREADS + threadIdx.x;      // my group jg: my[jg * TK_THREADS]
-    const int64_t n_vis = (int64_t)sr < G ? (G - sr + SUB - 1) / SUB : 0;       // my visits: blocks sr, sr + SUB, ...
-    const int64_t n_grp = (n_vis + TK_GRP - 1) / TK_GRP;
-    {   // sweep 1: the largest key of every TK_GRP visits
-      uint32_t gm[4] = {0u, 0u, 0u, 0u};
-      int64_t gj = 0;
-      tk_sweep_strided(col, qs4, (int64_t)sr, (int64_t)SUB, G, [&](int64_t g, const float4& v4) {
-        const int64_t jg = ((g - sr) / SUB) / TK_GRP;
-        if (jg != gj) { my[gj * TK_THREADS] = make_uint4(gm[0], gm[1], gm[2], gm[3]); gm[0] = gm[1] = gm[2] = gm[3] = 0u; gj = jg; }
-        const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { const uint32_t key = tk_key(vv[c]); gm[c] = key > gm[c] ? key : gm[c]; }
-      });
-      if (n_vis > 0) my[gj * TK_THREADS] = make_uint4(gm[0], gm[1], gm[2], gm[3]);
-    }
-    // the m-th largest coarse key of every query: four radix digits over the keys this thread wrote itself
-    uint32_t cmask = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      for (int j = threadIdx.x; j < HCOPY * 256 * NQS; j += TK_THREADS) hist[j] = 0;
-      __syncthreads();
-      uint32_t prefix[4];
+        for (int u = 0; u < 8; ++u) {
+          const int64_t g = sr + (jg * TK_GRP + u0 + u) * (int64_t)st.SUB;
+          if (g >= G) continue;
+          const float vv[4] = {f8[u].x, f8[u].y, f8[u].z, f8[u].w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) prefix[c] = s_prefix[4 * qv + c];
-      tk_coarse_walk(my, n_grp, [&](int64_t, const uint4& k4) {
-        const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if ((kk[c] & cmask) == prefix[c]) atomicAdd(&myhist[((kk[c] >> shift) & 255) * NQS + c], 1u);
-      });
-      __syncthreads();
-      if (threadIdx.x < NQS) {
-        const int qi = threadIdx.x;
-        const uint32_t rem = s_rem[qi];
-        if (rem > 0) {
-          uint32_t cum = 0;
-          int dg = 255;
-          for (; dg > 0; --dg) {
-            uint32_t cnt = 0;
-#pragma unroll
-            for (int hc = 0; hc < HCOPY; ++hc) cnt += hist[(hc * 256 + dg) * NQS + qi];
-            if (cum + cnt >= rem) break;
-            cum += cnt;
-          }
-          s_prefix[qi] |= (uint32_t)dg << shift;
-          s_rem[qi] = rem - cum;
-        }
-      }
-      cmask |= 0xFFu << shift;
-      __syncthreads();
-    }
-    // the groups that reach tau_c: their maxima >= tau_c into the query's list
-    {
-      uint32_t tauc[4];
-      bool live[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { tauc[c] = s_prefix[4 * qv + c]; live[c] = valid[c]; }
-      tk_coarse_walk(my, n_grp, [&](int64_t jg, const uint4& k4) {
-        const uint32_t kk[4] = {k4.x, k4.y, k4.z, k4.w};
-        bool q_[4], any = false;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { q_[c] = live[c] && kk[c] >= tauc[c]; any |= q_[c]; }
-        if (!any) return;
-        for (int u0 = 0; u0 < TK_GRP; u0 += 8) {      // the group's maxima again, eight loads in flight
-          float4 f8[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int64_t g = sr + (jg * TK_GRP + u0 + u) * (int64_t)SUB;
-            f8[u] = col[(g < G ? g : (int64_t)sr) * qs4];
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int64_t g = sr + (jg * TK_GRP + u0 + u) * (int64_t)SUB;
-            if (g >= G) continue;
-            const float vv[4] = {f8[u].x, f8[u].y, f8[u].z, f8[u].w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              if (!q_[c]) continue;
-              const uint32_t key = tk_key(vv[c]);
-              if (key >= tauc[c]) {
-                const uint32_t i = atomicAdd(&s_bn[4 * qv + c], 1u);
-                if (i < (uint32_t)TK_CL) { s_bkey[(4 * qv + c) * TK_CL + i] = key; s_bg[(4 * qv + c) * TK_CL + i] = (int32_t)g; }
-              }
+          for (int c = 0; c < 4; ++c) {
+            if (!q_[c]) continue;
+            const uint32_t key = tk_key(vv[c]);
+            if (key >= tauc[c]) {
+              const uint32_t i = atomicAdd(&st.lds.bn[4 * qv + c], 1u);
+              if (i < (uint32_t)TK_CL) { st.lds.bkey[(4 * qv + c) * TK_CL + i] = key; st.lds.bg[(4 * qv + c) * TK_CL + i] = (int32_t)g; }
             }
           }
         }
-      });
-    }
-    __syncthreads();
-    bool over_c = false;
-    if (threadIdx.x < NQS) over_c = s_bn[threadIdx.x] > (uint32_t)TK_CL;
-    if (!__syncthreads_or(over_c ? 1 : 0)) {
-      // rank the lists: entry e of query qi is candidate number `ahead` if ahead < m
-      for (int t = threadIdx.x; t < NQS * TK_CL; t += TK_THREADS) {
-        const int qi = t / TK_CL, e = t % TK_CL;
-        const int64_t ql = qs0 + qi;
-        const uint32_t nb = s_bn[qi];
-        if (ql >= Bc || (uint32_t)e >= nb) continue;
-        const int64_t qg = q0 + ql;
-        const int64_t beg = indptr[qg] - indptr[0];
-        const int64_t nslots = (int64_t)k + (indptr[qg + 1] - indptr[0] - beg);
-        const uint32_t m = (uint32_t)(nslots < G ? nslots : G);
-        const uint32_t key = s_bkey[qi * TK_CL + e];
-        const int32_t g = s_bg[qi * TK_CL + e];
-        uint32_t ahead = 0;
-        for (uint32_t t2 = 0; t2 < nb; ++t2) {
-          const uint32_t k2 = s_bkey[qi * TK_CL + t2];
-          ahead += (k2 > key || (k2 == key && s_bg[qi * TK_CL + t2] < g)) ? 1u : 0u;
-        }
-        if (ahead >= m) continue;
-        const int64_t o = (int64_t)k * qg + beg;
-        cand_blk[o + ahead] = key > kinf ? g : -1;       // blocks whose maximum is -inf hold nothing: their slots stay unused
-        if (ahead == m - 1) cand_tau[qg] = (nslots <= G && key > kinf) ? key : 0u;
       }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (!valid[c]) continue;
-        const int qi = 4 * qv + c;
-        const int64_t m = slots[c] < G ? slots[c] : G;
-        for (int64_t j = sr; j < slots[c]; j += SUB) {
-          cand_q[off[c] + j] = (int32_t)(q0 + qs0 + qi);
-          if (j >= m) cand_blk[off[c] + j] = -1;
-        }
-      }
-      coarse_done = true;
-    } else {
-      // a list overflowed: the strip takes the three-sweep route from the start
-      if (threadIdx.x < NQS) {
-        const int64_t ql = qs0 + threadIdx.x;
-        int64_t m64 = 0;
-        if (ql < Bc) {
-          m64 = (int64_t)k + (indptr[q0 + ql + 1] - indptr[q0 + ql]);
-          if (m64 > G) m64 = G;
-        }
-        s_prefix[threadIdx.x] = 0;
-        s_rem[threadIdx.x] = (uint32_t)m64;
-        s_slot[threadIdx.x] = 0;
-        s_bn[threadIdx.x] = 0;
-      }
-      __syncthreads();
-    }
+    });
   }
-  if (!coarse_done) {
-  radix_pass(0);
-  radix_pass(1);
+  __syncthreads();
+  bool over = false;
+  if (threadIdx.x < st.NQS) over = st.lds.bn[threadIdx.x] > (uint32_t)TK_CL;
+  if (__syncthreads_or(over ? 1 : 0)) {
+    tk_strip_reset(st);
+    __syncthreads();
+    return false;
+  }
+  tk_rank_list<TK_CL>(st, true);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) tk_fill_slots(st, c, st.slots[c] < G ? st.slots[c] : G);
+  return true;
+}
 
-  // ---- sweep 3: above the 16-bit bin -> candidate; inside it -> LDS list
+// ---- the fast path.  false: a threshold bin holds more than TK_BIN blocks, nothing the strip wrote so far counts.
+template <int QV, int HCOPY>
+__device__ __forceinline__ bool tk_route_fast(const TkStrip<QV, HCOPY>& st) {
+  const int qv = st.qv;
+  tk_radix_pass(st, 0);
+  tk_radix_pass(st, 1);
+  // sweep 3: above the 16-bit bin -> candidate; inside it -> LDS list
   {
     uint32_t p16[4];
     bool live[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      p16[c] = s_prefix[4 * qv + c] >> 16;
-      live[c] = valid[c] && s_rem[4 * qv + c] > 0;
+      p16[c] = st.lds.prefix[4 * qv + c] >> 16;
+      live[c] = st.valid[c] && st.lds.rem[4 * qv + c] > 0;
     }
-    sweep_any_order([&](int64_t g, const float4& v4) {
+    tk_sweep_strided(st.col, st.qs4, (int64_t)st.sr, (int64_t)st.SUB, st.G, [&](int64_t g, const float4& v4) {
       const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -428,122 +459,99 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_threshold_emit(const float*
         const uint32_t key = tk_key(vv[c]);
         const uint32_t k16 = key >> 16;
         if (k16 > p16[c]) {
-          cand_blk[off[c] + atomicAdd(&s_slot[4 * qv + c], 1u)] = (int32_t)g;
+          st.cand_blk[st.off[c] + atomicAdd(&st.lds.slot[4 * qv + c], 1u)] = (int32_t)g;
         } else if (k16 == p16[c]) {
-          const uint32_t i = atomicAdd(&s_bn[4 * qv + c], 1u);
-          if (i < (uint32_t)TK_BIN) { s_bkey[(4 * qv + c) * TK_BIN + i] = key; s_bg[(4 * qv + c) * TK_BIN + i] = (int32_t)g; }
+          const uint32_t i = atomicAdd(&st.lds.bn[4 * qv + c], 1u);
+          if (i < (uint32_t)TK_BIN) { st.lds.bkey[(4 * qv + c) * TK_BIN + i] = key; st.lds.bg[(4 * qv + c) * TK_BIN + i] = (int32_t)g; }
         }
       }
     });
   }
   __syncthreads();
   bool over = false;
-  if (threadIdx.x < NQS) over = s_bn[threadIdx.x] > (uint32_t)TK_BIN;
-  if (!__syncthreads_or(over ? 1 : 0)) {
-    // rank the bin lists: entry e of query qi is candidate number (gt + ahead) if ahead < rem
-    for (int t = threadIdx.x; t < NQS * TK_BIN; t += TK_THREADS) {
-      const int qi = t / TK_BIN, e = t % TK_BIN;
-      const int64_t ql = qs0 + qi;
-      const uint32_t nb = s_bn[qi], rem = s_rem[qi];
-      if (ql >= Bc || (uint32_t)e >= nb || rem == 0) continue;
-      const uint32_t key = s_bkey[qi * TK_BIN + e];
-      const int32_t g = s_bg[qi * TK_BIN + e];
-      uint32_t ahead = 0;
-      for (uint32_t t2 = 0; t2 < nb; ++t2) {
-        const uint32_t k2 = s_bkey[qi * TK_BIN + t2];
-        ahead += (k2 > key || (k2 == key && s_bg[qi * TK_BIN + t2] < g)) ? 1u : 0u;
-      }
-      if (ahead >= rem) continue;
-      const int64_t qg = q0 + ql;
-      const int64_t beg = indptr[qg] - indptr[0];
-      const int64_t o = (int64_t)k * qg + beg;
-      const int64_t nslots = (int64_t)k + (indptr[qg + 1] - indptr[0] - beg);
-      // blocks whose maximum is -inf hold nothing: their slots stay unused
-      cand_blk[o + s_slot[qi] + ahead] = key > kinf ? g : -1;
-      // what the selection may discard unseen: logits below tau, when tau is a real m-th largest (at least k unmasked
-      // logits >= tau exist then); with every block a candidate (m clamped to G) or a -inf tau nothing is discarded
-      if (ahead == rem - 1) cand_tau[qg] = (nslots <= G && key > kinf) ? key : 0u;
-    }
-    // query ids of all slots; slots past the m candidates (m clamped to the number of blocks) are unused
+  if (threadIdx.x < st.NQS) over = st.lds.bn[threadIdx.x] > (uint32_t)TK_BIN;
+  if (__syncthreads_or(over ? 1 : 0)) return false;
+  tk_rank_list<TK_BIN>(st, false);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) tk_fill_slots(st, c, (int64_t)st.lds.slot[4 * qv + c] + st.lds.rem[4 * qv + c]);
+  return true;
+}
+
+// ---- the general route, after the fast path's two digits: the remaining two, then count and emit in block order
+template <int QV, int HCOPY>
+__device__ __forceinline__ void tk_route_general(const TkStrip<QV, HCOPY>& st) {
+  const int qv = st.qv, sr = st.sr;
+  const uint32_t kinf = tk_key(-INFINITY);
+  tk_radix_pass(st, 2);
+  tk_radix_pass(st, 3);
+  uint32_t tau[4], cgt[4] = {0, 0, 0, 0}, ceq[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) tau[c] = st.lds.prefix[4 * qv + c];
+  tk_sweep(st.col, st.qs4, st.g_lo, st.g_hi, [&](int64_t, const float4& v4) {
+    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      if (!valid[c]) continue;
-      const int qi = 4 * qv + c;
-      const int64_t used = (int64_t)s_slot[qi] + s_rem[qi];
-      for (int64_t j = sr; j < slots[c]; j += SUB) {
-        cand_q[off[c] + j] = (int32_t)(q0 + qs0 + qi);
-        if (j >= used) cand_blk[off[c] + j] = -1;
+      const uint32_t key = tk_key(vv[c]);
+      cgt[c] += key > tau[c] ? 1u : 0u;
+      ceq[c] += key == tau[c] ? 1u : 0u;
+    }
+  });
+#pragma unroll
+  for (int c = 0; c < 4; ++c) { st.lds.cgt[sr * st.NQS + 4 * qv + c] = cgt[c]; st.lds.ceq[sr * st.NQS + 4 * qv + c] = ceq[c]; }
+  __syncthreads();
+  // bgt, beq: blocks above / at tau in the sub-ranges before mine; c1: blocks above tau; need: blocks at tau that are wanted
+  uint32_t bgt[4], beq[4], c1[4], need[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int qi = 4 * qv + c;
+    bgt[c] = beq[c] = c1[c] = 0;
+    for (int s2 = 0; s2 < st.SUB; ++s2) {
+      const uint32_t x = st.lds.cgt[s2 * st.NQS + qi];
+      if (s2 < sr) { bgt[c] += x; beq[c] += st.lds.ceq[s2 * st.NQS + qi]; }
+      c1[c] += x;
+    }
+    need[c] = tau[c] > kinf ? st.lds.rem[qi] : 0u;
+    if (st.valid[c] && sr == 0) st.cand_tau[st.q0 + st.qs0 + qi] = (st.slots[c] <= st.G && tau[c] > kinf) ? tau[c] : 0u;
+    tk_fill_slots(st, c, (int64_t)(c1[c] + need[c]));
+  }
+  tk_sweep(st.col, st.qs4, st.g_lo, st.g_hi, [&](int64_t g, const float4& v4) {
+    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (!st.valid[c]) continue;
+      const uint32_t key = tk_key(vv[c]);
+      if (key > tau[c]) {
+        st.cand_blk[st.off[c] + bgt[c]++] = (int32_t)g;
+      } else if (key == tau[c]) {
+        if (beq[c] < need[c]) st.cand_blk[st.off[c] + c1[c] + beq[c]] = (int32_t)g;
+        ++beq[c];
       }
     }
-  } else {
+  });
+}
+
+template <int QV, int HCOPY>
+__global__ __launch_bounds__(TK_THREADS) void k_topk_threshold_emit(const float* __restrict__ gmax, int64_t G, int64_t Qs, int64_t q0,
+                                                                    int64_t Bc, int k, const int64_t* __restrict__ indptr,
+                                                                    int32_t* __restrict__ cand_blk, int32_t* __restrict__ cand_q,
+                                                                    int32_t* __restrict__ blk_cnt, int nseg,
+                                                                    uint32_t* __restrict__ cand_tau, int pair_xcd,
+                                                                    uint4* __restrict__ coarse, int64_t NG) {
+  extern __shared__ uint32_t tk_lds[];
+  const TkStrip<QV, HCOPY> st(*(TkLds<QV, HCOPY>*)tk_lds, gmax, G, Qs, q0, Bc, k, indptr, cand_blk, cand_q, cand_tau, pair_xcd);
+  tk_strip_reset(st);
+  bool done = coarse && tk_route_coarse(st, coarse, NG);
+  if (!done) done = tk_route_fast(st);
+  if (!done) {
 #ifdef COPER_DBG_TK_OVER
     if (threadIdx.x == 0) atomicAdd(&g_tk_over, 1);
 #endif
-    // ---- general route: the remaining two digits, then count and emit in block order
-    radix_pass(2);
-    radix_pass(3);
-    uint32_t tau[4], cgt[4] = {0, 0, 0, 0}, ceq[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) tau[c] = s_prefix[4 * qv + c];
-    tk_sweep(col, qs4, g_lo, g_hi, [&](int64_t, const float4& v4) {
-      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t key = tk_key(vv[c]);
-        cgt[c] += key > tau[c] ? 1u : 0u;
-        ceq[c] += key == tau[c] ? 1u : 0u;
-      }
-    });
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { s_cgt[sr * NQS + 4 * qv + c] = cgt[c]; s_ceq[sr * NQS + 4 * qv + c] = ceq[c]; }
-    __syncthreads();
-    uint32_t bgt[4], beq[4], c1[4], need[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int qi = 4 * qv + c;
-      bgt[c] = beq[c] = c1[c] = 0;
-      for (int s2 = 0; s2 < SUB; ++s2) {
-        const uint32_t x = s_cgt[s2 * NQS + qi];
-        if (s2 < sr) { bgt[c] += x; beq[c] += s_ceq[s2 * NQS + qi]; }
-        c1[c] += x;
-      }
-      need[c] = tau[c] > kinf ? s_rem[qi] : 0u;
-      if (valid[c]) {
-        if (sr == 0) cand_tau[q0 + qs0 + qi] = (slots[c] <= G && tau[c] > kinf) ? tau[c] : 0u;
-        for (int64_t j = sr; j < slots[c]; j += SUB) {
-          cand_q[off[c] + j] = (int32_t)(q0 + qs0 + qi);
-          if (j >= (int64_t)(c1[c] + need[c])) cand_blk[off[c] + j] = -1;
-        }
-      }
-    }
-    tk_sweep(col, qs4, g_lo, g_hi, [&](int64_t g, const float4& v4) {
-      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (!valid[c]) continue;
-        const uint32_t key = tk_key(vv[c]);
-        if (key > tau[c]) {
-          cand_blk[off[c] + bgt[c]++] = (int32_t)g;
-        } else if (key == tau[c]) {
-          if (beq[c] < need[c]) cand_blk[off[c] + c1[c] + beq[c]] = (int32_t)g;
-          ++beq[c];
-        }
-      }
-    });
+    tk_route_general(st);
   }
-  }   // (!coarse_done)
-  // ---- candidates are scored block by block: how many slots want block g (nseg counters per block thin out the
-  // same-address atomics when there are few blocks)
+  // cand_blk is read back by other threads than the ones that wrote it
   __threadfence_block();
   __syncthreads();
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    if (!valid[c] || !blk_cnt) continue;      // (blk_cnt == NULL: 64-entity candidates, counted after their expansion: k_topk_expand64)
-    for (int64_t j = sr; j < slots[c]; j += SUB) {
-      const int32_t g = cand_blk[off[c] + j];
-      if (g >= 0) atomicAdd(&blk_cnt[(int64_t)g * nseg + ((off[c] + j) & (nseg - 1))], 1);
-    }
-  }
+  tk_count_blocks(st, blk_cnt, nseg);
 }
 
 // Large tables (topk_expand == 2): the threshold kernel worked on 64-entity block maxima; every candidate slot becomes two slots, the block's two
@@ -564,10 +572,6 @@ __global__ __launch_bounds__(256) void k_topk_expand64(const int32_t* __restrict
   }
 }
 
-template <int QV, int HCOPY>
-constexpr size_t tk_emit_lds() {
-  return sizeof(uint32_t) * (HCOPY * 256 * 4 * QV + 4 * 4 * QV + 2 * (TK_THREADS / QV) * 4 * QV + 2 * 4 * QV * TK_CL);
-}
 
 // ---- group the candidate slots by entity block: every block's slots padded to a multiple of 32 (one wave each)
 // blk_off[g] = first position of block g in `sorted`, blk_off[G] = total (a multiple of 32)
@@ -866,12 +870,9 @@ static void tk_launch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0, i
   }
   // the coarse route (TK_GRP): long block axes, when the scratch was reserved for this (G, qs)
   static const bool no_coarse = getenv("COPER_TK_NO_COARSE") != nullptr;     // A/B switch, read once
-  constexpr int64_t SUB = TK_THREADS / QV;
-  const int64_t NG = ((G + SUB - 1) / SUB + TK_GRP - 1) / TK_GRP, strips = qs / (4 * QV);
-  const size_t cbytes = (size_t)strips * NG * TK_THREADS * sizeof(uint4);
-  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->tk_coarse_ws && cbytes <= h->tk_coarse_ws.size()) ? (uint4*)h->tk_coarse_ws : nullptr;
-  hipLaunchKernelGGL((k_topk_threshold_emit<QV, HCOPY>), dim3((unsigned)(qs / (4 * QV))), dim3(TK_THREADS), lds, s, h->gmax_ws, G, qs, q0, bc,
-                     k, indptr, out_blk, out_q, out_cnt, topk_nseg(G), h->cand_tau_ws, tk_pair_xcd() ? 1 : 0, coarse, NG);
+  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->tk_coarse_ws && tk_coarse_bytes(G, qs, QV) <= h->tk_coarse_ws.size()) ? (uint4*)h->tk_coarse_ws : nullptr;
+  hipLaunchKernelGGL((k_topk_threshold_emit<QV, HCOPY>), dim3((unsigned)tk_strips(qs, QV)), dim3(TK_THREADS), lds, s, h->gmax_ws, G, qs, q0, bc,
+                     k, indptr, out_blk, out_q, out_cnt, topk_nseg(G), h->cand_tau_ws, tk_pair_xcd() ? 1 : 0, coarse, tk_coarse_groups(G, QV));
 }
 
 // strip width / histogram copies of the threshold kernel by shape
