@@ -102,6 +102,10 @@ PROTOTYPES = {
     "coper_encode_rank": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "coper_predict_topk": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, C.c_int32, _P, _P, _P]),
     "coper_predict_stats": (C.c_int, [_P, C.c_int32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_float), _P]),
+    "coper_set_known_facts": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P]),
+    "coper_known_filter": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I64, C.POINTER(_I64), _P]),
+    "coper_predict_topk_known": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, _P, _P, _P]),
+    "coper_encode_rank_known": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "coper_check_ids": (C.c_int, [_P, C.POINTER(_I64), _P]),
     "coper_stale_passes": (C.c_int, [_P, C.POINTER(_I64), _P]),
     "coper_live_device_bytes": (_I64, []),

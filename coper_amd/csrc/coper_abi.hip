@@ -1245,6 +1245,150 @@ COPER_API int coper_predict_stats(coper_handle* h, int32_t reset, int64_t* n_que
   return COPER_OK;
 }
 
+// ---- the known-facts index: the (e1, rel) -> known tails table resident on the handle (kernels_known.hip) ----
+static void known_clear(coper_handle* h) {
+  h->known_n_keys = 0; h->known_nnz = 0; h->known_wide = false;
+  h->known_keys.reset(); h->known_indptr.reset(); h->known_tails.reset();
+  h->known_row_ws.reset(); h->known_ip_ws.reset(); h->known_ix_ws.reset();
+}
+
+COPER_API int coper_set_known_facts(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* tail_indptr,
+                                    const int64_t* tail_idx, int64_t n_keys, int64_t nnz, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (n_keys < 0 || nnz < 0) return fail(h, COPER_EINVAL, "coper_set_known_facts: n_keys >= 0, nnz >= 0");
+  if (h->cfg.role == COPER_ROLE_ENCODE)
+    return fail(h, COPER_EUNSUPPORTED, "coper_set_known_facts: a COPER_ROLE_ENCODE handle answers no queries (set the index on the scoring handle)");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_keys == 0) {
+    if (h->known_n_keys > 0) {
+      COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+      COPER_HIP_TRY(h, hipStreamSynchronize(s));     // (lookups of the old index may still be running)
+    }
+    known_clear(h);
+    return COPER_OK;
+  }
+  if (!e1 || !rel || !tail_indptr || (nnz > 0 && !tail_idx)) return fail(h, COPER_EINVAL, "coper_set_known_facts: null array");
+  const Dims& dm = h->dm;
+  if (n_keys > 0x7fffffff) return fail(h, COPER_EUNSUPPORTED, "coper_set_known_facts: more than 2^31 - 1 rows");
+  if (dm.E > INT64_MAX / dm.R) return fail(h, COPER_EUNSUPPORTED, "coper_set_known_facts: num_ent * num_rel does not fit the 64-bit key");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  if (stream_is_capturing(s)) return fail(h, COPER_EUNSUPPORTED, "coper_set_known_facts synchronises: not for a stream that is being captured");
+  // checked and copied into fresh buffers in one pass; they replace the index in force only when the pass found nothing
+  const bool wide = dm.E > 0x7fffffff;
+  DevBuf<int64_t> keys, indptr;
+  DevBuf<char> tails;
+  DevBuf<unsigned> viol;
+  int rc;
+  if ((rc = keys.alloc(h, (size_t)n_keys, "known-facts keys")) || (rc = indptr.alloc(h, (size_t)n_keys + 1, "known-facts indptr")) ||
+      (rc = tails.alloc(h, (size_t)nnz * (wide ? 8 : 4), "known-facts tails")) || (rc = viol.alloc(h, KNOWN_BAD_WORDS, "known-facts check")))
+    return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(viol, 0, KNOWN_BAD_WORDS * sizeof(unsigned), s));
+  if ((rc = launch_known_build(h, e1, rel, tail_indptr, tail_idx, n_keys, nnz, keys, indptr, tails.get(), wide, viol, s))) return rc;
+  unsigned v[KNOWN_BAD_WORDS];
+  COPER_HIP_TRY(h, hipMemcpyAsync(v, viol, sizeof v, hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  static const char* const kinds[KNOWN_BAD_KINDS] = {
+      "keys e1 * num_rel + rel are not ascending", "a key (e1, rel) occurs twice", "an e1 is outside [0, num_ent)",
+      "a rel is outside [0, num_rel)", "a tail is outside [0, num_ent)", "the tails of a row are not strictly ascending",
+      "tail_indptr[0] != 0", "tail_indptr decreases", "tail_indptr[n_keys] != nnz"};
+  for (int i = 0; i < KNOWN_BAD_KINDS; ++i)
+    if (v[i]) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "coper_set_known_facts: %s (%u place%s); the index in force is unchanged", kinds[i], v[i], v[i] == 1 ? "" : "s");
+      return fail(h, COPER_EINVAL, buf);
+    }
+  h->known_keys = std::move(keys); h->known_indptr = std::move(indptr); h->known_tails = std::move(tails);
+  h->known_n_keys = n_keys; h->known_nnz = nnz; h->known_wide = wide;
+  return COPER_OK;
+}
+
+// steps 1 - 2 and the readback: filt_indptr [B + 1] on the device, its last entry on the host
+static int known_lookup(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* filt_indptr, int64_t* total, hipStream_t s) {
+  int rc;
+  if ((size_t)B > h->known_row_ws.size()) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = h->known_row_ws.alloc(h, (size_t)(B < 64 ? 64 : B), "known-facts rows of a batch"))) return rc;
+  }
+  if ((rc = launch_known_find_scan(h, e1, rel, B, h->known_row_ws, filt_indptr, s))) return rc;
+  COPER_HIP_TRY(h, hipMemcpyAsync(total, filt_indptr + B, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  return COPER_OK;
+}
+
+COPER_API int coper_known_filter(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* filt_indptr, int64_t* filt_idx,
+                                 int64_t cap, int64_t* nnz, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (B < 0 || cap < 0 || !nnz || (B > 0 && (!e1 || !rel || !filt_indptr)))
+    return fail(h, COPER_EINVAL, "coper_known_filter: B >= 0, cap >= 0, e1 / rel / filt_indptr / nnz given");
+  if (B > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_known_filter: batch too large");
+  if (h->known_n_keys == 0) return fail(h, COPER_ESTATE, "coper_known_filter: no known-facts index (coper_set_known_facts)");
+  *nnz = 0;
+  if (B == 0) return COPER_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (stream_is_capturing(s)) return fail(h, COPER_EUNSUPPORTED, "coper_known_filter reads the total back: not for a stream that is being captured");
+  int rc;
+  int64_t total = 0;
+  if ((rc = known_lookup(h, e1, rel, B, filt_indptr, &total, s))) return rc;
+  *nnz = total;
+  if (!filt_idx) return COPER_OK;
+  if (cap < total) return fail(h, COPER_EINVAL, "coper_known_filter: filt_idx holds fewer than filt_indptr[B] entries (nothing was written to it)");
+  return launch_known_gather(h, filt_indptr, h->known_row_ws, B, total, filt_idx, s);
+}
+
+// the lookup of a fused call into the handle's own CSR workspaces, which grow between the scan and the gather
+static int known_filter_ws(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* total, hipStream_t s) {
+  int rc;
+  if ((size_t)(B + 1) > h->known_ip_ws.size()) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = h->known_ip_ws.alloc(h, (size_t)(B < 64 ? 64 : B) + 1, "known-facts filter rows"))) return rc;
+  }
+  if ((rc = known_lookup(h, e1, rel, B, h->known_ip_ws, total, s))) return rc;
+  if ((size_t)*total > h->known_ix_ws.size() || !h->known_ix_ws) {      // (the stream is idle: known_lookup has just synchronised it)
+    if ((rc = h->known_ix_ws.alloc(h, (size_t)*total, "known-facts filter entries"))) return rc;
+  }
+  return launch_known_gather(h, h->known_ip_ws, h->known_row_ws, B, *total, h->known_ix_ws, s);
+}
+
+COPER_API int coper_predict_topk_known(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, int32_t k,
+                                       float* topk_val, int64_t* topk_idx, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (k <= 0 || B < 0) return fail(h, COPER_EINVAL, "coper_predict_topk_known: k >= 1, B >= 0");
+  if (B > 0 && (!e1 || !rel)) return fail(h, COPER_EINVAL, "coper_predict_topk_known: e1 and rel are needed (they form the key)");
+  if (B > 0 && (!topk_val || !topk_idx)) return fail(h, COPER_EINVAL, "coper_predict_topk_known: no output buffers");
+  if (B > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_predict_topk_known: batch too large");
+  if (!h->prepared) return fail(h, COPER_ESTATE, "coper_prepare has not been called");
+  if (h->cfg.role == COPER_ROLE_ENCODE) return fail(h, COPER_EUNSUPPORTED, "coper_predict_topk_known: a COPER_ROLE_ENCODE handle has no entity table");
+  COPER_REQUIRE_ENCODER(h);
+  if (h->known_n_keys == 0) return fail(h, COPER_ESTATE, "coper_predict_topk_known: no known-facts index (coper_set_known_facts)");
+  if (B == 0) return COPER_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (stream_is_capturing(s)) return fail(h, COPER_EUNSUPPORTED, "coper_predict_topk_known reads the filter's size back: not for a stream that is being captured");
+  int rc;
+  int64_t total = 0;
+  if ((rc = known_filter_ws(h, e1, rel, B, &total, s))) return rc;
+  return coper_predict_topk(h, e1, rel, e1_rows, nullptr, h->known_ip_ws, h->known_ix_ws, total, B, k, topk_val, topk_idx, stream);
+}
+
+COPER_API int coper_encode_rank_known(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const int64_t* e2, int64_t B,
+                                      float* h_out, int32_t* ranks, int32_t* n_equal, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (B < 0) return fail(h, COPER_EINVAL, "coper_encode_rank_known: B >= 0");
+  if (B > 0 && (!e1 || !rel || !e2 || !ranks)) return fail(h, COPER_EINVAL, "coper_encode_rank_known: e1 (it forms the key), rel, e2 and ranks are needed");
+  if (B > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_encode_rank_known: batch too large");
+  COPER_REQUIRE_PREPARED(h);
+  COPER_REQUIRE_ENCODER(h);
+  COPER_REQUIRE_SCORER(h);
+  if (h->dm.n_local != h->dm.E) return fail(h, COPER_ESTATE, "coper_encode_rank_known needs the whole table (see coper_rank)");
+  if (h->known_n_keys == 0) return fail(h, COPER_ESTATE, "coper_encode_rank_known: no known-facts index (coper_set_known_facts)");
+  if (B == 0) return COPER_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (stream_is_capturing(s)) return fail(h, COPER_EUNSUPPORTED, "coper_encode_rank_known reads the filter's size back: not for a stream that is being captured");
+  int rc;
+  int64_t total = 0;
+  if ((rc = known_filter_ws(h, e1, rel, B, &total, s))) return rc;
+  return coper_encode_rank(h, e1, rel, e1_rows, e2, h->known_ip_ws, h->known_ix_ws, total, B, h_out, ranks, n_equal, stream);
+}
+
 COPER_API int coper_band_audit(coper_handle* h, int32_t reset, float* max_ratio, int64_t* n_pairs, void* stream) {
   if (!h) return COPER_EINVAL;
   if (max_ratio) *max_ratio = 0.f;

@@ -168,6 +168,9 @@ constexpr int BAND_NCONST = 8;
 enum { GROUP_CHK_REL = 0, GROUP_CHK_E1 = 1, GROUP_CHK_PERM = 2, GROUP_CHK_LO = 3, GROUP_CHK_NLOCAL = 4, GROUP_CHK_RALL = 5,
        GROUP_CHK_STALE = 6, GROUP_CHK_WORDS = 8 };
 constexpr int EBLK_ALIGN = 16;  // entity blocks consumed per workgroup iteration in score_count (8 waves x 2)
+// what the build pass of the known-facts index counts (kernels_known.hip), in the order coper_set_known_facts reports them
+enum { KNOWN_BAD_ORDER = 0, KNOWN_BAD_DUP = 1, KNOWN_BAD_E1 = 2, KNOWN_BAD_REL = 3, KNOWN_BAD_TAIL = 4, KNOWN_BAD_ASC = 5,
+       KNOWN_BAD_IP0 = 6, KNOWN_BAD_IP_DECR = 7, KNOWN_BAD_IPN = 8, KNOWN_BAD_KINDS = 9, KNOWN_BAD_WORDS = 16 };
 
 struct Timer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -334,6 +337,17 @@ struct coper_handle {
   coper::DevBuf<int32_t> heavy_ws;      // fused tail: [0] number of listed blocks, [1] finished workgroups, [2..] 32-query blocks whose CSR entries
                                         //   exceed what their workgroup corrects itself (k_filter_excess_bf16x3); zero between passes
   coper::DevBuf<float> hfrag_ws;        // h re-packed in MFMA-fragment order [ceil(B/128)*4][KS][64] float4
+  // ---- the known-facts index (coper_set_known_facts; kernels_known.hip): copies of the caller's arrays, no function of the
+  // parameters -- coper_prepare, training steps and coper_reserve leave it alone
+  int64_t known_n_keys = 0;             // rows of the index; 0: none set
+  int64_t known_nnz = 0;
+  bool known_wide = false;              // tails held as int64 (num_ent beyond int32) instead of int32
+  coper::DevBuf<int64_t> known_keys;    // [n_keys] e1 * num_rel + rel, ascending
+  coper::DevBuf<int64_t> known_indptr;  // [n_keys + 1]
+  coper::DevBuf<char> known_tails;      // [nnz] int32 or int64 (known_wide) global ids, ascending within a row
+  coper::DevBuf<int32_t> known_row_ws;  // [B] the index row of every query of the running lookup, -1: none
+  coper::DevBuf<int64_t> known_ip_ws;   // [B + 1], [nnz]: the CSR the fused entry points (coper_predict_topk_known,
+  coper::DevBuf<int64_t> known_ix_ws;   //   coper_encode_rank_known) look up and hand to the bodies of the explicit-CSR calls
   int num_cus = 256;
   void* train = nullptr;          // coper::TrainState (coper_train.hip)
   bool dense_attr_done = false;
@@ -585,6 +599,14 @@ int launch_bias_pad(coper_handle* h, const float* bias, hipStream_t s);
 int launch_topk(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
                 int64_t B, int k, float* topk_val, int64_t* topk_idx, float* logits_ws, int64_t chunk_rows,
                 hipStream_t s);
+
+// kernels_known.hip: the known-facts index
+int launch_known_build(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* ip, const int64_t* ix, int64_t n_keys,
+                       int64_t nnz, int64_t* keys, int64_t* ip_out, void* tails, bool wide, unsigned* viol, hipStream_t s);
+int launch_known_find_scan(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int32_t* row, int64_t* filt_indptr,
+                           hipStream_t s);
+int launch_known_gather(coper_handle* h, const int64_t* filt_indptr, const int32_t* row, int64_t B, int64_t total, int64_t* out,
+                        hipStream_t s);
 
 // COPER_DBG_SYNC=1 in the environment: synchronise after the launches that carry this hook and report the first failing one
 // (localises a faulting kernel; read once per process)

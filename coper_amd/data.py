@@ -280,6 +280,24 @@ def synthetic_queries(md: dict, Q: int, seed: int = 0, mean_filter: float = 4.0,
     return dict(e1=e1, rel=rel, e2=e2, filt_indptr=indptr, filt_idx=idx.astype(np.int64))
 
 
+def known_facts_from_queries(q: dict) -> Dict[str, np.ndarray]:
+    """The known-facts index (`ConvE.set_known_facts`) of a synthetic query set: one row per distinct (e1, rel), rows ascending by
+    (e1, rel) -- the order of the key e1 * num_rel + rel --, each row the filter row of the FIRST
+    query with that pair (`synthetic_queries` can draw a pair twice with different rows; a KG has one row per pair, e1rel_to_e2_full.json
+    of data.py:464-469).  Returns dict(e1, rel, tail_indptr, tail_idx) like `KGLoader.known_facts()`."""
+    e1, rel = np.asarray(q["e1"], np.int64), np.asarray(q["rel"], np.int64)
+    indptr, idx = np.asarray(q["filt_indptr"], np.int64), np.asarray(q["filt_idx"], np.int64)
+    order = np.lexsort((np.arange(len(e1)), rel, e1))          # by (e1, rel), first occurrence first
+    first = np.ones(len(order), dtype=bool)
+    first[1:] = (e1[order][1:] != e1[order][:-1]) | (rel[order][1:] != rel[order][:-1])
+    keep = order[first]
+    rows = [np.unique(idx[indptr[i]:indptr[i + 1]]) for i in keep]
+    tail_indptr = np.zeros(len(keep) + 1, dtype=np.int64)
+    tail_indptr[1:] = np.cumsum([len(r) for r in rows])
+    return dict(e1=e1[keep], rel=rel[keep], tail_indptr=tail_indptr,
+                tail_idx=np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64))
+
+
 def dense_filter_to_csr(e2_multi, device=None):
     """Dense 0/1 mask [B,|E|] (data.py:182-186) -> (indptr int64 [B+1], idx int64 sorted).
     With a HIP `device` the scan runs there (the mask crosses PCIe once: 0.7 ms per 512 x 14,541 batch on the MI355X box

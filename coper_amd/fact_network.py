@@ -49,5 +49,11 @@ class FactNetworkScorer(object):
         val, idx = self.model.predict_topk(e1.reshape(-1), r.reshape(-1), k, filt_indptr, filt_idx)
         return torch.sigmoid(val), idx
 
+    def set_known_facts(self, e1=None, rel=None, tail_indptr=None, tail_idx=None):
+        """Keeps the KG's known facts on the engine (`ConvE.set_known_facts`); `self.model.predict_topk_known(e1, r, k)` then answers
+        bare (e1, r) pairs with their known answers masked."""
+        self.model.set_known_facts(e1, rel, tail_indptr, tail_idx)
+        return self
+
     def close(self):
         self.model.close()

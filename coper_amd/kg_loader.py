@@ -193,6 +193,36 @@ class TSVKGLoader(object):
             self.assign_ids()
         return EvalDataset(self.encoded_split(dataset_type, include_inv_relations), batch_size, self.num_ent, dense_mask)
 
+    def known_facts(self, splits=("train", "dev", "test"), include_inv_relations: bool = True):
+        """The known facts of the KG as the index `ConvE.set_known_facts` keeps on the device: one row per distinct (e1, rel) of the
+        union of the splits' graphs -- with all three, what the reference writes as e1rel_to_e2_full.json and reads back per sample as
+        `e2_multi` (data.py:464-469, 494-503) -- rows ascending by e1 * num_rel + rel, tails sorted and unique.  Every triple feeds
+        its `_reverse` relation too, as in the full graph (data.py:422-437); `include_inv_relations=False` leaves those rows out.
+        Returns dict(e1, rel, tail_indptr, tail_idx), the layout of `train_samples()`."""
+        if not self.entity_ids:
+            self.assign_ids()
+        E, Rm = self.entity_ids, self.relation_ids
+        names = {"train": self.filetypes[0], "dev": self.filetypes[1], "test": self.filetypes[2]}
+        facts: Dict[Tuple[int, int], set] = {}
+        for split in splits:
+            # (a split's own graph holds its reverse edges only where add_reverse_per_filetype says so: both directions are
+            # taken from the forward edges here, as the full graph takes them from every triple)
+            for (e1, rel), tails in self.graphs[names[split]].items():
+                if rel.endswith("_reverse") or not tails:
+                    continue
+                facts.setdefault((E[e1], Rm[rel]), set()).update(E[t] for t in tails)
+                if include_inv_relations:
+                    for t in tails:
+                        facts.setdefault((E[t], Rm[rel + "_reverse"]), set()).add(E[e1])
+        keys = sorted(facts)
+        e1, rel, indptr, idx = [], [], [0], []
+        for key in keys:
+            e1.append(key[0]); rel.append(key[1])
+            idx.extend(sorted(facts[key]))
+            indptr.append(len(idx))
+        return dict(e1=np.asarray(e1, np.int64), rel=np.asarray(rel, np.int64), tail_indptr=np.asarray(indptr, np.int64),
+                    tail_idx=np.asarray(idx, np.int64))
+
     # ---------------------------------------------------------------- data.py:89-166
     def train_samples(self, include_inv_relations: bool = True):
         """One record per (e1, rel) of the train graph with the list of all its train tails -- the content of the

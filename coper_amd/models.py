@@ -643,6 +643,74 @@ class ConvE(object):
                                                           self._stream()))
         return {"queries": int(nq.value), "unresolved": int(nu.value), "rescored": int(nr.value), "max_ratio": float(ratio.value)}
 
+    # ---------------------------------------------------------------- the known-facts index
+    def set_known_facts(self, e1=None, rel=None, tail_indptr=None, tail_idx=None):
+        """Keeps the KG's known facts on the handle (coper_set_known_facts): one row of known tails per distinct (e1, rel), rows
+        ascending by e1 * num_rel + rel, tails strictly ascending -- the layout of `KGLoader.known_facts()` /
+        `data.known_facts_from_queries`.  Host arrays or device tensors; the library keeps a copy of its own.  None or empty arrays
+        clear the index.  A second call replaces it; prepare() and training steps leave it alone.  Returns self."""
+        with torch.cuda.device(self.device):
+            if e1 is None or len(e1) == 0:
+                _lib.check(self._h, self._lib.coper_set_known_facts(self._h, None, None, None, None, 0, 0, self._stream()))
+                return self
+            e1, rel, ip, ix = self._ids(e1), self._ids(rel), self._ids(tail_indptr), self._ids(tail_idx)
+            if rel.numel() != e1.numel() or ip.numel() != e1.numel() + 1:
+                raise ValueError("set_known_facts: e1 and rel of one length, tail_indptr one longer")
+            _lib.check(self._h, self._lib.coper_set_known_facts(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), e1.numel(), ix.numel(),
+                                                                self._stream()))
+        return self
+
+    def known_filter(self, e1, rel):
+        """(filt_indptr int64 [B + 1], filt_idx int64 [nnz]) device tensors: the CSR of known answers of the queries (e1, rel), looked
+        up in the resident index (coper_known_filter) -- what the explicit-CSR calls take.  Keys the index does not hold and ids outside
+        the model's range give empty rows."""
+        e1, rel = self._ids(e1), self._ids(rel)
+        B = rel.numel()
+        if e1.numel() != B:
+            raise ValueError("known_filter: e1 and rel of one length")
+        ip = torch.zeros((B + 1,), device=self.device, dtype=torch.int64)
+        nnz = C.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_known_filter(self._h, _ptr(e1), _ptr(rel), B, _ptr(ip), None, 0, C.byref(nnz), self._stream()))
+            ix = torch.empty((nnz.value,), device=self.device, dtype=torch.int64)
+            if nnz.value:
+                _lib.check(self._h, self._lib.coper_known_filter(self._h, _ptr(e1), _ptr(rel), B, _ptr(ip), _ptr(ix), nnz.value, C.byref(nnz),
+                                                                 self._stream()))
+        return ip, ix
+
+    def predict_topk_known(self, e1, rel, k, e1_rows=None):
+        """`predict_topk` with every query's known answers taken from the resident index (coper_predict_topk_known): the caller holds
+        bare (e1, rel) pairs.  Returns what `predict_topk` returns for the same filter."""
+        self._need_prepared()
+        if not isinstance(e1, torch.Tensor) and not isinstance(rel, torch.Tensor):
+            e1, rel = self.stage_batch(e1, rel)
+        e1, rel = self._ids(e1), self._ids(rel)
+        B = rel.numel()
+        if e1_rows is not None:
+            e1_rows = e1_rows.to(device=self.device, dtype=torch.float32).contiguous()
+        k = int(k)
+        tv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32)
+        ti = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.int64)
+        _lib.check(self._h, self._lib.coper_predict_topk_known(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), B, k, _ptr(tv), _ptr(ti),
+                                                               self._stream()))
+        return tv, ti
+
+    def rank_pass_known(self, e1, rel, e2, want_equal=True, e1_rows=None):
+        """`rank_pass` with the filter taken from the resident index (coper_encode_rank_known): (ranks int32 [B], n_equal or None).  The
+        target's own entry in its row stays exempt, as when `e2_multi` contains `e2`."""
+        self._need_prepared()
+        if not any(isinstance(a, torch.Tensor) for a in (e1, rel, e2)):
+            e1, rel, e2 = self.stage_batch(e1, rel, e2)
+        e1, rel, e2 = self._ids(e1), self._ids(rel), self._ids(e2)
+        B = rel.numel()
+        if e1_rows is not None:
+            e1_rows = e1_rows.to(device=self.device, dtype=torch.float32).contiguous()
+        ranks = torch.empty((B,), device=self.device, dtype=torch.int32)
+        ne = torch.empty((B,), device=self.device, dtype=torch.int32) if want_equal else None
+        _lib.check(self._h, self._lib.coper_encode_rank_known(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), _ptr(e2), B, None, _ptr(ranks),
+                                                              _ptr(ne), self._stream()))
+        return ranks, ne
+
     def capture_rank_pass(self, B, max_nnz, want_equal=True):
         """hipGraph capture of one encode -> fused-rank pass for batches of exactly B queries (the reference's
         per-`session.run` batch, B = 512, is launch-bound: ~14 kernel launches per batch).  Returns

@@ -355,6 +355,48 @@ COPER_API int coper_predict_topk(coper_handle* h, const int64_t* e1, const int64
 COPER_API int coper_predict_stats(coper_handle* h, int32_t reset, int64_t* n_queries, int64_t* n_unresolved, int64_t* n_rescored,
                                   float* max_ratio, void* stream);
 
+/* The known facts of the KG, resident on the handle.  Replaces the table the reference writes as e1rel_to_e2_full.json and looks up
+ * once per sample to form `e2_multi` (data.py:464-469, 494-503): the filter of a query (e1, rel) is a row of ONE fixed table, so a
+ * handle that holds the table needs three ids per query and no CSR from the caller.  All arrays are device int64, in the layout of
+ * coper_sample_train_batch's records: one row per distinct (e1, rel), rows ascending by key = e1 * num_rel + rel, tail_indptr
+ * [n_keys + 1] from 0 to nnz, tail_idx [nnz] GLOBAL ids strictly ascending within a row (a row may be empty).
+ * The library COPIES them into buffers of its own (entered in the ledger of coper_live_device_bytes; tails as int32 while num_ent
+ * fits): the caller's arrays may be freed once the stream has reached this call.  The same pass checks them on the device; the call
+ * synchronises the stream once and returns COPER_EINVAL -- coper_last_error names the first kind found, in this order: keys not
+ * ascending, a key twice, an e1 / rel / tail out of range, tails of a row not strictly ascending, tail_indptr[0] != 0, tail_indptr
+ * decreasing, tail_indptr[n_keys] != nnz -- leaving the index that was in force in force.  A second call replaces the index;
+ * n_keys == 0 removes it and frees everything it and its lookups allocated.  The index is no function of the parameters: it survives
+ * coper_prepare, coper_train_step and coper_reserve, and may be set before coper_prepare.  Entity shards take the whole table as it
+ * is (filters carry global ids).  COPER_ROLE_ENCODE handles answer no queries: COPER_EUNSUPPORTED; so are more than 2^31 - 1 rows,
+ * num_ent * num_rel beyond 63 bits and a stream that is being captured. */
+COPER_API int coper_set_known_facts(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* tail_indptr,
+                                    const int64_t* tail_idx, int64_t n_keys, int64_t nnz, void* stream);
+
+/* The CSR filter of a batch from the resident index: what `eval_dataset` reads back per sample as `e2_multi` (data.py:464-469,
+ * 494-503, then the dense mask of data.py:182-186), built on the device in three launches.  (1) a lane per query finds its key's row
+ * and writes the row's length -- 0 for a key the index does not hold and for an e1 / rel outside the model's range (the encoder
+ * clamps and counts those: coper_check_ids); (2) the lengths are scanned into filt_indptr [B + 1] (device int64; any B); (3) a lane
+ * per OUTPUT entry copies the rows into filt_idx (device int64, ascending within a row as stored): a row of thousands of tails is
+ * shared by as many lanes, stores are contiguous.  *nnz (host) = filt_indptr[B], read back with one 8-byte copy and one
+ * synchronisation of the stream -- the explicit-CSR entry points size their launches by it.
+ *   filt_idx == NULL: steps 1 - 2 and the readback only (size a buffer, call again);  filt_idx given with cap < *nnz: COPER_EINVAL,
+ *   nothing written to filt_idx;  no index set: COPER_ESTATE;  B == 0: COPER_OK, *nnz = 0;  a stream that is being captured:
+ *   COPER_EUNSUPPORTED (the readback).  Needs no prepared handle. */
+COPER_API int coper_known_filter(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* filt_indptr, int64_t* filt_idx,
+                                 int64_t cap, int64_t* nnz, void* stream);
+
+/* coper_predict_topk and coper_encode_rank with the filter looked up in the resident index instead of passed in: what the reference's
+ * evaluation gets from `e2_multi` of its records (data.py:464-469, 494-503; metrics.py:44-46).  coper_known_filter runs into
+ * workspaces of the handle (grown on demand where the total is known), then the body of the explicit-CSR call runs unchanged: same
+ * results as that call given the same CSR, bit for bit; ranking keeps the target's own entry exempt from the filter.  e1 is required
+ * (it forms the key) and e1_rows may accompany it for the encoder.  Every other argument, limit and error code is the explicit
+ * call's; no index set: COPER_ESTATE; neither call can be captured into a hipGraph (COPER_EUNSUPPORTED: the filter's size is read
+ * back). */
+COPER_API int coper_predict_topk_known(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, int32_t k,
+                                       float* topk_val, int64_t* topk_idx, void* stream);
+COPER_API int coper_encode_rank_known(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const int64_t* e2, int64_t B,
+                                      float* h_out, int32_t* ranks, int32_t* n_equal, void* stream);
+
 /* COPER_SCORE_BF16X3: the run-time audit of the exact band.  An AUDITED count launch (coper_config.band_audit_period: by default
  * the first after coper_prepare and every 8th, a sample of its workgroups, 128 pairs per round) re-scores pairs its band walk
  * decides (the competitors closest to each target) with the mode's own arithmetic as well and keeps the largest
