@@ -1291,7 +1291,11 @@ COPER_API int coper_set_known_facts(coper_handle* h, const int64_t* e1, const in
       "keys e1 * num_rel + rel are not ascending", "a key (e1, rel) occurs twice", "an e1 is outside [0, num_ent)",
       "a rel is outside [0, num_rel)", "a tail is outside [0, num_ent)", "the tails of a row are not strictly ascending",
       "tail_indptr[0] != 0", "tail_indptr decreases", "tail_indptr[n_keys] != nnz"};
-  for (int i = 0; i < KNOWN_BAD_KINDS; ++i)
+  // the row boundaries first: the pass finds a tail's row by a search over tail_indptr, so under boundaries that are not
+  // ascending from 0 to nnz its count of descending tails is about rows the caller never meant and would name the wrong cause
+  static const int report[KNOWN_BAD_KINDS] = {KNOWN_BAD_IP0, KNOWN_BAD_IPN, KNOWN_BAD_IP_DECR, KNOWN_BAD_E1, KNOWN_BAD_REL,
+                                              KNOWN_BAD_ORDER, KNOWN_BAD_DUP, KNOWN_BAD_TAIL, KNOWN_BAD_ASC};
+  for (const int i : report)
     if (v[i]) {
       char buf[200];
       snprintf(buf, sizeof buf, "coper_set_known_facts: %s (%u place%s); the index in force is unchanged", kinds[i], v[i], v[i] == 1 ? "" : "s");

@@ -168,7 +168,7 @@ constexpr int BAND_NCONST = 8;
 enum { GROUP_CHK_REL = 0, GROUP_CHK_E1 = 1, GROUP_CHK_PERM = 2, GROUP_CHK_LO = 3, GROUP_CHK_NLOCAL = 4, GROUP_CHK_RALL = 5,
        GROUP_CHK_STALE = 6, GROUP_CHK_WORDS = 8 };
 constexpr int EBLK_ALIGN = 16;  // entity blocks consumed per workgroup iteration in score_count (8 waves x 2)
-// what the build pass of the known-facts index counts (kernels_known.hip), in the order coper_set_known_facts reports them
+// what the build pass of the known-facts index counts (kernels_known.hip); coper_set_known_facts reports the tail_indptr kinds first
 enum { KNOWN_BAD_ORDER = 0, KNOWN_BAD_DUP = 1, KNOWN_BAD_E1 = 2, KNOWN_BAD_REL = 3, KNOWN_BAD_TAIL = 4, KNOWN_BAD_ASC = 5,
        KNOWN_BAD_IP0 = 6, KNOWN_BAD_IP_DECR = 7, KNOWN_BAD_IPN = 8, KNOWN_BAD_KINDS = 9, KNOWN_BAD_WORDS = 16 };
 

@@ -132,3 +132,101 @@ def rank_defining_logits(O, m, h, params):
     lo, hi = m.shard
     return O.score_chain(np.ascontiguousarray(h.cpu().numpy()), np.ascontiguousarray(np.asarray(params["ent_emb"], np.float32)[lo:hi]),
                          np.ascontiguousarray(np.asarray(params["pred_bias"], np.float32)[lo:hi]))
+
+
+# ---------------------------------------------------------------------------------------------------- the known-facts index
+def known_filter_np(kf, md, e1, rel):
+    """The CSR of the queries (e1, rel) from the host index: absent keys and ids outside the model's range give empty rows."""
+    E, R = int(md["num_ent"]), int(md["num_rel"])
+    e1, rel = np.asarray(e1, np.int64), np.asarray(rel, np.int64)
+    key = kf["e1"] * R + kf["rel"]
+    ok = (e1 >= 0) & (e1 < E) & (rel >= 0) & (rel < R)
+    qk = np.where(ok, e1 * R + rel, -1)
+    pos = np.minimum(np.searchsorted(key, qk), len(key) - 1)
+    ok &= key[pos] == qk
+    rows = [kf["tail_idx"][kf["tail_indptr"][p]:kf["tail_indptr"][p + 1]] if f else np.zeros(0, np.int64) for p, f in zip(pos, ok)]
+    ip = np.zeros(len(e1) + 1, np.int64)
+    ip[1:] = np.cumsum([len(r) for r in rows])
+    return ip, (np.concatenate(rows).astype(np.int64) if len(rows) and ip[-1] else np.zeros(0, np.int64))
+
+
+def known_filter_brute(kf, md, e1, rel):
+    """What known_filter_np computes, without a search and without a key: a dict {(e1, rel): list of tails} filled row by row from
+    the index, and one Python loop over the queries."""
+    E, R = int(md["num_ent"]), int(md["num_rel"])
+    table = {}
+    for i in range(len(kf["e1"])):
+        pair = (int(kf["e1"][i]), int(kf["rel"][i]))
+        assert pair not in table
+        table[pair] = [int(t) for t in kf["tail_idx"][int(kf["tail_indptr"][i]):int(kf["tail_indptr"][i + 1])]]
+    ip, ix = [0], []
+    for a, r in zip(e1, rel):
+        a, r = int(a), int(r)
+        if 0 <= a < E and 0 <= r < R:
+            ix.extend(table.get((a, r), []))
+        ip.append(len(ix))
+    return np.array(ip, np.int64), np.array(ix, np.int64)
+
+
+def known_index(rows):
+    """{(e1, rel): tails} -> dict(e1, rel, tail_indptr, tail_idx), rows ascending by (e1, rel); a row may be empty."""
+    pairs = sorted(rows)
+    ip = np.zeros(len(pairs) + 1, np.int64)
+    ip[1:] = np.cumsum([len(rows[p]) for p in pairs])
+    tails = [np.asarray(rows[p], np.int64) for p in pairs]
+    return dict(e1=np.array([p[0] for p in pairs], np.int64), rel=np.array([p[1] for p in pairs], np.int64), tail_indptr=ip,
+                tail_idx=np.concatenate(tails) if ip[-1] else np.zeros(0, np.int64))
+
+
+GEOMETRY_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000)
+GEOMETRY_ONES = 300           # further one-tail rows: a wave of 64 and a workgroup of 256 DIFFERENT one-entry owners
+
+
+def geometry_index(md):
+    """The index of the gather-geometry cases: an empty row at the first possible key, in the middle and at the last possible key; a
+    row of every length of GEOMETRY_LENGTHS; GEOMETRY_ONES further one-tail rows.  Returns (index, names): names maps a row's length
+    (the rows of GEOMETRY_LENGTHS), ("one", i), "empty_first" / "empty_mid" / "empty_last" and "absent" (a pair between two rows
+    that the index does not hold) to the pair (e1, rel)."""
+    E, R = int(md["num_ent"]), int(md["num_rel"])
+    assert E >= 1200 + GEOMETRY_ONES and R >= 8
+    rng = np.random.default_rng(23)
+    rows, names = {}, {}
+    for i, n in enumerate(GEOMETRY_LENGTHS):
+        names[n] = (10 + 3 * i, (5 * i) % R)
+        rows[names[n]] = np.sort(rng.choice(E, n, replace=False))
+    for i in range(GEOMETRY_ONES):
+        names[("one", i)] = (1000 + i, i % 7)
+        rows[names[("one", i)]] = [(i * 37 + 11) % E]
+    names.update(empty_first=(0, 0), empty_mid=(500, 3), empty_last=(E - 1, R - 1), absent=(700, 2))
+    for k in ("empty_first", "empty_mid", "empty_last"):
+        rows[names[k]] = []
+    assert names["absent"] not in rows
+    return known_index(rows), names
+
+
+def empty_row_indexes(md):
+    """Small indexes that must be ACCEPTED, by name: empty rows at the front, in the middle and at the end; a descent of the tails
+    across row boundaries only ([5, 9], an empty row, [3, 4]); one key; every row empty (nnz == 0, n_keys > 0)."""
+    E, R = int(md["num_ent"]), int(md["num_rel"])
+    return {
+        "empty rows at the front, in the middle and at the end": known_index(
+            {(0, 0): [], (0, 1): [], (2, 1): [4, 8], (2, 2): [], (2, 3): [], (3, 0): [0, 1, E - 1], (3, 1): [7], (E - 1, R - 2): [], (E - 1, R - 1): []}),
+        "a descent across boundaries only": known_index({(1, 1): [5, 9], (1, 2): [], (1, 3): [3, 4]}),
+        "one key": known_index({(7, 3): [1, 2, 6]}),
+        "every row empty": known_index({(0, 0): [], (5, 1): [], (5, 2): [], (E - 1, R - 1): []}),
+    }
+
+
+def known_probe_queries(kf, md, seed):
+    """(e1, rel) that look at an index from every side: each of its keys (shuffled, some twice), the pairs next to each key, both ends
+    of the key range, and ids outside the model's range on either side."""
+    E, R = int(md["num_ent"]), int(md["num_rel"])
+    rng = np.random.default_rng(seed)
+    key = kf["e1"] * R + kf["rel"]
+    near = np.concatenate([key, key, key - 1, key + 1, [0, E * R - 1]])
+    near = near[(near >= 0) & (near < E * R)]
+    rng.shuffle(near)
+    e1, rel = near // R, near % R
+    out = np.array([[E, 0], [-1, 0], [0, R], [0, -1], [E, R], [int(kf["e1"][0]), R], [E, int(kf["rel"][0])]], np.int64)
+    at = rng.integers(0, len(e1) + 1, len(out))
+    return np.insert(e1, at, out[:, 0]), np.insert(rel, at, out[:, 1])

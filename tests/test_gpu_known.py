@@ -11,6 +11,7 @@ import torch
 
 from coper_amd import _lib
 from coper_amd import data as cdata
+from tests.helpers import known_filter_np as _np_filter
 
 pytestmark = pytest.mark.gpu
 
@@ -21,21 +22,6 @@ EINVAL, ESTATE = 1, 5
 def _model(md, p, **kw):
     from coper_amd.models import ConvE
     return ConvE(md, device=DEV, **kw).load_parameters(p).prepare()
-
-
-def _np_filter(kf, md, e1, rel):
-    """The CSR of the queries (e1, rel) from the host index: absent keys and ids outside the model's range give empty rows."""
-    E, R = int(md["num_ent"]), int(md["num_rel"])
-    e1, rel = np.asarray(e1, np.int64), np.asarray(rel, np.int64)
-    key = kf["e1"] * R + kf["rel"]
-    ok = (e1 >= 0) & (e1 < E) & (rel >= 0) & (rel < R)
-    qk = np.where(ok, e1 * R + rel, -1)
-    pos = np.minimum(np.searchsorted(key, qk), len(key) - 1)
-    ok &= key[pos] == qk
-    rows = [kf["tail_idx"][kf["tail_indptr"][p]:kf["tail_indptr"][p + 1]] if f else np.zeros(0, np.int64) for p, f in zip(pos, ok)]
-    ip = np.zeros(len(e1) + 1, np.int64)
-    ip[1:] = np.cumsum([len(r) for r in rows])
-    return ip, (np.concatenate(rows).astype(np.int64) if len(rows) and ip[-1] else np.zeros(0, np.int64))
 
 
 def _same_csr(got, want, what):
@@ -265,10 +251,11 @@ def test_index_lifetime():
     m.close()
 
 
-@pytest.mark.parametrize("what", ["swapped keys", "duplicated key", "tail == num_ent", "descending tails", "indptr[n_keys] != nnz"])
+@pytest.mark.parametrize("what", ["swapped keys", "duplicated key", "tail == num_ent", "descending tails", "indptr[n_keys] != nnz",
+                                  "e1 == num_ent", "e1 == -1", "rel == num_rel", "indptr[0] == 1", "indptr decreases once"])
 def test_device_validation_keeps_the_index_in_force(what):
     md, p = _small()
-    E = md["num_ent"]
+    E, R = md["num_ent"], md["num_rel"]
     q = cdata.synthetic_queries(md, 400, seed=4)
     kf = cdata.known_facts_from_queries(q)
     m = _model(md, p, score_mode="bf16x3").set_known_facts(**kf)
@@ -289,12 +276,35 @@ def test_device_validation_keeps_the_index_in_force(what):
     elif what == "descending tails":
         bad["tail_idx"][[at, at + 1]] = bad["tail_idx"][[at + 1, at]]
         frag = "strictly ascending"
-    else:
+    elif what == "indptr[n_keys] != nnz":
         bad["tail_indptr"][-1] += 1
         frag = "tail_indptr[n_keys] != nnz"
+    elif what == "e1 == num_ent":
+        bad["e1"][-1] = E                                                   # (the last key: the keys before it stay ascending)
+        frag = "an e1 is outside"
+    elif what == "e1 == -1":
+        bad["e1"][0] = -1
+        frag = "an e1 is outside"
+    elif what == "rel == num_rel":
+        bad["rel"][30] = R
+        frag = "a rel is outside"
+    elif what == "indptr[0] == 1":
+        assert bad["tail_indptr"][1] >= 1                                   # (no decrease comes with it)
+        bad["tail_indptr"][0] = 1
+        frag = "tail_indptr[0] != 0"
+    else:
+        # boundary k is raised to boundary k + 2: it stays inside [0, nnz], the last entry stays nnz, and the only decrease is
+        # from k to k + 1 (every row of a synthetic index holds its target: no two boundaries are equal)
+        ip, k = bad["tail_indptr"], long_row + 1
+        assert 0 < k and k + 2 < len(ip) and np.all(np.diff(ip) > 0)
+        ip[k] = ip[k + 2]
+        assert int((np.diff(ip) < 0).sum()) == 1 and ip[0] == 0 and ip[-1] == len(bad["tail_idx"]) and 0 <= ip.min() and ip.max() == ip[-1]
+        frag = "tail_indptr decreases"
     with pytest.raises(_lib.CoperError) as ei:
         m.set_known_facts(**bad)
     assert ei.value.code == EINVAL and frag in str(ei.value), str(ei.value)
+    if what not in ("swapped keys", "duplicated key", "tail == num_ent", "descending tails", "indptr[n_keys] != nnz"):
+        assert "(1 place)" in str(ei.value), str(ei.value)
     e1, rel, e2 = q["e1"][:130], q["rel"][:130], q["e2"][:130]
     _answers_equal(m, kf, md, e1, rel, e2, "after a refused index (%s)" % what)
     m.close()
