@@ -16,16 +16,26 @@
 //                                          per packed batch (split16.h) -- and whatever leaves is multiplied by 2^-(e_E + e_h)]
 //     for j in 0 .. NP-1   (NP = KS16 / 2 pairs of k-steps):
 //         acc += T1(2j); acc += T1(2j+1); acc += T2(2j); acc += T2(2j+1); acc += T3(2j); acc += T3(2j+1)
-//     if KS16 is odd (last k-step t = KS16 - 1):
-//         acc += T1(t); acc += T2(t); acc += T3(t)            [the K = 32 form adds an all-zero second half to T3: acc + 0]
+//     if KS16 is odd (last k-step t = KS16 - 1), by the handle's tail kind (bx3_tail_kind below, one function of (d, KS16)):
+//       full tail:  acc += T1(t); acc += T2(t); acc += T3(t)  [the K = 32 form adds an all-zero second half to T3: acc + 0]
+//       half tail (the last k-step holds at most 8 real values, k = 16t .. 16t + 7: its upper 8 k are zero on both sides, and the
+//                  three products over 8 k are 24 terms -- fewer than the 32 K-slots of one 16x16x32 instruction):
+//                   acc += [E_lo . h_hi over the 8 k, then E_hi . h_lo over the 8 k]        ONE K = 16 accumulation step
+//                   acc += [E_hi . h_hi over the 8 k | 8 zeros]                             the second K = 16 step
+//                  one 16x16x32 instruction (by 16-lane quarter: entities [lo | hi | hi | 0], queries [hi | lo | hi | 0]) or two
+//                  chained 32x32x16 (A = [el | eh], B = [qh | ql]; then A = [eh | 0], B = [qh | 0]): BX3_LAST_HALF below.
 //
 // Count-kernel images ("f3"): per block of 16 rows (entities) or 16 columns (queries), per step s (NP pair steps, then
-// the tail step when KS16 is odd), two 64-lane registers of 16 bytes; lane l holds row (l & 15), 8 consecutive k of one
+// the tail step when KS16 is odd), two 64-lane registers of 16 bytes (a half-tail step: ONE; f3_regs below counts the
+// registers of a block); lane l holds row (l & 15), 8 consecutive k of one
 // plane: k = 16 ks + 8 ((l >> 4) & 1), with (plane, ks) chosen per half-wave (l >> 5):
 //     pair step s:   reg 0 = [lo(2s) | lo(2s+1)]      reg 1 = [hi(2s) | hi(2s+1)]                  (both sides)
 //     tail step:     entities: reg 0 = [lo(t) | hi(t)], reg 1 = [hi(t) | 0]
 //                    queries:  reg 0 = [hi(t) | 0],     reg 1 = [hi(t) | lo(t)]
-// and the instructions of a step are  (e.reg0, q.reg1), (e.reg1, q.reg0), and for pair steps (e.reg1, q.reg1).
+//     half tail:     by quarter (l >> 4), every quarter the 8 k of 16 t:  entities: reg 0 = [lo | hi | hi | 0]
+//                                                                          queries:  reg 0 = [hi | lo | hi | 0]
+// and the instructions of a step are  (e.reg0, q.reg1), (e.reg1, q.reg0), and for pair steps (e.reg1, q.reg1); of a half-tail
+// step (e.reg0, q.reg0) alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,30 +72,76 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define BX3_LAST_QA(eh, el, qh, ql, c) \
   { (c) = BX3_MFMA32(qh, el, c); (c) = BX3_MFMA32(ql, eh, c); (c) = BX3_MFMA32(qh, eh, c); }
 
+// ---- the tail kind of a handle: the one function of (d, KS16) every kernel of the mode branches on (Dims::x3_tail, recorded
+// at coper_create) ----
+enum { BX3_TAIL_NONE = 0, BX3_TAIL_FULL = 1, BX3_TAIL_HALF = 2 };
+// The half tail is enabled where the count kernel has a half-tail instantiation (build time): KS16 = 13, d = 193 .. 200.
+__host__ __device__ constexpr bool bx3_half_instantiated(int KS16) { return KS16 == 13; }
+__host__ __device__ constexpr int bx3_tail_kind(int d, int KS16) {
+  return (KS16 & 1) == 0 ? BX3_TAIL_NONE : (bx3_half_instantiated(KS16) && d <= 16 * KS16 - 8 ? BX3_TAIL_HALF : BX3_TAIL_FULL);
+}
+
+// The half tail on the 32x32x16 shape, from the ordinary fragments of the last k-step (lane (row, half) holds k = 16 t + 8 half ..
+// + 7 of a plane; the upper halves are the zero padding of both sides): [first | second] = lanes 0 .. 31 keep `first`, lanes
+// 32 .. 63 take what lane - 32 holds of `second` -- one v_permlane32_swap per register, inside the vector unit.  (A select
+// around __shfl_xor does not do: the compiler moves the shuffle under the select's condition, where the lanes it reads from are
+// switched off.)  Every lane of the wave must run it.
+__device__ __forceinline__ unsigned bx3_half_join1(const unsigned first, const unsigned second) {
+  return __builtin_amdgcn_permlane32_swap(first, second, false, false)[0];     // first[32 .. 63] <-> second[0 .. 31]
+}
+__device__ __forceinline__ uint4 bx3_half_join(const uint4& first, const uint4& second) {
+  return make_uint4(bx3_half_join1(first.x, second.x), bx3_half_join1(first.y, second.y), bx3_half_join1(first.z, second.z),
+                    bx3_half_join1(first.w, second.w));
+}
+// A = [el | eh], B = [qh | ql]; then A = [eh | 0], B = [qh | 0] (the fragments' own upper halves)
+#define BX3_LAST_HALF(eh, el, qh, ql, c)                                                    \
+  {                                                                                         \
+    const uint4 bx3_a_ = coper::bx3_half_join(el, eh), bx3_b_ = coper::bx3_half_join(qh, ql); \
+    (c) = BX3_MFMA32(bx3_a_, bx3_b_, c); (c) = BX3_MFMA32(eh, qh, c);                       \
+  }
+#define BX3_LAST_HALF_QA(eh, el, qh, ql, c)                                                 \
+  {                                                                                         \
+    const uint4 bx3_a_ = coper::bx3_half_join(el, eh), bx3_b_ = coper::bx3_half_join(qh, ql); \
+    (c) = BX3_MFMA32(bx3_b_, bx3_a_, c); (c) = BX3_MFMA32(qh, eh, c);                       \
+  }
+// the last k-step of an odd count by the handle's tail kind (wave-uniform `half_tail`)
+#define BX3_LAST_BY(half_tail, eh, el, qh, ql, c) \
+  { if (half_tail) BX3_LAST_HALF(eh, el, qh, ql, c) else BX3_LAST(eh, el, qh, ql, c) }
+
 // ---- f3 images ------------------------------------------------------------------------------------------------------
-__host__ __device__ inline int f3_steps(int KS16) { return (KS16 + 1) / 2; }          // NS = NP + TAIL
-// uint4 index of register (blk16, step s, which) lane l
-__host__ __device__ inline int64_t f3_at(int64_t blk16, int NS, int s, int which, int l) { return ((blk16 * NS + s) * 2 + which) * 64 + l; }
+__host__ __device__ inline int f3_steps(int KS16) { return (KS16 + 1) / 2; }          // NS = NP + (a tail step)
+// registers per 16-row block: two per pair step, two for a full-tail step, one for a half-tail step
+__host__ __device__ constexpr int f3_regs(int KS16, int tail_kind) {
+  return 2 * (KS16 / 2) + (tail_kind == BX3_TAIL_HALF ? 1 : (tail_kind == BX3_TAIL_FULL ? 2 : 0));
+}
+// uint4 index of register (blk16, step s, which) lane l; RB = f3_regs (the tail step is a block's last: 2 s + which holds for all)
+__host__ __device__ inline int64_t f3_at(int64_t blk16, int RB, int s, int which, int l) { return ((blk16 * RB + s * 2 + which) * 64) + l; }
 
 // Writes the 16-byte pieces (hi, lo) of (row, k-step ks, half) into an f3 image.  `query_side`: the queries' tail layout.
 // Zero halves of the tail registers are never written: the image is zero-filled when it is allocated.
-__device__ __forceinline__ void f3_store_piece(uint4* __restrict__ img, int KS16, int64_t row, int ks, int half, const uint4& hi,
+__device__ __forceinline__ void f3_store_piece(uint4* __restrict__ img, int KS16, int tail_kind, int64_t row, int ks, int half, const uint4& hi,
                                                const uint4& lo, bool query_side) {
-  const int NS = f3_steps(KS16), NP = KS16 / 2;
+  const int RB = f3_regs(KS16, tail_kind), NP = KS16 / 2;
   const int64_t blk = row >> 4;
   const int r = (int)(row & 15) + 16 * half;
   if (ks < 2 * NP) {
     const int s = ks >> 1, l = r + 32 * (ks & 1);
-    img[f3_at(blk, NS, s, 0, l)] = lo;
-    img[f3_at(blk, NS, s, 1, l)] = hi;
+    img[f3_at(blk, RB, s, 0, l)] = lo;
+    img[f3_at(blk, RB, s, 1, l)] = hi;
+  } else if (tail_kind == BX3_TAIL_HALF) {   // one register, quarters of 16 lanes; the upper 8 k (half 1) are padding: not stored
+    if (half == 0) {
+      img[f3_at(blk, RB, NP, 0, r)] = query_side ? hi : lo;          // entities [lo | hi | hi | 0], queries [hi | lo | hi | 0]
+      img[f3_at(blk, RB, NP, 0, r + 16)] = query_side ? lo : hi;
+      img[f3_at(blk, RB, NP, 0, r + 32)] = hi;
+    }
   } else if (!query_side) {   // entities: reg 0 = [lo | hi], reg 1 = [hi | 0]
-    img[f3_at(blk, NS, NP, 0, r)] = lo;
-    img[f3_at(blk, NS, NP, 0, r + 32)] = hi;
-    img[f3_at(blk, NS, NP, 1, r)] = hi;
+    img[f3_at(blk, RB, NP, 0, r)] = lo;
+    img[f3_at(blk, RB, NP, 0, r + 32)] = hi;
+    img[f3_at(blk, RB, NP, 1, r)] = hi;
   } else {                    // queries: reg 0 = [hi | 0], reg 1 = [hi | lo]
-    img[f3_at(blk, NS, NP, 0, r)] = hi;
-    img[f3_at(blk, NS, NP, 1, r)] = hi;
-    img[f3_at(blk, NS, NP, 1, r + 32)] = lo;
+    img[f3_at(blk, RB, NP, 0, r)] = hi;
+    img[f3_at(blk, RB, NP, 1, r)] = hi;
+    img[f3_at(blk, RB, NP, 1, r + 32)] = lo;
   }
 }
 

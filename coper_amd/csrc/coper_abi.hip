@@ -276,7 +276,7 @@ static int alloc_workspace(coper_handle* h, int64_t cap, int ksplit, hipStream_t
     return rc;
   if (h->cfg.score_mode == COPER_SCORE_F32) return h->hfrag_ws.alloc(h, (size_t)((cap + 127) / 128) * 128 * dm.d_pad8, "hfrag_ws");
   const size_t plane = (size_t)((cap + 127) / 128) * 4 * dm.KS16 * 64;          // uint4
-  const size_t f3 = (size_t)((cap + 127) / 128) * 8 * f3_steps(dm.KS16) * 2 * 64;   // the count kernel's query image (uint4)
+  const size_t f3 = (size_t)((cap + 127) / 128) * 8 * dm.f3_rb * 64;   // the count kernel's query image (uint4)
   if ((rc = h->hfrag16_hi.alloc(h, plane, "bf16 query planes")) || (rc = h->hfrag16_lo.alloc(h, plane, "bf16 query planes")) ||
       (rc = h->hrm16_hi.alloc(h, plane, "bf16 query planes")) || (rc = h->hrm16_lo.alloc(h, plane, "bf16 query planes")) ||
       (rc = h->hf3_ws.alloc(h, f3, "query image")))
@@ -425,6 +425,8 @@ COPER_API int coper_create(const coper_config* cfg, coper_handle** out) {
   dm.d_pad16 = (dm.d + 15) / 16 * 16; dm.nfb = dm.d_pad16 / 16;
   dm.d_pad8 = (dm.d + 7) / 8 * 8; dm.KS = dm.d_pad8 / 8;
   dm.KS16 = (dm.d + 15) / 16;
+  dm.x3_tail = bx3_tail_kind(dm.d, dm.KS16);
+  dm.f3_rb = f3_regs(dm.KS16, dm.x3_tail);
   dm.n_local = cfg->shard_hi - cfg->shard_lo;
   dm.n_eblk = ((dm.n_local + 31) / 32 + EBLK_ALIGN - 1) / EBLK_ALIGN * EBLK_ALIGN;
   if (dm.d > COPER_MAX_ENT_EMB) return bad("ent_emb_size too large for the LDS query tile in two halves of K (d <= 640)");
@@ -714,7 +716,7 @@ static int prepare_entity_images(coper_handle* h, hipStream_t s) {
       (rc = h->bias_pad.alloc(h, (size_t)dm.n_eblk * 32, "bias_pad")))
     return rc;
   if ((rc = launch_bias_pad(h, lv.pred_bias->ptr, s))) return rc;
-  const size_t f3 = (size_t)dm.n_eblk * 2 * f3_steps(dm.KS16) * 2 * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
+  const size_t f3 = (size_t)dm.n_eblk * 2 * dm.f3_rb * 64;    // the count kernel's image (bf16x3_chain.h; uint4)
   if ((rc = h->Ef3.alloc(h, f3, "entity image"))) return rc;
   COPER_HIP_TRY(h, hipMemsetAsync(h->Ef3, 0, f3 * sizeof(uint4), s));
   PassCtx none;

@@ -151,6 +151,8 @@ struct Dims {
   int d_pad8 = 0;      // d rounded up to 8 (k-steps of the score kernels)
   int KS = 0;          // d_pad8 / 8
   int KS16 = 0;        // ceil(d / 16): k-steps of the bf16 MFMA
+  int x3_tail = 0;     // how the x3 mode sums the last k-step of an odd KS16 (bf16x3_chain.h: bx3_tail_kind), recorded at coper_create
+  int f3_rb = 0;       // registers per 16-row block of the count kernel's images (f3_regs)
   int64_t n_local = 0; // shard rows
   int64_t n_eblk = 0;  // 32-row entity blocks (padded to a multiple of EBLK_ALIGN)
 };

@@ -59,10 +59,19 @@ static_assert(SC3_MB == 2 || SC3_MB == 4, "mask words are written as whole 16-by
 // queries, top-10: 48.9 -> 45.6 ms), small ones GM = 1 (FB15k-237, k = 10: 0.69 against 0.84 ms): topk_expand (coper_internal.h).
 __host__ __device__ constexpr int sc3_gmask(int GM) { return GM == 2 ? 15 : 7; }        // a maximum is complete at value V with (V & mask) == mask
 __host__ __device__ constexpr int sc3_gm_rows(int GM) { return GM == 2 ? 1 : SC3_MB / 2; }   // rows of gmax per entity block of 16 SC3_MB rows
+// TAIL: the handle's tail kind (bf16x3_chain.h: BX3_TAIL_NONE / _FULL / _HALF)
+__host__ __device__ constexpr int sc3_steps(int NP, int TAIL) { return NP + (TAIL ? 1 : 0); }
+// The half tail's share of the epilogue: a half-tail region has MB instructions, room for ONE value in their shadow, so the
+// values of a block are dealt by a table (generated: 2 or 3 per pair region, 1 per short one; SC3_HT_V0[R] = the first value of
+// region R = 8 s + b) instead of an equal chunk per step.
+#include "sc3_half_tail_values.inc"
 template <int NP, int TAIL, int PD, int GM>
 struct SC3 {
   static constexpr int MB = SC3_MB;
-  static constexpr int NS = NP + TAIL;                    // steps per half-row
+  static constexpr int NS = sc3_steps(NP, TAIL);          // steps per half-row
+  static constexpr int RB = f3_regs(2 * NP + (TAIL ? 1 : 0), TAIL);   // f3 registers per 16-row (16-query) block
+  static_assert(TAIL != BX3_TAIL_HALF || (NP > 0 && PD <= NP && SC3_MB == 4 && NS * 8 + 1 == sizeof(SC3_HT_V0)),
+                "half tail: the chains start in a pair step, the prefetch across blocks lands on pair steps, the table is this shape's");
   static constexpr int NB = 8;                            // 16-query column blocks of the tile
   static constexpr int NR = NS * NB;                      // regions per half-row
   static constexpr int NV = 32 * MB;                      // accumulator values per lane per half-row: MB row blocks x 8 x 4
@@ -246,8 +255,12 @@ __device__ __forceinline__ void sc3_load_bias(SC3<NP, TAIL, PD, GM>& S, const fl
 }
 
 // the instructions of region (step s, column block b) on the MB accumulator chains of block M, chains interleaved
-template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, int... m2>
+template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, bool half, int... m2>
 __device__ __forceinline__ void sc3_mfmas(SC3<NP, TAIL, PD, GM>& S, std::integer_sequence<int, m2...>) {
+  if constexpr (half) {     // (e.reg0, q.reg0): [T1 then T2 over the 8 k | T3 over the 8 k and zeros]
+    ((S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q0[rs], S.acc[M][m2][b])), ...);
+    return;
+  }
   // (e.reg0, q.reg1): T1 of both k-steps (tail: T1 then T2); step 0 starts the chains from pred_bias
   if constexpr (s == 0) ((S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q1[rs], S.biasv[M][m2])), ...);
   else ((S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q1[rs], S.acc[M][m2][b])), ...);
@@ -277,7 +290,7 @@ __device__ __forceinline__ void sc3_slot_pieces(SC3<NP, TAIL, PD, GM>& S, float*
 // stay the compiler's (named operands).  Shapes: steps s > 0 (step 0 starts the chains from pred_bias; with the bias quads as
 // four more operands the allocator spilled 174 registers), 1 - 3 values that share one mask word; top-k launches fold their
 // block maxima in (sc3_region_asm_gm.inc).  Everything else takes the form above.
-template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, int v0, int cnt>
+template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, bool half, int v0, int cnt>
 __device__ __forceinline__ void sc3_region_asm(SC3<NP, TAIL, PD, GM>& S, const SC3Ptrs& X, const int lane, const bool store_ok, float* __restrict__ gm_row,
                                                const int64_t gm_col, uint4* __restrict__ mask_row) {
   constexpr int MB = SC3_MB;
@@ -311,13 +324,15 @@ __device__ __forceinline__ void sc3_region_asm(SC3<NP, TAIL, PD, GM>& S, const S
 
 // One slot of a region: MFMA number I of the region (term I / MB on chain I % MB) and, behind it, PP pieces of the other
 // block's epilogue (piece k of the region = piece k % 3 of value v0 + k / 3); a scheduling barrier pins the order.
-template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, int v0, int cnt, int PP, int I>
+template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, bool half, int v0, int cnt, int PP, int I>
 __device__ __forceinline__ void sc3_slot(SC3<NP, TAIL, PD, GM>& S, float* sc, const int lane, const bool store_ok,
                                          float* __restrict__ gm_row, const int64_t gm_col, uint4* __restrict__ mask_row) {
-  constexpr int MB = SC3_MB, NM = tail ? 2 * MB : 3 * MB;
+  constexpr int MB = SC3_MB, NM = half ? MB : (tail ? 2 * MB : 3 * MB);
   if constexpr (I < NM) {
     constexpr int t = I / MB, m2 = I % MB;
-    if constexpr (t == 0) {
+    if constexpr (half) {
+      S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q0[rs], S.acc[M][m2][b]);
+    } else if constexpr (t == 0) {
       if constexpr (s == 0) S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q1[rs], S.biasv[M][m2]);
       else S.acc[M][m2][b] = BX3_MFMA16(S.a0[sa][sl][m2], S.q1[rs], S.acc[M][m2][b]);
     } else if constexpr (t == 1) {
@@ -332,11 +347,11 @@ __device__ __forceinline__ void sc3_slot(SC3<NP, TAIL, PD, GM>& S, float* sc, co
   SC3_FENCE();
 }
 
-template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, int v0, int cnt, int PP, int... I>
+template <int NP, int TAIL, int PD, int GM, int M, int s, int b, int sa, int sl, int rs, bool tail, bool half, int v0, int cnt, int PP, int... I>
 __device__ __forceinline__ void sc3_slots(SC3<NP, TAIL, PD, GM>& S, float* sc, const int lane, const bool store_ok,
                                           float* __restrict__ gm_row, const int64_t gm_col, uint4* __restrict__ mask_row,
                                           std::integer_sequence<int, I...>) {
-  (sc3_slot<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, v0, cnt, PP, I>(S, sc, lane, store_ok, gm_row, gm_col, mask_row), ...);
+  (sc3_slot<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, half, v0, cnt, PP, I>(S, sc, lane, store_ok, gm_row, gm_col, mask_row), ...);
 }
 
 // Region (step s, column block b) of block M: in front, one entity-fragment load PD steps ahead (regions b < 2 MB: the
@@ -346,27 +361,29 @@ template <int NP, int TAIL, int PD, int GM, int M, int s, int b>
 __device__ __forceinline__ void sc3_region(SC3<NP, TAIL, PD, GM>& S, const SC3Ptrs& X, const int lane, const bool prev_valid,
                                            float* __restrict__ gm_row, const int64_t gm_col, uint4* __restrict__ mask_row) {
   typedef SC3<NP, TAIL, PD, GM> ST;
-  constexpr int MB = SC3_MB, NS = ST::NS, NR = ST::NR, G = ST::G, CH = ST::CH, NV = ST::NV;
-  constexpr bool tail = TAIL && s == NP;
+  constexpr int MB = SC3_MB, NS = ST::NS, NR = ST::NR, G = ST::G, CH = ST::CH, NV = ST::NV, RB = ST::RB;
+  constexpr bool tail = TAIL == BX3_TAIL_FULL && s == NP;
+  constexpr bool half = TAIL == BX3_TAIL_HALF && s == NP;      // one register per side, MB instructions
   constexpr int PA = (G & 1) ? M : 0;        // entity-fragment set of this block's step 0
   constexpr int PA_NEXT = (PA + G) & 1;      // ... of the next block's step 0
   constexpr int sa = (PA + s / PD) & 1, sl = s % PD, tk = s + PD;
 #ifndef COPER_DBG_SC3_SKIP_GL
   if constexpr (b < 2 * MB) {
     constexpr int m2 = b >> 1, wh = b & 1;
-    constexpr int BLKB = MB * NS * 2 * 1024;     // bytes of one entity block's registers
+    constexpr int BLKB = MB * RB * 1024;         // bytes of one entity block's registers
     if constexpr (tk < NS) {
       constexpr int ta = (PA + tk / PD) & 1, tl = tk % PD;
-      if constexpr (wh == 0) S.a0[ta][tl][m2] = sc3_bload(X.ra, X.voff, M * BLKB + ((m2 * NS + tk) * 2 + 0) * 1024);
-      else S.a1[ta][tl][m2] = sc3_bload(X.ra, X.voff, M * BLKB + ((m2 * NS + tk) * 2 + 1) * 1024);
+      if constexpr (wh == 0) S.a0[ta][tl][m2] = sc3_bload(X.ra, X.voff, M * BLKB + (m2 * RB + tk * 2 + 0) * 1024);
+      else if constexpr (!(TAIL == BX3_TAIL_HALF && tk == NP))     // (a half-tail step has no second register)
+        S.a1[ta][tl][m2] = sc3_bload(X.ra, X.voff, M * BLKB + (m2 * RB + tk * 2 + 1) * 1024);
     } else if constexpr (M == 0) {           // step tk - NS of this row's block 1
       constexpr int u = tk - NS;
-      if constexpr (wh == 0) S.a0[PA_NEXT][u][m2] = sc3_bload(X.ra, X.voff, BLKB + ((m2 * NS + u) * 2 + 0) * 1024);
-      else S.a1[PA_NEXT][u][m2] = sc3_bload(X.ra, X.voff, BLKB + ((m2 * NS + u) * 2 + 1) * 1024);
+      if constexpr (wh == 0) S.a0[PA_NEXT][u][m2] = sc3_bload(X.ra, X.voff, BLKB + (m2 * RB + u * 2 + 0) * 1024);
+      else S.a1[PA_NEXT][u][m2] = sc3_bload(X.ra, X.voff, BLKB + (m2 * RB + u * 2 + 1) * 1024);
     } else {                                 // ... of the next row's block 0
       constexpr int u = tk - NS;
-      if constexpr (wh == 0) S.a0[PA_NEXT][u][m2] = sc3_bload(X.rn, X.voff, ((m2 * NS + u) * 2 + 0) * 1024);
-      else S.a1[PA_NEXT][u][m2] = sc3_bload(X.rn, X.voff, ((m2 * NS + u) * 2 + 1) * 1024);
+      if constexpr (wh == 0) S.a0[PA_NEXT][u][m2] = sc3_bload(X.rn, X.voff, (m2 * RB + u * 2 + 0) * 1024);
+      else S.a1[PA_NEXT][u][m2] = sc3_bload(X.rn, X.voff, (m2 * RB + u * 2 + 1) * 1024);
     }
   }
 #endif
@@ -382,11 +399,13 @@ __device__ __forceinline__ void sc3_region(SC3<NP, TAIL, PD, GM>& S, const SC3Pt
 #endif
     {
       // (a ds_read offset holds 16 bits: registers beyond 64 KiB go through the second base instead of an add per read)
-      constexpr int i0 = ((b2 * NS + s2) * 2 + 0) * 64, i1 = i0 + 64;
+      constexpr int i0 = (b2 * RB + s2 * 2 + 0) * 64, i1 = i0 + 64;
+      constexpr bool one_reg = TAIL == BX3_TAIL_HALF && s2 == NP;     // (a half-tail step: one LDS read)
       if constexpr (i0 <= 4095) S.q0[(R + SC3_LD) & 3] = X.hl[i0]; else S.q0[(R + SC3_LD) & 3] = sc3_lds_hi(X.hl_hi, i0 - 4096);
 #ifdef COPER_DBG_SC3_ONE_LDS   /* ablation (wrong results): one of the two reads */
       if constexpr (R < 4)
 #endif
+      if constexpr (one_reg) {} else
       if constexpr (i1 <= 4095) S.q1[(R + SC3_LD) & 3] = X.hl[i1]; else S.q1[(R + SC3_LD) & 3] = sc3_lds_hi(X.hl_hi, i1 - 4096);
     }
   }
@@ -403,16 +422,18 @@ __device__ __forceinline__ void sc3_region(SC3<NP, TAIL, PD, GM>& S, const SC3Pt
   SC3_FENCE();     // experiment: the region's loads are issued before its first instruction of the matrix pipe
 #endif
   // epilogue of the other block: this step's chunk of CH values is dealt to the eight regions in order
-  constexpr int c0 = b * CH / 8, c1 = (b + 1) * CH / 8, v0 = s * CH + c0;
-  constexpr int cnt = v0 >= NV ? 0 : (v0 + (c1 - c0) > NV ? NV - v0 : c1 - c0);
+  constexpr int c0 = b * CH / 8, c1 = (b + 1) * CH / 8;
+  constexpr int v0 = TAIL == BX3_TAIL_HALF ? (int)SC3_HT_V0[R] : s * CH + c0;
+  constexpr int cw = TAIL == BX3_TAIL_HALF ? (int)SC3_HT_V0[R + 1] - (int)SC3_HT_V0[R] : c1 - c0;
+  constexpr int cnt = v0 >= NV ? 0 : (v0 + cw > NV ? NV - v0 : cw);
 #if !defined(COPER_DBG_SC3_NO_EPI) && !defined(COPER_DBG_SC3_NO_BAND) && !defined(COPER_DBG_SC3_EPI_R0)
   if constexpr (MB == 4 && s > 0 && cnt >= 1 && cnt <= 3 && (v0 >> 5) == ((v0 + cnt - 1) >> 5) && !(GM && cnt == 3 && (v0 & sc3_gmask(GM)) == sc3_gmask(GM))) {
-    sc3_region_asm<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, v0, cnt>(S, X, lane, prev_valid, gm_row, gm_col, mask_row);
+    sc3_region_asm<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, half, v0, cnt>(S, X, lane, prev_valid, gm_row, gm_col, mask_row);
     SC3_FENCE();
     return;
   }
 #endif
-  sc3_mfmas<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail>(S, std::make_integer_sequence<int, MB>{});
+  sc3_mfmas<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, half>(S, std::make_integer_sequence<int, MB>{});
 #ifndef COPER_DBG_SC3_NO_EPI
   // (Also tried: pinning value i between terms i and i + 1 of the region by a never-read accumulator operand, so that no two
   // values end up behind one MFMA -- 0.275 against 0.263 ms: the compiler's own placement is the better one.)
@@ -449,8 +470,9 @@ __device__ __forceinline__ void sc3_half(SC3<NP, TAIL, PD, GM>& S, const SC3Ptrs
 
 template <int NP, int TAIL, int PD, int GM, int J, int... m2>
 __device__ __forceinline__ void sc3_prologue_a_(SC3<NP, TAIL, PD, GM>& S, const uint4* __restrict__ pa, std::integer_sequence<int, m2...>) {
-  constexpr int NS = NP + TAIL, JJ = J < NS ? J : NS - 1;
-  ((S.a0[0][J][m2] = pa[((m2 * NS + JJ) * 2 + 0) * 64], S.a1[0][J][m2] = pa[((m2 * NS + JJ) * 2 + 1) * 64]), ...);
+  constexpr int NS = sc3_steps(NP, TAIL), RB = SC3<NP, TAIL, PD, GM>::RB, JJ = J < NS ? J : NS - 1;
+  static_assert(!(TAIL == BX3_TAIL_HALF && JJ == NP), "the first PD steps of a half-tail block are pair steps");
+  ((S.a0[0][J][m2] = pa[(m2 * RB + JJ * 2 + 0) * 64], S.a1[0][J][m2] = pa[(m2 * RB + JJ * 2 + 1) * 64]), ...);
 }
 template <int NP, int TAIL, int PD, int GM, int... J>
 __device__ __forceinline__ void sc3_prologue_a(SC3<NP, TAIL, PD, GM>& S, const uint4* __restrict__ pa, std::integer_sequence<int, J...>) {
@@ -481,8 +503,9 @@ __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __r
   typedef SC3<NP, TAIL, PD, GM> ST;
   constexpr int NS = ST::NS, NB = ST::NB, NV = ST::NV;
   static_assert(PD <= NS, "the prefetch reaches at most one half-row ahead");
-  extern __shared__ uint4 hl3[];  // [NB][NS][2][64]
-  constexpr int TILE_REGS = NB * NS * 2;          // KiB of a query tile
+  extern __shared__ uint4 hl3[];  // [NB][RB][64]
+  constexpr int RB = ST::RB;
+  constexpr int TILE_REGS = NB * RB;              // KiB of a query tile
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   // Two ways to deal the rows (a row: this workgroup's 8 entity blocks against one query tile):
   //  rows_per_item == 0: an equal contiguous share for each of num_cus workgroups -- entity tables that L2 / MALL hold whole;
@@ -532,7 +555,7 @@ __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __r
   const std::make_integer_sequence<int, NS> SSEQ{};
   const std::make_integer_sequence<int, NV> VSEQ{};
   constexpr int MB = SC3_MB;
-  constexpr int64_t BLK_REGS = MB * NS * 2;   // f3 registers of one entity block (MB 16-row blocks)
+  constexpr int64_t BLK_REGS = MB * RB;       // f3 registers of one entity block (MB 16-row blocks)
   constexpr int64_t MW = 64 * (MB / 2);       // 16-byte mask pieces of one row of a wave
 
   // (Round 4 tried carrying (tile, row) along instead of these four 64-bit divisions per row -- some 100 instructions of a wave
@@ -586,9 +609,9 @@ __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __r
       prev_valid = false;
       __syncthreads();
       // query fragments of the first SC3_LD regions (step 0, column blocks 0 ..)
-      S.q0[0] = hl3[((0 * NS + 0) * 2 + 0) * 64 + lane]; S.q1[0] = hl3[((0 * NS + 0) * 2 + 1) * 64 + lane];
-      if constexpr (SC3_LD >= 2) { S.q0[1] = hl3[((1 * NS + 0) * 2 + 0) * 64 + lane]; S.q1[1] = hl3[((1 * NS + 0) * 2 + 1) * 64 + lane]; }
-      if constexpr (SC3_LD >= 3) { S.q0[2] = hl3[((2 * NS + 0) * 2 + 0) * 64 + lane]; S.q1[2] = hl3[((2 * NS + 0) * 2 + 1) * 64 + lane]; }
+      S.q0[0] = hl3[(0 * RB + 0) * 64 + lane]; S.q1[0] = hl3[(0 * RB + 1) * 64 + lane];
+      if constexpr (SC3_LD >= 2) { S.q0[1] = hl3[(1 * RB + 0) * 64 + lane]; S.q1[1] = hl3[(1 * RB + 1) * 64 + lane]; }
+      if constexpr (SC3_LD >= 3) { S.q0[2] = hl3[(2 * RB + 0) * 64 + lane]; S.q1[2] = hl3[(2 * RB + 1) * 64 + lane]; }
 #if defined(COPER_DBG_SC3_SKIP_LDS) || defined(COPER_DBG_SC3_SKIP_GL)
       S.q0[1] = S.q0[0]; S.q1[1] = S.q1[0]; S.q0[2] = S.q0[0]; S.q1[2] = S.q1[0]; S.q0[3] = S.q0[0]; S.q1[3] = S.q1[0];
       sc3_prologue_a1<NP, TAIL, PD, GM>(S, std::make_integer_sequence<int, PD>{});
@@ -849,6 +872,7 @@ __device__ __forceinline__ void band_audit_group(const BandArgs& A, const unsign
   const bool live = have && sx == sx;
   const int eh = A.x3s[0], sexp = A.x3s[1];
   const int KS = A.KS16, d = A.d;
+  const bool half_tail = bx3_tail_kind(d, KS) == BX3_TAIL_HALF;
   __builtin_amdgcn_wave_barrier();
   if (half == 0) s_e[i] = live ? e : -1;
   __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -895,7 +919,7 @@ __device__ __forceinline__ void band_audit_group(const BandArgs& A, const unsign
 #pragma unroll
     for (int u = 0; u < CB; u += 2) {   // wave-uniform
       if (ks + u + 1 < KS) { BX3_PAIR(ah[u], al[u], bh[u], bl[u], ah[u + 1], al[u + 1], bh[u + 1], bl[u + 1], acc); }
-      else if (ks + u < KS) { BX3_LAST(ah[u], al[u], bh[u], bl[u], acc); }
+      else if (ks + u < KS) { BX3_LAST_BY(half_tail, ah[u], al[u], bh[u], bl[u], acc); }
     }
   }
   const bool diag_lane = ((i >> 2) & 1) == half;
@@ -1090,11 +1114,12 @@ __device__ __forceinline__ void filter_excess_body(const FilterArgs& F, const in
     const float t_hi = live ? F.tband[q].y : 0.f;
     uint4 bh[KS], bl[KS];
     const int eh = F.x3s[0], sexp = F.x3s[1];
+    const bool half_tail = bx3_tail_kind(F.d, KS) == BX3_TAIL_HALF;
     tail_fragments_from_rows<KS>(F.hvec, q, live, F.d, half, eh, bh, bl);
     for (int64_t pb = p0 + 32 * t0; pb < p_end; pb += 32 * (int64_t)G) {
       float sc;
       int qi;
-      const int64_t frow = tail_filter_tile<KS>(pb, p_end, my_lo, my_e2, F.idx, F.n_local, s_e, F.Ehi, F.Elo, F.bias_pad, bh, bl, i, half, sexp, sc, qi);
+      const int64_t frow = tail_filter_tile<KS>(pb, p_end, my_lo, my_e2, F.idx, F.n_local, s_e, F.Ehi, F.Elo, F.bias_pad, bh, bl, i, half, sexp, half_tail, sc, qi);
       const float tq = __shfl(t_hi, qi);
       tail_take_back(half == 0 && frow >= 0 && sc > tq, qi, i, half, q0, F.ranks);
     }
@@ -1162,7 +1187,7 @@ int launch_filter_excess_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec
 // ------------------------------------------------------------------------------------------------
 template <int NP, int TAIL, int GM>
 static int sc3_go(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s) {
-  constexpr int NS = NP + TAIL;
+  constexpr int NS = sc3_steps(NP, TAIL), RB = f3_regs(2 * NP + (TAIL ? 1 : 0), TAIL);
 #ifdef COPER_SC3_PD
   constexpr int PD = COPER_SC3_PD < NS ? COPER_SC3_PD : NS;
 #else
@@ -1193,8 +1218,8 @@ static int sc3_go(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* g
     }
   }
   if (rows_per_item) grid = ((rows_per_tile + rows_per_item - 1) / rows_per_item + 7) / 8 * 8 * q_tiles;
-  const size_t lds = (size_t)8 * NS * 2 * 64 * sizeof(uint4);
-  const uint4* hf3 = (const uint4*)h->hf3_ws + (q0 / 16) * NS * 2 * 64;
+  const size_t lds = (size_t)8 * RB * 64 * sizeof(uint4);
+  const uint4* hf3 = (const uint4*)h->hf3_ws + (q0 / 16) * RB * 64;
   static bool attr_done[16] = {};
   const int dev = h->cfg.device & 15;
   if (!attr_done[dev]) {
@@ -1211,8 +1236,11 @@ static int sc3_go(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* g
 
 template <int NP, int TAIL>
 static int sc3_gm(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s) {
+  if constexpr (TAIL == BX3_TAIL_FULL && bx3_half_instantiated(2 * NP + 1)) {     // the handle's tail kind (Dims::x3_tail) picks the form
+    if (h->dm.x3_tail == BX3_TAIL_HALF) return sc3_gm<NP, BX3_TAIL_HALF>(h, q0, Bc, ng, gmax, gm_stride, s);
+  }
   if (!gmax) return sc3_go<NP, TAIL, 0>(h, q0, Bc, ng, gmax, gm_stride, s);
-  if constexpr (SC3_MB == 4 && (2 * NP + TAIL == 13 || 2 * NP + TAIL == 16)) {     // (64-entity maxima: topk_expand, coper_internal.h)
+  if constexpr (SC3_MB == 4 && (2 * NP + (TAIL ? 1 : 0) == 13 || 2 * NP + (TAIL ? 1 : 0) == 16)) {     // (64-entity maxima: topk_expand, coper_internal.h)
     if (topk_expand(h) == 2) return sc3_go<NP, TAIL, 2>(h, q0, Bc, ng, gmax, gm_stride, s);
   }
   return sc3_go<NP, TAIL, 1>(h, q0, Bc, ng, gmax, gm_stride, s);

@@ -29,7 +29,7 @@ __device__ __forceinline__ void split8(const float* v, uint4& hi, uint4& lo) { s
 // gather from, and the f3 image of the count kernel (bf16x3_chain.h): the same 16-byte pieces, placed three ways.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rows_to_frag_bf16(const float* __restrict__ src, int64_t n_rows, int d,
-                                                           int KS16, uint4* __restrict__ hi, uint4* __restrict__ lo,
+                                                           int KS16, int tail_kind, uint4* __restrict__ hi, uint4* __restrict__ lo,
                                                            uint4* __restrict__ rm_hi, uint4* __restrict__ rm_lo,
                                                            uint4* __restrict__ f3, int query_side,
                                                            int64_t total, int32_t* __restrict__ cnt, int32_t cnt_base,
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_rows_to_frag_bf16(const float* __restri
     rm_hi[o] = h4;
     rm_lo[o] = l4;
   }
-  if (f3) f3_store_piece(f3, KS16, row, ks, l >> 5, h4, l4, query_side != 0);
+  if (f3) f3_store_piece(f3, KS16, tail_kind, row, ks, l >> 5, h4, l4, query_side != 0);
 }
 
 int launch_rows_to_frag_bf16(coper_handle* h, PassCtx& ctx, const float* src, int64_t n_rows, int64_t n_blk, uint4* hi, uint4* lo,
@@ -76,7 +76,7 @@ int launch_rows_to_frag_bf16(coper_handle* h, PassCtx& ctx, const float* src, in
   int64_t total = n_blk * dm.KS16 * 64;
   int32_t* const done = h->group_done();
   hipLaunchKernelGGL(k_rows_to_frag_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, n_rows, dm.d,
-                     dm.KS16, hi, lo, rm_hi, rm_lo, f3, query_side ? 1 : 0, total, ctx.cnt, ctx.base, ctx.eq,
+                     dm.KS16, dm.x3_tail, hi, lo, rm_hi, rm_lo, f3, query_side ? 1 : 0, total, ctx.cnt, ctx.base, ctx.eq,
                      h->x3_ent_exp, query_side ? h->grouping().x3m : nullptr, h->x3s,
                      ctx.cnt && ctx.chk ? (const int32_t*)(ctx.chk + GROUP_CHK_STALE) : nullptr, done ? done + 2 : nullptr);
   if (ctx.cnt) ctx.preset = true;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void k_score_all_bf16x3(const uint4* __rest
                                                              const uint4* __restrict__ Elo,
                                                              const float* __restrict__ bias_pad,
                                                              const uint4* __restrict__ Hhi,
-                                                             const uint4* __restrict__ Hlo, int64_t B, int KS,
+                                                             const uint4* __restrict__ Hlo, int64_t B, int KS, int half_tail,
                                                              int64_t n_eblk, int64_t n_local,
                                                              float* __restrict__ logits, int64_t ld,
                                                              const int32_t* __restrict__ x3s) {
@@ -194,7 +194,10 @@ __global__ __launch_bounds__(256, 2) void k_score_all_bf16x3(const uint4* __rest
 #define STEP_LAST(eh, el, qh, ql)                                                                    \
   {                                                                                                  \
     _Pragma("unroll") for (int b = 0; b < NQ; ++b) _Pragma("unroll") for (int a = 0; a < ME; ++a)    \
-      BX3_LAST_QA(eh[a], el[a], qh[b], ql[b], acc[b][a]);                                            \
+    {                                                                                                \
+      if (half_tail) BX3_LAST_HALF_QA(eh[a], el[a], qh[b], ql[b], acc[b][a])                         \
+      else BX3_LAST_QA(eh[a], el[a], qh[b], ql[b], acc[b][a]);                                       \
+    }                                                                                                \
   }
   LOAD_EQ(eh0, el0, qh0, ql0, 0);
   LOAD_EQ(eh1, el1, qh1, ql1, KCL(1));
@@ -246,7 +249,7 @@ int launch_score_all_bf16x3(coper_handle* h, const float* hvec, int64_t B, float
   ScopedKernelTimer t(h, "score_all", s);
   hipLaunchKernelGGL(k_score_all_bf16x3, dim3((unsigned)q_groups, (unsigned)e_groups), dim3(256), 0, s,
                      (const uint4*)h->Ef16_hi, (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hfrag16_hi,
-                     (const uint4*)h->hfrag16_lo, B, dm.KS16, dm.n_eblk, dm.n_local, logits, ld, h->x3s);
+                     (const uint4*)h->hfrag16_lo, B, dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, dm.n_eblk, dm.n_local, logits, ld, h->x3s);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -261,7 +264,7 @@ int launch_score_all_bf16x3(coper_handle* h, const float* hvec, int64_t B, float
 __global__ __launch_bounds__(256) void k_pair_bf16x3(const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo,
                                                      const float* __restrict__ bias_pad,
                                                      const uint4* __restrict__ Hhi, const uint4* __restrict__ Hlo,
-                                                     int KS, int mode, int64_t n_pairs, int64_t B, int64_t L,
+                                                     int KS, int half_tail, int mode, int64_t n_pairs, int64_t B, int64_t L,
                                                      const int64_t* __restrict__ e2, const int32_t* __restrict__ lookup,
                                                      const int64_t* __restrict__ indptr, const int64_t* __restrict__ idx,
                                                      const int32_t* __restrict__ row_of, const float2* __restrict__ tband,
@@ -353,7 +356,7 @@ __global__ __launch_bounds__(256) void k_pair_bf16x3(const uint4* __restrict__ E
 #pragma unroll
     for (int u = 0; u < PB; u += 2) {   // wave-uniform
       if (ks + u + 1 < KS) { BX3_PAIR(ah[u], al[u], bh[u], bl[u], ah[u + 1], al[u + 1], bh[u + 1], bl[u + 1], acc); }
-      else if (ks + u < KS) { BX3_LAST(ah[u], al[u], bh[u], bl[u], acc); }
+      else if (ks + u < KS) { BX3_LAST_BY(half_tail, ah[u], al[u], bh[u], bl[u], acc); }
     }
   }
   // D[i][i] sits in lane i + 32*((i>>2)&1), register (i&3) + 4*(i>>3)
@@ -407,7 +410,7 @@ static void pair_launch(coper_handle* h, int mode, int64_t n_pairs, int64_t B, i
   const int wpb = n_pairs <= (1 << 22) ? 1 : 4;
   hipLaunchKernelGGL(k_pair_bf16x3, dim3((unsigned)((n_pairs + 32 * wpb - 1) / (32 * wpb))), dim3(64 * wpb), 0, s, (const uint4*)h->Erm16_hi,
                      (const uint4*)h->Erm16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo,
-                     dm.KS16, mode, n_pairs, B, L, e2, lookup, indptr, idx, row_of, tband, (int64_t)h->cfg.shard_lo,
+                     dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, mode, n_pairs, B, L, e2, lookup, indptr, idx, row_of, tband, (int64_t)h->cfg.shard_lo,
                      dm.n_local, out, ng, h->x3s);
 }
 

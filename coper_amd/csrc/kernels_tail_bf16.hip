@@ -163,7 +163,8 @@ __device__ __forceinline__ void tl_gather(const uint4* __restrict__ Ehi, const u
 //   tl_mma:    the tile, query fragments from LDS
 template <int KS>
 __device__ __forceinline__ f32x16 tl_mma(const float* __restrict__ bias_pad, const int64_t* s_e, const uint4 (&ah)[KS + 1], const uint4 (&al)[KS + 1],
-                                         const uint4 (*s_bh)[64], const uint4 (*s_bl)[64], const int lane, const int half, const int sexp) {
+                                         const uint4 (*s_bh)[64], const uint4 (*s_bl)[64], const int lane, const int half, const int sexp,
+                                         const bool half_tail) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -177,7 +178,7 @@ __device__ __forceinline__ f32x16 tl_mma(const float* __restrict__ bias_pad, con
       BX3_PAIR(ah[u], al[u], bh0, bl0, ah[u + 1], al[u + 1], bh1, bl1, acc);
     } else {
       const uint4 bh0 = s_bh[u][lane], bl0 = s_bl[u][lane];
-      BX3_LAST(ah[u], al[u], bh0, bl0, acc);
+      BX3_LAST_BY(half_tail, ah[u], al[u], bh0, bl0, acc);
     }
   }
   return acc;
@@ -211,6 +212,8 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
   const int64_t blk = blockIdx.x, q0 = blk * 32, q = q0 + i;
   const bool live = q < B;
+  const int tail_kind = bx3_tail_kind(d, KS);
+  const bool half_tail = tail_kind == BX3_TAIL_HALF;
   if (threadIdx.x < 32) s_corr[threadIdx.x] = 0;
   TL_STAMP(0);
   // ids of the later phases, requested before the finalize so that their latency lies under it
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
         for (int c = 0; c < 8; ++c) { n2 = fmaf(yv[u][c], yv[u][c], n2); y[c] = x3_scale(yv[u][c], eh); }
         uint4 h4, l4;
         split8_bf16(y, h4, l4);
-        f3_store_piece(hf3, KS, q, ks, half, h4, l4, true);   // rows past B: zero pieces (the count kernel's tile is whole)
+        f3_store_piece(hf3, KS, tail_kind, q, ks, half, h4, l4, true);   // rows past B: zero pieces (the count kernel's tile is whole)
         s_bh[ks][lane] = h4;
         s_bl[ks][lane] = l4;
       }
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
   // finalize 10.7 us, round 0 10.7, remaining tiles 7 - 13.  Round 4 before this form: fragments 5.1, round 0 12.2, rest 10 - 20.)
   float sc0 = 0.f;
   if (have0) {
-    const f32x16 acc = tl_mma<KS>(bias_pad, s_e[wave], ah, al, s_bh, s_bl, lane, half, sexp);
+    const f32x16 acc = tl_mma<KS>(bias_pad, s_e[wave], ah, al, s_bh, s_bl, lane, half, sexp, half_tail);
     if (wave == 0) {
       // D[i][i] sits in lane i + 32 * ((i >> 2) & 1), register (i & 3) + 4 * (i >> 3)
       float diag = 0.f;
@@ -348,7 +351,7 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
     const int64_t pn = pb + 32 * TL_WAVES + i;      // the ids of the tile after this one
     f_cur = pn < p_end ? idx[pn] : -1;
     f_prev = (pn < p_end && pn > p_begin) ? idx[pn - 1] : -1;
-    const f32x16 acc = tl_mma<KS>(bias_pad, s_e[wave], ah, al, s_bh, s_bl, lane, half, sexp);
+    const f32x16 acc = tl_mma<KS>(bias_pad, s_e[wave], ah, al, s_bh, s_bl, lane, half, sexp, half_tail);
     const float sc = tl_entry_score(acc, qi, i);
     const float tq = __shfl(t, qi);
     if (half == 0 && frow >= 0 && sc > tq) atomicAdd(&s_corr[qi], 1);

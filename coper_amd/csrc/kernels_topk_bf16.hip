@@ -702,7 +702,7 @@ __global__ __launch_bounds__(256) void k_topk_blk_scatter(const int32_t* __restr
 // ends with 16 rows of its slot's 32 logits; known answers of the slot's query, except its target, become -inf.
 __global__ __launch_bounds__(256) void k_topk_score_blocks(const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo,
                                                            const float* __restrict__ bias_pad, const uint4* __restrict__ Hrm_hi,
-                                                           const uint4* __restrict__ Hrm_lo, int KS, int64_t G,
+                                                           const uint4* __restrict__ Hrm_lo, int KS, int half_tail, int64_t G,
                                                            const int64_t* __restrict__ e2, const int64_t* __restrict__ indptr,
                                                            const int64_t* __restrict__ idx, const int32_t* __restrict__ cand_blk,
                                                            const int32_t* __restrict__ cand_q, const int32_t* __restrict__ blk_off,
@@ -741,7 +741,7 @@ __global__ __launch_bounds__(256) void k_topk_score_blocks(const uint4* __restri
 #pragma unroll
     for (int u = 0; u < 4; u += 2) {   // wave-uniform
       if (ks + u + 1 < KS) { BX3_PAIR(ah[u], al[u], bh[u], bl[u], ah[u + 1], al[u + 1], bh[u + 1], bl[u + 1], acc); }
-      else if (ks + u < KS) { BX3_LAST(ah[u], al[u], bh[u], bl[u], acc); }
+      else if (ks + u < KS) { BX3_LAST_BY(half_tail, ah[u], al[u], bh[u], bl[u], acc); }
     }
   }
   if (w < 0) return;
@@ -926,7 +926,7 @@ int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, 
                      h->blk_cnt_ws + GV, nseg, h->cand_sorted_ws);
   const int64_t waves = topk_sorted_cap(GV, T) / 32;
   hipLaunchKernelGGL(k_topk_score_blocks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)h->Ef16_hi,
-                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, GV, e2,
+                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, GV, e2,
                      indptr, idx, h->cand_blk_ws, h->cand_q_ws, h->blk_off_ws, h->cand_sorted_ws, (int64_t)h->cfg.shard_lo,
                      h->cand_val_ws, h->x3s);
   hipLaunchKernelGGL(k_topk_select_cand, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, h->cand_val_ws, h->cand_blk_ws, h->cand_tau_ws, indptr, B,
@@ -1224,7 +1224,7 @@ int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t
                      h->blk_cnt_ws + GV, nseg, h->cand_sorted_ws);
   const int64_t waves = topk_sorted_cap(GV, T) / 32;
   hipLaunchKernelGGL(k_topk_score_blocks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)h->Ef16_hi,
-                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, GV, no_target,
+                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, GV, no_target,
                      indptr, idx, h->cand_blk_ws, h->cand_q_ws, h->blk_off_ws, h->cand_sorted_ws, (int64_t)h->cfg.shard_lo,
                      h->cand_val_ws, h->x3s);
   PredictArgs A;

@@ -16,7 +16,7 @@ namespace coper {
 template <int KS>
 __device__ __forceinline__ f32x16 tail_tile(const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo, const float* __restrict__ bias_pad,
                                             const int64_t* s_e, const int64_t my_erow, const uint4 (&bh)[KS], const uint4 (&bl)[KS],
-                                            const int half, const int sexp) {
+                                            const int half, const int sexp, const bool half_tail) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -41,7 +41,7 @@ __device__ __forceinline__ f32x16 tail_tile(const uint4* __restrict__ Ehi, const
 #pragma unroll
     for (int u = 0; u < PB; u += 2) {
       if (k0 + u + 1 < KS) { BX3_PAIR(ah[u], al[u], bh[k0 + u], bl[k0 + u], ah[u + 1], al[u + 1], bh[k0 + u + 1], bl[k0 + u + 1], acc); }
-      else if (k0 + u < KS) { BX3_LAST(ah[u], al[u], bh[k0 + u], bl[k0 + u], acc); }
+      else if (k0 + u < KS) { BX3_LAST_BY(half_tail, ah[u], al[u], bh[k0 + u], bl[k0 + u], acc); }
     }
   }
   return acc;
@@ -56,7 +56,7 @@ __device__ __forceinline__ int64_t tail_filter_tile(const int64_t pb, const int6
                                                     const int64_t* __restrict__ idx, const int64_t n_local, int64_t* s_e,
                                                     const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo,
                                                     const float* __restrict__ bias_pad, const uint4 (&bh)[KS], const uint4 (&bl)[KS],
-                                                    const int i, const int half, const int sexp, float& sc, int& qi_out) {
+                                                    const int i, const int half, const int sexp, const bool half_tail, float& sc, int& qi_out) {
   const int64_t p = pb + i;
   // every lane runs the same cross-lane reads (a shuffle must not sit in divergent code: inactive lanes supply nothing);
   // lanes past the last entry carry frow = -1
@@ -83,7 +83,7 @@ __device__ __forceinline__ int64_t tail_filter_tile(const int64_t pb, const int6
   if (half == 0) s_e[i] = frow;
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): wave-local LDS exchange
   __builtin_amdgcn_wave_barrier();
-  const f32x16 acc = tail_tile<KS>(Ehi, Elo, bias_pad, s_e, frow, bh, bl, half, sexp);
+  const f32x16 acc = tail_tile<KS>(Ehi, Elo, bias_pad, s_e, frow, bh, bl, half, sexp, half_tail);
   // entry i wants D[i][qi]: register (i & 3) + 4 * (i >> 3) of lane qi + 32 * ((i >> 2) & 1)
   const int src = qi + 32 * ((i >> 2) & 1);
   const int reg = (i & 3) + 4 * (i >> 3);

@@ -15,10 +15,15 @@ G3="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES SQ_ACTIVE_
 G4="TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_READ_REQ_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum"
 G5="FETCH_SIZE"
 G6="WRITE_SIZE"
+# PMC_GROUPS="1 2": only those groups (default: all six).  A pass that fails or runs into its limit ends the job: nothing more is
+# started on a GPU that may have faulted.
 i=0
 for G in "$G1" "$G2" "$G3" "$G4" "$G5" "$G6"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/g$i -- python3 "$@" > $OUT/g$i.log 2>&1
+  case " ${PMC_GROUPS:-1 2 3 4 5 6} " in *" $i "*) ;; *) continue ;; esac
+  timeout -k 10 ${PMC_PASS_LIMIT:-600} rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/g$i -- python3 "$@" > $OUT/g$i.log 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "pmc pass $i: exit status $rc"; tail -n 20 $OUT/g$i.log; exit $rc; fi
 done
 python3 - "$OUT" "$FILT" <<'PY'
 import csv, glob, os, sys
