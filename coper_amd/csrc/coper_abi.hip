@@ -292,14 +292,11 @@ static int alloc_workspace(coper_handle* h, int64_t cap, int ksplit, hipStream_t
 
 static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t s) {
   int rc;
+  StreamGrow grow{h, s};
   if (nnz > h->ws_nnz) h->ws_nnz = nnz;
-  if (h->cfg.score_mode != COPER_SCORE_F32 && (size_t)nnz > h->row_of_ws.size()) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->row_of_ws.alloc(h, (size_t)nnz, "row_of_ws"))) return rc;
-  }
+  if (h->cfg.score_mode != COPER_SCORE_F32 && (rc = grow(h->row_of_ws, (size_t)nnz, "row_of_ws"))) return rc;
   if (h->factored && h->fac_chunk > 0 && factored_workspace_short(h, B)) {     // (its own group: bounded by the chunk, not by the batch)
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = factored_workspace(h, B))) return rc;
+    if ((rc = grow.sync()) || (rc = factored_workspace(h, B))) return rc;
   }
   if (h->ws_queries > 0 && B <= h->ws_queries) return COPER_OK;
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
@@ -326,21 +323,12 @@ static int ensure_workspace(coper_handle* h, int64_t B, int64_t nnz, hipStream_t
 static int ensure_rank_workspace(coper_handle* h, int64_t B, int64_t nnz, bool need_h, hipStream_t s) {
   int rc;
   if ((rc = ensure_workspace(h, B, nnz, s))) return rc;
-  if (need_h && (!h->h_ws || h->h_ws.size() < (size_t)B * h->dm.d)) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    const int64_t rows = B > h->ws_queries ? B : h->ws_queries;
-    if ((rc = h->h_ws.alloc(h, (size_t)rows * h->dm.d, "h_ws"))) return rc;
-  }
+  StreamGrow grow{h, s};
+  if (need_h && (rc = grow(h->h_ws, (size_t)B * h->dm.d, "h_ws", (size_t)h->ws_queries * h->dm.d))) return rc;
   if (h->cfg.score_mode == COPER_SCORE_F32) return COPER_OK;
   // the longest count launch any path issues: the mask has the size of the block maxima of the pruned top-k (one bit per logit
   // against one float per 32), so both are cut into the same chunks of queries
-  const int64_t qc = topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats);
-  const size_t need = score_count3_mask_bytes(h, qc);
-  if (need > h->mask_ws.size()) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->mask_ws.alloc(h, need, "band mask"))) return rc;
-  }
-  return COPER_OK;
+  return grow(h->mask_ws, score_count3_mask_bytes(h, topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats)), "band mask");
 }
 
 int score_all_dispatch(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s) {
@@ -1003,37 +991,6 @@ COPER_API int coper_score_rows(coper_handle* h, const float* hvec, const float* 
   return launch_exact_rows(h, hvec, rows, bias, B, out, (hipStream_t)stream);     // (the chain is the f32 mode's own logit)
 }
 
-// the workspaces of the pruned top-k (kernels_topk_bf16.hip) for B queries, k candidate blocks per query beside the filter entries
-static bool topk_pruned_fits(const coper_handle* h, int64_t B, int64_t k, int64_t filt_nnz) {
-  return topk_expand(h) * (k * B + filt_nnz) + 32 * h->dm.n_eblk * topk_nseg(h->dm.n_eblk) < 0x7fffffffLL;   // int32 slot ids
-}
-static int ensure_topk_workspace(coper_handle* h, int64_t B, int32_t k, int64_t filt_nnz, hipStream_t s) {
-  int rc;
-  const int XF = topk_expand(h);      // (2 on large tables: 64-entity candidate blocks, expanded to two 32-entity ones)
-  const size_t gneed = (size_t)(topk_gm_rows(h) * topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
-  const size_t t64 = (size_t)((int64_t)k * B + filt_nnz), tneed = (size_t)XF * t64;
-  const size_t cneed = topk_coarse_bytes(topk_gm_rows(h), topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats));
-  const size_t gv = (size_t)(h->dm.n_eblk * topk_nseg(h->dm.n_eblk));
-  if (gneed > h->gmax_ws.size() || tneed > h->cand_cap || (size_t)B > h->cand_tau_ws.size() || cneed > h->tk_coarse_ws.size() ||
-      !h->blk_cnt_ws || !h->blk_off_ws) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->tk_coarse_ws.ensure(h, cneed, "top-k coarse level")) || (rc = h->gmax_ws.ensure(h, gneed, "block maxima"))) return rc;
-    if (tneed > h->cand_cap) {
-      h->cand_cap = 0;
-      const size_t tlist = tneed + (XF > 1 ? t64 : 0);      // (+ the 64-entity level's own lists, behind the expanded ones)
-      if ((rc = h->cand_blk_ws.alloc(h, tlist, "candidate blocks")) || (rc = h->cand_q_ws.alloc(h, tlist, "candidate queries")) ||
-          (rc = h->cand_val_ws.alloc(h, tneed * 32, "candidate logits")) ||
-          (rc = h->cand_sorted_ws.alloc(h, topk_sorted_cap(gv, (int64_t)tneed), "sorted candidates")))
-        return rc;
-      h->cand_cap = tneed;
-    }
-    if ((rc = h->cand_tau_ws.ensure(h, (size_t)B, "candidate thresholds")) || (rc = h->blk_cnt_ws.ensure(h, 2 * gv, "block counts")) ||
-        (rc = h->blk_off_ws.ensure(h, gv + 1 + gv / 4096 + 2, "block offsets")))   // + chunk sums of the scan
-      return rc;
-  }
-  return COPER_OK;
-}
-
 static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt, const int64_t* e2,
                             const int64_t* filt_indptr, const int64_t* filt_idx, int64_t filt_nnz, int64_t B, int32_t k,
                             int32_t* n_greater, int32_t* n_equal, float* topk_val, int64_t* topk_idx, hipStream_t s) {
@@ -1047,8 +1004,9 @@ static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, co
   if ((rc = ensure_rank_workspace(h, B, filt_nnz, false, s))) return rc;
   // 0 < k <= COPER_TOPK_PRUNED_MAX (128): the count pass also writes block maxima and the top-k is selected from the few blocks that can
   // hold it (kernels_topk_bf16.hip): no logits workspace
-  const bool pruned = k > 0 && k <= COPER_TOPK_PRUNED_MAX && topk_pruned_fits(h, B, k, filt_nnz);
-  if (pruned && (rc = ensure_topk_workspace(h, B, k, filt_nnz, s))) return rc;
+  const TopkPlan plan = topk_plan(h, B, k, filt_nnz);
+  const bool pruned = k > 0 && k <= COPER_TOPK_PRUNED_MAX && plan.fits;
+  if (pruned && (rc = h->topk.ensure(h, plan, s))) return rc;
   if (h->cfg.score_mode != COPER_SCORE_F32) {
     if (!(ctx.packed_hvec == hvec && ctx.packed_B == B) && (rc = launch_pack_h_bf16(h, ctx, hvec, B, s))) return rc;
     COPER_DBG_SYNC(h, s, "pack_h");
@@ -1056,7 +1014,7 @@ static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, co
     if ((rc = launch_band_setup(h, hvec, tgt, B, s))) return rc;
     COPER_DBG_SYNC(h, s, "band_setup");
     if (pruned)
-      rc = launch_topk_pruned_bf16x3(h, ctx, hvec, tgt + B, e2, filt_indptr, filt_idx, filt_nnz, B, k, n_greater, n_equal, topk_val, topk_idx, s);
+      rc = launch_topk_pruned_bf16x3(h, ctx, plan, hvec, tgt + B, e2, filt_indptr, filt_idx, n_greater, n_equal, topk_val, topk_idx, s);
     else
       rc = launch_score_count_bf16x3(h, ctx, hvec, tgt + B, e2, filt_indptr, filt_idx, B, n_greater, n_equal, s);
     if (rc) return rc;
@@ -1064,7 +1022,7 @@ static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, co
     COPER_DBG_SYNC(h, s, "filter_correct");
   } else {
     if (pruned)
-      rc = launch_topk_pruned_f32(h, hvec, tgt, e2, filt_indptr, filt_idx, filt_nnz, B, k, n_greater, n_equal, topk_val, topk_idx, s);
+      rc = launch_topk_pruned_f32(h, plan, hvec, tgt, e2, filt_indptr, filt_idx, n_greater, n_equal, topk_val, topk_idx, s);
     else
       rc = launch_score_count(h, hvec, tgt, B, n_greater, n_equal, s);
     if (rc) return rc;
@@ -1076,10 +1034,7 @@ static int rank_counts_body(coper_handle* h, PassCtx& ctx, const float* hvec, co
     int64_t rows = (int64_t)(256ll << 20) / (h->dm.n_local * 4);
     if (rows < 1) rows = 1;
     if (rows > B) rows = B;
-    if ((size_t)rows * h->dm.n_local > h->logits_ws.size()) {
-      COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if ((rc = h->logits_ws.alloc(h, (size_t)rows * h->dm.n_local, "top-k logits"))) return rc;
-    }
+    if ((rc = StreamGrow{h, s}(h->logits_ws, (size_t)rows * h->dm.n_local, "top-k logits"))) return rc;
     return launch_topk(h, hvec, e2, filt_indptr, filt_idx, B, k, topk_val, topk_idx, h->logits_ws,
                        (int64_t)(h->logits_ws.size() / h->dm.n_local), s);
   }
@@ -1186,64 +1141,41 @@ COPER_API int coper_predict_topk(coper_handle* h, const int64_t* e1, const int64
   if (B == 0) return COPER_OK;
   if (B > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_predict_topk: batch too large");
   const bool x3 = h->cfg.score_mode != COPER_SCORE_F32;
-  const int32_t kb = x3 ? k + PREDICT_SLACK : k;      // candidate blocks per query beside the filter entries
-  if (k > COPER_TOPK_PRUNED_MAX || !topk_pruned_fits(h, B, kb, filt_nnz))
+  const TopkPlan plan = topk_plan(h, B, x3 ? k + PREDICT_SLACK : k, filt_nnz);
+  if (k > COPER_TOPK_PRUNED_MAX || !plan.fits)
     return fail(h, COPER_EUNSUPPORTED, "coper_predict_topk: k <= 128 and (k + 4) B + filt_nnz candidate slots within int32 (split the batch)");
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = ensure_rank_workspace(h, B, filt_nnz, by_ids, s)) || (rc = ensure_topk_workspace(h, B, kb, filt_nnz, s))) return rc;
-  const size_t n_rows = x3 ? (size_t)(predict_rows_workgroups(h, B) * h->dm.n_local) : 0;
-  if ((size_t)(2 * B + 1) > h->pred_ids_ws.size() || (x3 && ((size_t)(3 * B) > h->pred_q_ws.size() || !h->pred_stats || n_rows > h->pred_rows_ws.size()))) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->pred_ids_ws.ensure(h, (size_t)(2 * B + 1), "predict ids"))) return rc;
-    if (x3) {
-      if ((rc = h->pred_q_ws.ensure(h, (size_t)(3 * B), "predict per-query words")) || (rc = h->pred_rows_ws.ensure(h, n_rows, "predict rows")))
-        return rc;
-      if (!h->pred_stats) {
-        if ((rc = h->pred_stats.alloc(h, 8, "predict statistics"))) return rc;
-        COPER_HIP_TRY(h, hipMemsetAsync(h->pred_stats, 0, 8 * sizeof(uint32_t), s));
-      }
-    }
-  }
-  // "no target" for the kernels that exempt one from the filter, and the empty CSR of a raw call
-  int64_t* no_target = h->pred_ids_ws;
-  COPER_HIP_TRY(h, hipMemsetAsync(no_target, 0xFF, sizeof(int64_t) * B, s));
-  if (raw) {
-    COPER_HIP_TRY(h, hipMemsetAsync(no_target + B, 0, sizeof(int64_t) * (B + 1), s));
-    filt_indptr = no_target + B;
-    filt_idx = no_target + B;      // (never read: every row is empty)
-  }
+  const int64_t* no_target = nullptr;
+  if ((rc = ensure_rank_workspace(h, B, filt_nnz, by_ids, s)) || (rc = h->topk.ensure(h, plan, s)) || (rc = h->pred.ensure(h, B, s)) ||
+      (rc = predict_filter_args(h, B, raw, &no_target, &filt_indptr, &filt_idx, s)))
+    return rc;
   const float* hv = hvec;
   if (by_ids) {
     if ((rc = coper_encode(h, e1, rel, B, e1_rows, h->h_ws, stream))) return rc;
     hv = h->h_ws;
   }
-  h->pred_queries += B;
+  h->pred.pred_queries += B;
   if (x3) {
     PassCtx ctx;
     if ((rc = launch_pack_h_bf16(h, ctx, hv, B, s))) return rc;
-    return launch_predict_topk_bf16x3(h, hv, no_target, filt_indptr, filt_idx, filt_nnz, B, k, topk_val, topk_idx, s);
+    return launch_predict_topk_bf16x3(h, plan, hv, no_target, filt_indptr, filt_idx, k, topk_val, topk_idx, s);
   }
   // fp32 mode: block maxima and candidates ARE chain values; the counters of the count pass go to scratch, against targets no logit reaches
   COPER_HIP_TRY(h, hipMemsetAsync(h->tgt_ws, 0x7f, sizeof(float) * 2 * B, s));
-  return launch_topk_pruned_f32(h, hv, h->tgt_ws, no_target, filt_indptr, filt_idx, filt_nnz, B, k, h->cnt_ws, nullptr, topk_val, topk_idx, s);
+  return launch_topk_pruned_f32(h, plan, hv, h->tgt_ws, no_target, filt_indptr, filt_idx, h->cnt_ws, nullptr, topk_val, topk_idx, s);
 }
 
 COPER_API int coper_predict_stats(coper_handle* h, int32_t reset, int64_t* n_queries, int64_t* n_unresolved, int64_t* n_rescored,
                                   float* max_ratio, void* stream) {
   if (!h) return COPER_EINVAL;
   uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipStream_t s = (hipStream_t)stream;
-  if (h->pred_stats) {
-    COPER_HIP_TRY(h, hipMemcpyAsync(v, h->pred_stats, sizeof v, hipMemcpyDeviceToHost, s));
-    if (reset) COPER_HIP_TRY(h, hipMemsetAsync(h->pred_stats, 0, sizeof v, s));
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-  }
-  if (n_queries) *n_queries = h->pred_queries;
+  if (int rc = predict_stats_read(h, reset != 0, v, (hipStream_t)stream)) return rc;
+  if (n_queries) *n_queries = h->pred.pred_queries;
   if (n_unresolved) *n_unresolved = (int64_t)v[0];
   if (n_rescored) { uint64_t r; memcpy(&r, &v[6], sizeof r); *n_rescored = (int64_t)r; }
   if (max_ratio) memcpy(max_ratio, &v[2], sizeof(float));
-  if (reset) h->pred_queries = 0;
+  if (reset) h->pred.pred_queries = 0;
   return COPER_OK;
 }
 
@@ -1311,10 +1243,7 @@ COPER_API int coper_set_known_facts(coper_handle* h, const int64_t* e1, const in
 // steps 1 - 2 and the readback: filt_indptr [B + 1] on the device, its last entry on the host
 static int known_lookup(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* filt_indptr, int64_t* total, hipStream_t s) {
   int rc;
-  if ((size_t)B > h->known_row_ws.size()) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->known_row_ws.alloc(h, (size_t)(B < 64 ? 64 : B), "known-facts rows of a batch"))) return rc;
-  }
+  if ((rc = StreamGrow{h, s}(h->known_row_ws, (size_t)B, "known-facts rows of a batch", 64))) return rc;
   if ((rc = launch_known_find_scan(h, e1, rel, B, h->known_row_ws, filt_indptr, s))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(total, filt_indptr + B, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   COPER_HIP_TRY(h, hipStreamSynchronize(s));
@@ -1344,10 +1273,7 @@ COPER_API int coper_known_filter(coper_handle* h, const int64_t* e1, const int64
 // the lookup of a fused call into the handle's own CSR workspaces, which grow between the scan and the gather
 static int known_filter_ws(coper_handle* h, const int64_t* e1, const int64_t* rel, int64_t B, int64_t* total, hipStream_t s) {
   int rc;
-  if ((size_t)(B + 1) > h->known_ip_ws.size()) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    if ((rc = h->known_ip_ws.alloc(h, (size_t)(B < 64 ? 64 : B) + 1, "known-facts filter rows"))) return rc;
-  }
+  if ((rc = StreamGrow{h, s}(h->known_ip_ws, (size_t)B + 1, "known-facts filter rows", 65))) return rc;
   if ((rc = known_lookup(h, e1, rel, B, h->known_ip_ws, total, s))) return rc;
   if ((size_t)*total > h->known_ix_ws.size() || !h->known_ix_ws) {      // (the stream is idle: known_lookup has just synchronised it)
     if ((rc = h->known_ix_ws.alloc(h, (size_t)*total, "known-facts filter entries"))) return rc;

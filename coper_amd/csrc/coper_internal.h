@@ -1,6 +1,7 @@
 // Internal declarations shared by the libcoper_hip.so translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdlib>
 #include <stdint.h>
 #include <deque>
@@ -174,6 +175,34 @@ constexpr int EBLK_ALIGN = 16;  // entity blocks consumed per workgroup iteratio
 enum { KNOWN_BAD_ORDER = 0, KNOWN_BAD_DUP = 1, KNOWN_BAD_E1 = 2, KNOWN_BAD_REL = 3, KNOWN_BAD_TAIL = 4, KNOWN_BAD_ASC = 5,
        KNOWN_BAD_IP0 = 6, KNOWN_BAD_IP_DECR = 7, KNOWN_BAD_IPN = 8, KNOWN_BAD_KINDS = 9, KNOWN_BAD_WORDS = 16 };
 
+// The workspaces of the pruned top-k, sized by a TopkPlan (below) and reserved by ensure() beside the launchers that use them
+// (kernels_topk_bf16.hip).  The slot counts are the plan's: T64 = k_blocks * B + nnz candidate blocks, T of them as 32-entity slots.
+struct TopkPlan;
+struct TopkWs {
+  DevBuf<float> gmax_ws;           // [Gm][query chunk]: block maxima written by the count pass
+  size_t cand_cap = 0;             // the candidate slots T the group of four below holds (0 while any of it is missing)
+  DevBuf<int32_t> cand_blk_ws;     // [list_len] candidate blocks, query q's at k_blocks*q + indptr[q]
+  DevBuf<float> cand_val_ws;       // [T][32] their logits
+  DevBuf<int32_t> cand_q_ws;       // [list_len] the query of every candidate slot
+  DevBuf<int32_t> cand_sorted_ws;  // [sorted_cap] candidate slots grouped by entity block, 32-padded per block
+  DevBuf<char> tk_coarse_ws;       // the threshold kernel's coarse level (coarse_bytes)
+  DevBuf<uint32_t> cand_tau_ws;    // [B] selection threshold per query (ordered float bits; 0: none)
+  DevBuf<int32_t> blk_cnt_ws;      // [2 GV] slots per (block, segment) | scatter cursors
+  DevBuf<int32_t> blk_off_ws;      // [GV + 1] their offsets | the scan's chunk sums
+  int ensure(coper_handle* h, const TopkPlan& p, hipStream_t s);
+  bool holds(const TopkPlan& p) const;
+};
+// coper_predict_topk's own workspaces (kernels_topk_bf16.hip: the predict section)
+struct PredictWs {
+  DevBuf<int64_t> pred_ids_ws;     // [B] -1: "no target" for the kernels that exempt e2 from the filter | [B + 1] zeros: the raw call's CSR
+  DevBuf<int32_t> pred_q_ws;       // [B] chain re-scores of the query (-1: unresolved) | [B] its audit ratio's float bits | [B] unresolved queries
+  DevBuf<uint32_t> pred_stats;     // [8] since the last reset: [0] unresolved queries, [2] largest audit ratio (float bits), [4] unresolved of the
+                                   //   running call, [6..7] chain re-scores (64 bit); zeroed when allocated
+  DevBuf<float> pred_rows_ws;      // [workgroups][n_local] chain logits of the unresolved queries being served
+  int64_t pred_queries = 0;        // queries answered since the last reset (host count)
+  int ensure(coper_handle* h, int64_t B, hipStream_t s);
+};
+
 struct Timer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   double total_ms = 0.0;
@@ -308,25 +337,9 @@ struct coper_handle {
   coper::DevBuf<int32_t> cnt_ws;  // [2B]
   coper::DevBuf<float> h_ws;      // internal h of coper_encode_rank when the caller does not want it (fp32 mode)
   coper::DevBuf<float> logits_ws; // top-k path only: [chunk_rows, n_local]
-  // pruned top-k (k <= COPER_TOPK_PRUNED_MAX; kernels_topk_bf16.hip)
-  int64_t gmax_max_floats = (int64_t)1 << 28;   // set from the device memory size at prepare
-  coper::DevBuf<float> gmax_ws;         // [n_eblk][query chunk]: block maxima written by the count pass
-  size_t cand_cap = 0;                  // the candidate slots the group of four below holds (0 while any of it is missing)
-  coper::DevBuf<int32_t> cand_blk_ws;   // [k*B + nnz] candidate blocks, query q's at k*q + indptr[q]
-  coper::DevBuf<float> cand_val_ws;     // [k*B + nnz][32] their logits
-  coper::DevBuf<int32_t> cand_q_ws;     // [k*B + nnz] the query of every candidate slot
-  coper::DevBuf<int32_t> cand_sorted_ws;  // candidate slots grouped by entity block, 32-padded per block
-  coper::DevBuf<char> tk_coarse_ws;     // the threshold kernel's coarse level (topk_coarse_bytes)
-  coper::DevBuf<uint32_t> cand_tau_ws;  // [B] selection threshold per query (ordered float bits; 0: none)
-  coper::DevBuf<int32_t> blk_cnt_ws;    // [2 n_eblk] slots per block | scatter cursors
-  coper::DevBuf<int32_t> blk_off_ws;    // [n_eblk + 1] (+ the scan's chunk sums)
-  // coper_predict_topk (kernels_topk_bf16.hip: the predict section)
-  coper::DevBuf<int64_t> pred_ids_ws;   // [B] -1: "no target" for the kernels that exempt e2 from the filter | [B + 1] zeros: the raw call's CSR
-  coper::DevBuf<int32_t> pred_q_ws;     // [B] chain re-scores of the query (-1: unresolved) | [B] its audit ratio's float bits | [B] unresolved queries
-  coper::DevBuf<uint32_t> pred_stats;   // [8] since the last reset: [0] unresolved queries, [2] largest audit ratio (float bits), [4] unresolved of the
-                                        //   running call, [6..7] chain re-scores (64 bit); zeroed when allocated
-  coper::DevBuf<float> pred_rows_ws;    // [workgroups][n_local] chain logits of the unresolved queries being served
-  int64_t pred_queries = 0;             // queries answered since the last reset (host count)
+  int64_t gmax_max_floats = (int64_t)1 << 28;   // most block maxima held at a time; set from the device memory size at prepare
+  coper::TopkWs topk;                   // pruned top-k (k <= COPER_TOPK_PRUNED_MAX) and
+  coper::PredictWs pred;                //   coper_predict_topk: reserved and used in kernels_topk_bf16.hip
   coper::DevBuf<uint4> hfrag16_hi;      // bf16x3: h hi / lo planes in fragment order
   coper::DevBuf<uint4> hfrag16_lo;
   coper::DevBuf<uint4> hrm16_hi;        //   row-major twins
@@ -409,6 +422,18 @@ int hip_fail(coper_handle* h, hipError_t e, const char* what);
     hipError_t _e = (expr);                                       \
     if (_e != hipSuccess) return coper::hip_fail((h), _e, #expr); \
   } while (0)
+
+// Growing buffers that launches already on the stream may read: the stream is synchronised once, before the first buffer that is
+// replaced, and not at all when every buffer holds.  b gets max(need, rounded) elements when it has fewer than `need`.
+struct StreamGrow {
+  coper_handle* h; hipStream_t s; bool synced = false;
+  int sync() { if (!synced) COPER_HIP_TRY(h, hipStreamSynchronize(s)); synced = true; return COPER_OK; }
+  template <typename T> int operator()(DevBuf<T>& b, size_t need, const char* what, size_t rounded = 0) {
+    if (need <= b.size()) return COPER_OK;
+    if (int rc = sync()) return rc;
+    return b.alloc(h, need > rounded ? need : rounded, what);
+  }
+};
 
 // kernels_prepare.hip
 int launch_fold_bn(coper_handle* h, const float* gamma, const float* beta, const float* mean, const float* var,
@@ -493,13 +518,6 @@ inline int64_t tk_coarse_groups(int64_t G, int QV) {  // coarse keys a thread wr
 inline size_t tk_coarse_bytes(int64_t G, int64_t qs, int QV) {   // four keys (a thread's four queries) per thread, group and strip
   return (size_t)tk_strips(qs, QV) * tk_coarse_groups(G, QV) * TK_THREADS * sizeof(uint4);
 }
-// bytes of the scratch for G blocks x qs queries, for either strip width; 0: no coarse route
-inline size_t topk_coarse_bytes(int64_t G, int64_t qs) {
-  if (G < TK_COARSE_MIN_BLOCKS) return 0;
-  const size_t b4 = tk_coarse_bytes(G, qs, 4), b8 = tk_coarse_bytes(G, qs, 8);
-  return b4 > b8 ? b4 : b8;
-}
-// size of the block-grouped slot list: every block with candidates is padded to a multiple of 32
 // counters per block for the grouping of candidate slots: few blocks = many slots per block = contended atomics
 inline int topk_nseg(int64_t n_eblk) { return n_eblk < 4096 ? 8 : 1; }
 // Large tables: the x3 count kernel writes one block maximum per 64 entities instead of 32 (kernels_score3_bf16.hip: GM = 2),
@@ -516,8 +534,38 @@ inline int topk_expand(const coper_handle* h) {
   if (force && (force[0] == '1' || force[0] == '2')) return force[0] - '0';
   return h->dm.n_local >= 65536 ? 2 : 1;
 }
-inline int64_t topk_gm_rows(const coper_handle* h) { return h->dm.n_eblk / topk_expand(h); }     // rows of gmax (n_eblk is a multiple of 16)
-inline size_t topk_sorted_cap(int64_t n_eblk, int64_t T) { return (size_t)((T + 31 * (n_eblk < T ? n_eblk : T) + 31) / 32 * 32); }
+// The geometry of one pruned top-k call, computed once (topk_plan) and read by the reservation (TopkWs::ensure), the launchers and
+// the entry points: no size of the top-k is written anywhere else.  The f32 mode is the same plan with XF == 1.
+constexpr int TK_SCAN_CHUNK = 4096;   // counters per workgroup of the long block scan: 256 threads x 16
+struct TopkPlan {
+  int64_t B = 0;
+  int k_blocks = 0;         // candidate blocks per query beside its filter entries: k (the ranker), k + PREDICT_SLACK (the x3 predictor)
+  int XF = 1;               // 2: the count kernel writes 64-entity maxima (topk_expand), candidates are expanded to 32-entity slots
+  int64_t G = 0, Gm = 0;    // 32-entity blocks | rows of gmax: G / XF (n_eblk is a multiple of 16)
+  int nseg = 1;             // counters per block for the grouping of candidate slots (topk_nseg)
+  int64_t GV = 0, qc = 0;   // (block, segment) counters: G * nseg | queries whose block maxima are held at a time
+  int64_t T64 = 0, T = 0;   // candidate blocks: k_blocks + (filter entries) per query | ... as 32-entity slots: XF * T64
+  size_t list_len = 0;      // cand_blk / cand_q: T (+ the 64-entity level's own lists, behind the expanded ones)
+  size_t sorted_cap = 0;    // the block-grouped slot list: every (block, segment) with candidates is padded to a multiple of 32
+  size_t coarse_bytes = 0;  // the coarse level for Gm blocks x qc queries, for either strip width; 0: no coarse route
+  size_t cand_val_len = 0, gmax_floats = 0, blk_cnt_len = 0, blk_off_len = 0;
+  int64_t scan_tmp_cap = 0; // chunk sums of the long block scan, behind blk_off
+  bool fits = false;        // slot ids are int32
+};
+inline TopkPlan topk_plan(const coper_handle* h, int64_t B, int64_t k_blocks, int64_t filt_nnz) {
+  TopkPlan p;
+  p.B = B; p.k_blocks = (int)k_blocks; p.XF = topk_expand(h);
+  p.G = h->dm.n_eblk; p.Gm = p.G / p.XF;
+  p.nseg = topk_nseg(p.G); p.GV = p.G * p.nseg; p.qc = topk_chunk_queries(p.G, B, h->gmax_max_floats);
+  p.T64 = k_blocks * B + filt_nnz; p.T = p.XF * p.T64;
+  p.list_len = (size_t)(p.T + (p.XF > 1 ? p.T64 : 0));
+  p.sorted_cap = (size_t)((p.T + 31 * (p.GV < p.T ? p.GV : p.T) + 31) / 32 * 32);
+  p.cand_val_len = (size_t)(32 * p.T); p.gmax_floats = (size_t)(p.Gm * p.qc);
+  if (p.Gm >= TK_COARSE_MIN_BLOCKS) p.coarse_bytes = std::max(tk_coarse_bytes(p.Gm, p.qc, 4), tk_coarse_bytes(p.Gm, p.qc, 8));
+  p.scan_tmp_cap = p.GV / TK_SCAN_CHUNK + 2; p.blk_cnt_len = (size_t)(2 * p.GV); p.blk_off_len = (size_t)(p.GV + 1 + p.scan_tmp_cap);
+  p.fits = p.T + 32 * p.GV < 0x7fffffffLL;
+  return p;
+}
 void score_count_begin_bf16x3(const PassCtx& ctx, int64_t B, int32_t* ng, int32_t* ne, hipStream_t s);
 // kernels_score3_bf16.hip: the count kernel (16x16x32, software-pipelined, one wave per SIMD) and the exact band
 int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
@@ -551,19 +599,20 @@ int score_count_chunk_f32(coper_handle* h, int64_t q0, int64_t Bc, const float* 
                           int64_t gm_stride, hipStream_t s);
 int launch_topk_score_blocks_f32(coper_handle* h, const float* hvec, int64_t T, const int64_t* e2, const int64_t* indptr,
                                  const int64_t* idx, hipStream_t s);
-int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
-                           const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
-                           int64_t* topk_idx, hipStream_t s);
-// coper_predict_topk: blocks emitted beyond the k + (filter entries) that hold the x3 top-k, so that the chain's top-k provably sits in
-// emitted blocks (kernels_topk_bf16.hip); the candidate workspaces are sized for k + PREDICT_SLACK
-constexpr int PREDICT_SLACK = 4;
-int64_t predict_rows_workgroups(const coper_handle* h, int64_t B);
-int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t* no_target, const int64_t* indptr, const int64_t* idx, int64_t nnz,
-                               int64_t B, int k, float* topk_val, int64_t* topk_idx, hipStream_t s);
 int score_count3_maxima_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s);
-int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
-                              const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
-                              int64_t* topk_idx, hipStream_t s);
+// kernels_topk_bf16.hip: the launchers of a plan whose workspaces h->topk (and h->pred) hold (ensure() first)
+int launch_topk_pruned_f32(coper_handle* h, const TopkPlan& p, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
+                           const int64_t* idx, int32_t* ng, int32_t* ne, float* topk_val, int64_t* topk_idx, hipStream_t s);
+int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const TopkPlan& p, const float* hvec, const float* tgt_x, const int64_t* e2,
+                              const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* topk_val, int64_t* topk_idx, hipStream_t s);
+// coper_predict_topk: blocks emitted beyond the k + (filter entries) that hold the x3 top-k, so that the chain's top-k provably sits in
+// emitted blocks; the plan of the x3 predictor has k_blocks = k + PREDICT_SLACK
+constexpr int PREDICT_SLACK = 4;
+// "no target" for the kernels that exempt one from the filter; a raw call (no CSR given) also gets its empty one
+int predict_filter_args(coper_handle* h, int64_t B, bool raw, const int64_t** no_target, const int64_t** indptr, const int64_t** idx, hipStream_t s);
+int launch_predict_topk_bf16x3(coper_handle* h, const TopkPlan& p, const float* hvec, const int64_t* no_target, const int64_t* indptr,
+                               const int64_t* idx, int k, float* topk_val, int64_t* topk_idx, hipStream_t s);
+int predict_stats_read(coper_handle* h, bool reset, uint32_t v[8], hipStream_t s);   // pred_stats into v (untouched before the first x3 call)
 // kernels_encode_bf16.hip
 bool conv_bf16_supported(const Dims& dm);
 int launch_wfrag_to_bf16(coper_handle* h, const float* Wf, int64_t Rw, void* hi, void* lo, int32_t* w_exp, hipStream_t s);

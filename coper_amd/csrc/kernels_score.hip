@@ -808,8 +808,8 @@ int launch_topk_score_blocks_f32(coper_handle* h, const float* hvec, int64_t T, 
                                  const int64_t* idx, hipStream_t s) {
   const Dims& dm = h->dm;
   hipLaunchKernelGGL(k_topk_score_blocks_f32, dim3((unsigned)((T * 32 + 255) / 256)), dim3(256), 0, s, h->lv.ent_emb->ptr,
-                     h->lv.pred_bias->ptr, hvec, dm.d, T, e2, indptr, idx, h->cand_blk_ws, h->cand_q_ws, (int64_t)h->cfg.shard_lo,
-                     dm.n_local, h->cand_val_ws);
+                     h->lv.pred_bias->ptr, hvec, dm.d, T, e2, indptr, idx, h->topk.cand_blk_ws, h->topk.cand_q_ws, (int64_t)h->cfg.shard_lo,
+                     dm.n_local, h->topk.cand_val_ws);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }

@@ -1,6 +1,6 @@
 // Pruned top-k of the filtered rows (coper_rank_counts with 0 < k <= 128): the logits are never materialised, also
 // not for the top-k.  Kernels of the bf16x3 mode; the fp32-exact mode shares the threshold and selection kernels
-// (launch_topk_pruned_f32 at the end; its block maxima and VALU rescoring live in kernels_score.hip).
+// (launch_topk_pruned_f32; its block maxima and VALU rescoring live in kernels_score.hip).
 //
 // The per-shard top-k is what the entity-sharded ranker exchanges (the masked row of
 // metrics.py:44-46 is the thing it is the top of).  At 1.25 M entities per shard a [B, |E_shard|] logit
@@ -597,7 +597,6 @@ __global__ __launch_bounds__(1024) void k_topk_blk_scan(const int32_t* __restric
 // Long block axes (the 10M-entity table: 312,500 counters): the same exclusive scan in three coalesced launches -- chunk sums,
 // a scan of the chunk sums, chunk-local scans.  The single workgroup above walks 305 counters per thread with a stride of
 // 1.2 KB between lanes: 0.58 ms; these take ~0.02 ms together.
-constexpr int TK_SCAN_CHUNK = 4096;   // counters per workgroup: 256 threads x 16
 __global__ __launch_bounds__(256) void k_topk_blk_chunk_sums(const int32_t* __restrict__ blk_cnt, int64_t G, int32_t* __restrict__ chunk_sum) {
   __shared__ int32_t red[256];
   const int64_t base = (int64_t)blockIdx.x * TK_SCAN_CHUNK;
@@ -870,15 +869,14 @@ static void tk_launch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0, i
   }
   // the coarse route (TK_GRP): long block axes, when the scratch was reserved for this (G, qs)
   static const bool no_coarse = getenv("COPER_TK_NO_COARSE") != nullptr;     // A/B switch, read once
-  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->tk_coarse_ws && tk_coarse_bytes(G, qs, QV) <= h->tk_coarse_ws.size()) ? (uint4*)h->tk_coarse_ws : nullptr;
-  hipLaunchKernelGGL((k_topk_threshold_emit<QV, HCOPY>), dim3((unsigned)tk_strips(qs, QV)), dim3(TK_THREADS), lds, s, h->gmax_ws, G, qs, q0, bc,
-                     k, indptr, out_blk, out_q, out_cnt, topk_nseg(G), h->cand_tau_ws, tk_pair_xcd() ? 1 : 0, coarse, tk_coarse_groups(G, QV));
+  uint4* coarse = (!no_coarse && G >= TK_COARSE_MIN_BLOCKS && h->topk.tk_coarse_ws && tk_coarse_bytes(G, qs, QV) <= h->topk.tk_coarse_ws.size()) ? (uint4*)h->topk.tk_coarse_ws : nullptr;
+  hipLaunchKernelGGL((k_topk_threshold_emit<QV, HCOPY>), dim3((unsigned)tk_strips(qs, QV)), dim3(TK_THREADS), lds, s, h->topk.gmax_ws, G, qs, q0, bc,
+                     k, indptr, out_blk, out_q, out_cnt, topk_nseg(G), h->topk.cand_tau_ws, tk_pair_xcd() ? 1 : 0, coarse, tk_coarse_groups(G, QV));
 }
 
 // strip width / histogram copies of the threshold kernel by shape
 static void tk_dispatch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0, int64_t bc, int k, const int64_t* indptr, hipStream_t s,
-                             int32_t* out_blk = nullptr, int32_t* out_q = nullptr, int32_t* out_cnt = nullptr) {
-  if (!out_blk) { out_blk = h->cand_blk_ws; out_q = h->cand_q_ws; out_cnt = h->blk_cnt_ws; }
+                             int32_t* out_blk, int32_t* out_q, int32_t* out_cnt) {
   static const char* force = getenv("COPER_TK_EMIT");   // experiments: "8_1", "8_2", "4_4"
   if (force && force[0] == '8' && force[2] == '1') return tk_launch_emit<8, 1>(h, G, qs, q0, bc, k, indptr, s, out_blk, out_q, out_cnt);
   if (force && force[0] == '8' && force[2] == '2') return tk_launch_emit<8, 2>(h, G, qs, q0, bc, k, indptr, s, out_blk, out_q, out_cnt);
@@ -890,79 +888,103 @@ static void tk_dispatch_emit(coper_handle* h, int64_t G, int64_t qs, int64_t q0,
   else tk_launch_emit<4, 4>(h, G, qs, q0, bc, k, indptr, s, out_blk, out_q, out_cnt);
 }
 
-int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const float* hvec, const float* tgt_x, const int64_t* e2, const int64_t* indptr,
-                              const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
-                              int64_t* topk_idx, hipStream_t s) {
-  const Dims& dm = h->dm;
-  const int XF = topk_expand(h);            // 2: the count kernel writes 64-entity maxima (large tables), candidates are expanded below
-  const int64_t G = dm.n_eblk, Gm = G / XF;
-  const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
-  const int64_t T64 = (int64_t)k * B + nnz;   // candidate blocks: k + (filter entries) per query
-  const int64_t T = XF * T64;                 // ... as 32-entity slots
-  if ((size_t)(Gm * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap)
-    return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
+// ---- the workspaces of a plan: reserved here, beside the launchers that use them.  Reservation and use read one plan, so holds() is
+// the only comparison a launcher makes ----
+bool TopkWs::holds(const TopkPlan& p) const {
+  return p.fits && p.gmax_floats <= gmax_ws.size() && (size_t)p.T <= cand_cap && p.list_len <= cand_blk_ws.size() && p.list_len <= cand_q_ws.size() &&
+         p.cand_val_len <= cand_val_ws.size() && p.sorted_cap <= cand_sorted_ws.size() && p.coarse_bytes <= tk_coarse_ws.size() &&
+         (size_t)p.B <= cand_tau_ws.size() && p.blk_cnt_len <= blk_cnt_ws.size() && p.blk_off_len <= blk_off_ws.size();
+}
+
+int TopkWs::ensure(coper_handle* h, const TopkPlan& p, hipStream_t s) {
+  if (holds(p)) return COPER_OK;
+  StreamGrow grow{h, s};
   int rc;
-  score_count_begin_bf16x3(ctx, B, ng, ne, s);
-  // slots no query owns (filt_nnz may be a capacity larger than the CSR) must read as unused
-  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_blk_ws, 0xFF, sizeof(int32_t) * (T + (XF > 1 ? T64 : 0)), s));
-  const int nseg = topk_nseg(G);
-  const int64_t GV = G * nseg;   // (block, segment) counters
-  COPER_HIP_TRY(h, hipMemsetAsync(h->blk_cnt_ws, 0, sizeof(int32_t) * 2 * GV, s));          // counts | scatter cursors
-  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_sorted_ws, 0xFF, sizeof(int32_t) * topk_sorted_cap(GV, T), s));
-  int32_t* blk64 = XF > 1 ? h->cand_blk_ws + T : nullptr;      // the 64-entity level's own lists, behind the expanded ones
-  int32_t* q64 = XF > 1 ? h->cand_q_ws + T : nullptr;
-  for (int64_t q0 = 0; q0 < B; q0 += qc) {
-    const int64_t bc = B - q0 < qc ? B - q0 : qc;
-    const int64_t qs = (bc + 127) / 128 * 128;
-    if ((rc = score_count3_chunk_bf16x3(h, ctx, q0, bc, hvec, tgt_x, e2, indptr, idx, ng, ne, h->gmax_ws, qs, s))) return rc;
-    if (XF > 1) tk_dispatch_emit(h, Gm, qs, q0, bc, k, indptr, s, blk64, q64, nullptr);
-    else tk_dispatch_emit(h, G, qs, q0, bc, k, indptr, s);
+  if ((rc = grow(tk_coarse_ws, p.coarse_bytes, "top-k coarse level")) || (rc = grow(gmax_ws, p.gmax_floats, "block maxima"))) return rc;
+  if ((size_t)p.T > cand_cap || p.list_len > cand_blk_ws.size() || p.sorted_cap > cand_sorted_ws.size()) {
+    // the group of four moves together: a growth that fails part-way leaves it marked unusable, and the next call allocates it again
+    if ((rc = grow.sync())) return rc;
+    cand_cap = 0; cand_blk_ws.reset(); cand_q_ws.reset(); cand_val_ws.reset(); cand_sorted_ws.reset();
+    if ((rc = grow(cand_blk_ws, p.list_len, "candidate blocks")) || (rc = grow(cand_q_ws, p.list_len, "candidate queries")) ||
+        (rc = grow(cand_val_ws, p.cand_val_len, "candidate logits")) || (rc = grow(cand_sorted_ws, p.sorted_cap, "sorted candidates")))
+      return rc;
+    cand_cap = (size_t)p.T;
   }
-  if (XF > 1)
-    hipLaunchKernelGGL(k_topk_expand64, dim3((unsigned)((T64 + 255) / 256)), dim3(256), 0, s, blk64, q64, T64, h->cand_blk_ws, h->cand_q_ws,
-                       h->blk_cnt_ws, nseg);
-  tk_launch_blk_scan(h->blk_cnt_ws, GV, h->blk_off_ws, h->blk_off_ws + GV + 1, GV / TK_SCAN_CHUNK + 2, s);   // (chunk sums behind blk_off: reserved with it)
-  hipLaunchKernelGGL(k_topk_blk_scatter, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, h->cand_blk_ws, T, h->blk_off_ws,
-                     h->blk_cnt_ws + GV, nseg, h->cand_sorted_ws);
-  const int64_t waves = topk_sorted_cap(GV, T) / 32;
+  if ((rc = grow(cand_tau_ws, (size_t)p.B, "candidate thresholds")) || (rc = grow(blk_cnt_ws, p.blk_cnt_len, "block counts"))) return rc;
+  return grow(blk_off_ws, p.blk_off_len, "block offsets");
+}
+
+// ---- the candidate pipeline, each step once ----
+// reset the candidate lists; slots no query owns (filt_nnz may be a capacity larger than the CSR) must read as unused
+static int tk_reset_lists(coper_handle* h, const TopkPlan& p, bool grouped, hipStream_t s) {
+  TopkWs& w = h->topk;
+  COPER_HIP_TRY(h, hipMemsetAsync(w.cand_blk_ws, 0xFF, sizeof(int32_t) * p.list_len, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(w.blk_cnt_ws, 0, sizeof(int32_t) * p.blk_cnt_len, s));          // counts | scatter cursors
+  if (grouped) COPER_HIP_TRY(h, hipMemsetAsync(w.cand_sorted_ws, 0xFF, sizeof(int32_t) * p.sorted_cap, s));
+  return COPER_OK;
+}
+
+// chunks of qc queries: count(q0, bc, gmax, qs) is the route's count launch, which writes the chunk's block maxima; then the threshold
+// kernel emits k_blocks + (filter entries) blocks per query -- into the 64-entity level's own lists, behind the expanded ones, when XF > 1
+template <typename Count>
+static int tk_chunks(coper_handle* h, const TopkPlan& p, const int64_t* indptr, hipStream_t s, Count count) {
+  TopkWs& w = h->topk;
+  for (int64_t q0 = 0; q0 < p.B; q0 += p.qc) {
+    const int64_t bc = p.B - q0 < p.qc ? p.B - q0 : p.qc;
+    const int64_t qs = (bc + 127) / 128 * 128;
+    if (int rc = count(q0, bc, w.gmax_ws.get(), qs)) return rc;
+    if (p.XF > 1) tk_dispatch_emit(h, p.Gm, qs, q0, bc, p.k_blocks, indptr, s, w.cand_blk_ws + p.T, w.cand_q_ws + p.T, nullptr);
+    else tk_dispatch_emit(h, p.G, qs, q0, bc, p.k_blocks, indptr, s, w.cand_blk_ws, w.cand_q_ws, w.blk_cnt_ws);
+  }
+  return COPER_OK;
+}
+
+// x3: the candidate slots grouped by entity block and re-scored; known answers except e2[q] are masked
+static void tk_group_rescore(coper_handle* h, const TopkPlan& p, const int64_t* e2, const int64_t* indptr, const int64_t* idx, hipStream_t s) {
+  TopkWs& w = h->topk;
+  if (p.XF > 1)
+    hipLaunchKernelGGL(k_topk_expand64, dim3((unsigned)((p.T64 + 255) / 256)), dim3(256), 0, s, w.cand_blk_ws + p.T, w.cand_q_ws + p.T, p.T64,
+                       w.cand_blk_ws, w.cand_q_ws, w.blk_cnt_ws, p.nseg);
+  tk_launch_blk_scan(w.blk_cnt_ws, p.GV, w.blk_off_ws, w.blk_off_ws + p.GV + 1, p.scan_tmp_cap, s);
+  hipLaunchKernelGGL(k_topk_blk_scatter, dim3((unsigned)((p.T + 255) / 256)), dim3(256), 0, s, w.cand_blk_ws, p.T, w.blk_off_ws,
+                     w.blk_cnt_ws + p.GV, p.nseg, w.cand_sorted_ws);
+  const int64_t waves = (int64_t)p.sorted_cap / 32;
   hipLaunchKernelGGL(k_topk_score_blocks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)h->Ef16_hi,
-                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, GV, e2,
-                     indptr, idx, h->cand_blk_ws, h->cand_q_ws, h->blk_off_ws, h->cand_sorted_ws, (int64_t)h->cfg.shard_lo,
-                     h->cand_val_ws, h->x3s);
-  hipLaunchKernelGGL(k_topk_select_cand, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, h->cand_val_ws, h->cand_blk_ws, h->cand_tau_ws, indptr, B,
-                     k, (int64_t)h->cfg.shard_lo, topk_val, topk_idx, h->x3s, XF);
+                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, h->dm.KS16, h->dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, p.GV, e2,
+                     indptr, idx, w.cand_blk_ws, w.cand_q_ws, w.blk_off_ws, w.cand_sorted_ws, (int64_t)h->cfg.shard_lo,
+                     w.cand_val_ws, h->x3s);
+}
+
+int launch_topk_pruned_bf16x3(coper_handle* h, PassCtx& ctx, const TopkPlan& p, const float* hvec, const float* tgt_x, const int64_t* e2,
+                              const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* topk_val, int64_t* topk_idx, hipStream_t s) {
+  int rc;
+  if (!h->topk.holds(p)) return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
+  score_count_begin_bf16x3(ctx, p.B, ng, ne, s);
+  auto count = [&](int64_t q0, int64_t bc, float* gmax, int64_t qs) { return score_count3_chunk_bf16x3(h, ctx, q0, bc, hvec, tgt_x, e2, indptr, idx, ng, ne, gmax, qs, s); };
+  if ((rc = tk_reset_lists(h, p, true, s)) || (rc = tk_chunks(h, p, indptr, s, count))) return rc;
+  tk_group_rescore(h, p, e2, indptr, idx, s);
+  hipLaunchKernelGGL(k_topk_select_cand, dim3((unsigned)((p.B + 3) / 4)), dim3(256), 0, s, h->topk.cand_val_ws, h->topk.cand_blk_ws, h->topk.cand_tau_ws,
+                     indptr, p.B, p.k_blocks, (int64_t)h->cfg.shard_lo, topk_val, topk_idx, h->x3s, p.XF);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
 
 // fp32-exact mode: same threshold / selection kernels on the block maxima of k_score_count_f32; candidates are
 // rescored by the VALU chain (kernels_score.hip), which needs no grouping by block
-int launch_topk_pruned_f32(coper_handle* h, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
-                           const int64_t* idx, int64_t nnz, int64_t B, int k, int32_t* ng, int32_t* ne, float* topk_val,
-                           int64_t* topk_idx, hipStream_t s) {
-  const Dims& dm = h->dm;
-  const int64_t G = dm.n_eblk;
-  const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
-  const int64_t T = (int64_t)k * B + nnz;
-  if ((size_t)(G * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap)
-    return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
+int launch_topk_pruned_f32(coper_handle* h, const TopkPlan& p, const float* hvec, const float* tgt, const int64_t* e2, const int64_t* indptr,
+                           const int64_t* idx, int32_t* ng, int32_t* ne, float* topk_val, int64_t* topk_idx, hipStream_t s) {
   int rc;
-  score_count_begin_f32(h, hvec, B, ng, ne, s);
-  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_blk_ws, 0xFF, sizeof(int32_t) * T, s));
-  COPER_HIP_TRY(h, hipMemsetAsync(h->blk_cnt_ws, 0, sizeof(int32_t) * 2 * G * topk_nseg(G), s));
-  for (int64_t q0 = 0; q0 < B; q0 += qc) {
-    const int64_t bc = B - q0 < qc ? B - q0 : qc;
-    const int64_t qs = (bc + 127) / 128 * 128;
-    if ((rc = score_count_chunk_f32(h, q0, bc, tgt, ng, ne, h->gmax_ws, qs, s))) return rc;
-    tk_dispatch_emit(h, G, qs, q0, bc, k, indptr, s);
-  }
-  if ((rc = launch_topk_score_blocks_f32(h, hvec, T, e2, indptr, idx, s))) return rc;
-  hipLaunchKernelGGL(k_topk_select_cand, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, h->cand_val_ws, h->cand_blk_ws, h->cand_tau_ws, indptr, B,
-                     k, (int64_t)h->cfg.shard_lo, topk_val, topk_idx, (const int32_t*)nullptr, 1);
+  if (!h->topk.holds(p)) return fail(h, COPER_ESTATE, "pruned top-k: workspace not reserved");
+  score_count_begin_f32(h, hvec, p.B, ng, ne, s);
+  auto count = [&](int64_t q0, int64_t bc, float* gmax, int64_t qs) { return score_count_chunk_f32(h, q0, bc, tgt, ng, ne, gmax, qs, s); };
+  if ((rc = tk_reset_lists(h, p, false, s)) || (rc = tk_chunks(h, p, indptr, s, count)) ||
+      (rc = launch_topk_score_blocks_f32(h, hvec, p.T, e2, indptr, idx, s)))
+    return rc;
+  hipLaunchKernelGGL(k_topk_select_cand, dim3((unsigned)((p.B + 3) / 4)), dim3(256), 0, s, h->topk.cand_val_ws, h->topk.cand_blk_ws, h->topk.cand_tau_ws,
+                     indptr, p.B, p.k_blocks, (int64_t)h->cfg.shard_lo, topk_val, topk_idx, (const int32_t*)nullptr, 1);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // coper_predict_topk, COPER_SCORE_BF16X3: the top-k of a query WITHOUT a target, exact by the fp32 chain.
@@ -1179,64 +1201,66 @@ __global__ __launch_bounds__(256) void k_predict_rows(const int32_t* __restrict_
 }
 
 // workgroups (= scratch rows) of k_predict_rows: at most 64 MiB of rows, 256 workgroups, one per query
-int64_t predict_rows_workgroups(const coper_handle* h, int64_t B) {
-  int64_t w = ((int64_t)64 << 20) / (h->dm.n_local * 4);
-  if (w > 256) w = 256;
-  if (w > B) w = B;
+static int64_t predict_rows_workgroups(const coper_handle* h, int64_t B) {
+  const int64_t w = std::min(std::min(((int64_t)64 << 20) / (h->dm.n_local * 4), (int64_t)256), B);
   return w < 1 ? 1 : w;
 }
 
-int launch_predict_topk_bf16x3(coper_handle* h, const float* hvec, const int64_t* no_target, const int64_t* indptr, const int64_t* idx, int64_t nnz,
-                               int64_t B, int k, float* topk_val, int64_t* topk_idx, hipStream_t s) {
-  const Dims& dm = h->dm;
-  const int ks = k + PREDICT_SLACK;
-  const int XF = topk_expand(h);
-  const int64_t G = dm.n_eblk, Gm = G / XF;
-  const int64_t qc = topk_chunk_queries(G, B, h->gmax_max_floats);
-  const int64_t T64 = (int64_t)ks * B + nnz;
-  const int64_t T = XF * T64;
-  const int64_t W = predict_rows_workgroups(h, B);
-  if ((size_t)(Gm * qc) > h->gmax_ws.size() || (size_t)T > h->cand_cap || (size_t)(3 * B) > h->pred_q_ws.size() || !h->pred_stats ||
-      (size_t)(W * dm.n_local) > h->pred_rows_ws.size())
-    return fail(h, COPER_ESTATE, "predict top-k: workspace not reserved");
+int PredictWs::ensure(coper_handle* h, int64_t B, hipStream_t s) {
+  StreamGrow grow{h, s};
   int rc;
+  if ((rc = grow(pred_ids_ws, (size_t)(2 * B + 1), "predict ids")) || h->cfg.score_mode == COPER_SCORE_F32) return rc;
+  if ((rc = grow(pred_q_ws, (size_t)(3 * B), "predict per-query words")) ||
+      (rc = grow(pred_rows_ws, (size_t)(predict_rows_workgroups(h, B) * h->dm.n_local), "predict rows")))
+    return rc;
+  if (pred_stats) return COPER_OK;
+  if ((rc = grow(pred_stats, 8, "predict statistics"))) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(pred_stats, 0, 8 * sizeof(uint32_t), s));
+  return COPER_OK;
+}
+
+int predict_filter_args(coper_handle* h, int64_t B, bool raw, const int64_t** no_target, const int64_t** indptr, const int64_t** idx, hipStream_t s) {
+  int64_t* ids = h->pred.pred_ids_ws;
+  COPER_HIP_TRY(h, hipMemsetAsync(ids, 0xFF, sizeof(int64_t) * B, s));
+  *no_target = ids;
+  if (!raw) return COPER_OK;
+  COPER_HIP_TRY(h, hipMemsetAsync(ids + B, 0, sizeof(int64_t) * (B + 1), s));
+  *indptr = *idx = ids + B;      // (idx is never read: every row is empty)
+  return COPER_OK;
+}
+
+int predict_stats_read(coper_handle* h, bool reset, uint32_t v[8], hipStream_t s) {
+  if (!h->pred.pred_stats) return COPER_OK;
+  COPER_HIP_TRY(h, hipMemcpyAsync(v, h->pred.pred_stats, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (reset) COPER_HIP_TRY(h, hipMemsetAsync(h->pred.pred_stats, 0, 8 * sizeof(uint32_t), s));
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  return COPER_OK;
+}
+
+int launch_predict_topk_bf16x3(coper_handle* h, const TopkPlan& p, const float* hvec, const int64_t* no_target, const int64_t* indptr,
+                               const int64_t* idx, int k, float* topk_val, int64_t* topk_idx, hipStream_t s) {
+  const Dims& dm = h->dm;
+  TopkWs& w = h->topk;
+  PredictWs& pw = h->pred;
+  const int64_t B = p.B, W = predict_rows_workgroups(h, B);
+  int rc;
+  if (!w.holds(p) || (size_t)(3 * B) > pw.pred_q_ws.size() || !pw.pred_stats || (size_t)(W * dm.n_local) > pw.pred_rows_ws.size())
+    return fail(h, COPER_ESTATE, "predict top-k: workspace not reserved");
   // a band no logit reaches (0x7f7f7f7f = 3.4e38 on both ends): the count kernel counts nothing and marks nothing
   COPER_HIP_TRY(h, hipMemsetAsync(h->tband_ws, 0x7f, sizeof(float) * h->tband_ws.size(), s));
-  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_blk_ws, 0xFF, sizeof(int32_t) * (T + (XF > 1 ? T64 : 0)), s));
-  const int nseg = topk_nseg(G);
-  const int64_t GV = G * nseg;
-  COPER_HIP_TRY(h, hipMemsetAsync(h->blk_cnt_ws, 0, sizeof(int32_t) * 2 * GV, s));
-  COPER_HIP_TRY(h, hipMemsetAsync(h->cand_sorted_ws, 0xFF, sizeof(int32_t) * topk_sorted_cap(GV, T), s));
-  int32_t* blk64 = XF > 1 ? h->cand_blk_ws + T : nullptr;
-  int32_t* q64 = XF > 1 ? h->cand_q_ws + T : nullptr;
-  for (int64_t q0 = 0; q0 < B; q0 += qc) {
-    const int64_t bc = B - q0 < qc ? B - q0 : qc;
-    const int64_t qs = (bc + 127) / 128 * 128;
-    if ((rc = score_count3_maxima_bf16x3(h, q0, bc, h->cnt_ws, h->gmax_ws, qs, s))) return rc;
-    if (XF > 1) tk_dispatch_emit(h, Gm, qs, q0, bc, ks, indptr, s, blk64, q64, nullptr);
-    else tk_dispatch_emit(h, G, qs, q0, bc, ks, indptr, s);
-  }
-  if (XF > 1)
-    hipLaunchKernelGGL(k_topk_expand64, dim3((unsigned)((T64 + 255) / 256)), dim3(256), 0, s, blk64, q64, T64, h->cand_blk_ws, h->cand_q_ws,
-                       h->blk_cnt_ws, nseg);
-  tk_launch_blk_scan(h->blk_cnt_ws, GV, h->blk_off_ws, h->blk_off_ws + GV + 1, GV / TK_SCAN_CHUNK + 2, s);
-  hipLaunchKernelGGL(k_topk_blk_scatter, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, h->cand_blk_ws, T, h->blk_off_ws,
-                     h->blk_cnt_ws + GV, nseg, h->cand_sorted_ws);
-  const int64_t waves = topk_sorted_cap(GV, T) / 32;
-  hipLaunchKernelGGL(k_topk_score_blocks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)h->Ef16_hi,
-                     (const uint4*)h->Ef16_lo, h->bias_pad, (const uint4*)h->hrm16_hi, (const uint4*)h->hrm16_lo, dm.KS16, dm.x3_tail == BX3_TAIL_HALF ? 1 : 0, GV, no_target,
-                     indptr, idx, h->cand_blk_ws, h->cand_q_ws, h->blk_off_ws, h->cand_sorted_ws, (int64_t)h->cfg.shard_lo,
-                     h->cand_val_ws, h->x3s);
+  auto count = [&](int64_t q0, int64_t bc, float* gmax, int64_t qs) { return score_count3_maxima_bf16x3(h, q0, bc, h->cnt_ws, gmax, qs, s); };
+  if ((rc = tk_reset_lists(h, p, true, s)) || (rc = tk_chunks(h, p, indptr, s, count))) return rc;
+  tk_group_rescore(h, p, no_target, indptr, idx, s);
   PredictArgs A;
-  A.cand_val = h->cand_val_ws; A.cand_blk = h->cand_blk_ws; A.cand_tau = h->cand_tau_ws; A.indptr = indptr;
+  A.cand_val = w.cand_val_ws; A.cand_blk = w.cand_blk_ws; A.cand_tau = w.cand_tau_ws; A.indptr = indptr;
   A.hvec = hvec; A.ent = h->lv.ent_emb->ptr; A.bias = h->lv.pred_bias->ptr; A.consts = h->band_consts; A.x3s = h->x3s;
-  A.out_val = topk_val; A.out_idx = topk_idx; A.q_kept = h->pred_q_ws; A.q_ratio = (uint32_t*)(h->pred_q_ws + B);
-  A.B = B; A.lo = (int64_t)h->cfg.shard_lo; A.k = k; A.ks = ks; A.xf = XF; A.d = dm.d; A.kappa = band_kappa(h);
+  A.out_val = topk_val; A.out_idx = topk_idx; A.q_kept = pw.pred_q_ws; A.q_ratio = (uint32_t*)(pw.pred_q_ws + B);
+  A.B = B; A.lo = (int64_t)h->cfg.shard_lo; A.k = k; A.ks = p.k_blocks; A.xf = p.XF; A.d = dm.d; A.kappa = band_kappa(h);
   hipLaunchKernelGGL(k_predict_select_x3, dim3((unsigned)B), dim3(256), 0, s, A);
-  hipLaunchKernelGGL(k_predict_reduce, dim3(1), dim3(1024), 0, s, (const int32_t*)h->pred_q_ws, (const uint32_t*)(h->pred_q_ws + B), B,
-                     h->pred_q_ws + 2 * B, (uint32_t*)h->pred_stats);
-  hipLaunchKernelGGL(k_predict_rows, dim3((unsigned)W), dim3(256), 0, s, (const int32_t*)(h->pred_q_ws + 2 * B), (const uint32_t*)h->pred_stats,
-                     hvec, A.ent, A.bias, indptr, idx, A.lo, dm.n_local, dm.d, k, h->pred_rows_ws, topk_val, topk_idx);
+  hipLaunchKernelGGL(k_predict_reduce, dim3(1), dim3(1024), 0, s, (const int32_t*)pw.pred_q_ws, (const uint32_t*)(pw.pred_q_ws + B), B,
+                     pw.pred_q_ws + 2 * B, (uint32_t*)pw.pred_stats);
+  hipLaunchKernelGGL(k_predict_rows, dim3((unsigned)W), dim3(256), 0, s, (const int32_t*)(pw.pred_q_ws + 2 * B), (const uint32_t*)pw.pred_stats,
+                     hvec, A.ent, A.bias, indptr, idx, A.lo, dm.n_local, dm.d, k, pw.pred_rows_ws, topk_val, topk_idx);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }

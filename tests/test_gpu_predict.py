@@ -373,3 +373,95 @@ def test_codes_on_a_prepared_handle():
     assert e.value.code == 7
     enc.close()
     m.close()
+
+
+# ---------------------------------------------------------------------------------------------------- 9. the candidate pipeline's geometry
+# d = 200 (13 k-steps: 32- and 64-entity block maxima are both instantiated), 5,000 entities, 300 queries: three query chunks of 128 (the
+# last of 44) under COPER_TOPK_CHUNK_QUERIES=128.
+def _chunk_table():
+    md = cdata.model_descriptors("fb15k237_cpg", num_ent=5000, num_rel=12)
+    return md, cdata.synthetic_params(md, 11), cdata.synthetic_queries(md, 300, seed=5, mean_filter=6.0, max_filter=40)
+
+
+def _predict_forms(m, q, h, k, filt):
+    a = (q["filt_indptr"], q["filt_idx"]) if filt else (None, None)
+    return m.predict_topk(None, None, k, a[0], a[1], h=h), m.predict_topk(q["e1"], q["rel"], k, a[0], a[1])
+
+
+@pytest.fixture(scope="module")
+def chunk_table():
+    """The table, and per score mode the answers of a handle created with neither geometry variable set (one chunk, the default
+    block-maximum granularity), computed once: [mode][k, filtered] -> (h form, (e1, rel) form)."""
+    assert "COPER_TOPK_CHUNK_QUERIES" not in os.environ and "COPER_TOPK_EXPAND" not in os.environ
+    md, p, q = _chunk_table()
+    plain = {}
+    for mode in ("f32", "bf16x3"):
+        m = _model(md, p, score_mode=mode)
+        h = m.encode(q["e1"], q["rel"])
+        plain[mode] = {(k, filt): _predict_forms(m, q, h, k, filt) for k in (1, 10, 128) for filt in (True, False)}
+        m.close()
+    return md, p, q, plain
+
+
+@pytest.mark.parametrize("mode,expand", [("bf16x3", "1"), ("bf16x3", "2"), ("f32", None)])
+def test_several_query_chunks_and_both_block_maximum_granularities(chunk_table, mode, expand, monkeypatch):
+    """The predictor's run of the candidate pipeline where the ranker's is tested (test_gpu_parity.py: test_pruned_topk_matches_masked_row_topk,
+    test_topk_block_maxima_granularity): every answer equals the f32 handle's masked, sorted row, and is bit-equal to the answer of a
+    handle of the same mode created with neither variable set (the variables are read per call and must not change under a handle
+    that has made a top-k call, so that handle is another one)."""
+    md, p, q, plain = chunk_table
+    monkeypatch.setenv("COPER_TOPK_CHUNK_QUERIES", "128")
+    if expand:
+        monkeypatch.setenv("COPER_TOPK_EXPAND", expand)
+    m, m32 = _model(md, p, score_mode=mode), _model(md, p, score_mode="f32")
+    h = m.encode(q["e1"], q["rel"])
+    for k in (1, 10, 128):
+        for filt in (True, False):
+            what = "%s expand=%s k=%d %s" % (mode, expand, k, "filtered" if filt else "raw")
+            got_h, got_ids = _predict_forms(m, q, h, k, filt)
+            _same(got_h, _expected(m32, h, q["filt_indptr"] if filt else None, q["filt_idx"] if filt else None, k), what + " h-form")
+            _same(got_ids, got_h, what + " (e1, rel)-form against h-form")
+            _same(got_h, plain[mode][k, filt][0], what + " h-form against the plain handle")
+            _same(got_ids, plain[mode][k, filt][1], what + " (e1, rel)-form against the plain handle")
+    st = m.predict_stats()
+    print("%s expand=%s: %s" % (mode, expand, st))
+    assert st["max_ratio"] <= AUDIT_BOUND, st
+    m.close()
+    m32.close()
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16x3"])
+def test_topk_workspaces_that_grow_between_calls_of_one_handle(mode):
+    """rank_counts and predict_topk share the top-k workspaces of a handle: a sequence of calls in which they grow, are reused at a
+    smaller size, and the first call is repeated, gives call by call the bits of the same call on a fresh handle."""
+    md, p, q300 = _chunk_table()
+    q40 = cdata.synthetic_queries(md, 40, seed=6, mean_filter=6.0, max_filter=40)
+    q10 = cdata.synthetic_queries(md, 10, seed=7, mean_filter=6.0, max_filter=40)
+
+    def counts(q, k):
+        def run(m):
+            h = m.encode(q["e1"], q["rel"])
+            return m.rank_counts(h, m.target_scores(h, q["e2"]), q["e2"], q["filt_indptr"], q["filt_idx"], k=k)
+        return run
+
+    def predict(q, k):
+        return lambda m: m.predict_topk(q["e1"], q["rel"], k, q["filt_indptr"], q["filt_idx"])
+
+    steps = [("rank_counts k=4, 40 queries", counts(q40, 4)),
+             ("predict_topk k=4, 40 queries: k + 4 blocks, the candidate group grows", predict(q40, 4)),
+             ("rank_counts k=128, 300 queries: everything grows", counts(q300, 128)),
+             ("predict_topk k=2, 10 queries: nothing grows", predict(q10, 2)),
+             ("rank_counts k=4, 40 queries again", counts(q40, 4))]
+
+    def bits(out):
+        return [t.view(torch.int32).cpu() if t.dtype == torch.float32 else t.cpu() for t in out]
+
+    m = _model(md, p, score_mode=mode)
+    got = [bits(run(m)) for _, run in steps]
+    m.close()
+    for (what, run), g in zip(steps, got):
+        fresh = _model(md, p, score_mode=mode)
+        want = bits(run(fresh))
+        fresh.close()
+        assert len(g) == len(want) and all(torch.equal(a, b) for a, b in zip(g, want)), "%s %s: differs from a fresh handle" % (mode, what)
+    assert all(torch.equal(a, b) for a, b in zip(got[4], got[0])), "%s: step 5 differs from step 1" % mode
