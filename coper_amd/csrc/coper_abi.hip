@@ -326,9 +326,8 @@ static int ensure_rank_workspace(coper_handle* h, int64_t B, int64_t nnz, bool n
   StreamGrow grow{h, s};
   if (need_h && (rc = grow(h->h_ws, (size_t)B * h->dm.d, "h_ws", (size_t)h->ws_queries * h->dm.d))) return rc;
   if (h->cfg.score_mode == COPER_SCORE_F32) return COPER_OK;
-  // the longest count launch any path issues: the mask has the size of the block maxima of the pruned top-k (one bit per logit
-  // against one float per 32), so both are cut into the same chunks of queries
-  return grow(h->mask_ws, score_count3_mask_bytes(h, topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats)), "band mask");
+  // (the longest count launch any path issues, with the gt plane where the pass reads its filter correction from it)
+  return grow(h->mask_ws, rank_mask_bytes(h, B), "band mask");
 }
 
 int score_all_dispatch(coper_handle* h, const float* hvec, int64_t B, float* logits, int64_t ld, hipStream_t s) {

@@ -405,6 +405,9 @@ struct PassCtx {
   // the filter-excess role, deferred to the next band launch (kernels_score3_bf16.hip)
   bool excess_pending = false;
   FilterArgs excess = {};
+  // the fused tail left the whole filter correction to the look-up role of the band launches (filter_bits_supported): the count
+  // launches of the pass store their gt plane
+  bool gt_bits = false;
   // the pass runs on a grouping prepared ahead: the set's check words (its tiles compare the live ids with what was sorted; the
   // kernels that preset the rank counters read the verdict); nullptr: the pass grouped itself
   int64_t* chk = nullptr;
@@ -572,6 +575,7 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s);
 size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc);
+size_t score_count3_mask_words_bytes(const coper_handle* h, int64_t Bc);     // one plane: a bit per logit of the launch
 // The count kernels hold the fragments of a 128-query tile in the CU's 160 KiB of LDS: whole up to KS16 = 20 / KS = 40
 // (ent_emb_size <= 320), in two halves of K beyond that (kernels_score3_wide_bf16.hip, k_score_count_wide_f32) -- up to
 // ent_emb_size = 640, the bound coper_create enforces.
@@ -589,6 +593,13 @@ int launch_exact_rows(coper_handle* h, const float* hvec, const float* rows, con
 float band_kappa(const coper_handle* h);
 // kernels_tail_bf16.hip: finalize + targets + filter correction of a ranking pass in one launch
 bool tail_fused_supported(const coper_handle* h);
+// The filter correction of a ranks-only pass of B queries is read from the count kernel's own compare bits (the gt plane,
+// kernels_score3_bf16.hip: SC3_GT) instead of being scored a second time by the tail kernel: where the fused tail serves the handle
+// and the plane of the pass's longest count launch stays within FILTER_BITS_PLANE_CAP.  The ONE predicate of the path: the
+// workspace (ensure_rank_workspace) and every launch of the pass decide by it.
+constexpr size_t FILTER_BITS_PLANE_CAP = (size_t)64 << 20;
+bool filter_bits_supported(const coper_handle* h, int64_t B);
+size_t rank_mask_bytes(const coper_handle* h, int64_t B);     // mask_ws of a ranking pass of B queries: band words, gt plane if any, summaries
 int launch_finalize_targets_filter_bf16x3(coper_handle* h, PassCtx& ctx, int64_t B, int ksplit, float* h_out, const int64_t* e2, const int64_t* indptr,
                                           const int64_t* idx, int64_t nnz, float* tgt, int32_t* ranks, hipStream_t s);
 int launch_finalize_h_publish(coper_handle* h, int64_t B, int ksplit, float* h_out, hipStream_t s);

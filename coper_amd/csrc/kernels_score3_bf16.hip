@@ -34,8 +34,6 @@
 
 namespace coper {
 
-size_t score_count3_mask_words_bytes(const coper_handle* h, int64_t Bc);
-
 #define SC3_FENCE() __builtin_amdgcn_sched_barrier(0)
 #ifndef COPER_SC3_LD
 #define COPER_SC3_LD 2
@@ -59,6 +57,14 @@ static_assert(SC3_MB == 2 || SC3_MB == 4, "mask words are written as whole 16-by
 // queries, top-10: 48.9 -> 45.6 ms), small ones GM = 1 (FB15k-237, k = 10: 0.69 against 0.84 ms): topk_expand (coper_internal.h).
 __host__ __device__ constexpr int sc3_gmask(int GM) { return GM == 2 ? 15 : 7; }        // a maximum is complete at value V with (V & mask) == mask
 __host__ __device__ constexpr int sc3_gm_rows(int GM) { return GM == 2 ? 1 : SC3_MB / 2; }   // rows of gmax per entity block of 16 SC3_MB rows
+// GM = 3 (SC3_GT): no block maxima -- a ranks-only launch of the fused-tail path that also STORES the words it counts from:
+// S.mg[], one bit per logit "above the band", in the layout of the band words.  The look-up role of the band launch that follows
+// (band_lookup_body) takes the known answers back from `ranks` by reading their bits there instead of scoring them once more.
+// The gt plane of a row of a wave lies right behind its band words (a row of a wave is sc3_planes(GM) x 64 MB / 2 pieces): one
+// base pointer, a compile-time offset, no register the loop would have to carry.
+constexpr int SC3_GT = 3;
+__host__ __device__ constexpr bool sc3_maxima(int GM) { return GM == 1 || GM == 2; }
+__host__ __device__ constexpr int sc3_planes(int GM) { return GM == SC3_GT ? 2 : 1; }
 // TAIL: the handle's tail kind (bf16x3_chain.h: BX3_TAIL_NONE / _FULL / _HALF)
 __host__ __device__ constexpr int sc3_steps(int NP, int TAIL) { return NP + (TAIL ? 1 : 0); }
 // The half tail's share of the epilogue: a half-tail region has MB instructions, room for ONE value in their shadow, so the
@@ -130,7 +136,7 @@ __device__ __forceinline__ void sc3_value_tail(SC3<NP, TAIL, PD, GM>& S, const i
       S.cg[B0 + i] += __builtin_popcount(S.mg[w] & (FM << (32 - 4 * MB * (i + 1))));
     S.mk[w] &= ~S.mg[w];
   }
-  if constexpr (GM) {
+  if constexpr (sc3_maxima(GM)) {
     if constexpr ((V & sc3_gmask(GM)) == sc3_gmask(GM)) {
       // the other rows of the 32-entity block sit in lanes + 16, + 32, + 48: two lane swaps inside the vector unit
       // (v_permlane32_swap / v_permlane16_swap; __shfl_xor goes through the LDS pipe and its wait falls on the query-
@@ -157,7 +163,16 @@ __device__ __forceinline__ void sc3_value_tail(SC3<NP, TAIL, PD, GM>& S, const i
 #pragma unroll
         for (int i = 0; i < MB / 2; ++i) mask_row[lane * (MB / 2) + i] = make_uint4(S.mk[4 * i], S.mk[4 * i + 1], S.mk[4 * i + 2], S.mk[4 * i + 3]);
       }
-      if (lane == 0) S.summ_base[(mask_row - S.mask_base) / (64 * (MB / 2))] = which;
+      if (lane == 0) S.summ_base[(mask_row - S.mask_base) / (64 * (MB / 2) * sc3_planes(GM))] = which;
+    }
+    if constexpr (GM == SC3_GT) {
+      // the gt words of the row (block 0's were completed beside block 1's instructions and have not moved since): every lane,
+      // every row -- these bits are dense
+      if (store_ok) {
+#pragma unroll
+        for (int i = 0; i < MB / 2; ++i)
+          mask_row[64 * (MB / 2) + lane * (MB / 2) + i] = make_uint4(S.mg[4 * i], S.mg[4 * i + 1], S.mg[4 * i + 2], S.mg[4 * i + 3]);
+      }
     }
 #endif
   }
@@ -195,7 +210,7 @@ __device__ __forceinline__ void sc3_value(SC3<NP, TAIL, PD, GM>& S, const int la
       : "a"(S.acc[M][m2][b][j]), "v"(S.thi[b]), "v"(S.tlo[b])
       : "vcc");
 #endif
-  if constexpr (GM) {   // block maxima per (32 entities, query): the eight values of two consecutive 16-row blocks
+  if constexpr (sc3_maxima(GM)) {   // block maxima per (32 entities, query): the eight values of two consecutive 16-row blocks
     // two values per v_max3 (the kernel is bound by instruction issue: a v_max per value and the library fmaxf's quieting
     // moves were a fifth of the top-k launch), written as instructions because the values come out of an asm block
     if constexpr ((V & 1) == 0) {
@@ -236,7 +251,7 @@ __device__ __forceinline__ void sc3_piece2(SC3<NP, TAIL, PD, GM>& S, const float
 #ifndef COPER_DBG_SC3_NO_BAND
   asm volatile("v_cmp_ge_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(S.mk[w]) : "v"(sc), "v"(S.tlo[b]) : "vcc");
 #endif
-  if constexpr (GM) {
+  if constexpr (sc3_maxima(GM)) {
     if constexpr ((V & 1) == 0) S.px = sc;
     else if constexpr ((V & sc3_gmask(GM)) == 1) asm volatile("v_max_f32 %0, %1, %2" : "=v"(S.mx) : "v"(S.px), "v"(sc));
     else asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(S.mx) : "v"(S.px), "v"(sc));
@@ -305,7 +320,7 @@ __device__ __forceinline__ void sc3_region_asm(SC3<NP, TAIL, PD, GM>& S, const S
   float sc;
   typedef unsigned sc3_u4 __attribute__((ext_vector_type(4)));     // (a HIP uint4 is a struct: not a register operand)
 #define SC3_Q(x) (*(const sc3_u4*)&(x))
-  if constexpr (GM) {       // top-k launches: block maxima folded in (even values wait in S.px, odd ones fold the pair into S.mx)
+  if constexpr (sc3_maxima(GM)) {       // top-k launches: block maxima folded in (even values wait in S.px, odd ones fold the pair into S.mx)
     constexpr int vm = v0 & sc3_gmask(GM);
     static_assert(!(cnt == 3 && vm == sc3_gmask(GM)), "the maximum of a group is stored after the block: it must not hold the next group's first pair");
     if constexpr (GM == 2) {
@@ -427,7 +442,7 @@ __device__ __forceinline__ void sc3_region(SC3<NP, TAIL, PD, GM>& S, const SC3Pt
   constexpr int cw = TAIL == BX3_TAIL_HALF ? (int)SC3_HT_V0[R + 1] - (int)SC3_HT_V0[R] : c1 - c0;
   constexpr int cnt = v0 >= NV ? 0 : (v0 + cw > NV ? NV - v0 : cw);
 #if !defined(COPER_DBG_SC3_NO_EPI) && !defined(COPER_DBG_SC3_NO_BAND) && !defined(COPER_DBG_SC3_EPI_R0)
-  if constexpr (MB == 4 && s > 0 && cnt >= 1 && cnt <= 3 && (v0 >> 5) == ((v0 + cnt - 1) >> 5) && !(GM && cnt == 3 && (v0 & sc3_gmask(GM)) == sc3_gmask(GM))) {
+  if constexpr (MB == 4 && s > 0 && cnt >= 1 && cnt <= 3 && (v0 >> 5) == ((v0 + cnt - 1) >> 5) && !(sc3_maxima(GM) && cnt == 3 && (v0 & sc3_gmask(GM)) == sc3_gmask(GM))) {
     sc3_region_asm<NP, TAIL, PD, GM, M, s, b, sa, sl, rs, tail, half, v0, cnt>(S, X, lane, prev_valid, gm_row, gm_col, mask_row);
     SC3_FENCE();
     return;
@@ -491,7 +506,8 @@ __device__ unsigned long long g_sc3_clk[2 * 1024];
 
 // Ef3: the entities' f3 image; Hf3: the queries' (one 128-query tile = 8 column blocks = 16 NS KiB, copied to LDS as it lies);
 // tband[q] = {t_lo, t_hi}; mask: [tile][row][wave][lane] MB / 2 x 16 bytes (band bits of the 32 MB entities x 128 queries of a
-// wave's row), written only where a bit is set; summ: [tile][row][wave] 8 bytes: the lanes whose mask words were written
+// wave's row), written only where a bit is set; summ: [tile][row][wave] 8 bytes: the lanes whose mask words were written.
+// GM = SC3_GT: [tile][row][wave][plane][lane], plane 0 the band words as above, plane 1 the gt words, written by every lane
 template <int NP, int TAIL, int PD, int GM>
 __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __restrict__ Ef3, const float* __restrict__ bias_pad,
                                                                  const uint4* __restrict__ Hf3, const float2* __restrict__ tband,
@@ -556,7 +572,7 @@ __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __r
   const std::make_integer_sequence<int, NV> VSEQ{};
   constexpr int MB = SC3_MB;
   constexpr int64_t BLK_REGS = MB * RB;       // f3 registers of one entity block (MB 16-row blocks)
-  constexpr int64_t MW = 64 * (MB / 2);       // 16-byte mask pieces of one row of a wave
+  constexpr int64_t MW = 64 * (MB / 2) * sc3_planes(GM);       // 16-byte mask pieces of one row of a wave (SC3_GT: band words, then gt words)
 
   // (Round 4 tried carrying (tile, row) along instead of these four 64-bit divisions per row -- some 100 instructions of a wave
   // that issues one every four cycles: the two loop-carried values pushed the allocator into scratch (100 bytes, vmcnt(0) waits
@@ -633,14 +649,14 @@ __global__ __launch_bounds__(256, 1) void k_score_count3_bf16x3(const uint4* __r
     }
     uint4* mask_cur = mask + ((cur_tile * rows_per_tile + row) * 4 + wave) * MW;
     // block 0 (epilogue of the previous row's block 1 beside it: its last value completes that row's mask), then block 1
-    sc3_half<NP, TAIL, PD, GM, 0>(S, X, bias_pad, eb_next, lane, prev_valid, GM ? gmax + (eb_prev + 1) * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col,
+    sc3_half<NP, TAIL, PD, GM, 0>(S, X, bias_pad, eb_next, lane, prev_valid, sc3_maxima(GM) ? gmax + (eb_prev + 1) * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col,
                                   mask_cur - 4 * MW, SSEQ);
-    sc3_half<NP, TAIL, PD, GM, 1>(S, X, bias_pad, eb_next + 1, lane, true, GM ? gmax + eb * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col, mask_cur, SSEQ);
+    sc3_half<NP, TAIL, PD, GM, 1>(S, X, bias_pad, eb_next + 1, lane, true, sc3_maxima(GM) ? gmax + eb * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col, mask_cur, SSEQ);
     eb_prev = eb;
     prev_valid = true;
     if (last_of_tile) {
       // drain: block 1's accumulators have no next row of the same tile to hide behind
-      sc3_values<NP, TAIL, PD, GM, 1, 0>(S, lane, true, GM ? gmax + (eb + 1) * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col, mask_cur, VSEQ);
+      sc3_values<NP, TAIL, PD, GM, 1, 0>(S, lane, true, sc3_maxima(GM) ? gmax + (eb + 1) * sc3_gm_rows(GM) * gm_stride : nullptr, gm_col, mask_cur, VSEQ);
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -954,7 +970,8 @@ __device__ __forceinline__ void band_audit_group(const BandArgs& A, const unsign
 // units give ~90 (one walk) and 290 workgroups instead of 73
 constexpr int BE_CAP = 4096, BE_ITEMS = 2048, BE_UPW = COPER_BE_UPW;
 constexpr int BE_AUDIT = 128;     // pairs of a round the audit re-scores, 32 per wave (a workgroup walks ~90 at FB15k-237 shapes: all of them)
-template <int CB = COPER_CHAIN_CB>
+// PL: planes per row of a wave in `mask` (sc3_planes: 2 behind a count launch that stored its gt words beside the band words)
+template <int CB = COPER_CHAIN_CB, int PL = 1>
 __device__ __forceinline__ void band_exact_body(const uint4* __restrict__ mask, const unsigned long long* __restrict__ summ, const int64_t n_units,
                                                 const unsigned rows4 /* rows per tile x 4 waves */, const BandArgs& A, const int64_t wg) {
   constexpr int MB = SC3_MB, NW = 2 * MB;      // 32-bit mask words per lane and row of a wave
@@ -996,7 +1013,7 @@ __device__ __forceinline__ void band_exact_body(const uint4* __restrict__ mask, 
       eb = ((unsigned)unit - tile * rows4) * 2;       // (row * 4 + wave) * 2: the wave's first entity block (16 MB rows each)
 #pragma unroll
       for (int i = 0; i < MB / 2; ++i) {
-        const uint4 w = mask[(unit * 64 + l) * (MB / 2) + i];
+        const uint4 w = mask[(unit * (64 * PL) + l) * (MB / 2) + i];
         wc[4 * i] = w.x; wc[4 * i + 1] = w.y; wc[4 * i + 2] = w.z; wc[4 * i + 3] = w.w;
       }
     }
@@ -1062,7 +1079,7 @@ __device__ __forceinline__ void band_exact_body(const uint4* __restrict__ mask, 
       const int l = __builtin_ctzll(lanes);
       lanes &= lanes - 1;
       for (int i = 0; i < MB / 2; ++i) {
-        const uint4 w = mask[(unit * 64 + l) * (MB / 2) + i];
+        const uint4 w = mask[(unit * (64 * PL) + l) * (MB / 2) + i];
         const unsigned ww[4] = {w.x, w.y, w.z, w.w};
         for (int cc = 0; cc < 4; ++cc) {
           unsigned bits = ww[cc];
@@ -1152,6 +1169,114 @@ __global__ __launch_bounds__(256) void k_band_excess_bf16x3(const uint4* __restr
   else filter_excess_body<KS>(F, (int)blockIdx.x - n_band, (int)gridDim.x - n_band, s_e_all);
 }
 
+// The look-up role of the band launch behind a count launch that stored its gt plane (SC3_GT): the filter correction without a
+// second score.  For every CSR entry (q, f) of the launch's queries that the dense mask of metrics.py:40-46 changes -- tl_prep's
+// rule (kernels_tail_bf16.hip): not equal to its predecessor in the row, not the target, inside [0, n_local) -- the count kernel has
+// compared logit(q, f) with t_hi and counted it into ranks[q] when it was above; that comparison is one bit of the gt plane, at the
+// place band_exact_body decodes the band bits from: tile q / 128, row of a wave f / (32 MB), lane 16 ((f / 4) & 3) + (q & 15),
+// value V = 4 MB ((q & 127) / 16) + 4 ((f / 16) & (MB - 1)) + (f & 3) of block M = (f / (16 MB)) & 1: word MB M + (V >> 5), bit
+// 31 - (V & 31).  Set bits are taken back from ranks[q].  Entries inside the band are not gt: the band walk passes them over as
+// known answers, as it always did.  A wave owns BL_QW consecutive queries -- their entries are contiguous, 64 per round, each lane
+// finds its entry's query by binary lifting over the first entries the lanes hold -- and every run of one query subtracts once.
+// Long rows (real KGs hold (e1, rel) pairs with thousands of known tails: the reason for the excess role above): a wave takes back
+// the first BL_OWN entries of its 16 queries itself; what lies beyond is dealt, 64 entries at a time, over ALL waves of the role.
+// No list and no hand-over between workgroups: every wave reads the first entry of every 16-query range of the launch (one indptr
+// word in 16: 1,281 words at 20,480 queries, independent loads) and finds the long ranges itself; tile t of the excess of range r
+// belongs to wave (t + 61 r) mod G, as the excess role deals its tiles.
+constexpr int BL_QW = 16;
+constexpr int64_t BL_OWN = 256;
+// one round: entries [pb, min(pb + 64, p_lim)) of the range whose queries start at qw0 (lane j < nq: my_lo = the first entry of
+// query qw0 + j, my_e2 its target; lanes beyond: my_lo = the range's end)
+template <int PL>
+__device__ __forceinline__ void band_lookup_round(const unsigned* __restrict__ words, const unsigned rows4, const BandArgs& A, const int64_t qw0,
+                                                  const int64_t my_lo, const int64_t my_e2, const int64_t pb, const int64_t p_lim, const int lane) {
+  constexpr int MB = SC3_MB;
+  static_assert(MB == 4, "the bit address below is written for 64-entity blocks");
+  const int64_t p = pb + lane;
+  const bool valid = p < p_lim;
+  int qi = 0;                                                         // the last j with first entry <= p
+#pragma unroll
+  for (int step = BL_QW / 2; step >= 1; step >>= 1) {
+    const int64_t first = __shfl(my_lo, qi + step);
+    qi = (valid && first <= p) ? qi + step : qi;
+  }
+  const int64_t qfirst = __shfl(my_lo, qi), qe2 = __shfl(my_e2, qi);
+  bool hit = false;
+  if (valid) {
+    const int64_t f = A.idx[p];
+    const int64_t f_prev = p > qfirst ? A.idx[p - 1] : -1;
+    if (f != f_prev && f != qe2 && f >= 0 && f < A.n_local) {
+      const unsigned q = (unsigned)(qw0 + qi), blk = (unsigned)(f >> 6), r = (unsigned)f & 63u;
+      const int64_t unit = (int64_t)(q >> 7) * rows4 + (blk >> 1);
+      const unsigned l = 16u * ((r >> 2) & 3u) + (q & 15u);
+      const unsigned V = 4u * MB * ((q & 127u) >> 4) + 4u * (r >> 4) + (r & 3u);
+      const unsigned w = words[((unit * PL + 1) * 64 + l) * (2 * MB) + MB * (blk & 1u) + (V >> 5)];
+      hit = (w >> (31u - (V & 31u))) & 1u;
+    }
+  }
+  const int q_prev = __shfl_up(qi, 1);
+  const bool head = valid && (lane == 0 || q_prev != qi);
+  const unsigned long long heads = __ballot(head), hits = __ballot(hit);
+  if (head) {
+    const unsigned long long later = lane < 63 ? heads >> (lane + 1) : 0ull;
+    const int end = later ? lane + 1 + __builtin_ctzll(later) : 64;
+    const unsigned long long run = (end >= 64 ? ~0ull : (1ull << end) - 1ull) & ~((1ull << lane) - 1ull);
+    const int c = __builtin_popcountll(hits & run);
+    if (c) atomicSub(&A.ng[qw0 + qi], c);
+  }
+}
+
+template <int PL>
+__device__ __forceinline__ void band_lookup_body(const unsigned* __restrict__ words, const unsigned rows4, const BandArgs& A, const int64_t wg,
+                                                 const int64_t n_wg) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t me = wg * 4 + wave, G = n_wg * 4;
+  // ---- the wave's own 16 queries: the first BL_OWN of their entries
+  const int64_t qw0 = me * BL_QW;
+  if (qw0 < A.Bc) {
+    const int64_t qw1 = qw0 + BL_QW < A.Bc ? qw0 + BL_QW : A.Bc;
+    const int nq = (int)(qw1 - qw0);
+    const int64_t p_end = A.indptr[qw1];
+    const int64_t my_lo = lane < nq ? A.indptr[qw0 + lane] : p_end;
+    const int64_t my_e2 = lane < nq ? A.e2[qw0 + lane] : -1;
+    const int64_t p_begin = __shfl(my_lo, 0);
+    const int64_t p_lim = p_end - p_begin > BL_OWN ? p_begin + BL_OWN : p_end;
+    for (int64_t pb = p_begin; pb < p_lim; pb += 64)                  // (wave-uniform)
+      band_lookup_round<PL>(words, rows4, A, qw0, my_lo, my_e2, pb, p_lim, lane);
+  }
+  // ---- the excess of long ranges, found by every wave for itself
+  const int64_t n_ranges = (A.Bc + BL_QW - 1) / BL_QW;
+  for (int64_t r0 = 0; r0 < n_ranges; r0 += 64) {
+    const int64_t r = r0 + lane;
+    bool is_long = false;
+    if (r < n_ranges) {
+      const int64_t qa = r * BL_QW, qb = qa + BL_QW < A.Bc ? qa + BL_QW : A.Bc;
+      is_long = A.indptr[qb] - A.indptr[qa] > BL_OWN;
+    }
+    unsigned long long longs = __ballot(is_long);
+    while (longs) {                                                   // (wave-uniform)
+      const int64_t rr = r0 + __builtin_ctzll(longs);
+      longs &= longs - 1;
+      const int64_t qa = rr * BL_QW, qb = qa + BL_QW < A.Bc ? qa + BL_QW : A.Bc;
+      const int nq = (int)(qb - qa);
+      const int64_t p_end = A.indptr[qb];
+      const int64_t my_lo = lane < nq ? A.indptr[qa + lane] : p_end;
+      const int64_t my_e2 = lane < nq ? A.e2[qa + lane] : -1;
+      const int64_t p0 = __shfl(my_lo, 0) + BL_OWN;
+      const int64_t t0 = ((me - 61 * rr) % G + G) % G;
+      for (int64_t pb = p0 + 64 * t0; pb < p_end; pb += 64 * G)
+        band_lookup_round<PL>(words, rows4, A, qa, my_lo, my_e2, pb, p_end, lane);
+    }
+  }
+}
+
+// the band walk of a count launch that stored its gt plane, with the look-up role in further workgroups of the same launch
+__global__ __launch_bounds__(256) void k_band_lookup_bf16x3(const uint4* __restrict__ mask, const unsigned long long* __restrict__ summ,
+                                                            int64_t n_units, unsigned rows4, BandArgs A, int n_band) {
+  if ((int)blockIdx.x < n_band) band_exact_body<COPER_CHAIN_CB, sc3_planes(SC3_GT)>(mask, summ, n_units, rows4, A, blockIdx.x);
+  else band_lookup_body<sc3_planes(SC3_GT)>((const unsigned*)mask, rows4, A, (int64_t)blockIdx.x - n_band, (int64_t)gridDim.x - n_band);
+}
+
 static FilterArgs filter_args(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
                               const float2* tband, int64_t B, int32_t* ranks) {
   FilterArgs F;
@@ -1228,16 +1353,23 @@ static int sc3_go(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* g
   }
   hipLaunchKernelGGL((k_score_count3_bf16x3<NP, TAIL, PD, GM>), dim3((unsigned)grid), dim3(256), lds, s, (const uint4*)h->Ef3, h->bias_pad, hf3,
                      (const float2*)h->tband_ws + q0, Bc, rows_per_tile, total_rows, ng + q0, (uint4*)h->mask_ws,
-                     (unsigned long long*)((char*)h->mask_ws + score_count3_mask_words_bytes(h, Bc)), gmax, gm_stride, rows_per_item,
+                     (unsigned long long*)((char*)h->mask_ws + sc3_planes(GM) * score_count3_mask_words_bytes(h, Bc)), gmax, gm_stride, rows_per_item,
                      h->x3s);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
 
+// gt: the launch stores its gt plane (SC3_GT; ranks-only launches of the shapes the fused tail serves)
 template <int NP, int TAIL>
-static int sc3_gm(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, hipStream_t s) {
+static int sc3_gm(coper_handle* h, int64_t q0, int64_t Bc, int32_t* ng, float* gmax, int64_t gm_stride, bool gt, hipStream_t s) {
   if constexpr (TAIL == BX3_TAIL_FULL && bx3_half_instantiated(2 * NP + 1)) {     // the handle's tail kind (Dims::x3_tail) picks the form
-    if (h->dm.x3_tail == BX3_TAIL_HALF) return sc3_gm<NP, BX3_TAIL_HALF>(h, q0, Bc, ng, gmax, gm_stride, s);
+    if (h->dm.x3_tail == BX3_TAIL_HALF) return sc3_gm<NP, BX3_TAIL_HALF>(h, q0, Bc, ng, gmax, gm_stride, gt, s);
+  }
+  if (gt) {
+    if constexpr (SC3_MB == 4 && (2 * NP + (TAIL ? 1 : 0) == 13 || 2 * NP + (TAIL ? 1 : 0) == 16)) {
+      if (!gmax) return sc3_go<NP, TAIL, SC3_GT>(h, q0, Bc, ng, gmax, gm_stride, s);
+    }
+    return fail(h, COPER_ESTATE, "score_count3: no count kernel of this shape stores the gt plane");
   }
   if (!gmax) return sc3_go<NP, TAIL, 0>(h, q0, Bc, ng, gmax, gm_stride, s);
   if constexpr (SC3_MB == 4 && (2 * NP + (TAIL ? 1 : 0) == 13 || 2 * NP + (TAIL ? 1 : 0) == 16)) {     // (64-entity maxima: topk_expand, coper_internal.h)
@@ -1261,12 +1393,14 @@ size_t score_count3_mask_bytes(const coper_handle* h, int64_t Bc) {
 int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t Bc, const float* hvec, const float* tgt_x, const int64_t* e2,
                               const int64_t* indptr, const int64_t* idx, int32_t* ng, int32_t* ne, float* gmax, int64_t gm_stride,
                               hipStream_t s) {
-  if (score_count3_mask_bytes(h, Bc) > h->mask_ws.size()) return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
+  const bool gt = ctx.gt_bits;       // the fused tail left the filter correction to the look-up role: the count launch stores its gt plane
+  if (score_count3_mask_bytes(h, Bc) + (gt ? score_count3_mask_words_bytes(h, Bc) : 0) > h->mask_ws.size())
+    return fail(h, COPER_ESTATE, "score_count3: band mask workspace not reserved");
   int rc;
   {
     ScopedKernelTimer t(h, "score_count", s);
     switch (h->dm.KS16) {
-#define SC3_CASE(KS_) case KS_: rc = sc3_gm<(KS_) / 2, (KS_) & 1>(h, q0, Bc, ng, gmax, gm_stride, s); break;
+#define SC3_CASE(KS_) case KS_: rc = sc3_gm<(KS_) / 2, (KS_) & 1>(h, q0, Bc, ng, gmax, gm_stride, gt, s); break;
       SC3_CASE(1) SC3_CASE(2) SC3_CASE(3) SC3_CASE(4) SC3_CASE(5) SC3_CASE(6) SC3_CASE(7) SC3_CASE(8) SC3_CASE(9) SC3_CASE(10)
       SC3_CASE(11) SC3_CASE(12) SC3_CASE(13) SC3_CASE(14) SC3_CASE(15) SC3_CASE(16) SC3_CASE(17) SC3_CASE(18) SC3_CASE(19) SC3_CASE(20)
 #undef SC3_CASE
@@ -1308,8 +1442,13 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
     const int64_t n_units = sc3_units(h, Bc);
     if (rows_per_tile * 4 > 0x7fffffffLL || n_units > 0x7fffffffLL) return fail(h, COPER_EUNSUPPORTED, "band mask beyond 2^31 units");
     const unsigned n_band = (unsigned)((n_units + BE_UPW - 1) / BE_UPW);
-    const unsigned long long* summ = (const unsigned long long*)((const char*)h->mask_ws + score_count3_mask_words_bytes(h, Bc));
-    if (ctx.excess_pending) {
+    const unsigned long long* summ = (const unsigned long long*)((const char*)h->mask_ws + (gt ? 2 : 1) * score_count3_mask_words_bytes(h, Bc));
+    if (gt) {
+      const unsigned n_look = (unsigned)((Bc + 4 * BL_QW - 1) / (4 * BL_QW));
+      if (h->profile) h->timers["band_lookup"].launches += 1;     // (coper_profile_read("band_lookup"): how many band launches carried the role; no time of its own)
+      hipLaunchKernelGGL(k_band_lookup_bf16x3, dim3(n_band + n_look), dim3(256), 0, s, (const uint4*)h->mask_ws, summ, n_units,
+                         (unsigned)(rows_per_tile * 4), A, (int)n_band);
+    } else if (ctx.excess_pending) {
       ctx.excess_pending = false;
       if (h->dm.KS16 == 13)
         hipLaunchKernelGGL(k_band_excess_bf16x3<13>, dim3(n_band + FX_GRID), dim3(256), 0, s, (const uint4*)h->mask_ws, summ, n_units,
@@ -1344,7 +1483,7 @@ int score_count3_maxima_bf16x3(coper_handle* h, int64_t q0, int64_t Bc, int32_t*
   int rc;
   ScopedKernelTimer t(h, "predict_maxima", s);
   switch (h->dm.KS16) {
-#define SC3_CASE(KS_) case KS_: rc = sc3_gm<(KS_) / 2, (KS_) & 1>(h, q0, Bc, ng, gmax, gm_stride, s); break;
+#define SC3_CASE(KS_) case KS_: rc = sc3_gm<(KS_) / 2, (KS_) & 1>(h, q0, Bc, ng, gmax, gm_stride, false, s); break;
     SC3_CASE(1) SC3_CASE(2) SC3_CASE(3) SC3_CASE(4) SC3_CASE(5) SC3_CASE(6) SC3_CASE(7) SC3_CASE(8) SC3_CASE(9) SC3_CASE(10)
     SC3_CASE(11) SC3_CASE(12) SC3_CASE(13) SC3_CASE(14) SC3_CASE(15) SC3_CASE(16) SC3_CASE(17) SC3_CASE(18) SC3_CASE(19) SC3_CASE(20)
 #undef SC3_CASE

@@ -196,6 +196,9 @@ __device__ __forceinline__ float tl_entry_score(const f32x16& acc, const int qi,
   return sc;
 }
 
+// (Steps 0 - 2 have a TWIN: k_finalize_targets_bf16x3 below repeats them statement by statement, without the filter waves.  An
+// edit to the fragments, the targets or the band here has to be made there too; tests/test_gpu_filter_bits.py compares the two
+// kernels' ranks.  One body with a compile-time switch compiled THIS kernel to another schedule, so they are two functions.)
 template <int KS>
 __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_targets_filter_bf16x3(
     int64_t B, int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3,
@@ -367,6 +370,111 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
   TL_STAMP(5);
 }
 
+// k_finalize_targets_bf16x3 -- the kernel above without its step 3, for passes that take their filter correction from the count
+// kernel's own compare bits (filter_bits_supported below; kernels_score3_bf16.hip: SC3_GT and the look-up role of the band launch):
+// fragments and targets only.  No CSR entry is read, no filter tile scored, no block listed as heavy; ranks are preset to 1 (or the
+// stale value) and the look-up role takes the known answers above the band back.  Steps 1 and 2 are the statements of the kernel
+// above -- the same fragments, targets and bands, bit for bit.  (The same workgroup shape: three of the four waves only build
+// fragments now, which is most of what the launch still does.)
+template <int KS>
+__global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_targets_bf16x3(
+    int64_t B, int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3,
+    const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo, const float* __restrict__ bias_pad, int64_t n_local,
+    const int64_t* __restrict__ e2, float* __restrict__ tgt, float kappa, const unsigned* __restrict__ band_consts,
+    const float* __restrict__ x3m, int ent_exp, int32_t* __restrict__ x3s, float2* __restrict__ tband, int32_t* __restrict__ ranks,
+    const int32_t* __restrict__ stale, int32_t* __restrict__ stale_count) {
+  __shared__ uint4 s_bh[KS][64], s_bl[KS][64];   // the block's B-operand fragments (hi / lo)
+  __shared__ int64_t s_e[32];
+  __shared__ float s_n2[TL_WAVES][32];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
+  const int64_t blk = blockIdx.x, q0 = blk * 32, q = q0 + i;
+  const bool live = q < B;
+  const int tail_kind = bx3_tail_kind(d, KS);
+  const bool half_tail = tail_kind == BX3_TAIL_HALF;
+  TL_STAMP(0);
+  // ---- 0. wave 0 requests the target rows (pair i = (query i, e2[query i]): the diagonal of its tile) before the fragments exist
+  const int64_t my_e2 = live ? e2[q] : -1;
+  int64_t erow = my_e2;
+  if (erow < 0 || erow >= n_local) erow = -1;
+  uint4 ah[KS + 1], al[KS + 1];
+  if (wave == 0) {
+    if (half == 0) s_e[i] = erow;
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+    tl_gather<KS>(Ehi, Elo, erow, half, ah, al);
+  }
+  // ---- 1. the block's fragments: wave w takes k-steps w, w + 4, ...
+  static_assert(TL_WAVES == 4, "x3_batch_exp: 256 threads");
+  int eh, sexp;
+  int32_t x3l[2];
+  {
+    const bool vec_ok = (d & 3) == 0 && (((uintptr_t)h_rows) & 15) == 0;
+    constexpr int NKW = (KS + TL_WAVES - 1) / TL_WAVES;      // k-steps of a wave
+    float yv[NKW][8];
+#pragma unroll
+    for (int u = 0; u < NKW; ++u) {
+      const int ks = wave + TL_WAVES * u;
+      const int k0 = 16 * ks + 8 * half;
+      if (ks < KS) {
+        if (live && k0 + 8 <= d && vec_ok) {
+          const float4 a = *(const float4*)(h_rows + q * d + k0), b = *(const float4*)(h_rows + q * d + k0 + 4);
+          yv[u][0] = a.x; yv[u][1] = a.y; yv[u][2] = a.z; yv[u][3] = a.w; yv[u][4] = b.x; yv[u][5] = b.y; yv[u][6] = b.z; yv[u][7] = b.w;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) yv[u][c] = (live && k0 + c < d) ? h_rows[q * d + k0 + c] : 0.f;
+        }
+      }
+    }
+    eh = x3_batch_exp(x3m, ent_exp, x3s, &s_n2[0][0]); sexp = eh + ent_exp; x3l[0] = eh; x3l[1] = sexp;
+    __syncthreads();                        // (s_n2 served as the reduction's scratch)
+    float n2 = 0.f;
+#pragma unroll
+    for (int u = 0; u < NKW; ++u) {
+      const int ks = wave + TL_WAVES * u;
+      if (ks < KS) {
+        float y[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { n2 = fmaf(yv[u][c], yv[u][c], n2); y[c] = x3_scale(yv[u][c], eh); }
+        uint4 h4, l4;
+        split8_bf16(y, h4, l4);
+        f3_store_piece(hf3, KS, tail_kind, q, ks, half, h4, l4, true);   // rows past B: zero pieces (the count kernel's tile is whole)
+        s_bh[ks][lane] = h4;
+        s_bl[ks][lane] = l4;
+      }
+    }
+    n2 += __shfl_xor(n2, 32);
+    if (half == 0) s_n2[wave][i] = n2;
+  }
+  TL_STAMP(1);
+  __syncthreads();
+  TL_STAMP(2);
+  // ---- 2. the targets: the diagonal of wave 0's tile against the fragments in LDS; tau_q and the band
+  if (wave == 0) {
+    const f32x16 acc = tl_mma<KS>(bias_pad, s_e, ah, al, s_bh, s_bl, lane, half, sexp, half_tail);
+    // D[i][i] sits in lane i + 32 * ((i >> 2) & 1), register (i & 3) + 4 * (i >> 3)
+    float diag = 0.f;
+    const int reg = (i & 3) + 4 * (i >> 3);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) diag = (r == reg) ? acc[r] : diag;
+    float t0 = __shfl(diag, i + 32 * ((i >> 2) & 1));   // lane i (both halves): the target of query i
+    t0 = erow >= 0 ? t0 : 0.f;
+    if (half == 0) {
+      float n2 = 0.f;
+#pragma unroll
+      for (int w2 = 0; w2 < TL_WAVES; ++w2) n2 += s_n2[w2][i];
+      const float tau = x3_scale(x3_band_tau(n2, kappa, band_consts, d, x3l), sexp);
+      if (live) { tgt[q] = x3_scale(t0, -sexp); tband[q] = make_float2(t0 - tau, t0 + tau); }
+    }
+  }
+  TL_STAMP(3);
+  TL_STAMP(4);
+  // (a stale pass: as above -- what the count launch adds and the look-up role subtracts keeps COPER_RANK_STALE negative)
+  const bool is_stale = stale != nullptr && *stale != 0;
+  if (wave == 0 && half == 0 && live) ranks[q] = is_stale ? COPER_RANK_STALE : 1;
+  if (is_stale && blk == 0 && threadIdx.x == 0) atomicAdd(stale_count, 1);
+  TL_STAMP(5);
+}
+
 #ifdef COPER_DBG_TL_CLOCK
 extern "C" __attribute__((visibility("default"))) int coper_dbg_tl_clock(int n_wg, double* out /* [TL_NSTAMP] medians, us from the earliest start */) {
   static unsigned long long hbuf[TL_NSTAMP * 1024];
@@ -390,6 +498,34 @@ bool tail_fused_supported(const coper_handle* h) {
   static const bool off = getenv("COPER_TAIL_UNFUSED") != nullptr;   // A/B switch, read once
   if (off) return false;
   return (h->dm.KS16 == 13 || h->dm.KS16 == 16) && h->dm.n_local == h->dm.E;   // (the resident fragments: KS16 registers x 2 per lane)
+}
+
+bool filter_bits_supported(const coper_handle* h, int64_t B) {
+  static const bool off = getenv("COPER_FILTER_BITS_OFF") != nullptr;   // A/B switch, read once
+  if (off || !tail_fused_supported(h)) return false;
+#ifdef COPER_DBG_SC3_NO_BAND
+  return false;        // (that build runs no band launch: nothing would carry the look-up role)
+#endif
+  // tables from 500,000 rows on keep their own band kernel (k_band_exact<COPER_BAND_CB_LARGE>) and today's path
+  if (h->dm.n_local >= 500000) return false;
+  return score_count3_mask_words_bytes(h, topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats)) <= FILTER_BITS_PLANE_CAP;
+}
+
+size_t rank_mask_bytes(const coper_handle* h, int64_t B) {
+  // the longest count launch any path issues: the mask has the size of the block maxima of the pruned top-k (one bit per logit
+  // against one float per 32), so both are cut into the same chunks of queries
+  const int64_t qc = topk_chunk_queries(h->dm.n_eblk, B, h->gmax_max_floats);
+  size_t need = score_count3_mask_bytes(h, qc);
+  // The predicate is not monotone in B (a larger batch can leave the cap), and a reservation for B covers every smaller pass: so
+  // the gt plane is sized for the longest launch of ANY pass of up to B queries that takes the path -- the largest chunk within
+  // the cap.  One workspace serves every ranking entry point of the handle (coper_rank and n_equal passes never read the plane):
+  // sized once here, no pass grows it behind a coper_reserve.  Handles the path never serves reserve what they did.
+  if (filter_bits_supported(h, 1)) {
+    int64_t qg = (int64_t)(FILTER_BITS_PLANE_CAP / score_count3_mask_words_bytes(h, X3_TILE_Q)) * X3_TILE_Q;
+    if (qg > qc) qg = qc;
+    if (qg > 0) need = std::max(need, score_count3_mask_bytes(h, qg) + score_count3_mask_words_bytes(h, qg));
+  }
+  return need;
 }
 
 // (Tried in round 3: the filter tiles moved out of this launch into extra workgroups of the band launch that follows the count
@@ -417,6 +553,22 @@ int launch_finalize_targets_filter_bf16x3(coper_handle* h, PassCtx& ctx, int64_t
   if (rc0) return rc0;
   const int64_t rows_pad = (B + 127) / 128 * 128;
   const unsigned grid = (unsigned)(rows_pad / 32);
+  if (filter_bits_supported(h, B)) {
+    // the filter correction comes from the gt plane of the pass's count launches: their band launches carry the look-up role
+#define TL_GO(KS_)                                                                                                                 \
+  hipLaunchKernelGGL(k_finalize_targets_bf16x3<KS_>, dim3(grid), dim3(64 * TL_WAVES), 0, s, B, dm.d, (const float*)h_out,           \
+                     (uint4*)h->hf3_ws, (const uint4*)h->Erm16_hi, (const uint4*)h->Erm16_lo, h->bias_pad, dm.n_local, e2, tgt,     \
+                     band_kappa(h), h->band_consts, h->grouping().x3m, h->x3_ent_exp, h->x3s, (float2*)h->tband_ws, ranks,          \
+                     ctx.chk ? (const int32_t*)(ctx.chk + GROUP_CHK_STALE) : nullptr, h->group_done() + 2)
+    if (dm.KS16 == 13) { TL_GO(13); } else { TL_GO(16); }
+#undef TL_GO
+    COPER_HIP_TRY(h, hipGetLastError());
+    ctx.cnt = ranks;
+    ctx.preset = true;
+    ctx.gt_bits = true;
+    ctx.excess_pending = false;
+    return COPER_OK;
+  }
 #define TL_GO(KS_)                                                                                                                 \
   hipLaunchKernelGGL(k_finalize_targets_filter_bf16x3<KS_>, dim3(grid), dim3(64 * TL_WAVES), 0, s, B, dm.d, (const float*)h_out,   \
                      (uint4*)h->hf3_ws, (const uint4*)h->Erm16_hi, (const uint4*)h->Erm16_lo,                                       \
