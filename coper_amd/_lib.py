@@ -57,7 +57,7 @@ class coper_train_config(C.Structure):
                 ("epsilon", C.c_float), ("clip_norm", C.c_float), ("label_smoothing_epsilon", C.c_float),
                 ("hidden_dropout", C.c_float), ("output_dropout", C.c_float), ("batch_norm_momentum", C.c_float),
                 ("batch_norm_train_stats", C.c_int32), ("seed", C.c_uint32), ("context_rel_dropout", C.c_float),
-                ("reserved", C.c_int32 * 7)]
+                ("one_vs_all_chunk", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 # name -> (restype, argtypes): every symbol include/coper_hip.h declares
@@ -114,6 +114,8 @@ PROTOTYPES = {
     "coper_train_init": (C.c_int, [_P, C.POINTER(coper_train_config)]),
     "coper_train_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "coper_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "coper_train_step_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "coper_train_forward_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "coper_train_grad": (C.c_int, [_P, C.c_char_p, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_double), _P]),
     "coper_train_slot": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, _I64, C.c_int32, C.POINTER(_I64), _P]),
     "coper_train_powers": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I64), C.POINTER(C.c_double),

@@ -12,7 +12,8 @@
 //            models.py:70,412 is never formed; g_lookup: one pass over the looked-up [F,d] rows  (k_tr_lookup_*)
 //     + dense bias, dropout, FCBN, ReLU -> h [B, d]                                   k_tr_fc_post(_slices), k_tr_fcbn_fwd
 //     sampled scorer s[b,l] = h[b] . ent_emb[lookup[b,l]] + pred_bias[...] and the loss: k_tr_score_loss_dh (round 6: with ds and
-//     dh = sum_l ds E[lookup] from the same pass over the gathered rows; k_tr_score_loss where d % 4 != 0) or 1-vs-all (GEMM)
+//     dh = sum_l ds E[lookup] from the same pass over the gathered rows; k_tr_score_loss where d % 4 != 0) or 1-vs-all (GEMM; from sparse labels
+//     in chunks of entity columns, forward and backward per chunk: Step::score_csr)
 //   backward: the transposes of the above (dense: dP[rho] = x^T (ctx[:,rho] . dz) batched, dA = dz P2^T one GEMM, then
 //   the contraction with ctx / x); embedding-row gradients by float atomics or, when B*|E| is small, through a dense
 //   d(loss)/d(logits) matrix and one GEMM.  Every GEMM is the split-fp16 MFMA kernel of train_gemm_bf16.hip (no library).
@@ -143,6 +144,7 @@ struct TrainState {
   PlaneSet mmX2, mmY2;               // tg_matmul's operand planes on the side stream (TrainState::side[0])
   DevBuf<float> mmP;
   DevBuf<float> z0, z1, hv, dh, dz, ds, dx, dc;
+  DevBuf<float> dhc;         // [B, d] a later chunk's share of dh (the 1-vs-all step from sparse labels, Step::score_csr)
   DevBuf<double> red;        // the reduction scratch in double (RedLayout)
   DevBuf<float> bnst;        // [BN_ROWS][mx]: Conv1BN's and FCBN's statistics of the forward pass (BnRow)
   int mx = 0;                // the widest BN layer: both are sized by it
@@ -324,6 +326,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   if (!(cfg->learning_rate > 0) || cfg->hidden_dropout < 0 || cfg->hidden_dropout >= 1 || cfg->output_dropout < 0 ||
       cfg->output_dropout >= 1)
     return fail(h, COPER_EINVAL, "coper_train_init: bad hyper-parameter");
+  if (cfg->one_vs_all_chunk < 0) return fail(h, COPER_EINVAL, "coper_train_init: one_vs_all_chunk is negative");
   for (const Leaf& lf : h->leaves)
     if (!lf.set) return fail(h, COPER_EINVAL, "coper_train_init: parameter not set: " + lf.name);
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -386,6 +389,20 @@ namespace {
 
 inline dim3 grid1d(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// 1-vs-all labels as id lists (include/coper_hip.h, coper_train_step_csr); indptr == nullptr: the dense-label call
+struct CsrLabels {
+  const int64_t *indptr = nullptr, *idx = nullptr, *row = nullptr;
+  int64_t n_rows = 0;
+};
+constexpr int64_t TR_OVA_GRAIN = 128;                            // a chunk of entity columns is rows of a GEMM operand plane: TG_ROW_PAD
+constexpr int64_t TR_OVA_WS_BYTES = 256LL * 1024 * 1024;         // the [B, chunk] logits of the library's own choice (as coper_rank_counts')
+// entity columns per chunk of the sparse-label step: the request rounded up to the grain, or the widest multiple of it within the bound
+inline int64_t ova_chunk(int64_t B, int64_t E, int32_t request) {
+  int64_t c = request > 0 ? (request + TR_OVA_GRAIN - 1) / TR_OVA_GRAIN * TR_OVA_GRAIN : TR_OVA_WS_BYTES / 4 / B / TR_OVA_GRAIN * TR_OVA_GRAIN;
+  if (c < TR_OVA_GRAIN) c = TR_OVA_GRAIN;
+  return c < E ? c : E;
+}
+
 // the side streams (TrainState::side): fork(i, k) lets side[k] start behind everything queued on s so far, join(i) lets s go on
 // behind what side[k] was given since.  Whatever leaves the step early joins what it forked.
 struct SideJoin {
@@ -416,6 +433,7 @@ struct Step {
   const int64_t *const e1, *const rel; const int32_t* const lookup; const float* const labels; const int64_t B, L;
   float *const loss_out, *const pred_out, *const h_out;
   const int apply;                  // 0: coper_train_forward
+  const CsrLabels csr;              // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
   const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
   const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
   const bool cat = dm.concat_rel, two_streams = T->side[0] != nullptr;
@@ -690,6 +708,56 @@ struct Step {
     if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)nBd, hipMemcpyDeviceToDevice, s));
     return COPER_OK;
   }
+  // The 1-vs-all scorer from sparse labels, forward AND backward, in chunks of entity columns [c0, c0 + w): the scorer is separable by
+  // column, so per chunk S_c = h E_c^T, the loss kernel (labels from membership in the row's id list; S_c becomes d(loss)/d(logits)),
+  // dbias[c0 : c0 + w] = column sums, dE[c0 : c0 + w] = S_c^T h, and the chunk's share of dh = S_c E_c -- the first chunk's into dh, a
+  // later one's into dhc and added behind it, in chunk order.  Neither the labels nor the logits exist as [B, |E|].  One chunk: the
+  // launches of fwd_score_loss + bwd_scorer with k_tr_csr_loss for k_tr_dense_loss.
+  // Operand exponents: h keeps one power of two for the whole step (one tensor: tg_matmul's cache); a chunk of the table and a chunk
+  // of S get their own -- per CHUNK, not per tensor: a chunk is packed when it is used, nothing scans the whole table first, and a
+  // chunk's own maximum wastes no bits on a larger row elsewhere.  Their cache words are handed back behind every chunk.
+  int score_csr() {
+    int rc;
+    float* const ent = lv.ent_emb->p;
+    const float* const pred_bias = lv.pred_bias->p;
+    float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
+    const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
+    const int64_t E = dm.E, cw = ova_chunk(B, E, tc.one_vs_all_chunk);
+    if ((size_t)(B * cw) > T->Sd.size() || (apply && cw < E && (size_t)nBd > T->dhc.size())) {
+      COPER_HIP_TRY(h, hipStreamSynchronize(s));
+      if ((rc = T->Sd.ensure(h, (size_t)(B * cw), "training workspace")) || (apply && cw < E && (rc = T->dhc.ensure(h, (size_t)nBd, "training workspace"))))
+        return rc;
+    }
+    const size_t cached = T->exp_cache.size();
+    for (int64_t c0 = 0; c0 < E; c0 += cw) {
+      const int64_t w = E - c0 < cw ? E - c0 : cw;
+      float* const ent_c = ent + c0 * d;
+      if ((rc = tg_matmul(h, T, s, MmView{T->hv, tg_idx(d), tg_idx(1), false}, B, MmView{ent_c, tg_idx(d), tg_idx(1), false}, w, d, T->Sd,
+                          tg_idx(w), tg_idx(1))))
+        return rc;
+      if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);
+      const int64_t n_stretch = (w + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH;
+      const int vec = (w & 3) == 0 && (((uintptr_t)T->Sd.get() | (uintptr_t)(pred_bias + c0)) & 15) == 0;
+      hipLaunchKernelGGL(k_tr_csr_loss, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
+                         csr.n_rows, c0, w, n_stretch, vec, eps, inv_E, inv_BL, red.loss());
+      if (apply) {
+        hipLaunchKernelGGL(k_tr_col_sum_f32, grid1d(w), dim3(256), 0, s, T->Sd, B, w, dbias + c0);
+        if ((rc = tg_matmul(h, T, s, MmView{T->Sd, tg_idx(1), tg_idx(w), true}, w, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE + c0 * d,
+                            tg_idx(d), tg_idx(1))))
+          return rc;
+        float* const share = c0 ? T->dhc.get() : T->dh.get();
+        if ((rc = tg_matmul(h, T, s, MmView{T->Sd, tg_idx(w), tg_idx(1), false}, B, MmView{ent_c, tg_idx(1), tg_idx(d), true}, d, w, share,
+                            tg_idx(d), tg_idx(1))))
+          return rc;
+        if (c0) hipLaunchKernelGGL(k_tr_add_to, grid1d(nBd), dim3(256), 0, s, T->dh, T->dhc, nBd);
+      }
+      // (h, packed first, stays; the chunk's S and table rows are other data at the next chunk, S at the same address)
+      if (T->exp_cache.size() > cached + 1) T->exp_cache.resize(cached + 1);
+    }
+    if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, red.loss(), 1.0 / ((double)B * (double)L), loss_out);
+    if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)nBd, hipMemcpyDeviceToDevice, s));
+    return COPER_OK;
+  }
   // ---- backward
   // d(loss)/d(logits) -> dh [B, d], d(pred_bias), d(ent_emb): through a GEMM on the dense S where B * |E| is small, else by float atomics.
   // Behind the caller's fork (scorer_bwd_on_side) S, dbias and dE = S^T h (~70 us that need ds and h only) run on side[0] beside the dense
@@ -895,19 +963,27 @@ struct Step {
 }  // namespace
 
 static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
-                           int64_t B, int64_t L, float* loss_out, void* stream, const int apply, float* pred_out, float* h_out) {
+                           int64_t B, int64_t L, float* loss_out, void* stream, const int apply, float* pred_out, float* h_out,
+                           const CsrLabels csr = CsrLabels()) {
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_step: call coper_train_init first");
+  if (csr.indptr) {      // sparse 1-vs-all labels: L is num_ent, no [B, L] matrix exists and nothing is indexed by B * L in 32 bits
+    if (!e1 || !rel || !csr.idx || B <= 0 || csr.n_rows < 0 || (!csr.row && csr.n_rows != B))
+      return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_row == NULL needs n_rows == B)");
+    if (B * ((h->dm.E + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff)
+      return fail(h, COPER_EINVAL, "coper_train_step_csr: batch too large for the loss kernel's grid");
+  } else {
   if (!e1 || !rel || !labels || B <= 0 || L <= 0 || B * L > 0x7fffffff)
     return fail(h, COPER_EINVAL, "coper_train_step: bad argument");
   if (!lookup && L != h->dm.E) return fail(h, COPER_EINVAL, "coper_train_step: lookup == NULL needs labels of shape [B, num_ent]");
   if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
+  }
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (apply) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_step: batch too large for the dropout counter");
-  Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply};
+  Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply, csr};
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
   st.zero_accumulators();
@@ -917,14 +993,16 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   st.fwd_conv_bn1();
   if ((rc = st.fwd_dense())) return rc;
   st.fwd_fcbn();
-  if ((rc = st.fwd_score_loss())) return rc;
+  if ((rc = csr.indptr ? st.score_csr() : st.fwd_score_loss())) return rc;      // (score_csr: the scorer's backward too, chunk by chunk)
   if (!apply) {      // coper_train_forward: nothing is differentiated, nothing updated, the step counter (dropout masks) stays
     COPER_HIP_TRY(h, hipGetLastError());
     return COPER_OK;
   }
 
-  if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
-  if ((rc = st.bwd_scorer())) return rc;
+  if (!csr.indptr) {
+    if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
+    if ((rc = st.bwd_scorer())) return rc;
+  }
   st.bwd_fcbn();
   if ((rc = st.bwd_dense())) return rc;      // (generated: forks SJ_DP in front of the dP product, Step::bwd_dense_dP)
   if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
@@ -955,6 +1033,21 @@ COPER_API int coper_train_step(coper_handle* h, const int64_t* e1, const int64_t
 COPER_API int coper_train_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                                   int64_t B, int64_t L, float* loss_out, float* pred_out, float* h_out, void* stream) {
   return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 0, pred_out, h_out);
+}
+
+COPER_API int coper_train_step_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
+                                   const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 1, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+}
+
+COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
+                                      const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out, float* pred_out, float* h_out,
+                                      void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 0, pred_out, h_out, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
 }
 
 COPER_API int coper_train_grad(coper_handle* h, const char* leaf_name, float* out, int64_t cap, int64_t* n, double* global_norm,

@@ -650,6 +650,88 @@ __global__ __launch_bounds__(256) void k_tr_col_sum_f32(const float* __restrict_
   out[c] = a;
 }
 
+// 1-vs-all training from SPARSE labels (coper_train_step_csr): k_tr_dense_loss on one chunk of entity columns [c0, c0 + w) of the
+// logits, S [B, w], with the label of (sample b, column c) taken from MEMBERSHIP of c in the sample's sorted id list instead of a
+// dense [B, |E|] matrix.  A workgroup per (sample, stretch of TR_CSR_STRETCH columns): two binary searches bound the row's entries
+// inside the stretch, the lanes set their bits in an LDS bitmask (integer atomics), and the elementwise pass is a plain stream --
+// 16 bytes per lane where the row stride allows it (vec: w % 4 == 0, S and the bias chunk 16-byte aligned), the four label bits of a
+// lane from one LDS word that eight neighbouring lanes read together (a broadcast: no bank conflict).  The work of a row with
+// thousands of positives and of an empty one differs by the bit-setting loop only.  Ids outside the stretch -- so every id outside
+// [0, |E|) -- set nothing; a lab_row outside the table is an empty row.  Per element the expression is k_tr_dense_loss's.
+constexpr int TR_CSR_STRETCH = 2048;      // columns per workgroup: a 64-word bitmask, two 16-byte accesses per lane
+__global__ __launch_bounds__(256) void k_tr_csr_loss(float* __restrict__ S, const float* __restrict__ pred_bias_c /* + c0 */,
+                                                     const int64_t* __restrict__ indptr, const int64_t* __restrict__ idx,
+                                                     const int64_t* __restrict__ lab_row, int64_t n_rows, int64_t c0, int64_t w,
+                                                     int64_t n_stretch, int vec, float ls_eps, float inv_E, float inv_BL,
+                                                     double* __restrict__ loss_acc) {
+  __shared__ unsigned mask[TR_CSR_STRETCH / 32];
+  __shared__ double part[256];
+  const int tid = threadIdx.x;
+  const int64_t b = (int64_t)blockIdx.x / n_stretch, j0 = ((int64_t)blockIdx.x % n_stretch) * TR_CSR_STRETCH;
+  const int n = (int)(w - j0 < TR_CSR_STRETCH ? w - j0 : TR_CSR_STRETCH);
+  const int64_t g0 = c0 + j0;      // the entity of the stretch's first column
+  if (tid < TR_CSR_STRETCH / 32) mask[tid] = 0u;
+  const int64_t row = lab_row ? lab_row[b] : b;
+  int64_t lo = 0, hi = 0;
+  if (row >= 0 && row < n_rows) { lo = indptr[row]; hi = indptr[row + 1]; }
+  auto lower_bound = [&](int64_t key) {      // the first entry of [lo, hi) that is >= key
+    int64_t a = lo, z = hi;
+    while (a < z) {
+      const int64_t m = a + ((z - a) >> 1);
+      if (idx[m] < key) a = m + 1; else z = m;
+    }
+    return a;
+  };
+  const int64_t p0 = lower_bound(g0), p1 = lower_bound(g0 + n);
+  __syncthreads();
+  for (int64_t p = p0 + tid; p < p1; p += 256) {
+    const int64_t e = idx[p] - g0;
+    if (e >= 0 && e < n) atomicOr(&mask[e >> 5], 1u << (e & 31));
+  }
+  __syncthreads();
+  float* const Sr = S + b * w + j0;
+  const float* const pb = pred_bias_c + j0;
+  double acc = 0.0;
+  auto element = [&](float logit, float bias, unsigned bit) {
+    const float s = logit + bias;
+    const float t = (1.f - ls_eps) * (bit ? 1.f : 0.f) + inv_E;
+    acc += (double)(fmaxf(s, 0.f) - s * t + log1pf(expf(-fabsf(s))));
+    return (1.f / (1.f + expf(-s)) - t) * inv_BL;
+  };
+  if (vec) {
+    for (int j = tid * 4; j < n; j += 1024) {      // (n % 4 == 0 with w % 4 == 0)
+      float4 v = *reinterpret_cast<const float4*>(Sr + j);
+      const float4 bb = *reinterpret_cast<const float4*>(pb + j);
+      const unsigned bits = mask[j >> 5] >> (j & 31);
+      v.x = element(v.x, bb.x, bits & 1u);
+      v.y = element(v.y, bb.y, bits & 2u);
+      v.z = element(v.z, bb.z, bits & 4u);
+      v.w = element(v.w, bb.w, bits & 8u);
+      *reinterpret_cast<float4*>(Sr + j) = v;
+    }
+  } else {
+    for (int j = tid; j < n; j += 256) Sr[j] = element(Sr[j], pb[j], (mask[j >> 5] >> (j & 31)) & 1u);
+  }
+  part[tid] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) part[tid] += part[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) atomicAdd(loss_acc, part[0]);
+}
+// out[b, c0 + j] = S[b, j] + pred_bias[c0 + j]: a chunk's logits into the [B, |E|] pred_out of coper_train_forward_csr
+__global__ __launch_bounds__(256) void k_tr_add_bias_out_cols(const float* __restrict__ S, const float* __restrict__ pred_bias_c, int64_t w,
+                                                              int64_t total, int64_t E, float* __restrict__ out_c /* + c0 */) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) out_c[(i / w) * E + i % w] = S[i] + pred_bias_c[i % w];
+}
+// dst += src: a later chunk's share of dh, added in chunk order
+__global__ __launch_bounds__(256) void k_tr_add_to(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] += src[i];
+}
+
 // ---- g_MLP generator chain pieces (small matrices: B <= a few thousand, widths <= a few hundred)
 // out[b,j] = sum_i in[b,i] P[i,j]
 __global__ __launch_bounds__(256) void k_tr_small_mm(const float* __restrict__ in, const float* __restrict__ P, int64_t B, int ni, int nj,

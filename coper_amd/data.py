@@ -398,12 +398,13 @@ class SyntheticKGLoader(object):
 
     def train_dataset(self, directory=None, batch_size=512, include_inv_relations=True, num_parallel_readers=None,
                       num_parallel_batches=None, buffer_size=None, prefetch_buffer_size=None, prop_negatives=10.0,
-                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None):
+                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None, sparse_labels=False):
         """The reference loader's `train_dataset` signature (data.py:89-100) over the synthetic graph; `num_labels=None` = 1-vs-all
-        labels (data.py:157-158); `device` (extra keyword): sample / densify on that device."""
+        labels (data.py:157-158); `device` (extra keyword): sample / densify on that device; `sparse_labels` (extra keyword, 1-vs-all
+        only): the labels stay id lists (`OneVsAllTrainDataset(labels="csr")`)."""
         samples = self.train_samples()
         if num_labels is None:
-            return OneVsAllTrainDataset(samples, self.num_ent, batch_size, seed, device=device)
+            return OneVsAllTrainDataset(samples, self.num_ent, batch_size, seed, device=device, labels="csr" if sparse_labels else "dense")
         if device is not None:
             return DeviceTrainDataset(samples, self.num_ent, batch_size, num_labels, seed, device=device,
                                       one_positive_label_per_sample=one_positive_label_per_sample, prop_negatives=prop_negatives)
@@ -708,6 +709,26 @@ class DeviceTrainDataset(object):
             yield b
 
 
+def _ascending_rows(indptr, idx):
+    """A CSR table with every row strictly ascending (what coper_train_step_csr's membership search asks for): the table itself
+    when it already is -- the loaders write sorted sets -- else a copy with every row sorted and its repeats dropped."""
+    indptr, idx = np.asarray(indptr, np.int64), np.asarray(idx, np.int64)
+    step_ok = np.ones(max(len(idx) - 1, 0), bool)
+    if len(idx) > 1:
+        step_ok = idx[1:] > idx[:-1]
+        starts = indptr[1:-1]
+        step_ok[starts[(starts > 0) & (starts < len(idx))] - 1] = True      # (the step from one row's last entry to the next row's first)
+    if step_ok.all():
+        return indptr, idx
+    owner = np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
+    order = np.lexsort((idx, owner))
+    owner, idx = owner[order], idx[order]
+    keep = np.ones(len(idx), bool)
+    keep[1:] = (owner[1:] != owner[:-1]) | (idx[1:] != idx[:-1])
+    owner, idx = owner[keep], idx[keep]
+    return np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=len(indptr) - 1))]).astype(np.int64), idx
+
+
 class OneVsAllTrainDataset(object):
     """1-vs-all training batches: `train_dataset(..., num_labels=None)` (data.py:157-158 -> `_add_lookup_values`, :314-330;
     selected by an empty `num_labels` in `config_nations_plain.yaml:22`, `config_umls_cpg.yaml:20`; `run_cpg.py:116` then builds the
@@ -718,9 +739,17 @@ class OneVsAllTrainDataset(object):
     Rows pass through the shuffle buffer of 1000 (data.py:160) and are batched; the record stream repeats (data.py:136).
     `device`: the dense label matrix is built THERE from the CSR tail lists (one scatter of the batch's known tails into a zeroed
     [B, |E|] tensor -- 30 MB per 512 x 14,541 batch never crosses PCIe) and the batch is a dict of device tensors that
-    `ConvE.train_step` takes as it is; without it, NumPy arrays in the reference's dtypes."""
+    `ConvE.train_step` takes as it is; without it, NumPy arrays in the reference's dtypes.
+    `labels="csr"`: the labels stay the id lists they are stored as (the reference densifies them for TensorFlow only).  The tail
+    table goes to the device ONCE; a batch is e1, rel, e2 = -1 and `lab_row` int64 [B] (the record of every sample = its row of the
+    table) beside the two table tensors `lab_indptr` / `lab_idx`, the same objects in every batch -- no per-batch label work, no
+    [B, |E|] matrix; `ConvE.train_step` takes it through coper_train_step_csr at any number of entities.  Records, shuffle buffer and
+    seeds are those of the dense mode: the same seed yields the same records."""
 
-    def __init__(self, samples, num_ent, batch_size, seed=0, shuffle_buffer=1000, device=None):
+    def __init__(self, samples, num_ent, batch_size, seed=0, shuffle_buffer=1000, device=None, labels="dense"):
+        if labels not in ("dense", "csr"):
+            raise ValueError("OneVsAllTrainDataset: labels is 'dense' or 'csr'")
+        self.labels = labels
         self.num_ent, self.batch_size, self.shuffle_buffer = int(num_ent), int(batch_size), int(shuffle_buffer)
         self.rng = np.random.default_rng(seed)
         self.e1 = np.asarray(samples["e1"], np.int64)
@@ -730,6 +759,8 @@ class OneVsAllTrainDataset(object):
         self.n_rec = len(self.e1)
         if self.n_rec == 0:
             raise ValueError("OneVsAllTrainDataset: the train graph has no (e1, rel) record")
+        if labels == "csr":
+            self.ip, self.tails = _ascending_rows(self.ip, self.tails)
         self.device = torch.device(device) if device is not None else None
         if self.device is not None:
             self.d_e1 = torch.as_tensor(self.e1).to(self.device)
@@ -774,9 +805,21 @@ class OneVsAllTrainDataset(object):
         return dict(e1=self.d_e1[r], rel=self.d_rel[r], e2=torch.full((B,), -1, dtype=torch.int64, device=dev), e2_multi=lab,
                     lookup_values=torch.zeros((B, 0), dtype=torch.int32, device=dev))
 
+    def _csr_batch(self, rec):
+        B = len(rec)
+        if self.device is None:
+            return dict(e1=self.e1[rec], rel=self.rel[rec], e2=np.full(B, -1, np.int64), lab_row=np.asarray(rec, np.int64),
+                        lab_indptr=self.ip, lab_idx=self.tails)
+        r = torch.as_tensor(rec).to(self.device)
+        return dict(e1=self.d_e1[r], rel=self.d_rel[r], e2=torch.full((B,), -1, dtype=torch.int64, device=self.device), lab_row=r,
+                    lab_indptr=self.d_ip, lab_idx=self.d_tails)
+
     def __iter__(self) -> Iterator[dict]:
         for rec in self._record_batches():
-            yield self._host_batch(rec) if self.device is None else self._device_batch(rec)
+            if self.labels == "csr":
+                yield self._csr_batch(rec)
+            else:
+                yield self._host_batch(rec) if self.device is None else self._device_batch(rec)
 
 
 class TrainDataset(object):

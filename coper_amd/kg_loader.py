@@ -244,11 +244,13 @@ class TSVKGLoader(object):
 
     def train_dataset(self, directory=None, batch_size=512, include_inv_relations=True, num_parallel_readers=None,
                       num_parallel_batches=None, buffer_size=None, prefetch_buffer_size=None, prop_negatives=10.0,
-                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None):
+                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None, sparse_labels=False):
         """`device` (extra keyword): sample on that device (`DeviceTrainDataset`: batches of device tensors; the
-        both samplers) instead of on the host."""
+        both samplers) instead of on the host.  `sparse_labels` (extra keyword, 1-vs-all only): the labels stay id lists
+        (`OneVsAllTrainDataset(labels="csr")`: no [B, |E|] matrix, `ConvE.train_step` takes the batch through coper_train_step_csr)."""
+        csr = "csr" if sparse_labels else "dense"
         if num_labels is None:      # 1-vs-all labels (data.py:157-158, 314-330)
-            return OneVsAllTrainDataset(self.train_samples(include_inv_relations), self.num_ent, batch_size, seed, device=device)
+            return OneVsAllTrainDataset(self.train_samples(include_inv_relations), self.num_ent, batch_size, seed, device=device, labels=csr)
         if device is not None:
             return DeviceTrainDataset(self.train_samples(include_inv_relations), self.num_ent, batch_size, num_labels, seed, device=device,
                                       one_positive_label_per_sample=one_positive_label_per_sample, prop_negatives=prop_negatives)
@@ -295,7 +297,7 @@ class TFRecordKGLoader(object):
 
     def train_dataset(self, directory=None, batch_size=512, include_inv_relations=True, num_parallel_readers=None,
                       num_parallel_batches=None, buffer_size=None, prefetch_buffer_size=None, prop_negatives=10.0,
-                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None):
+                      num_labels=100, cache=False, one_positive_label_per_sample=True, seed=0, device=None, sparse_labels=False):
         from . import tf_records
         if self.num_ent is None:
             self.maybe_create_tf_record_files(directory)
@@ -307,7 +309,7 @@ class TFRecordKGLoader(object):
                        tail_indptr=np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64),
                        tail_idx=np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64))
         if num_labels is None:      # 1-vs-all labels (data.py:157-158, 314-330)
-            return OneVsAllTrainDataset(samples, self.num_ent, batch_size, seed, device=device)
+            return OneVsAllTrainDataset(samples, self.num_ent, batch_size, seed, device=device, labels="csr" if sparse_labels else "dense")
         if device is not None:
             return DeviceTrainDataset(samples, self.num_ent, batch_size, num_labels, seed, device=device,
                                       one_positive_label_per_sample=one_positive_label_per_sample, prop_negatives=prop_negatives)

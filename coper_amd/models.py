@@ -877,18 +877,44 @@ class ConvE(object):
         cfg.batch_norm_momentum = float(md.get("batch_norm_momentum", 0.1))
         cfg.batch_norm_train_stats = 1 if md.get("batch_norm_train_stats", False) else 0
         cfg.seed = int(seed) & 0xFFFFFFFF
+        cfg.one_vs_all_chunk = int(md.get("one_vs_all_chunk", 0) or 0)     # entity columns per chunk of the sparse-label step; 0: the library's
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
         return self
 
+    def _csr_labels(self, batch, B):
+        """The sparse 1-vs-all labels of a batch (`lab_indptr`, `lab_idx`, optional `lab_row`) as device int64 tensors + the table's
+        row count.  Tensors already on the device pass through untouched: a loader's table goes up once, not per batch."""
+        ip, ix = self._ids(batch["lab_indptr"]), self._ids(batch["lab_idx"])
+        row = batch.get("lab_row", None)
+        row = None if row is None else self._ids(row)
+        n_rows = ip.numel() - 1
+        if n_rows < 0 or (row is None and n_rows != B) or (row is not None and row.numel() != B):
+            raise ValueError("training batch: lab_indptr [n_rows + 1], lab_idx, and lab_row [B] (or n_rows == B without lab_row)")
+        return ip, ix, row, n_rows
+
     def train_step(self, batch):
         """`session.run((model.train_op, model.loss))` on one training batch in the reference batch contract
-        (models.py:139-152): e1, rel [B]; lookup_values int32 [B,L]; e2_multi float [B,L].  Returns the loss as
-        a 1-element device tensor (no synchronisation)."""
+        (models.py:139-152): e1, rel [B]; lookup_values int32 [B,L]; e2_multi float [B,L].  1-vs-all batches may carry their labels
+        as id lists instead of a dense e2_multi [B, num_ent]: `lab_indptr`, `lab_idx` (+ `lab_row`), coper_train_step_csr.  Returns the
+        loss as a 1-element device tensor (no synchronisation)."""
         if getattr(self, "_train_loss", None) is None:
             raise _lib.CoperError(5, "call train_init() first")
         e1, rel = self._ids(batch["e1"]), self._ids(batch["rel"])
+        if "e2_multi" not in batch and "lab_indptr" in batch:
+            B = e1.numel()
+            if rel.numel() != B:
+                raise ValueError("training batch: e1, rel [B]")
+            ip, ix, row, n_rows = self._csr_labels(batch, B)
+            self._sync_parameters()
+            with torch.cuda.device(self.device):
+                _lib.check(self._h, self._lib.coper_train_step_csr(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), _ptr(row), n_rows, B,
+                                                                   _ptr(self._train_loss), self._stream()))
+            self._prepared = False
+            self._ent_absmax_cache = None
+            self._versions = {n: _version(t) for n, t in self._tensors.items()}
+            return self._train_loss
         lv = batch.get("lookup_values", None)
         one_vs_all = lv is None or (hasattr(lv, "shape") and len(lv.shape) == 2 and lv.shape[1] == 0)   # data.py:322
         lookup = None if one_vs_all else self._ids(lv, torch.int32)
@@ -914,6 +940,19 @@ class ConvE(object):
         if getattr(self, "_train_loss", None) is None:
             self.train_init()
         e1, rel = self._ids(batch["e1"]), self._ids(batch["rel"])
+        if "e2_multi" not in batch and "lab_indptr" in batch:
+            B = e1.numel()
+            if rel.numel() != B:
+                raise ValueError("training batch: e1, rel [B]")
+            ip, ix, row, n_rows = self._csr_labels(batch, B)
+            self._sync_parameters()
+            loss = torch.zeros(1, device=self.device, dtype=torch.float32)
+            pred = torch.empty((B, self.num_ent), device=self.device, dtype=torch.float32) if want_predictions else None
+            hv = torch.empty((B, self.ent_emb_size), device=self.device, dtype=torch.float32) if want_h else None
+            with torch.cuda.device(self.device):
+                _lib.check(self._h, self._lib.coper_train_forward_csr(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), _ptr(row), n_rows, B,
+                                                                      _ptr(loss), _ptr(pred), _ptr(hv), self._stream()))
+            return loss, pred, hv
         lv = batch.get("lookup_values", None)
         one_vs_all = lv is None or (hasattr(lv, "shape") and len(lv.shape) == 2 and lv.shape[1] == 0)
         lookup = None if one_vs_all else self._ids(lv, torch.int32)

@@ -40,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=128)
     ap.add_argument("--num-labels", type=int, default=100)
     ap.add_argument("--eval-every", type=int, default=200)
+    ap.add_argument("--sparse-labels", action="store_true",
+                    help="1-vs-all training (use_negative_sampling = False) with the labels kept as id lists: --num-labels is ignored, a batch "
+                         "is three ids per sample and the step runs in chunks of entity columns (coper_train_step_csr)")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--dense", choices=("cached", "factored"), default="cached",
                     help="generated dense layer at inference: the per-relation weight cache, or the factored path whose prepare after "
@@ -62,8 +65,11 @@ def main(argv=None):
     model.train_init(seed=0)
 
     # device=: the negative sampler runs on the GPU (coper_amd.data.DeviceTrainDataset; ~40 x the host sampler at FB15k-237 sizes)
-    train = iter(loader.train_dataset(work, batch_size=args.batch_size, num_labels=args.num_labels, prop_negatives=10.0,
-                                      one_positive_label_per_sample=True, device=model.device))
+    if args.sparse_labels:
+        train = iter(loader.train_dataset(work, batch_size=args.batch_size, num_labels=None, device=model.device, sparse_labels=True))
+    else:
+        train = iter(loader.train_dataset(work, batch_size=args.batch_size, num_labels=args.num_labels, prop_negatives=10.0,
+                                          one_positive_label_per_sample=True, device=model.device))
     dev = loader.eval_dataset(work, "dev", batch_size=512)
     test = loader.eval_dataset(work, "test", batch_size=512)
 

@@ -535,7 +535,11 @@ typedef struct coper_train_config {
   int32_t batch_norm_train_stats; /* BN uses batch statistics while training (models.py:62,358) */
   uint32_t seed;                  /* dropout stream */
   float context_rel_dropout;      /* dropout inside the g_MLP generators (models.py:67-68,118) */
-  int32_t reserved[7];
+  int32_t one_vs_all_chunk;       /* entity columns per chunk of coper_train_step_csr / coper_train_forward_csr; 0: the library's
+                                   * choice, the widest chunk whose [B, chunk] float workspace stays within 256 MiB.  A request is
+                                   * rounded UP to the GEMM column grain of 128 (the row padding of an operand plane) and capped at
+                                   * num_ent; negative: COPER_EINVAL.  Took the first reserved slot: layout and version unchanged */
+  int32_t reserved[6];
 } coper_train_config;
 
 /* Allocates gradients and the AMSGrad slots m, v, v_hat (zeros) for every trainable parameter; every
@@ -566,6 +570,30 @@ COPER_API int coper_train_step(coper_handle* h, const int64_t* e1, const int64_t
 COPER_API int coper_train_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup,
                                   const float* labels, int64_t B, int64_t L, float* loss_out, float* pred_out, float* h_out,
                                   void* stream);
+/* 1-vs-all training from SPARSE labels, at any number of entities: coper_train_step(lookup == NULL) / coper_train_forward(lookup ==
+ * NULL) with the dense e2_multi [B, num_ent] replaced by the id lists it is built from (the reference stores them that way and
+ * densifies them for TensorFlow only, data.py:318-322).  Everything not said here is the contract of those two calls: dropout
+ * counters, BN statistics, the side streams, stale inference caches, pred_out as [B, num_ent] logits, what is and is not written.
+ *   lab_indptr device int64 [n_rows + 1], lab_idx device int64: a CSR table of global entity ids, STRICTLY ASCENDING within a row
+ *     (the tail_indptr / tail_idx of coper_sample_train_batch's records is one);  lab_row device int64 [B]: the label row of sample
+ *     b is table row lab_row[b] -- the same row may occur several times in a batch, in any order.  lab_row == NULL: row b, and
+ *     n_rows must equal B (a plain per-batch CSR).  A row may be empty.
+ *   Labels are binary: 1.0 at the listed entities, 0.0 elsewhere; label_smoothing_epsilon and the + 1 / num_ent of models.py:450
+ *     apply on top, by the expression the dense-label call uses.
+ *   An entry of lab_idx outside [0, num_ent) and a lab_row outside [0, n_rows) are never dereferenced or written through: such an
+ *     entry is treated as ABSENT (a bad lab_row is an empty row), no error is raised.  lab_indptr itself is trusted.  A row that is
+ *     not ascending yields unspecified 0 / 1 labels for that row, nothing worse.
+ * Neither [B, num_ent] matrix exists: the scorer is walked in chunks of entity columns (coper_train_config.one_vs_all_chunk) --
+ * logits, loss, d(pred_bias), d(ent_emb) rows and the chunk's share of dh per chunk, shares added in ascending chunk order (no float
+ * atomics: the step is as repeatable as the dense-label one).  So neither the 512 MiB cap of the dense-label call nor B * L <= 2^31 - 1
+ * applies.  With one chunk (num_ent <= the chunk width) every launch but the loss kernel is the dense-label call's, and so is every
+ * gradient bit. */
+COPER_API int coper_train_step_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr,
+                                   const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out,
+                                   void* stream);
+COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr,
+                                      const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out,
+                                      float* pred_out, float* h_out, void* stream);
 /* Diagnostics: copies the (unclipped) gradient of the last step for a trainable leaf into `out` (device float
  * buffer of `cap` elements; may be NULL), returns its length in *n, and in *global_norm (optional, host) the
  * global gradient norm of the last step (synchronises).  The looked-up dense table's rows of relations the last batch did not hold are
