@@ -51,13 +51,19 @@ class coper_config(C.Structure):
 _P = C.c_void_p
 _I64 = C.c_int64
 
+class _coper_train_config_tail(C.Union):
+    """The anonymous union at the end of coper_train_config: `deterministic` is reserved[0] by name."""
+    _fields_ = [("deterministic", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class coper_train_config(C.Structure):
     """include/coper_hip.h: coper_train_config."""
+    _anonymous_ = ("_tail",)
     _fields_ = [("abi_version", C.c_int32), ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
                 ("epsilon", C.c_float), ("clip_norm", C.c_float), ("label_smoothing_epsilon", C.c_float),
                 ("hidden_dropout", C.c_float), ("output_dropout", C.c_float), ("batch_norm_momentum", C.c_float),
                 ("batch_norm_train_stats", C.c_int32), ("seed", C.c_uint32), ("context_rel_dropout", C.c_float),
-                ("one_vs_all_chunk", C.c_int32), ("reserved", C.c_int32 * 6)]
+                ("one_vs_all_chunk", C.c_int32), ("_tail", _coper_train_config_tail)]
 
 
 # name -> (restype, argtypes): every symbol include/coper_hip.h declares
@@ -112,6 +118,7 @@ PROTOTYPES = {
     "coper_profile_enable": (C.c_int, [_P, C.c_int]),
     "coper_profile_read": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "coper_train_init": (C.c_int, [_P, C.POINTER(coper_train_config)]),
+    "coper_train_deterministic": (C.c_int, [_P]),
     "coper_train_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "coper_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "coper_train_step_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),

@@ -21,8 +21,13 @@
 //   Schedule (round 6): the scorer's backward and the dP product run on two side streams of the training state, forked from and
 //   joined to the caller's stream by events (SideJoin; the forks and joins are in train_step_impl and where a phase begins); K slices of the few-tile products are added by the
 //   kernels that consume them (k_tr_fc_post_slices, k_tr_bn1_bwd_sums<NS>), not by a launch of their own.
+//   Deterministic mode (coper_train_config.deterministic): every atomic accumulation above has a second form with one defined
+//   order -- per-workgroup partial sums in TrainState::det_slab folded by k_tr_fold_det, one writer per embedding / relation row
+//   (k_tr_rows_by_key_det), S rows built in ascending lookup position (k_tr_build_S_det) -- chosen where the launch is made (`det`);
+//   the step is one chain on the caller's stream there.  With the mode off every launch is the one it was.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -146,6 +151,13 @@ struct TrainState {
   DevBuf<float> z0, z1, hv, dh, dz, ds, dx, dc;
   DevBuf<float> dhc;         // [B, d] a later chunk's share of dh (the 1-vs-all step from sparse labels, Step::score_csr)
   DevBuf<double> red;        // the reduction scratch in double (RedLayout)
+  // deterministic mode (coper_train_config.deterministic): no side streams; every reducing launch stores per-workgroup
+  // partial sums in det_slab (one use at a time, in stream order; sized by Step::grow_workspaces from the problem shape) and a fold
+  // launch adds them; the conv backward leaves d(img) per query in dimg [B, in_h in_w]; det_perm: the relation groups in ascending sample order
+  bool det = false;
+  DevBuf<double> det_slab;
+  DevBuf<float> dimg;
+  DevBuf<int32_t> det_perm;
   DevBuf<float> bnst;        // [BN_ROWS][mx]: Conv1BN's and FCBN's statistics of the forward pass (BnRow)
   int mx = 0;                // the widest BN layer: both are sized by it
   RedLayout red_layout() const { return RedLayout{red, (size_t)mx}; }
@@ -327,6 +339,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
       cfg->output_dropout >= 1)
     return fail(h, COPER_EINVAL, "coper_train_init: bad hyper-parameter");
   if (cfg->one_vs_all_chunk < 0) return fail(h, COPER_EINVAL, "coper_train_init: one_vs_all_chunk is negative");
+  if (cfg->deterministic != 0 && cfg->deterministic != 1) return fail(h, COPER_EINVAL, "coper_train_init: deterministic is 0 or 1");
   for (const Leaf& lf : h->leaves)
     if (!lf.set) return fail(h, COPER_EINVAL, "coper_train_init: parameter not set: " + lf.name);
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -334,6 +347,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   TrainState* T = new TrainState();
   h->train = T;
   T->cfg = *cfg;
+  T->det = cfg->deterministic == 1;
   T->b1p = cfg->beta1;   // the beta powers start at beta (amsgrad.py:108-113)
   T->b2p = cfg->beta2;
   T->nh = (dm.gen_fc && !dm.lookup) ? h->cfg.n_ctx_out : 0;
@@ -373,7 +387,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   PlaneSet* sets[10] = {&T->pX, &T->pXt, &T->pP1, &T->pP3, &T->pTn, &T->pTb, &T->mmX, &T->mmY, &T->mmX2, &T->mmY2};
   for (int i = 0; i < 10; ++i) sets[i]->exp = T->tg_exps + i;
   static const bool one_stream = getenv("COPER_TRAIN_ONE_STREAM") != nullptr;   // A/B switch: the step as one chain
-  if (!one_stream) {
+  if (!one_stream && !T->det) {      // (deterministic mode: one chain, one slab in use at a time)
     for (hipStream_t& st : T->side) COPER_HIP_TRY(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (int i = 0; i < 3; ++i) {
       COPER_HIP_TRY(h, hipEventCreateWithFlags(&T->ev_fork[i], hipEventDisableTiming));
@@ -437,6 +451,7 @@ struct Step {
   const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
   const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
   const bool cat = dm.concat_rel, two_streams = T->side[0] != nullptr;
+  const bool det = T->det;          // coper_train_config.deterministic: every sum in one defined order
   const bool lk = dm.lookup && dm.gen_fc;    // dense layer from g_lookup tables (otherwise static: models.py:217-228 with context_rel_out None)
   const bool gen = dm.gen_fc && !dm.lookup;
   const bool genc = dm.gen_conv && !dm.lookup, lkc = dm.gen_conv && dm.lookup;     // conv filters from projection generators / g_lookup tables
@@ -512,7 +527,23 @@ struct Step {
       // per-query filter / bias gradients: what the generators and tables reduce (gen_conv), and -- round 6 -- what the STATIC filters'
       // gradients are summed from (512 workgroups adding to the same 320 addresses were 50 of k_tr_conv_bwd's 60 us)
       if ((rc = ws(T->dKs, (size_t)cb * NT * C)) || (rc = ws(T->dkbs, (size_t)cb * C))) return rc;
+      if (det && ((rc = ws(T->dimg, (size_t)cb * isz)) || (rc = ws(T->det_perm, (size_t)cb)))) return rc;
       T->capB = cb; T->capL = cl;
+    }
+    if (det) {
+      // the slab of the widest reducing launch: DET_CS_WGS workgroups of column sums (2 mx doubles each), a loss kernel's grid (B, 2048,
+      // or B x the stretches of a chunk), k_tr_sumsq's 512 x tensors
+      const int64_t cwid = csr.indptr ? ova_chunk(B, dm.E, tc.one_vs_all_chunk) : 0;
+      size_t need = (size_t)DET_CS_WGS * 2 * T->mx;
+      // (as floats: the 64-row stretches of a column sum over |E|, the filter taps or d columns, or of the [rc_b, d] bias-projection product)
+      const size_t widest = std::max({(size_t)(one_vs_all ? 0 : dm.E), (size_t)NT * C, (size_t)d, (size_t)rc_b * d});
+      for (size_t n : {(size_t)2048, (size_t)B, (size_t)(B * ((cwid + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH)), (size_t)512 * TR_MAX_PARAMS,
+                       (size_t)((B + 63) / 64) * widest / 2 + 1})
+        need = n > need ? n : need;
+      if (need > T->det_slab.size()) {
+        COPER_HIP_TRY(h, hipStreamSynchronize(s));
+        if ((rc = T->det_slab.alloc(h, need, "deterministic slabs"))) return rc;
+      }
     }
     // (Round 6 tried the sampled scorer's forward and dh in ONE pass over the gathered rows -- a wave per row, the score a butterfly
     //  sum over its lanes: 242 us against 61 + 45 for the two kernels.  Thirty-two sequential iterations per wave, each with two
@@ -526,6 +557,26 @@ struct Step {
     K_ps = dm.gen_conv ? T->Kt.get() : nullptr;
     kb_ps = dm.gen_conv ? T->Kbv.get() : nullptr;
     return COPER_OK;
+  }
+  // ---- deterministic mode: the launches that replace an atomic site
+  static constexpr int DET_CS_WGS = 256;      // workgroups (= slabs) of a column-sum launch
+  void det_fold(int n, int64_t nslots, double* out, int accumulate) {
+    hipLaunchKernelGGL(k_tr_fold_det, dim3((unsigned)n), dim3(256), 0, s, T->det_slab.get(), n, nslots, out, accumulate);
+  }
+  // per-column sum | sum of squares of m [rows, cols] -> cs
+  void det_col_sums(const float* m, int64_t rows, int cols, double* cs, int wgs) {
+    hipLaunchKernelGGL(k_tr_col_sums<true>, dim3((unsigned)wgs), dim3(256), 0, s, m, rows, cols, T->det_slab.get(), 1);
+    det_fold(2 * cols, wgs, cs, 0);
+  }
+  // out[c] = the column sum of src [B, cols]: stretches of 64 rows as the default mode's launch, stored, then added in ascending stretch
+  void det_col_sum_f32(const float* src, int64_t cols, float* out, hipStream_t q) {
+    const unsigned nz = (unsigned)((B + 63) / 64);
+    hipLaunchKernelGGL(k_tr_col_sums_add<true>, dim3((unsigned)((cols + 255) / 256), nz), dim3(256), 0, q, src, B, cols, (float*)T->det_slab.get());
+    hipLaunchKernelGGL(k_tr_fold_f32_det, grid1d(cols), dim3(256), 0, q, (const float*)T->det_slab.get(), cols, (int)nz, out);
+  }
+  // dst[key[b]] += src[b, col0 : col0 + n], one writer per row, ascending b
+  void det_rows_by_key(const float* src, int64_t stride, int64_t col0, int n, const int64_t* keys, int64_t K, float* dst) {
+    hipLaunchKernelGGL(k_tr_rows_by_key_det, dim3((unsigned)B), dim3(256), 0, s, src, stride, col0, n, keys, K, B, dst);
   }
   // ---- zero what is accumulated by atomics: one launch
   void zero_accumulators() {
@@ -555,6 +606,10 @@ struct Step {
     h->gcur = 0;
     if ((rc = launch_group_by_relation(h, e1, rel, false, B, 32, s))) return rc;
     if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->grouping().rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
+    // (the grouping's order inside a relation is arrival order, and the order k_tr_lookup_dW sums in: a sorted copy for it)
+    if (det && apply)
+      hipLaunchKernelGGL(k_tr_sort_groups_det, dim3((unsigned)dm.R), dim3(256), 0, s, h->grouping().perm, h->grouping().rel_offset,
+                         h->grouping().rel_count, T->det_perm.get());
     return COPER_OK;
   }
   // ---- forward
@@ -569,7 +624,8 @@ struct Step {
       const float *ga = nullptr, *be = nullptr;
       if (dm.ctx_bn) {
         double* cs = red.colsum_slice(cs_chain(g, i));
-        if (use_batch) hipLaunchKernelGGL(k_tr_col_sums, dim3(64), dim3(256), 0, s, ch.u[i], B, nj, cs, 1);
+        if (use_batch && det) det_col_sums(ch.u[i], B, nj, cs, 64);
+        else if (use_batch) hipLaunchKernelGGL(k_tr_col_sums<false>, dim3(64), dim3(256), 0, s, ch.u[i], B, nj, cs, 1);
         hipLaunchKernelGGL(k_tr_bn_finish, dim3((nj + 63) / 64), dim3(64), 0, s, cs, nj, (double)B, use_batch, tc.batch_norm_momentum, 0 | nomov,
                            b.mov_mean, b.mov_var, ch.st[i], ch.st[i] + nj);
         ga = b.gamma->p;
@@ -600,8 +656,9 @@ struct Step {
                        dm.gen_conv ? nullptr : lv.conv1_weights->p, dm.gen_conv ? nullptr : lv.conv1_bias->p, dm.E, dm.R, d, r, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->img, ((gen || cat) && !genc) ? T->c.get() : nullptr, T->y, K_ps, kb_ps, dm.fh, dm.fw);
     double* const cs = red.cs_slots(CSS_BN1_FWD);
-    if (use_batch) {
-      hipLaunchKernelGGL(k_tr_col_sums, dim3(1024), dim3(256), 0, s, T->y, B * (int64_t)P, C, cs, TR_CS_SLOTS);
+    if (use_batch && det) det_col_sums(T->y, B * (int64_t)P, C, cs, DET_CS_WGS);
+    else if (use_batch) {
+      hipLaunchKernelGGL(k_tr_col_sums<false>, dim3(1024), dim3(256), 0, s, T->y, B * (int64_t)P, C, cs, TR_CS_SLOTS);
       hipLaunchKernelGGL(k_tr_fold_slots, dim3(1), dim3(256), 0, s, cs, 2 * C, TR_CS_SLOTS);
     }
     hipLaunchKernelGGL(k_tr_bn_finish, dim3((C + 63) / 64), dim3(64), 0, s, cs, C, (double)B * P, use_batch, tc.batch_norm_momentum, 1 | nomov,
@@ -665,7 +722,8 @@ struct Step {
 
   void fwd_fcbn() {
     double* const cs = red.colsum_slice(CS_FCBN);
-    if (use_batch) hipLaunchKernelGGL(k_tr_col_sums, dim3(64), dim3(256), 0, s, T->z1, B, d, cs, 1);
+    if (use_batch && det) det_col_sums(T->z1, B, d, cs, 64);
+    else if (use_batch) hipLaunchKernelGGL(k_tr_col_sums<false>, dim3(64), dim3(256), 0, s, T->z1, B, d, cs, 1);
     hipLaunchKernelGGL(k_tr_bn_finish, dim3((d + 63) / 64), dim3(64), 0, s, cs, d, (double)B, use_batch, tc.batch_norm_momentum, 0 | nomov,
                        lv.fcbn.mov_mean, lv.fcbn.mov_var, mean2, inv2);
     hipLaunchKernelGGL(k_tr_fcbn_fwd, grid1d(nBd), dim3(256), 0, s, T->z1, mean2, inv2, lv.fcbn.gamma->p, lv.fcbn.beta->p, d, nBd, T->hv);
@@ -692,16 +750,29 @@ struct Step {
       if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out, grid1d(B * dm.E), dim3(256), 0, s, T->Sd, pred_bias, dm.E, B * dm.E, pred_out);
       for (size_t i = 0; i < T->exp_cache.size(); ++i)      // (the loss kernel rewrites S in place: its power of two as an OUTPUT operand is gone)
         if (T->exp_cache[i].first == T->Sd) T->exp_cache[i].first = nullptr;
-      hipLaunchKernelGGL(k_tr_dense_loss, dim3(2048), dim3(256), 0, s, T->Sd, pred_bias, labels, dm.E, B * dm.E, eps, inv_E, inv_BL, red.loss());
+      if (det) {
+        hipLaunchKernelGGL(k_tr_dense_loss<true>, dim3(2048), dim3(256), 0, s, T->Sd, pred_bias, labels, dm.E, B * dm.E, eps, inv_E, inv_BL, T->det_slab.get());
+        det_fold(1, 2048, red.loss(), 1);
+      } else
+      hipLaunchKernelGGL(k_tr_dense_loss<false>, dim3(2048), dim3(256), 0, s, T->Sd, pred_bias, labels, dm.E, B * dm.E, eps, inv_E, inv_BL, red.loss());
     } else if (score_dh_fused) {
       const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
-      hipLaunchKernelGGL(k_tr_score_loss_dh, dim3((unsigned)B), dim3(256),
-                         sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + sizeof(int) * (size_t)L, s, T->hv, ent,
+      const size_t lds_sf = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + sizeof(int) * (size_t)L;
+      if (det)
+        hipLaunchKernelGGL(k_tr_score_loss_dh<true>, dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent,
+                           pred_bias, lookup, labels, dm.E, d, (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get());
+      else
+      hipLaunchKernelGGL(k_tr_score_loss_dh<false>, dim3((unsigned)B), dim3(256),
+                         lds_sf, s, T->hv, ent,
                          pred_bias, lookup, labels, dm.E, d, (int)L, eps, inv_E, inv_BL, T->ds, T->dh, red.loss());
+    } else if (det) {
+      hipLaunchKernelGGL(k_tr_score_loss<true>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d, L,
+                         eps, inv_E, inv_BL, T->ds, T->det_slab.get());
     } else {
-      hipLaunchKernelGGL(k_tr_score_loss, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d, L,
+      hipLaunchKernelGGL(k_tr_score_loss<false>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d, L,
                          eps, inv_E, inv_BL, T->ds, red.loss());
     }
+    if (det && !one_vs_all) det_fold(1, B, red.loss(), 1);      // (the B workgroups' loss shares, in sample order)
     if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, red.loss(), 1.0 / ((double)B * (double)L), loss_out);
     if (!one_vs_all && pred_out)
       hipLaunchKernelGGL(k_tr_scores_out, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, pred_bias, lookup, dm.E, d, L, pred_out);
@@ -738,7 +809,12 @@ struct Step {
       if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);
       const int64_t n_stretch = (w + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH;
       const int vec = (w & 3) == 0 && (((uintptr_t)T->Sd.get() | (uintptr_t)(pred_bias + c0)) & 15) == 0;
-      hipLaunchKernelGGL(k_tr_csr_loss, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
+      if (det) {      // (a later chunk's shares onto the earlier chunks' sum: chunk order)
+        hipLaunchKernelGGL(k_tr_csr_loss<true>, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
+                           csr.n_rows, c0, w, n_stretch, vec, eps, inv_E, inv_BL, T->det_slab.get());
+        det_fold(1, B * n_stretch, red.loss(), 1);
+      } else
+      hipLaunchKernelGGL(k_tr_csr_loss<false>, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
                          csr.n_rows, c0, w, n_stretch, vec, eps, inv_E, inv_BL, red.loss());
       if (apply) {
         hipLaunchKernelGGL(k_tr_col_sum_f32, grid1d(w), dim3(256), 0, s, T->Sd, B, w, dbias + c0);
@@ -783,9 +859,14 @@ struct Step {
     hipStream_t const q = sj.on[SJ_SCORER_BWD] >= 0 ? T->side[sj.on[SJ_SCORER_BWD]] : s;
     const size_t lds_s = sizeof(float) * (size_t)(dm.E < TR_S_CHUNK ? dm.E : TR_S_CHUNK);
     // (the kernel also holds 16 bytes of static LDS: asking for the whole 160 KB as dynamic is refused, and so is the launch after it)
-    if (lds_s > 64 * 1024) COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_build_S, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    if (!det && lds_s > 64 * 1024) COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_build_S, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    if (det) {      // duplicate ids of a row in ascending l; dbias[c] = the column sum of S in ascending b
+      hipLaunchKernelGGL(k_tr_build_S_det, dim3((unsigned)B), dim3(256), 0, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
+      det_col_sum_f32(T->Sd, dm.E, dbias, q);
+    } else {
     hipLaunchKernelGGL(k_tr_build_S, dim3((unsigned)B), dim3(256), lds_s, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
-    hipLaunchKernelGGL(k_tr_col_sums_add, dim3((unsigned)((dm.E + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, q, T->Sd, B, dm.E, dbias);
+    hipLaunchKernelGGL(k_tr_col_sums_add<false>, dim3((unsigned)((dm.E + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, q, T->Sd, B, dm.E, dbias);
+    }
     // dE[E,d] = S^T h  (overwrites the zeroed gradient; the e1-row contributions are added after it)
     if ((rc = tg_matmul(h, T, q, MmView{T->Sd, tg_idx(1), tg_idx(dm.E), true}, dm.E, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE,
                         tg_idx(d), tg_idx(1), nullptr, T->smax)))
@@ -817,7 +898,7 @@ struct Step {
     if ((rc = tg_pack(h, dTf, tg_idx(d), tg_idx2(d, nBd, 1), B, nrk, tg_rows_pad(B), false, T->pTb, s, T->tg_scratch, T->pTn.exp))) return rc;
     if (!p3_packed && (rc = tg_pack(h, W->p, tg_idx(d), tg_idx2(d, F * (int64_t)d, 1), F, nrk, tg_rows_pad(F), false, T->pP3, s, T->tg_scratch, T->pP1.exp))) return rc;
     // (the K slices of dx stay in the partial-sum pool for k_tr_bn1_bwd_sums when dx IS the conv features' gradient: no concat_rel)
-    if ((rc = tg_gemm_split(h, T, s, T->pTb, B, T->pP3, F, nrk, dxin, tg_idx(F), tg_idx(1), cat ? nullptr : &dx_slices))) return rc;
+    if ((rc = tg_gemm_split(h, T, s, T->pTb, B, T->pP3, F, nrk, dxin, tg_idx(F), tg_idx(1), (cat || det) ? nullptr : &dx_slices))) return rc;
     if ((rc = bwd_dense_dP())) return rc;
     hipLaunchKernelGGL(k_tr_dc_from_partials, dim3((unsigned)((B * rc_w + 3) / 4)), dim3(256), 0, s, T->dz, Tf, B, rc_w, d, T->chain[0].dv[nh].get());
     return COPER_OK;
@@ -827,40 +908,58 @@ struct Step {
   // itself the two took 211 us for 100 + 84: a SIMD holds one wave of either.)
   int bwd_dense_dP() {
     if (two_streams) sj.fork(SJ_DP, 1);
-    sumsq_done = W;   // the GEMM adds |dP|^2 to the global-norm accumulator as it stores
+    sumsq_done = det ? nullptr : W;   // the GEMM adds |dP|^2 to the global-norm accumulator as it stores (deterministic mode: k_tr_sumsq does, as for every leaf)
     return tg_gemm_nt(h, T->pXt, F, T->pTn, (int64_t)rc_w * d, B, W->g, tg_idx(d), tg_idx2(d, F * (int64_t)d, 1), two_streams ? T->side[1] : s, 1,
-                      nullptr, red.sumsq_slots());
+                      nullptr, det ? nullptr : red.sumsq_slots());
   }
 
   int bwd_dense() {
     int rc;
     if (lk) {
-      hipLaunchKernelGGL(k_tr_lookup_post_bwd, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o, ks_o, lv.fc_bias->g);
+      if (det) {
+        hipLaunchKernelGGL(k_tr_lookup_post_bwd<true>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o, ks_o, lv.fc_bias->g);
+        det_rows_by_key(T->dz, d, 0, d, rel, dm.R, lv.fc_bias->g);
+      } else
+      hipLaunchKernelGGL(k_tr_lookup_post_bwd<false>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o, ks_o, lv.fc_bias->g);
       const int rows_per_wg = 32;
-      hipLaunchKernelGGL(k_tr_lookup_dW, dim3((unsigned)((F + rows_per_wg - 1) / rows_per_wg), (unsigned)dm.R), dim3(256), 0, s, T->x, T->dz, h->grouping().perm,
+      hipLaunchKernelGGL(k_tr_lookup_dW, dim3((unsigned)((F + rows_per_wg - 1) / rows_per_wg), (unsigned)dm.R), dim3(256), 0, s, T->x, T->dz, det ? T->det_perm.get() : h->grouping().perm,
                          h->grouping().rel_offset, h->grouping().rel_count, F, d, rows_per_wg, W->g);
       hipLaunchKernelGGL(k_tr_lookup_dx, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, W->p, rel, dm.R, F, d, T->dx);
       return COPER_OK;
     }
     // gradients of the two contexts: dcw [B, rc_w] (k_tr_dc_from_partials) and dcb [B, rc_b] (k_tr_fc_post_bwd)
     const TrainParam* const blast = gen ? lv.gen[1].proj[nh] : nullptr;
-    hipLaunchKernelGGL(k_tr_fc_post_bwd, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, cbv, gen ? blast->p : nullptr, rc_b, d, tc.seed,
+    if (det) {
+      hipLaunchKernelGGL(k_tr_fc_post_bwd<true>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, cbv, gen ? blast->p : nullptr, rc_b, d, tc.seed,
+                         step, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
+                         gen ? T->chain[1].dv[nh].get() : nullptr);
+      if (!gen) det_col_sum_f32(T->dz, d, lv.fc_bias->g.get(), s);
+    } else
+    hipLaunchKernelGGL(k_tr_fc_post_bwd<false>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, cbv, gen ? blast->p : nullptr, rc_b, d, tc.seed,
                        step, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
                        gen ? T->chain[1].dv[nh].get() : nullptr);
-    if (gen) {     // (into the zeroed gradient: 8 atomics per address)
-      hipLaunchKernelGGL(k_tr_wsum_rows_add, dim3((unsigned)rc_b, (unsigned)((B + 63) / 64)), dim3(256), 0, s, cbv, T->dz, B, rc_b, d, blast->g);
+    if (gen) {     // (into the zeroed gradient: 8 atomics per address; deterministic mode: one thread per entry, ascending b)
+      if (det) {
+        const unsigned nz = (unsigned)((B + 63) / 64);
+        hipLaunchKernelGGL(k_tr_wsum_rows_add<true>, dim3((unsigned)rc_b, nz), dim3(256), 0, s, cbv, T->dz, B, rc_b, d, (float*)T->det_slab.get());
+        hipLaunchKernelGGL(k_tr_fold_f32_det, grid1d((int64_t)rc_b * d), dim3(256), 0, s, (const float*)T->det_slab.get(), (int64_t)rc_b * d, (int)nz, blast->g.get());
+      } else
+      hipLaunchKernelGGL(k_tr_wsum_rows_add<false>, dim3((unsigned)rc_b, (unsigned)((B + 63) / 64)), dim3(256), 0, s, cbv, T->dz, B, rc_b, d, blast->g);
       if ((rc = bwd_dense_generated())) return rc;
     } else {
       // static dense layer (plain ConvE): dW[F,d] = x^T dz and dx[B,F] = dz W^T
       if ((rc = tg_matmul(h, T, s, MmView{xin, tg_idx(1), tg_idx(F), true}, F, MmView{T->dz, tg_idx(1), tg_idx(d), true}, d, B, W->g, tg_idx(d),
-                          tg_idx(1), red.sumsq_slots())))
+                          tg_idx(1), det ? nullptr : red.sumsq_slots())))
         return rc;
-      sumsq_done = W;
+      sumsq_done = det ? nullptr : W;
       if ((rc = tg_matmul(h, T, s, MmView{T->dz, tg_idx(d), tg_idx(1), false}, B, MmView{W->p, tg_idx(d), tg_idx(1), false}, F, d, dxin,
                           tg_idx(F), tg_idx(1))))
         return rc;
     }
-    if (cat) hipLaunchKernelGGL(k_tr_split, grid1d(B * F), dim3(256), 0, s, T->dxc, rel, dm.R, Fc, r, B * F, T->dx, lv.rel_emb->g);
+    if (cat && det) {
+      hipLaunchKernelGGL(k_tr_split<true>, grid1d(B * F), dim3(256), 0, s, T->dxc, rel, dm.R, Fc, r, B * F, T->dx, lv.rel_emb->g);
+      det_rows_by_key(T->dxc, F, Fc, r, rel, dm.R, lv.rel_emb->g);
+    } else if (cat) hipLaunchKernelGGL(k_tr_split<false>, grid1d(B * F), dim3(256), 0, s, T->dxc, rel, dm.R, Fc, r, B * F, T->dx, lv.rel_emb->g);
     return COPER_OK;
   }
   // back through a generator chain to the relation rows: dv[nhx] -> dv[0]
@@ -886,6 +985,11 @@ struct Step {
   void bwd_bn1() {
     double* const colsum = red.cs_slots(CSS_BN1_BWD);
     const dim3 g1((unsigned)((nBF + 255) / 256 < 2048 ? (nBF + 255) / 256 : 2048));
+    if (det) {      // (dx is whole: the dx product kept no K slices in this mode)
+      hipLaunchKernelGGL(k_tr_bn1_bwd_sums_det, dim3(DET_CS_WGS), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, lv.bn1.beta->p, C,
+                         B * (int64_t)P, tc.seed, step, thr_h, ks_h, T->det_slab.get());
+      det_fold(2 * C, DET_CS_WGS, colsum, 0);
+    } else {
 #define COPER_BN1_SUMS(NS)                                                                                                                           \
     case NS:                                                                                                                                         \
       hipLaunchKernelGGL(k_tr_bn1_bwd_sums<NS>, g1, dim3(256), 0, s, T->dx, NS ? T->mmP : nullptr, T->y, mean1, inv1,                                \
@@ -896,24 +1000,39 @@ struct Step {
     }
 #undef COPER_BN1_SUMS
     hipLaunchKernelGGL(k_tr_fold_slots, dim3(1), dim3(256), 0, s, colsum, 2 * C, TR_CS_SLOTS);
+    }
     hipLaunchKernelGGL(k_tr_bn1_bwd_apply, grid1d(nBF), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, colsum, C, nBF,
                        (double)B * P, use_batch, lv.bn1.gamma->g, lv.bn1.beta->g);
   }
   // the conv backward: adds the e1 rows to dE (so the scorer's dE is joined in front of it), leaves per-query filter gradients
   void bwd_conv() {
     const size_t lds_cb = sizeof(float) * (size_t)(isz + (size_t)P * (C + 1) + NT * C);
-    if (lds_cb > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_tr_conv_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (!det && lds_cb > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_tr_conv_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     sj.join(SJ_SCORER_BWD);      // (dE = S^T h is stored: the conv backward adds the e1 rows to it)
-    hipLaunchKernelGGL(k_tr_conv_bwd, dim3((unsigned)B), dim3(256), lds_cb, s, T->dx, T->img, dm.gen_conv ? nullptr : lv.conv1_weights->p, e1, rel,
+    if (det) {
+      // d(img) per query, then one writer per embedding row: the e1 rows onto what the scorer's GEMM stored in dE, ascending b
+      if (lds_cb > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_tr_conv_bwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL(k_tr_conv_bwd<true>, dim3((unsigned)B), dim3(256), lds_cb, s, T->dx, T->img, dm.gen_conv ? nullptr : lv.conv1_weights->p, e1, rel,
+                         dm.E, dm.R, d, r, dm.in_h, dm.in_w, dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->dimg.get(),
+                         (float*)nullptr, K_ps, T->dKs, T->dkbs, dm.fh, dm.fw);
+      det_rows_by_key(T->dimg, isz, 0, d, e1, dm.E, lv.ent_emb->g);
+      if (dm.stacked) det_rows_by_key(T->dimg, isz, d, r, rel, dm.R, lv.rel_emb->g);
+      return;
+    }
+    hipLaunchKernelGGL(k_tr_conv_bwd<false>, dim3((unsigned)B), dim3(256), lds_cb, s, T->dx, T->img, dm.gen_conv ? nullptr : lv.conv1_weights->p, e1, rel,
                        dm.E, dm.R, d, r, dm.in_h, dm.in_w, dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, lv.ent_emb->g,
                        lv.rel_emb ? lv.rel_emb->g.get() : nullptr, K_ps, T->dKs, T->dkbs, dm.fh, dm.fw);
   }
   // per-query filter gradients -> static filters, generators' last projections and chains, or table rows; every chain's dv[0] -> relation rows
   void bwd_conv_filters() {
+    if (!dm.gen_conv && det) {
+      det_col_sum_f32(T->dKs, (int64_t)NT * C, lv.conv1_weights->g.get(), s);
+      det_col_sum_f32(T->dkbs, C, lv.conv1_bias->g.get(), s);
+    } else
     if (!dm.gen_conv) {      // static filters: their gradients are the column sums of the per-query ones (added to the zeroed gradients)
-      hipLaunchKernelGGL(k_tr_col_sums_add, dim3((unsigned)((NT * C + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, s, T->dKs, B,
+      hipLaunchKernelGGL(k_tr_col_sums_add<false>, dim3((unsigned)((NT * C + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, s, T->dKs, B,
                          (int64_t)NT * C, lv.conv1_weights->g);
-      hipLaunchKernelGGL(k_tr_col_sums_add, dim3(1, (unsigned)((B + 63) / 64)), dim3(256), 0, s, T->dkbs, B, (int64_t)C, lv.conv1_bias->g);
+      hipLaunchKernelGGL(k_tr_col_sums_add<false>, dim3(1, (unsigned)((B + 63) / 64)), dim3(256), 0, s, T->dkbs, B, (int64_t)C, lv.conv1_bias->g);
     }
     if (genc) {
       const TrainParam *const cwlast = lv.gen[2].proj[nhc], *const cblast = lv.gen[3].proj[nhc];
@@ -922,13 +1041,18 @@ struct Step {
       hipLaunchKernelGGL(k_tr_small_mm_tn, grid1d((int64_t)rc_cb * C), dim3(256), 0, s, ccb, T->dkbs, B, rc_cb, C, cblast->g);
       hipLaunchKernelGGL(k_tr_small_mm_nt, grid1d(B * rc_cb), dim3(256), 0, s, T->dkbs, cblast->p, B, rc_cb, C, 0, T->chain[3].dv[nhc]);
       for (int g : {2, 3}) chain_backward(g, nhc);
+    } else if (lkc && det) {
+      det_rows_by_key(T->dKs, (int64_t)NT * C, 0, NT * C, rel, dm.R, lv.conv1_weights->g);
+      det_rows_by_key(T->dkbs, C, 0, C, rel, dm.R, lv.conv1_bias->g);
     } else if (lkc) {
       // table rows: d(conv1_weights)[rel[b]] += dK[b] (the table gradients were zeroed above)
       hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * NT * C), dim3(256), 0, s, T->dKs, rel, dm.R, NT * C, B * NT * C, lv.conv1_weights->g);
       hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * C), dim3(256), 0, s, T->dkbs, rel, dm.R, C, B * C, lv.conv1_bias->g);
     }
     for (int g = 0; g < 4; ++g)
-      if (g < 2 ? gen : genc)
+      if (!(g < 2 ? gen : genc)) continue;
+      else if (det) det_rows_by_key(T->chain[g].dv[0], r, 0, r, rel, dm.R, lv.rel_emb->g);      // (chain after chain, each onto the sum so far)
+      else
         hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * r), dim3(256), 0, s, T->chain[g].dv[0], rel, dm.R, r, B * r, lv.rel_emb->g);
   }
   // ---- clip + AMSGrad
@@ -952,7 +1076,11 @@ struct Step {
       }
     }
     double* const ssq = red.sumsq_slots();
-    hipLaunchKernelGGL(k_tr_sumsq, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
+    if (det) {      // (skip is -1: no GEMM added squares) every workgroup's sum into the slab, their fold into slot 0 of the zeroed slots
+      hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, T->det_slab.get());
+      det_fold(1, (int64_t)512 * np, ssq, 0);
+    } else
+    hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
     const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
     hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, ssq, red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1, tc.beta2,
                        tc.epsilon);
@@ -979,6 +1107,13 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (!lookup && L != h->dm.E) return fail(h, COPER_EINVAL, "coper_train_step: lookup == NULL needs labels of shape [B, num_ent]");
   if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
+  }
+  if (T->det) {      // what the mode does not put in order is refused, never served unordered
+    if (lookup && !((double)B * (double)h->dm.E * 4.0 <= 512.0 * 1024 * 1024 && h->dm.E <= 0x7fffffff))
+      return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: sampled labels at B*num_ent*4 > 512 MiB take the atomic scorer backward");
+    // (routes chosen by pointer alignment -- the fused scorer, the 16-byte loss stream of the CSR chunks -- sum in another order)
+    if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
+      return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
   }
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (apply) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
@@ -1048,6 +1183,12 @@ COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const 
   if (!h) return COPER_EINVAL;
   if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
   return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 0, pred_out, h_out, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+}
+
+COPER_API int coper_train_deterministic(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->det ? 1 : 0) : -COPER_ESTATE;
 }
 
 COPER_API int coper_train_grad(coper_handle* h, const char* leaf_name, float* out, int64_t cap, int64_t* n, double* global_norm,

@@ -110,12 +110,15 @@ __global__ __launch_bounds__(256) void k_tr_fold_slots(double* __restrict__ base
     base[j] = a;
   }
 }
+// DET (deterministic mode): workgroup w STORES its partial sums in a slab of its own, out[w][2 cols]; k_tr_fold_det adds the slabs
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_col_sums(const float* __restrict__ m, int64_t rows, int cols, double* __restrict__ out, int nslots) {
   // per-column sum and sum of squares in double; a block reduces its row lanes in LDS and issues ONE atomic pair per
   // column (many blocks adding to the same few addresses are contention-bound: 14x slower per add -- 1024 workgroups on the 64
   // addresses of Conv1BN's statistics took 33 us for a 3 us read, so those go to TR_CS_SLOTS copies of the slice)
   __shared__ double sh[2][256];
-  out += (size_t)(blockIdx.x % nslots) * 2 * cols;
+  if constexpr (DET) out += (size_t)blockIdx.x * 2 * cols;
+  else out += (size_t)(blockIdx.x % nslots) * 2 * cols;
   if (cols <= 256) {
     const int cpt = 256 / cols;                         // row lanes per column
     const int col = threadIdx.x % cols, rl = threadIdx.x / cols;
@@ -141,8 +144,11 @@ __global__ __launch_bounds__(256) void k_tr_col_sums(const float* __restrict__ m
     __syncthreads();
     if (threadIdx.x < cols) {
       for (int l = 1; l < cpt; ++l) { s += sh[0][threadIdx.x + l * cols]; q += sh[1][threadIdx.x + l * cols]; }
+      if constexpr (DET) { out[col] = s; out[cols + col] = q; }
+      else {
       atomicAdd(&out[col], s);
       atomicAdd(&out[cols + col], q);
+      }
     }
   } else {
     for (int cc = threadIdx.x; cc < cols; cc += 256) {
@@ -152,8 +158,11 @@ __global__ __launch_bounds__(256) void k_tr_col_sums(const float* __restrict__ m
         s += v;
         q += v * v;
       }
+      if constexpr (DET) { out[cc] = s; out[cols + cc] = q; }
+      else {
       atomicAdd(&out[cc], s);
       atomicAdd(&out[cols + cc], q);
+      }
     }
   }
 }
@@ -279,6 +288,8 @@ __global__ __launch_bounds__(256) void k_tr_fcbn_fwd(const float* __restrict__ z
 }
 
 // sampled scorer + loss + d(loss)/ds.  One workgroup per query; h[b] in LDS; one lookup entry per thread.
+// DET (here and in the other loss kernels): the workgroup's loss share is STORED at loss_acc[blockIdx.x], a slab k_tr_fold_det adds
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__ hv, const float* __restrict__ ent,
                                                        const float* __restrict__ pred_bias,
                                                        const int32_t* __restrict__ lookup, const float* __restrict__ labels,
@@ -318,7 +329,10 @@ __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__
     if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(loss_acc, part[0]);
+  if (threadIdx.x == 0) {
+    if constexpr (DET) loss_acc[blockIdx.x] = part[0];
+    else atomicAdd(loss_acc, part[0]);
+  }
 }
 
 // The sampled scorer of a training step in ONE pass over the gathered rows (round 6): scores, loss, ds AND dh = sum_l ds E[row].
@@ -334,6 +348,7 @@ __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__
 #endif
 constexpr int SF_U = COPER_SF_U;      // rows per slot and batch
 constexpr int SF_MAX_L = 8192;       // lookup entries of a query held in LDS (32 KB)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restrict__ hv, const float* __restrict__ ent,
                                                           const float* __restrict__ pred_bias, const int32_t* __restrict__ lookup,
                                                           const float* __restrict__ labels, int64_t E, int d, int L, float ls_eps,
@@ -435,7 +450,8 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
   if (threadIdx.x == 0) {      // (the loss terms, in thread order)
     double a = 0.0;
     for (int t = 0; t < 256; ++t) a += red[t];
-    atomicAdd(loss_acc, a);
+    if constexpr (DET) loss_acc[blockIdx.x] = a;
+    else atomicAdd(loss_acc, a);
   }
 }
 
@@ -581,6 +597,8 @@ __global__ __launch_bounds__(256) void k_tr_build_S(const int32_t* __restrict__ 
 }
 
 // out[c] += sum over rows of S[row, c]: row stretches of 64 per workgroup row, one float atomic per (stretch, column)
+// DET: stretch z STORES its sums at out[z][cols] (a slab; k_tr_fold_f32_det adds the stretches in ascending z)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_col_sums_add(const float* __restrict__ S, int64_t rows, int64_t cols, float* __restrict__ out) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= cols) return;
@@ -595,11 +613,14 @@ __global__ __launch_bounds__(256) void k_tr_col_sums_add(const float* __restrict
     for (int u = 0; u < 8; ++u) a += v[u];
   }
   for (; r < r1; ++r) a += S[r * cols + c];
+  if constexpr (DET) { out[(size_t)blockIdx.y * cols + c] = a; return; }
   if (a != 0.f) atomicAdd(&out[c], a);
 }
 
 // out[i, j] += sum over rows b of w[b, i] v[b, j]   (a [ni x B] x [B x nj] product with a short ni: the generated dense bias'
 // projection gradient dPb[rho, k] = sum_b c[b, rho] dz0[b, k]): a workgroup per (i, stretch of 64 rows), a thread per j
+// DET: stretch z STORES its [ni, nj] partial product at out[z] (a slab; k_tr_fold_f32_det adds the stretches in ascending z)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_wsum_rows_add(const float* __restrict__ w, const float* __restrict__ v, int64_t rows, int ni, int nj,
                                                           float* __restrict__ out) {
   const int i = blockIdx.x;
@@ -615,12 +636,14 @@ __global__ __launch_bounds__(256) void k_tr_wsum_rows_add(const float* __restric
       for (int u = 0; u < 8; ++u) a = fmaf(c[u], x[u], a);
     }
     for (; r < r1; ++r) a = fmaf(w[r * ni + i], v[r * nj + j], a);
-    atomicAdd(&out[(int64_t)i * nj + j], a);
+    if constexpr (DET) out[((size_t)blockIdx.y * ni + i) * nj + j] = a;
+    else atomicAdd(&out[(int64_t)i * nj + j], a);
   }
 }
 
 // 1-vs-all training (lookup == NULL, models.py:159-162,434-437): S holds the logits h E^T from a GEMM; add the bias,
 // accumulate the loss, overwrite with d(loss)/d(logit)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_dense_loss(float* __restrict__ S, const float* __restrict__ pred_bias,
                                                        const float* __restrict__ labels, int64_t E, int64_t total, float ls_eps,
                                                        float inv_E, float inv_BL, double* __restrict__ loss_acc) {
@@ -638,7 +661,10 @@ __global__ __launch_bounds__(256) void k_tr_dense_loss(float* __restrict__ S, co
     if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(loss_acc, part[0]);
+  if (threadIdx.x == 0) {
+    if constexpr (DET) loss_acc[blockIdx.x] = part[0];
+    else atomicAdd(loss_acc, part[0]);
+  }
 }
 
 // out[c] = sum_b S[b, c]   (pred_bias gradient of the 1-vs-all route)
@@ -659,6 +685,7 @@ __global__ __launch_bounds__(256) void k_tr_col_sum_f32(const float* __restrict_
 // thousands of positives and of an empty one differs by the bit-setting loop only.  Ids outside the stretch -- so every id outside
 // [0, |E|) -- set nothing; a lab_row outside the table is an empty row.  Per element the expression is k_tr_dense_loss's.
 constexpr int TR_CSR_STRETCH = 2048;      // columns per workgroup: a 64-word bitmask, two 16-byte accesses per lane
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_csr_loss(float* __restrict__ S, const float* __restrict__ pred_bias_c /* + c0 */,
                                                      const int64_t* __restrict__ indptr, const int64_t* __restrict__ idx,
                                                      const int64_t* __restrict__ lab_row, int64_t n_rows, int64_t c0, int64_t w,
@@ -718,7 +745,10 @@ __global__ __launch_bounds__(256) void k_tr_csr_loss(float* __restrict__ S, cons
     if (tid < o) part[tid] += part[tid + o];
     __syncthreads();
   }
-  if (tid == 0) atomicAdd(loss_acc, part[0]);
+  if (tid == 0) {
+    if constexpr (DET) loss_acc[blockIdx.x] = part[0];
+    else atomicAdd(loss_acc, part[0]);
+  }
 }
 // out[b, c0 + j] = S[b, j] + pred_bias[c0 + j]: a chunk's logits into the [B, |E|] pred_out of coper_train_forward_csr
 __global__ __launch_bounds__(256) void k_tr_add_bias_out_cols(const float* __restrict__ S, const float* __restrict__ pred_bias_c, int64_t w,
@@ -865,7 +895,8 @@ __global__ __launch_bounds__(256) void k_tr_lookup_post(const float* __restrict_
   for (int sl = 0; sl < nsl; ++sl) v += part[(int64_t)sl * total + i];
   z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? v * keep_scale : 0.f;
 }
-// dz0 = keep * dz1 / (1 - rate) (in place);  dbias_table[rel[b], k] += dz0[b,k]
+// dz0 = keep * dz1 / (1 - rate) (in place);  dbias_table[rel[b], k] += dz0[b,k]   (DET: the rows are added by k_tr_rows_by_key_det)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_lookup_post_bwd(float* __restrict__ dz, const int64_t* __restrict__ rel, int64_t R, int d,
                                                             int64_t total, uint32_t seed, uint32_t step, uint32_t thr,
                                                             float keep_scale, float* __restrict__ dbias_t) {
@@ -875,7 +906,7 @@ __global__ __launch_bounds__(256) void k_tr_lookup_post_bwd(float* __restrict__ 
   if (rid < 0 || rid >= R) rid = 0;
   const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? dz[i] * keep_scale : 0.f;
   dz[i] = v;
-  atomicAdd(&dbias_t[rid * d + i % d], v);
+  if constexpr (!DET) atomicAdd(&dbias_t[rid * d + i % d], v);
 }
 
 // FCBN backward, one workgroup per feature k (a column of [B, d]): gamma/beta gradients and dz1
@@ -917,7 +948,8 @@ __global__ __launch_bounds__(256) void k_tr_fcbn_bwd(const float* __restrict__ z
 }
 
 // dz0 = keep * dz1 / (1 - rate) (in place); dense-bias gradients: static dfc_bias[k] += dz0; generated
-// dPb[rho,k] += c[b,rho] dz0[b,k], dc[b,rho] = sum_k dz0[b,k] Pb[rho,k]
+// dPb[rho,k] += c[b,rho] dz0[b,k], dc[b,rho] = sum_k dz0[b,k] Pb[rho,k]   (DET: dfc_bias is the column sum of dz0, a launch of its own)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_fc_post_bwd(float* __restrict__ dz, const float* __restrict__ c,
                                                         const float* __restrict__ Pb, int r, int d, uint32_t seed,
                                                         uint32_t step, uint32_t thr, float keep_scale,
@@ -930,6 +962,7 @@ __global__ __launch_bounds__(256) void k_tr_fc_post_bwd(float* __restrict__ dz, 
     const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? dz[i] * keep_scale : 0.f;
     dz[i] = v;
     row[k] = v;
+    if constexpr (!DET)
     if (!Pb) atomicAdd(&dfc_bias[k], v);
   }
   __syncthreads();
@@ -1094,6 +1127,8 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_apply(float* __restrict__ dx
 
 // conv backward, one workgroup per query: the query's filter / bias gradients dK_ps[b], dkb_ps[b] (reduced by the caller: through the
 // generators / tables, or -- static filters -- by column sums), d(img) -> rows of dE / drel_emb
+// DET: d(img) is STORED per query at dE[b][isz] (a workspace, not the gradient); k_tr_rows_by_key_det adds the rows per entity / relation
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_conv_bwd(const float* __restrict__ dy, const float* __restrict__ img_all,
                                                      const float* __restrict__ K, const int64_t* __restrict__ e1,
                                                      const int64_t* __restrict__ rel, int64_t E, int64_t R, int d, int r,
@@ -1155,8 +1190,11 @@ __global__ __launch_bounds__(256) void k_tr_conv_bwd(const float* __restrict__ d
         for (int cc = 0; cc < C; ++cc) a = fmaf(gp[cc], tp[cc], a);
       }
     }
+    if constexpr (DET) dE[b * isz + t] = a;
+    else {
     if (t < d) atomicAdd(&dE[row * d + t], a);
     else if (stacked) atomicAdd(&drel[rid * r + (t - d)], a);
+    }
   }
 }
 
@@ -1179,13 +1217,15 @@ __global__ __launch_bounds__(256) void k_tr_concat(const float* __restrict__ x, 
   xc[i] = f < Fc ? x[b * Fc + f] : c[b * r + (f - Fc)];
 }
 
-// ... and back: dx[b] = dxc[b, :Fc];  drel_emb[rel[b], :] += dxc[b, Fc:]
+// ... and back: dx[b] = dxc[b, :Fc];  drel_emb[rel[b], :] += dxc[b, Fc:]   (DET: the second half by k_tr_rows_by_key_det)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_split(const float* __restrict__ dxc, const int64_t* __restrict__ rel, int64_t R, int64_t Fc, int r,
                                                   int64_t total, float* __restrict__ dx, float* __restrict__ drel) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int64_t b = i / (Fc + r), f = i - b * (Fc + r);
   if (f < Fc) { dx[b * Fc + f] = dxc[i]; return; }
+  if constexpr (DET) return;
   int64_t rid = rel[b];
   if (rid < 0 || rid >= R) rid = 0;
   atomicAdd(&drel[rid * r + (f - Fc)], dxc[i]);
@@ -1217,6 +1257,8 @@ struct TrainTensors {
   int wmax_of;
 };
 
+// DET: workgroup (x, y) STORES its sum at acc[y * gridDim.x + x] (a slab; k_tr_fold_det adds them into slot 0 of the squared-norm slots)
+template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_sumsq(TrainTensors tt, int skip, double* __restrict__ acc) {
   __shared__ double part[256];
   if ((int)blockIdx.y == skip) return;   // the GEMM that produced this gradient already added its squares
@@ -1259,6 +1301,10 @@ __global__ __launch_bounds__(256) void k_tr_sumsq(TrainTensors tt, int skip, dou
   for (int o = 128; o > 0; o >>= 1) {
     if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
     __syncthreads();
+  }
+  if constexpr (DET) {
+    if (threadIdx.x == 0) acc[blockIdx.x + (size_t)blockIdx.y * gridDim.x] = part[0];
+    return;
   }
   if (threadIdx.x == 0 && part[0] != 0.0) atomicAdd(acc + (blockIdx.x + blockIdx.y * gridDim.x) % TG_SUMSQ_SLOTS, part[0]);
 }
@@ -1384,6 +1430,153 @@ __global__ __launch_bounds__(256) void k_tr_add_bias_out(const float* __restrict
 __global__ __launch_bounds__(256) void k_tr_zero_absent_rows(float* __restrict__ out, const int32_t* __restrict__ rowcnt, int64_t rowlen, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     if (rowcnt[i / rowlen] == 0) out[i] = 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// deterministic mode (coper_train_config.deterministic): the kernels that only this mode launches
+// ------------------------------------------------------------------------------------------------
+// The fold of a slab [nslots][n] that the workgroups of a reducing launch stored (workgroup w: slot w): a workgroup per column j,
+// thread t adds slots t, t + 256, ... in ascending order, the 256 thread sums meet in a fixed LDS tree.  The order depends on
+// (n, nslots) alone -- the reducing launch's grid, which this mode sizes by the problem shape.  accumulate: onto what out[j] holds.
+__global__ __launch_bounds__(256) void k_tr_fold_det(const double* __restrict__ slab, int n, int64_t nslots, double* __restrict__ out,
+                                                     int accumulate) {
+  __shared__ double sh[256];
+  const int j = blockIdx.x;
+  double a = 0;
+  for (int64_t z = threadIdx.x; z < nslots; z += 256) a += slab[z * n + j];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[j] = accumulate ? out[j] + sh[0] : sh[0];
+}
+
+// out[e] = slab[0][e] + slab[1][e] + ... in ascending z: the row stretches of k_tr_col_sums_add<true> / k_tr_wsum_rows_add<true>
+__global__ __launch_bounds__(256) void k_tr_fold_f32_det(const float* __restrict__ slab, int64_t n, int nz, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  float a = 0.f;
+  for (int z = 0; z < nz; ++z) a += slab[(size_t)z * n + e];
+  out[e] = a;
+}
+
+// k_tr_bn1_bwd_sums for any C <= 256 without an LDS atomic: k_tr_col_sums' layout -- thread (row lane, channel), a workgroup's row
+// lanes added in lane order -- over the [B P, C] gradient; workgroup w stores its 2 C sums at slab[w]
+__global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums_det(float* __restrict__ dx, const float* __restrict__ y, const float* __restrict__ mean,
+                                                             const float* __restrict__ inv, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, int C, int64_t rows, uint32_t seed, uint32_t step,
+                                                             uint32_t thr, float keep_scale, double* __restrict__ slab) {
+  __shared__ double s1[256], s2[256];
+  double* const out = slab + (size_t)blockIdx.x * 2 * C;
+  const int cpt = 256 / C, c = threadIdx.x % C, rl = threadIdx.x / C;
+  double a1 = 0, a2 = 0;
+  if (rl < cpt) {
+    const float mc = mean[c], ic = inv[c], gc = gamma[c], bc = beta[c];
+    for (int64_t rr = (int64_t)blockIdx.x * cpt + rl; rr < rows; rr += (int64_t)gridDim.x * cpt) {
+      const int64_t i = rr * C + c;
+      const float yh = (y[i] - mc) * ic;
+      const float act = yh * gc + bc;
+      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i, thr) ? dx[i] * keep_scale : 0.f;
+      if (!(act > 0.f)) g = 0.f;
+      dx[i] = g;
+      a1 += g;
+      a2 += (double)g * yh;
+    }
+  }
+  s1[threadIdx.x] = a1; s2[threadIdx.x] = a2;
+  __syncthreads();
+  if ((int)threadIdx.x < C) {
+    for (int l = 1; l < cpt; ++l) { a1 += s1[threadIdx.x + l * C]; a2 += s2[threadIdx.x + l * C]; }
+    out[c] = a1;
+    out[C + c] = a2;
+  }
+}
+
+// Row scatter with ONE WRITER PER DESTINATION ROW: dst[key[b], 0 .. n) += src[b, col0 .. col0 + n) over the samples b of a key in
+// ASCENDING b, onto what dst holds.  A workgroup per sample: the one of a key's FIRST sample (a leader scan over the ids in front of
+// it) is the key's writer and walks the rest of the batch, 256 ids at a time through LDS; the others leave.  B^2 / 2 id compares per
+// launch, no sort, no workspace, any B.  Keys outside [0, K) count as 0, as everywhere in the step.
+__global__ __launch_bounds__(256) void k_tr_rows_by_key_det(const float* __restrict__ src, int64_t stride, int64_t col0, int n,
+                                                            const int64_t* __restrict__ keys, int64_t K, int64_t B, float* __restrict__ dst) {
+  __shared__ int64_t kc[256];
+  const int64_t b = blockIdx.x;
+  auto key = [&](int64_t i) { const int64_t k = keys[i]; return (k < 0 || k >= K) ? (int64_t)0 : k; };
+  const int64_t k = key(b);
+  int earlier = 0;
+  for (int64_t i = threadIdx.x; i < b; i += 256) earlier |= key(i) == k ? 1 : 0;
+  if (__syncthreads_or(earlier)) return;      // (uniform)
+  for (int t0 = 0; t0 < n; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    float a = t < n ? dst[k * n + t] : 0.f;
+    for (int64_t i0 = b; i0 < B; i0 += 256) {
+      __syncthreads();
+      kc[threadIdx.x] = i0 + threadIdx.x < B ? key(i0 + threadIdx.x) : (int64_t)-1;
+      __syncthreads();
+      const int m = (int)(B - i0 < 256 ? B - i0 : 256);
+      if (t < n)
+        for (int u = 0; u < m; ++u)
+          if (kc[u] == k) a += src[(i0 + u) * stride + col0 + t];
+    }
+    if (t < n) dst[k * n + t] = a;
+  }
+}
+
+// k_tr_build_S with the duplicate ids of a row added in ASCENDING l: rounds over a stretch of TR_SDET_CHUNK columns in LDS -- in
+// every round the lowest not yet placed l of a column wins an integer atomicMin (order-free) and is that column's only adder; the
+// rounds end when nothing is left: 1 + the largest multiplicity of an id in the row.
+constexpr int TR_SDET_CHUNK = 4096;
+__global__ __launch_bounds__(256) void k_tr_build_S_det(const int32_t* __restrict__ lookup, const float* __restrict__ ds, int64_t E, int64_t L,
+                                                        float* __restrict__ S, unsigned* __restrict__ max_slots) {
+  __shared__ float s_row[TR_SDET_CHUNK];
+  __shared__ int placed[TR_SDET_CHUNK], nxt[TR_SDET_CHUNK];
+  const int64_t b = blockIdx.x;
+  const int32_t* lk = lookup + b * L;
+  const float* g = ds + b * L;
+  float mx = 0.f;
+  for (int64_t c0 = 0; c0 < E; c0 += TR_SDET_CHUNK) {
+    const int n = (int)(E - c0 < TR_SDET_CHUNK ? E - c0 : TR_SDET_CHUNK);
+    for (int i = threadIdx.x; i < n; i += 256) { s_row[i] = 0.f; placed[i] = -1; }
+    for (;;) {
+      for (int i = threadIdx.x; i < n; i += 256) nxt[i] = 0x7fffffff;
+      __syncthreads();
+      int any = 0;
+      for (int64_t l = threadIdx.x; l < L; l += 256) {
+        int64_t row = lk[l];
+        if (row < 0 || row >= E) row = 0;
+        if (row >= c0 && row < c0 + n && (int)l > placed[row - c0]) { atomicMin(&nxt[row - c0], (int)l); any = 1; }
+      }
+      if (!__syncthreads_or(any)) break;      // (uniform)
+      for (int64_t l = threadIdx.x; l < L; l += 256) {
+        int64_t row = lk[l];
+        if (row < 0 || row >= E) row = 0;
+        if (row >= c0 && row < c0 + n && nxt[row - c0] == (int)l) { s_row[row - c0] += g[l]; placed[row - c0] = (int)l; }
+      }
+      __syncthreads();
+    }
+    float* out = S + b * E + c0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float v = s_row[i];
+      out[i] = v;
+      mx = fmaxf(mx, fabsf(v));
+    }
+    __syncthreads();
+  }
+  tr_block_max_to_slot(mx, max_slots);
+}
+
+// the samples of every relation group (perm / offset / count of the handle's grouping, whose order inside a group is arrival order) in
+// ASCENDING sample index -> out, by rank: a workgroup per relation, count^2 / 256 compares per thread.  The grouping itself is not touched.
+__global__ __launch_bounds__(256) void k_tr_sort_groups_det(const int32_t* __restrict__ perm, const int32_t* __restrict__ offset,
+                                                            const int32_t* __restrict__ count, int32_t* __restrict__ out) {
+  const int n = count[blockIdx.x], off = offset[blockIdx.x];
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int32_t p = perm[off + i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += perm[off + j] < p ? 1 : 0;
+    out[off + rank] = p;
+  }
 }
 
 }  // namespace

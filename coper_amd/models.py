@@ -860,10 +860,12 @@ class ConvE(object):
         return ms.value, n.value
 
     # ---------------------------------------------------------------- training
-    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, **overrides):
+    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, **overrides):
         """Allocates gradients and AMSGrad slots (amsgrad.py:112-118).  Hyper-parameters come from
         model_descriptors (models.py:99-130) unless overridden.  The tensors passed to load_parameters ARE the
-        variables: train_step updates them in place (BN moving statistics included)."""
+        variables: train_step updates them in place (BN moving statistics included).
+        deterministic=True: bit-reproducible steps (coper_train_config.deterministic in include/coper_hip.h has the contract): the same
+        state and the same batch give the same bits in every output, across calls, handles, processes and streams."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -877,11 +879,20 @@ class ConvE(object):
         cfg.batch_norm_momentum = float(md.get("batch_norm_momentum", 0.1))
         cfg.batch_norm_train_stats = 1 if md.get("batch_norm_train_stats", False) else 0
         cfg.seed = int(seed) & 0xFFFFFFFF
+        cfg.deterministic = int(deterministic)      # (True / False -> 1 / 0; any other integer reaches the library's COPER_EINVAL)
         cfg.one_vs_all_chunk = int(md.get("one_vs_all_chunk", 0) or 0)     # entity columns per chunk of the sparse-label step; 0: the library's
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
         return self
+
+    @property
+    def train_deterministic(self):
+        """The training mode in force (coper_train_deterministic): 1 after train_init(deterministic=True), else 0."""
+        v = self._lib.coper_train_deterministic(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
 
     def _csr_labels(self, batch, B):
         """The sparse 1-vs-all labels of a batch (`lab_indptr`, `lab_idx`, optional `lab_row`) as device int64 tensors + the table's

@@ -43,6 +43,9 @@ def main(argv=None):
     ap.add_argument("--sparse-labels", action="store_true",
                     help="1-vs-all training (use_negative_sampling = False) with the labels kept as id lists: --num-labels is ignored, a batch "
                          "is three ids per sample and the step runs in chunks of entity columns (coper_train_step_csr)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible training steps (coper_train_config.deterministic): two runs of this loop with the same "
+                         "arguments and the same batches reach the same variables bit for bit")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--dense", choices=("cached", "factored"), default="cached",
                     help="generated dense layer at inference: the per-relation weight cache, or the factored path whose prepare after "
@@ -62,7 +65,7 @@ def main(argv=None):
               batch_norm_momentum=0.1)
     model = ConvE(md, device="cuda:0", score_mode="bf16x3", dense=args.dense)
     model.load_parameters(cdata.synthetic_params(md, seed=0))      # random init of the named architecture
-    model.train_init(seed=0)
+    model.train_init(seed=0, deterministic=args.deterministic)
 
     # device=: the negative sampler runs on the GPU (coper_amd.data.DeviceTrainDataset; ~40 x the host sampler at FB15k-237 sizes)
     if args.sparse_labels:

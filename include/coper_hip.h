@@ -539,12 +539,35 @@ typedef struct coper_train_config {
                                    * choice, the widest chunk whose [B, chunk] float workspace stays within 256 MiB.  A request is
                                    * rounded UP to the GEMM column grain of 128 (the row padding of an operand plane) and capped at
                                    * num_ent; negative: COPER_EINVAL.  Took the first reserved slot: layout and version unchanged */
-  int32_t reserved[6];
+  union {                         /* the six words behind one_vs_all_chunk, where reserved[6] always was: word 0 has a name now */
+  int32_t deterministic;          /* 0: the step as it always was (the default; same launches, same results).  1: BIT-REPRODUCIBLE
+                                   * training: given the same library build and GPU model, the same coper_config and coper_train_config,
+                                   * the same variables, optimizer slots, beta powers and step counter, and the same batch arrays (same
+                                   * values in the same order), coper_train_step, coper_train_step_csr, coper_train_forward and
+                                   * coper_train_forward_csr return the same BITS in every output -- loss_out, pred_out, h_out, every
+                                   * coper_train_grad leaf and its global_norm (a double), every variable after the step (BN moving
+                                   * statistics included) and every AMSGrad slot -- from call to call, between handles and between
+                                   * processes, on any stream, with COPER_TRAIN_ONE_STREAM set or not, whatever else runs on the GPU and
+                                   * whatever addresses the allocations got.  Every sum of the step has one defined order: reducing
+                                   * launches store per-workgroup partial sums that a fold launch adds in ascending workgroup index, and
+                                   * embedding / relation rows have one writer that adds a row's samples in ascending sample index (then
+                                   * ascending lookup position) after what the scorer's GEMM stored there.  The step runs as one chain
+                                   * on `stream` (no side streams).  NOT promised: the default mode's bits; equality across permutations
+                                   * of a batch, across one_vs_all_chunk widths, GPU models or builds.  Refused with COPER_EUNSUPPORTED
+                                   * by the step, never served unordered: sampled labels with B * num_ent * 4 > 512 MiB (the scorer's
+                                   * atomic backward); an ent_emb or pred_bias tensor that is not 16-byte aligned (routes chosen by
+                                   * alignment sum in another order).  Any other value: COPER_EINVAL from coper_train_init.  Took the
+                                   * second reserved slot, reserved[0]: layout, sizeof and COPER_ABI_VERSION unchanged, and a caller
+                                   * built against the earlier header, which zeroed reserved[], asks for the default mode */
+  int32_t reserved[6];            /* [0] is `deterministic`; [1 .. 5] are reserved and must be 0 */
+  };
 } coper_train_config;
 
 /* Allocates gradients and the AMSGrad slots m, v, v_hat (zeros) for every trainable parameter; every
  * parameter must have been registered with coper_set_param. */
 COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg);
+/* The mode in force: 1 (coper_train_config.deterministic) or 0; -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle. */
+COPER_API int coper_train_deterministic(const coper_handle* h);
 /* One optimisation step on a training batch in the reference batch contract (models.py:139-152):
  * e1, rel int64 [B]; lookup int32 [B,L] (obj_lookup_values); labels float [B,L] (e2_multi for the looked-up
  * entities).  lookup == NULL with L == num_ent is 1-vs-all training (use_negative_sampling = False, run_cpg.py:116:
