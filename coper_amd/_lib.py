@@ -123,6 +123,12 @@ PROTOTYPES = {
     "coper_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "coper_train_step_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "coper_train_forward_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "coper_train_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "coper_train_backward_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "coper_train_grads_layout": (C.c_int, [_P, C.c_char_p, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "coper_train_grads_export": (C.c_int, [_P, _P, _I64, C.c_int32, _P]),
+    "coper_train_apply": (C.c_int, [_P, _P, _I64, C.c_double, _P]),
+    "coper_train_wmax_carried": (C.c_int, [_P]),
     "coper_train_grad": (C.c_int, [_P, C.c_char_p, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_double), _P]),
     "coper_train_slot": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, _I64, C.c_int32, C.POINTER(_I64), _P]),
     "coper_train_powers": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I64), C.POINTER(C.c_double),

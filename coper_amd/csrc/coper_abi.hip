@@ -474,7 +474,7 @@ COPER_API int coper_set_param(coper_handle* h, const char* leaf_name, const void
   lf->shape = got;
   lf->set = true;
   h->prepared = false;
-  return train_params_changed(h);
+  return train_params_changed(h, leaf_name);
 }
 
 COPER_API int coper_set_x3_ent_absmax(coper_handle* h, float absmax) {

@@ -417,7 +417,7 @@ struct PassCtx {
 
 int fail(coper_handle* h, int code, const std::string& msg);
 void train_destroy(coper_handle* h);   // coper_train.hip
-int train_params_changed(coper_handle* h);   // coper_set_param: the training state resolves its variables again
+int train_params_changed(coper_handle* h, const char* leaf_name);   // coper_set_param: the training state resolves its variables again
 int hip_fail(coper_handle* h, hipError_t e, const char* what);
 
 #define COPER_HIP_TRY(h, expr)                                    \

@@ -45,6 +45,7 @@ struct TrainParam {
   float* p = nullptr;   // the caller's variable, updated in place
   int64_t n = 0;
   DevBuf<float> g;      // gradient of the last step
+  int64_t flat_off = 0; // where the leaf starts in the flat gradient vector (coper_train_grads_layout)
   DevBuf<float> m;      // AMSGrad slots
   DevBuf<float> v;
   DevBuf<float> vh;
@@ -137,6 +138,11 @@ struct TrainState {
   // looked-up dense table: the relation counts of the last step's batch (R + 1), copied out of the grouping workspace behind the
   // step's grouping -- coper_train_grad hands out the rows of absent relations as zeros by them, whatever has been grouped since
   DevBuf<int32_t> step_rel_count;
+  DevBuf<int32_t> all_rel_count;    // R + 1 ones: every row present (coper_train_apply from a flat vector)
+  // the split step (coper_train_backward / _grads_export / _apply): the flat gradient vector's length, and whether the gradient
+  // buffers hold a backward pass that no update has consumed and nothing has zeroed since
+  int64_t flat_total = 0;
+  bool pending = false;
   // tg_matmul: the exponent of an operand tensor packed earlier in THIS step (x, the static W, dz and S are each packed for two
   // products): (tensor, its word).  Cleared at the start of a step and where a kernel rewrites a tensor in place.
   std::vector<std::pair<const float*, int32_t*>> exp_cache;
@@ -300,10 +306,12 @@ static int resolve_leaves(coper_handle* h, TrainState* T, bool create) {
 
 // coper_set_param: whatever the optimizer's last pass knew about the parameters (TrainState::wmax) no longer describes them, and a
 // variable may now live at another address (a checkpoint loaded between steps): the variables are the registered tensors
-int train_params_changed(coper_handle* h) {
+// (a BN moving statistic is no trainable leaf and says nothing about the dense weights: registering one again -- a data-parallel
+// trainer writes the ranks' average into it between steps -- leaves the carried maximum alone)
+int train_params_changed(coper_handle* h, const char* leaf_name) {
   TrainState* T = (TrainState*)h->train;
   if (!T) return COPER_OK;
-  T->wmax_valid = false;
+  if (!leaf_name || T->find(leaf_name)) T->wmax_valid = false;
   return resolve_leaves(h, T, false);
 }
 
@@ -369,6 +377,12 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
     COPER_HIP_TRY(h, hipMemset(tp.vh, 0, sizeof(float) * tp.n));
     COPER_HIP_TRY(h, hipMemset(tp.g, 0, sizeof(float) * tp.n));
   }
+  // the flat gradient vector: the trainable leaves in coper_param_spec order, each at a multiple of 64 floats
+  for (const Leaf& lf : h->leaves)
+    if (TrainParam* t = T->find(lf.name.c_str())) {
+      t->flat_off = T->flat_total;
+      T->flat_total += (t->n + 63) / 64 * 64;
+    }
   T->mx = dm.C > dm.d ? dm.C : dm.d;
   for (int i = 0; i < T->nh; ++i) T->mx = h->cfg.ctx_out[i] > T->mx ? h->cfg.ctx_out[i] : T->mx;
   for (int i = 0; i < T->nhc; ++i) T->mx = h->cfg.ctx_conv[i] > T->mx ? h->cfg.ctx_conv[i] : T->mx;
@@ -377,13 +391,18 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
       (rc = T->wmax[0].alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->wmax[1].alloc(h, TG_MAX_SLOTS, "max slots")) ||
       (rc = T->xmax.alloc(h, TG_MAX_SLOTS, "max slots")) || (rc = T->dtmax.alloc(h, TG_MAX_SLOTS, "max slots")) ||
       (rc = T->smax.alloc(h, TG_MAX_SLOTS, "max slots")) ||
-      (dm.lookup && dm.gen_fc && (rc = T->step_rel_count.alloc(h, (size_t)dm.R + 1, "relation counts"))))
+      (dm.lookup && dm.gen_fc && ((rc = T->step_rel_count.alloc(h, (size_t)dm.R + 1, "relation counts")) ||
+                                  (rc = T->all_rel_count.alloc(h, (size_t)dm.R + 1, "relation counts")))))
     return rc;
   COPER_HIP_TRY(h, hipMemset(T->tg_exps, 0, (10 + TR_EXP_CACHE) * sizeof(int32_t)));
   COPER_HIP_TRY(h, hipMemset(T->wmax[0], 0, TG_MAX_SLOTS * sizeof(unsigned)));
   COPER_HIP_TRY(h, hipMemset(T->wmax[1], 0, TG_MAX_SLOTS * sizeof(unsigned)));
   COPER_HIP_TRY(h, hipMemset(T->tg_scratch, 0, 4 * sizeof(unsigned)));
   if (T->step_rel_count) COPER_HIP_TRY(h, hipMemset(T->step_rel_count, 0, T->step_rel_count.size() * sizeof(int32_t)));
+  if (T->all_rel_count) {
+    const std::vector<int32_t> ones((size_t)dm.R + 1, 1);
+    COPER_HIP_TRY(h, hipMemcpy(T->all_rel_count, ones.data(), ones.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   PlaneSet* sets[10] = {&T->pX, &T->pXt, &T->pP1, &T->pP3, &T->pTn, &T->pTb, &T->mmX, &T->mmY, &T->mmX2, &T->mmY2};
   for (int i = 0; i < 10; ++i) sets[i]->exp = T->tg_exps + i;
   static const bool one_stream = getenv("COPER_TRAIN_ONE_STREAM") != nullptr;   // A/B switch: the step as one chain
@@ -437,6 +456,49 @@ struct SideJoin {
   ~SideJoin() { for (int i = 0; i < 3; ++i) join(i); }
 };
 
+// clip + AMSGrad over every trainable tensor: the squared norm (k_tr_sumsq; deterministic mode: through the slab and its fold), then
+// k_tr_amsgrad.  The caller has zeroed the squared-norm slots and wmax[wmax_cur ^ 1].  flat: the gradients are read from the flat
+// gradient vector in place (each leaf at its flat_off) instead of the gradient buffers.  sumsq_done: the leaf whose squares a GEMM of
+// the same step already added to the slots.  table_counts: the relation counts that say which rows of the looked-up dense table
+// exist.  gs: coper_train_apply's scale (1: the fused step).  Returns whether the pass carried the dense weights' maximum.
+static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, const float* flat, const TrainParam* sumsq_done,
+                             const int32_t* table_counts, double gs) {
+  const Dims& dm = h->dm;
+  const coper_train_config& tc = T->cfg;
+  const TrainLeaves& lv = T->lv;
+  const bool lk = dm.lookup && dm.gen_fc, gen = dm.gen_fc && !dm.lookup;
+  const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
+  const RedLayout red = T->red_layout();
+  TrainTensors tt;
+  const int np = (int)T->tp.size();
+  int skip = -1;
+  // the dense weights' largest |p_new| for the next step's packs (k_tr_amsgrad's 16-byte path only: it is the one that carries it)
+  tt.wmax = nullptr; tt.wmax_of = -1;
+  for (int i = 0; i < np; ++i) {
+    const TrainParam& t = T->tp[i];
+    tt.p[i] = t.p; tt.g[i] = flat ? const_cast<float*>(flat) + t.flat_off : t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
+    tt.n[i] = t.n;
+    const bool table = lk && &t == lv.fc_weights;
+    tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
+    tt.rowcnt[i] = table ? table_counts : nullptr;
+    if (&t == sumsq_done) skip = i;
+    if (!lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
+      tt.wmax = T->wmax[T->wmax_cur ^ 1];
+      tt.wmax_of = i;
+    }
+  }
+  double* const ssq = red.sumsq_slots();
+  if (T->det) {      // (skip is -1: no GEMM added squares) every workgroup's sum into the slab, their fold into slot 0 of the zeroed slots
+    hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, T->det_slab.get());
+    hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, ssq, 0);
+  } else
+    hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
+  const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
+  hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, ssq, red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1, tc.beta2,
+                     tc.epsilon, gs);
+  return tt.wmax != nullptr;
+}
+
 // One call of the step: the arguments, what they and the configuration decide once, the few values a phase hands to a later one, and
 // the phases themselves in the order of the header comment's schedule (train_step_impl runs them).
 struct Step {
@@ -446,7 +508,7 @@ struct Step {
   hipStream_t const s;
   const int64_t *const e1, *const rel; const int32_t* const lookup; const float* const labels; const int64_t B, L;
   float *const loss_out, *const pred_out, *const h_out;
-  const int apply;                  // 0: coper_train_forward
+  const int apply;                  // 0: coper_train_forward; 1: coper_train_step; 2: coper_train_backward (everything but the optimizer)
   const CsrLabels csr;              // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
   const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
   const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
@@ -590,7 +652,7 @@ struct Step {
     else if (gen) add(lv.gen[1].proj[nh]->g, sizeof(float) * rc_b * d);
     else add(lv.fc_bias->g, sizeof(float) * d);
     // (the dense S of the sampled scorer's backward is written whole by k_tr_build_S: nothing to zero)
-    if (apply) add(T->wmax[T->wmax_cur ^ 1], sizeof(unsigned) * TG_MAX_SLOTS);      // what this step's optimizer pass fills for the next step
+    if (apply == 1) add(T->wmax[T->wmax_cur ^ 1], sizeof(unsigned) * TG_MAX_SLOTS);      // what this step's optimizer pass fills for the next step
     for (unsigned* slots : {T->xmax.get(), T->dtmax.get(), T->smax.get()}) add(slots, sizeof(unsigned) * TG_MAX_SLOTS);
     hipLaunchKernelGGL(k_tr_zero_list, dim3(256, (unsigned)zl.n), dim3(256), 0, s, zl);
     T->exp_cache.clear();
@@ -1056,36 +1118,7 @@ struct Step {
         hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * r), dim3(256), 0, s, T->chain[g].dv[0], rel, dm.R, r, B * r, lv.rel_emb->g);
   }
   // ---- clip + AMSGrad
-  bool optimizer() {
-    TrainTensors tt;
-    const int np = (int)T->tp.size();
-    int skip = -1;
-    // the dense weights' largest |p_new| for the next step's packs (k_tr_amsgrad's 16-byte path only: it is the one that carries it)
-    tt.wmax = nullptr; tt.wmax_of = -1;
-    for (int i = 0; i < np; ++i) {
-      const TrainParam& t = T->tp[i];
-      tt.p[i] = t.p; tt.g[i] = t.g; tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
-      tt.n[i] = t.n;
-      const bool table = lk && &t == lv.fc_weights;
-      tt.rowlen[i] = table ? F * d : 1;
-      tt.rowcnt[i] = table ? h->grouping().rel_count : nullptr;
-      if (&t == sumsq_done) skip = i;
-      if (!lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
-        tt.wmax = T->wmax[T->wmax_cur ^ 1];
-        tt.wmax_of = i;
-      }
-    }
-    double* const ssq = red.sumsq_slots();
-    if (det) {      // (skip is -1: no GEMM added squares) every workgroup's sum into the slab, their fold into slot 0 of the zeroed slots
-      hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, T->det_slab.get());
-      det_fold(1, (int64_t)512 * np, ssq, 0);
-    } else
-    hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
-    const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
-    hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, ssq, red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1, tc.beta2,
-                       tc.epsilon);
-    return tt.wmax != nullptr;
-  }
+  bool optimizer() { return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0); }
 };
 
 }  // namespace
@@ -1116,11 +1149,12 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
   }
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
-  if (apply) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
+  if (apply == 1) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_step: batch too large for the dropout counter");
   Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply, csr};
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
+  T->pending = false;      // (the gradient buffers are zeroed next: what a coper_train_backward left in them is gone)
   st.zero_accumulators();
   if (st.lk && (rc = st.group_for_lookup())) return rc;
 
@@ -1148,6 +1182,12 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   st.sj.join(SJ_DP);      // (dP and its squared norm)
   st.sj.join(SJ_SCORER_BWD);
   if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_step: an event call of the side streams failed");
+  if (apply == 2) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
+    COPER_HIP_TRY(h, hipGetLastError());
+    T->step += 1;
+    T->pending = true;
+    return COPER_OK;
+  }
   const bool wmax_carried = st.optimizer();
   COPER_HIP_TRY(h, hipGetLastError());
   T->b1p *= T->cfg.beta1;
@@ -1183,6 +1223,101 @@ COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const 
   if (!h) return COPER_EINVAL;
   if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
   return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 0, pred_out, h_out, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+}
+
+// ---- the split step: backward | export | apply (include/coper_hip.h, "The step in three calls")
+COPER_API int coper_train_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
+                                   int64_t B, int64_t L, float* loss_out, void* stream) {
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 2, nullptr, nullptr);
+}
+
+COPER_API int coper_train_backward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
+                                       const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_backward_csr: bad argument (lab_indptr is NULL)");
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 2, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+}
+
+COPER_API int coper_train_grads_layout(coper_handle* h, const char* leaf_name, int64_t* offset, int64_t* n, int64_t* total) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_layout: call coper_train_init first");
+  if (total) *total = T->flat_total;
+  if (!leaf_name) return COPER_OK;
+  const TrainParam* t = T->find(leaf_name);
+  if (!t) return fail(h, COPER_EINVAL, std::string("coper_train_grads_layout: not a trainable leaf: ") + leaf_name);
+  if (offset) *offset = t->flat_off;
+  if (n) *n = t->n;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap, int32_t accumulate, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
+  if (!flat || ((uintptr_t)flat & 15) != 0) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat must be a 16-byte aligned device buffer");
+  if (cap < T->flat_total) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat holds fewer than coper_train_grads_layout's total");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  ExportList el;
+  const int np = (int)T->tp.size();
+  el.table = -1; el.rowlen = 1; el.rowcnt = nullptr;
+  for (int i = 0; i < np; ++i) {
+    const TrainParam& t = T->tp[i];
+    el.g[i] = t.g; el.off[i] = t.flat_off; el.n[i] = t.n; el.span[i] = (t.n + 63) / 64 * 64;
+    if (h->dm.lookup && h->dm.gen_fc && &t == T->lv.fc_weights) {      // rows of relations absent from the backward's batch: zeros
+      el.table = i; el.rowlen = h->dm.F * (int64_t)h->dm.d; el.rowcnt = T->step_rel_count;
+    }
+  }
+  if (accumulate) hipLaunchKernelGGL(k_tr_grads_export<true>, dim3(1024, (unsigned)np), dim3(256), 0, (hipStream_t)stream, el, flat);
+  else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, (hipStream_t)stream, el, flat);
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
+}
+
+COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, double scale, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
+  if (!flat && !T->pending)
+    return fail(h, COPER_ESTATE, "coper_train_apply: no gradients pending (no coper_train_backward since the last update, step, forward or init)");
+  if (flat && (n != T->flat_total || ((uintptr_t)flat & 15) != 0))
+    return fail(h, COPER_EINVAL, "coper_train_apply: flat must be 16-byte aligned and n coper_train_grads_layout's total");
+  if (!std::isfinite(scale)) return fail(h, COPER_EINVAL, "coper_train_apply: scale is not finite");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  int rc;
+  if (T->det && (size_t)512 * TR_MAX_PARAMS > T->det_slab.size()) {      // (an apply from a flat vector on a handle that ran no backward yet)
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = T->det_slab.alloc(h, (size_t)512 * TR_MAX_PARAMS, "deterministic slabs"))) return rc;
+  }
+  h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
+  T->pending = false;    // (whatever follows: the gradients are consumed, or describe variables that are about to change)
+  // the squared-norm slots hold what the last backward's GEMM epilogues added, wmax[wmax_cur ^ 1] what the update before last left
+  const RedLayout red = T->red_layout();
+  ZeroList zl;
+  zl.n = 2;
+  zl.p[0] = red.sumsq_slots(); zl.bytes[0] = sizeof(double) * TG_SUMSQ_SLOTS;
+  zl.p[1] = T->wmax[T->wmax_cur ^ 1].get(); zl.bytes[1] = sizeof(unsigned) * TG_MAX_SLOTS;
+  hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
+  // the norm over every leaf (the epilogues' squares belonged to one backward); absent rows of the looked-up table by the backward's
+  // snapshot, never by the grouping workspace (an evaluation pass may have grouped since); from a flat vector every row is present:
+  // no counts at all, so the table takes the 16-byte routes of every other leaf (3.0 + 4.7 ms of k_tr_sumsq + k_tr_amsgrad through
+  // the row-count route at the FB15k-237 table) -- except in deterministic mode, where counts of one keep it on the
+  // fused step's route and in its summation order
+  const int32_t* const counts = flat ? (T->det ? T->all_rel_count.get() : nullptr) : T->step_rel_count.get();
+  const bool wmax_carried = optimizer_launch(h, T, s, flat, nullptr, counts, scale);
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->b1p *= T->cfg.beta1;
+  T->b2p *= T->cfg.beta2;
+  T->wmax_cur ^= 1;
+  T->wmax_valid = wmax_carried;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_wmax_carried(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->wmax_valid ? 1 : 0) : -COPER_ESTATE;
 }
 
 COPER_API int coper_train_deterministic(const coper_handle* h) {

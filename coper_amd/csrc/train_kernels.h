@@ -1310,8 +1310,10 @@ __global__ __launch_bounds__(256) void k_tr_sumsq(TrainTensors tt, int skip, dou
 }
 
 // tf.clip_by_global_norm + AMSGrad (amsgrad.py:130-159), all in one pass over the parameters
+// gs (coper_train_apply's `scale`): the gradient applied is gs * g, its norm |gs| * |g|; the element factor gs * clip / max(norm, clip)
+// is formed once, in double -- gs == 1 (the fused step) multiplies by an exact 1 and leaves the factor's bits what they were
 __global__ __launch_bounds__(256) void k_tr_amsgrad(TrainTensors tt, const double* __restrict__ ssq, double* __restrict__ total,
-                                                    float clip, float lr_t, float b1, float b2, float eps) {
+                                                    float clip, float lr_t, float b1, float b2, float eps, double gs) {
   float* p = tt.p[blockIdx.y];
   const float* g = tt.g[blockIdx.y];
   float* m = tt.m[blockIdx.y];
@@ -1320,9 +1322,9 @@ __global__ __launch_bounds__(256) void k_tr_amsgrad(TrainTensors tt, const doubl
   const int64_t n = tt.n[blockIdx.y];
   double ss = 0;   // the slots in index order: every thread of every workgroup forms the same sum
   for (int i = 0; i < TG_SUMSQ_SLOTS; ++i) ss += ssq[i];
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *total = ss;   // what coper_train_grad reports
-  const double gn = sqrt(ss);
-  const float scale = (float)((double)clip / (gn > (double)clip ? gn : (double)clip));
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *total = ss * gs * gs;   // what coper_train_grad reports
+  const double gn = fabs(gs) * sqrt(ss);
+  const float scale = (float)(gs * (double)clip / (gn > (double)clip ? gn : (double)clip));
   const int32_t* rc = tt.rowcnt[blockIdx.y];
   const int64_t rl = tt.rowlen[blockIdx.y];
   // dense tensors (every gradient row exists): four elements per thread and step as 16-byte accesses -- nine streams of 4 bytes
@@ -1430,6 +1432,75 @@ __global__ __launch_bounds__(256) void k_tr_add_bias_out(const float* __restrict
 __global__ __launch_bounds__(256) void k_tr_zero_absent_rows(float* __restrict__ out, const int32_t* __restrict__ rowcnt, int64_t rowlen, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     if (rowcnt[i / rowlen] == 0) out[i] = 0.f;
+}
+
+// coper_train_grads_export: every trainable leaf's gradient into its slice of the flat gradient vector, one launch (blockIdx.y = leaf).
+// flat[off + i] = g[i], or += g[i] (ACC); the pad behind a leaf (up to the next multiple of 64 floats) is written as 0.  One thread
+// owns an element: no atomics, one defined order in either form.  The looked-up dense table (leaf `table`) hands out the rows of
+// relations absent from the batch as zeros by the step's relation counts (ACC: they add nothing) -- the only leaf that pays the
+// row test.  16-byte accesses, four of them in flight per thread; the scalar loop takes a leaf's last n % 4 elements and the pad.
+struct ExportList {
+  const float* g[TR_MAX_PARAMS];
+  int64_t off[TR_MAX_PARAMS];    // multiples of 64 floats: a 16-byte aligned `flat` keeps every slice 16-byte aligned
+  int64_t n[TR_MAX_PARAMS];
+  int64_t span[TR_MAX_PARAMS];   // n rounded up to a multiple of 64: the slice with its pad
+  int table;                     // -1: none
+  int64_t rowlen;
+  const int32_t* rowcnt;
+};
+template <bool ACC>
+__global__ __launch_bounds__(256) void k_tr_grads_export(ExportList el, float* __restrict__ flat) {
+  const int y = blockIdx.y;
+  const float* __restrict__ g = el.g[y];
+  float* __restrict__ out = flat + el.off[y];
+  const int64_t n = el.n[y], span = el.span[y];
+  const int64_t st = (int64_t)gridDim.x * 256, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t n4 = ((uintptr_t)g & 15) == 0 ? n >> 2 : 0;
+  const float4* g4 = (const float4*)g;
+  float4* o4 = (float4*)out;
+  auto put = [&](int64_t j, const float4& v) {
+    if constexpr (ACC) { const float4 o = o4[j]; o4[j] = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w); }
+    else o4[j] = v;
+  };
+  if (y == el.table) {
+    const int64_t rl = el.rowlen;
+    const int32_t* __restrict__ rc = el.rowcnt;
+    for (int64_t j = i; j < n4; j += st) {
+      const int64_t e = j * 4, row = e / rl, rem = e - row * rl;
+      if (rem + 3 < rl) {      // the four elements lie in one row
+        if (rc[row] != 0) put(j, g4[j]);
+        else if (!ACC) o4[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {                 // a row boundary inside: element by element
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const bool present = rc[(e + u) / rl] != 0;
+          if constexpr (ACC) { if (present) out[e + u] += g[e + u]; }
+          else out[e + u] = present ? g[e + u] : 0.f;
+        }
+      }
+    }
+  } else {
+    int64_t j = i;
+    for (; j + 3 * st < n4; j += 4 * st) {
+      const float4 v0 = g4[j], v1 = g4[j + st], v2 = g4[j + 2 * st], v3 = g4[j + 3 * st];
+      if constexpr (ACC) {
+        const float4 a0 = o4[j], a1 = o4[j + st], a2 = o4[j + 2 * st], a3 = o4[j + 3 * st];
+        o4[j] = make_float4(a0.x + v0.x, a0.y + v0.y, a0.z + v0.z, a0.w + v0.w);
+        o4[j + st] = make_float4(a1.x + v1.x, a1.y + v1.y, a1.z + v1.z, a1.w + v1.w);
+        o4[j + 2 * st] = make_float4(a2.x + v2.x, a2.y + v2.y, a2.z + v2.z, a2.w + v2.w);
+        o4[j + 3 * st] = make_float4(a3.x + v3.x, a3.y + v3.y, a3.z + v3.z, a3.w + v3.w);
+      } else {
+        o4[j] = v0; o4[j + st] = v1; o4[j + 2 * st] = v2; o4[j + 3 * st] = v3;
+      }
+    }
+    for (; j < n4; j += st) put(j, g4[j]);
+  }
+  for (int64_t e = 4 * n4 + i; e < span; e += st) {
+    if (e >= n) { out[e] = 0.f; continue; }      // the pad
+    const bool present = y != el.table || el.rowcnt[e / el.rowlen] != 0;
+    if constexpr (ACC) { if (present) out[e] += g[e]; }
+    else out[e] = present ? g[e] : 0.f;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

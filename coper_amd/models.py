@@ -884,6 +884,7 @@ class ConvE(object):
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
+        self._grads_layout = None
         return self
 
     @property
@@ -910,6 +911,20 @@ class ConvE(object):
         (models.py:139-152): e1, rel [B]; lookup_values int32 [B,L]; e2_multi float [B,L].  1-vs-all batches may carry their labels
         as id lists instead of a dense e2_multi [B, num_ent]: `lab_indptr`, `lab_idx` (+ `lab_row`), coper_train_step_csr.  Returns the
         loss as a 1-element device tensor (no synchronisation)."""
+        self._train_dispatch(batch, self._lib.coper_train_step, self._lib.coper_train_step_csr)
+        self._after_update()
+        return self._train_loss
+
+    def _after_update(self):
+        """The variables changed under the registered tensors (raw-pointer writes: no version counter moved)."""
+        self._prepared = False       # caches are stale; the next inference call prepares again
+        self._ent_absmax_cache = None
+        self._versions = {n: _version(t) for n, t in self._tensors.items()}
+
+    def _train_dispatch(self, batch, dense_fn, csr_fn):
+        """Routes a training batch in any of its three label forms (sampled lookup, dense 1-vs-all, sparse 1-vs-all) to the
+        step-shaped call `dense_fn` (the arguments of coper_train_step) or `csr_fn` (those of coper_train_step_csr); the loss lands
+        in self._train_loss."""
         if getattr(self, "_train_loss", None) is None:
             raise _lib.CoperError(5, "call train_init() first")
         e1, rel = self._ids(batch["e1"]), self._ids(batch["rel"])
@@ -920,12 +935,9 @@ class ConvE(object):
             ip, ix, row, n_rows = self._csr_labels(batch, B)
             self._sync_parameters()
             with torch.cuda.device(self.device):
-                _lib.check(self._h, self._lib.coper_train_step_csr(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), _ptr(row), n_rows, B,
-                                                                   _ptr(self._train_loss), self._stream()))
-            self._prepared = False
-            self._ent_absmax_cache = None
-            self._versions = {n: _version(t) for n, t in self._tensors.items()}
-            return self._train_loss
+                _lib.check(self._h, csr_fn(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), _ptr(row), n_rows, B,
+                                           _ptr(self._train_loss), self._stream()))
+            return
         lv = batch.get("lookup_values", None)
         one_vs_all = lv is None or (hasattr(lv, "shape") and len(lv.shape) == 2 and lv.shape[1] == 0)   # data.py:322
         lookup = None if one_vs_all else self._ids(lv, torch.int32)
@@ -937,12 +949,73 @@ class ConvE(object):
             raise ValueError("training batch: e1, rel [B]; lookup_values and e2_multi [B, L] (or e2_multi [B, num_ent] alone)")
         self._sync_parameters()      # (the step packs the dense weights by the magnitude the last step left: include/coper_hip.h)
         with torch.cuda.device(self.device):
-            _lib.check(self._h, self._lib.coper_train_step(self._h, _ptr(e1), _ptr(rel), _ptr(lookup), _ptr(labels), B, L,
-                                                           _ptr(self._train_loss), self._stream()))
-        self._prepared = False       # caches are stale; the next inference call prepares again
-        self._ent_absmax_cache = None
-        self._versions = {n: _version(t) for n, t in self._tensors.items()}
+            _lib.check(self._h, dense_fn(self._h, _ptr(e1), _ptr(rel), _ptr(lookup), _ptr(labels), B, L,
+                                         _ptr(self._train_loss), self._stream()))
+
+    # ---- the step in three calls (include/coper_hip.h: backward | export | apply)
+    def train_backward(self, batch):
+        """coper_train_backward / _csr: train_step without the update.  Routes batches like train_step; the loss, the BN moving
+        statistics and the dropout counter move, the gradients stay on the handle for train_grads_export / train_apply, no variable
+        changes and the model stays prepared (an evaluation in between folds BN from the moving statistics as the last prepare()
+        found them: call prepare() where the one momentum step matters).  Returns the loss as a 1-element device tensor (no synchronisation)."""
+        self._train_dispatch(batch, self._lib.coper_train_backward, self._lib.coper_train_backward_csr)
         return self._train_loss
+
+    def train_grads_layout(self):
+        """The flat gradient vector: ({leaf: (offset, n)} in coper_param_spec order, total length in floats).  Every leaf starts at
+        a multiple of 64 floats; the pad behind it is exported as zeros."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        if getattr(self, "_grads_layout", None) is not None:      # (fixed at train_init)
+            return dict(self._grads_layout[0]), self._grads_layout[1]
+        off, n, total = C.c_int64(), C.c_int64(), C.c_int64()
+        out = {}
+        for leaf in self._specs:
+            if leaf.endswith(("moving_mean", "moving_variance")):
+                continue
+            _lib.check(self._h, self._lib.coper_train_grads_layout(self._h, leaf.encode(), C.byref(off), C.byref(n), C.byref(total)))
+            out[leaf] = (off.value, n.value)
+        _lib.check(self._h, self._lib.coper_train_grads_layout(self._h, None, None, None, C.byref(total)))
+        self._grads_layout = (out, total.value)
+        return dict(out), total.value
+
+    @property
+    def train_wmax_carried(self):
+        """coper_train_wmax_carried: 1 when the next step packs the dense weights by the maximum the last optimizer pass recorded
+        (no pass over them), 0 when it will scan them -- diagnostics."""
+        v = self._lib.coper_train_wmax_carried(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
+
+    def train_grads_export(self, out=None, accumulate=False):
+        """coper_train_grads_export: the gradients the last backward (or step) left, as one flat float32 device vector: `out = g`, or
+        `out += g` with accumulate.  out=None allocates it (zeros when accumulating).  Returns `out`."""
+        if getattr(self, "_grads_layout", None) is None:
+            self.train_grads_layout()
+        total = self._grads_layout[1]
+        if out is None:
+            out = (torch.zeros if accumulate else torch.empty)(total, device=self.device, dtype=torch.float32)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.device != torch.device(self.device):
+            raise ValueError("train_grads_export: out must be a contiguous float32 tensor on the model's device")
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_grads_export(self._h, _ptr(out), out.numel(), 1 if accumulate else 0, self._stream()))
+        return out
+
+    def train_apply(self, flat=None, scale=1.0):
+        """coper_train_apply: clip + AMSGrad on the pending gradients of the last train_backward (flat=None), or on a flat gradient
+        vector (read in place; no backward needed).  `scale` multiplies the gradient before the clip: 1 / (micro-batches * ranks)
+        turns an accumulated, all-reduced sum into the mean."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        if flat is not None and (flat.dtype != torch.float32 or not flat.is_contiguous() or flat.device != torch.device(self.device)):
+            raise ValueError("train_apply: flat must be a contiguous float32 tensor on the model's device")
+        self._sync_parameters()
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_apply(self._h, _ptr(flat), flat.numel() if flat is not None else 0, float(scale),
+                                                            self._stream()))
+        self._after_update()
+        return self
 
     def train_forward(self, batch, want_predictions=False, want_h=False):
         """The training-mode graph without the update (coper_train_forward): `session.run(model.loss | model.predictions_lookup |

@@ -1,0 +1,151 @@
+"""Data-parallel training and gradient accumulation over the split step (include/coper_hip.h: coper_train_backward |
+coper_train_grads_export | coper_train_apply).
+
+Every rank holds a full replica of the model (`ConvE` after `train_init`).  An update is: per micro-batch a backward pass and an
+export that ADDS its gradient into one flat vector, ONE all-reduce (sum) of that vector over the ranks, then the optimizer on the sum
+scaled by 1 / (ranks * micro-batches).  The replicas start equal (rank 0's state is broadcast) and stay equal, because every rank
+applies the same bytes.  Entity-sharded (model-parallel) training is not built, the all-reduce does not overlap the backward pass,
+and there is no SyncBN.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .models import _ptr
+
+_PER_SAMPLE = ("e1", "rel", "lookup_values", "e2_multi", "lab_row")
+
+
+def shard_batch(batch, rank, world):
+    """Rank `rank`'s even slice of a training batch dict, in any of the three label forms `ConvE.train_step` takes: sampled
+    (`lookup_values`, `e2_multi` [B, L]), dense 1-vs-all (`e2_multi` [B, num_ent]) and sparse 1-vs-all (`lab_indptr`, `lab_idx`,
+    optional `lab_row`).  A sparse batch keeps its label table -- the same objects, not copies -- and slices `lab_row` (a batch
+    without one gets the row numbers of the slice).  B % world != 0 raises ValueError: every rank reports the MEAN loss of its
+    shard, and the mean of shard means is the batch mean only for equal shards."""
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("shard_batch: rank %d of world %d" % (rank, world))
+    B = len(batch["e1"])
+    if B % world:
+        raise ValueError("shard_batch: a batch of %d does not split evenly over %d ranks" % (B, world))
+    n = B // world
+    lo, hi = rank * n, (rank + 1) * n
+    out = {k: (v[lo:hi] if k in _PER_SAMPLE and v is not None else v) for k, v in batch.items()}
+    if "e2_multi" not in batch and "lab_indptr" in batch and batch.get("lab_row", None) is None:
+        ip = batch["lab_indptr"]
+        out["lab_row"] = (torch.arange(lo, hi, dtype=torch.int64, device=ip.device) if isinstance(ip, torch.Tensor)
+                          else np.arange(lo, hi, dtype=np.int64))
+    return out
+
+
+class DataParallelTrainer(object):
+    """`DataParallelTrainer(model, group=None, micro_batches=1)`: one replica per rank of a `torch.distributed` process group
+    (`group=None`: the default group; no initialised process group at all: one process, plain gradient accumulation).
+
+    Construction broadcasts rank 0's variables (BN moving statistics included), AMSGrad slots, beta powers and dropout counter.
+    `step(batches)` takes this rank's list of `micro_batches` local batches and makes one update:
+
+      * per micro-batch `train_backward` + `train_grads_export(accumulate)` into one flat vector;
+      * ONE `all_reduce(SUM)` of the flat vector;
+      * `train_apply(flat, 1 / (world * micro_batches))`: the clip acts on the norm of the MEAN gradient;
+      * the BN moving statistics, which every rank updated from its own batches, are averaged over the ranks in one small
+        all-reduce (the loss rides in it), so the replicas stay equal.
+
+    Batch statistics are per rank and per micro-batch, as in torch's DistributedDataParallel without SyncBN: a rank normalises by
+    the statistics of the micro-batch in front of it, never by the global batch's.  The gradient is therefore the mean of the
+    micro-batch gradients, not the gradient of the concatenated batch, wherever batch statistics are on.
+
+    Dropout masks are a function of (seed, dropout counter, element): ranks draw DIFFERENT masks only if the caller gave them
+    different seeds -- `model.train_init(seed=s + rank)`.  With one seed every rank drops the same positions of its own shard.
+
+    The averaged moving statistics are written into the caller's tensors in place.  That moves their version counters, and the
+    model registers them again (coper_set_param); registering a moving statistic again does not discard what the optimizer's
+    last pass recorded about the dense weights (their largest magnitude, which the next step's operand packing scales by)."""
+
+    def __init__(self, model, group=None, micro_batches=1):
+        import torch.distributed as dist
+        if getattr(model, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        self.model = model
+        self.micro_batches = int(micro_batches)
+        if self.micro_batches < 1:
+            raise ValueError("micro_batches >= 1")
+        self._dist = dist if dist.is_available() and dist.is_initialized() else None
+        if self._dist is None and group is not None:
+            raise ValueError("a process group needs torch.distributed to be initialised")
+        self.group = group
+        self.world = self._dist.get_world_size(group) if self._dist else 1
+        self.rank = self._dist.get_rank(group) if self._dist else 0
+        self.layout, total = model.train_grads_layout()
+        self.flat = torch.zeros(total, device=model.device, dtype=torch.float32)
+        self._stat_names = [k for k in model._tensors if k.endswith(("moving_mean", "moving_variance"))]
+        n_stats = sum(model._tensors[k].numel() for k in self._stat_names)
+        self._small = torch.zeros(n_stats + 1, device=model.device, dtype=torch.float32)      # moving statistics | loss
+        if self.world > 1:
+            self._broadcast_state()
+
+    # ---- construction
+    def _src(self):
+        return self._dist.get_global_rank(self.group, 0) if self.group is not None else 0
+
+    def _broadcast_state(self):
+        m, dist, src = self.model, self._dist, self._src()
+        for t in m._tensors.values():
+            dist.broadcast(t, src=src, group=self.group)
+        # (whether a collective into a tensor moves its version counter is the backend's business: register every tensor again --
+        #  stale inference caches, entity maximum and carried weight maximum go with it)
+        m.parameters_changed()
+        n = C.c_int64()
+        for leaf in m.trainable_leaves():
+            for which in range(3):
+                _lib.check(m._h, m._lib.coper_train_slot(m._h, leaf.encode(), which, None, 0, 0, C.byref(n), m._stream()))
+                buf = torch.empty(n.value, device=m.device, dtype=torch.float32)
+                _lib.check(m._h, m._lib.coper_train_slot(m._h, leaf.encode(), which, _ptr(buf), n.value, 0, C.byref(n), m._stream()))
+                dist.broadcast(buf, src=src, group=self.group)
+                _lib.check(m._h, m._lib.coper_train_slot(m._h, leaf.encode(), which, _ptr(buf), n.value, 1, C.byref(n), m._stream()))
+                torch.cuda.current_stream(m.device).synchronize()      # buf may be freed after this
+        b1, b2, st = C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(m._h, m._lib.coper_train_powers(m._h, None, None, None, C.byref(b1), C.byref(b2), C.byref(st)))
+        pw = torch.tensor([b1.value, b2.value, float(st.value)], dtype=torch.float64, device=m.device)
+        dist.broadcast(pw, src=src, group=self.group)
+        b1v, b2v, stv = pw.cpu().tolist()
+        b1, b2, st = C.c_double(b1v), C.c_double(b2v), C.c_int64(int(stv))
+        _lib.check(m._h, m._lib.coper_train_powers(m._h, C.byref(b1), C.byref(b2), C.byref(st), None, None, None))
+
+    # ---- one update
+    def step(self, batches):
+        """One update from this rank's `micro_batches` local batches (a list; a single dict when micro_batches == 1).  Returns
+        the loss averaged over ranks and micro-batches as a 1-element device tensor (no synchronisation of the host)."""
+        m = self.model
+        if isinstance(batches, dict):
+            batches = [batches]
+        if len(batches) != self.micro_batches:
+            raise ValueError("step: %d local batches, micro_batches = %d" % (len(batches), self.micro_batches))
+        small = self._small
+        loss = small[-1:]
+        for i, b in enumerate(batches):
+            li = m.train_backward(b)
+            m.train_grads_export(self.flat, accumulate=i > 0)
+            if i:
+                loss += li
+            else:
+                loss.copy_(li)
+        if self.world > 1:
+            dist = self._dist
+            dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
+            at = 0
+            for k in self._stat_names:
+                t = m._tensors[k]
+                small[at:at + t.numel()].copy_(t.reshape(-1))
+                at += t.numel()
+            dist.all_reduce(small, op=dist.ReduceOp.SUM, group=self.group)
+            small[:-1] /= float(self.world)
+            at = 0
+            for k in self._stat_names:
+                t = m._tensors[k]
+                t.copy_(small[at:at + t.numel()].reshape(t.shape))
+                at += t.numel()
+        m.train_apply(self.flat, 1.0 / (self.world * self.micro_batches))
+        return loss / float(self.world * self.micro_batches)

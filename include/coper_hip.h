@@ -617,6 +617,51 @@ COPER_API int coper_train_step_csr(coper_handle* h, const int64_t* e1, const int
 COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr,
                                       const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out,
                                       float* pred_out, float* h_out, void* stream);
+/* The step in three calls: backward | export | apply.  coper_train_step stays what it is; these split it where a caller wants an
+ * update from several batches (accumulation) or from several replicas (data-parallel training: all-reduce between export and apply).
+ * The one object that crosses the boundary is the FLAT GRADIENT VECTOR: one device float buffer that holds every trainable leaf's
+ * gradient, which the caller may add to, all-reduce or keep.
+ *
+ * coper_train_backward / coper_train_backward_csr: the arguments, routes, refusals and side streams of coper_train_step /
+ *   coper_train_step_csr, and everything they do up to the optimizer: the loss, the BN moving-statistics update, the dropout counter
+ *   advanced by one -- and the gradients, which stay in the handle's gradient buffers ("pending").  No variable, optimizer slot or
+ *   beta power is touched, and the handle stays prepared: evaluation between backward and apply needs no coper_prepare and changes
+ *   nothing that apply or export read (the batch's relation counts are kept apart, as for coper_train_grad).  The one thing such an
+ *   evaluation sees stale is BN: its folded scale and shift come from the moving statistics as the last coper_prepare found them,
+ *   one momentum step per backward behind the tensors.  Call coper_prepare where that matters.
+ * coper_train_grads_layout: where leaf `leaf_name` lies in the flat vector (*offset, *n floats) and the vector's length *total.  The
+ *   trainable leaves in coper_param_spec order, each starting at a multiple of 64 floats.  leaf_name == NULL: *total alone.  Any
+ *   output may be NULL.
+ * coper_train_grads_export: flat = g, or flat += g when accumulate != 0, over all leaves in one launch on `stream`.  Rows of the
+ *   looked-up dense table whose relation the backward's batch did not hold are exported as zeros (with accumulate they add
+ *   nothing); the pad behind every leaf is written as 0.  flat: device, 16-byte aligned, cap >= total floats; else COPER_EINVAL.
+ *   No atomics: one thread owns an element, in either form.
+ * coper_train_apply: the optimizer phase alone -- squared global norm, clip, AMSGrad; the beta powers advance, inference caches go
+ *   stale.  flat == NULL (n ignored): the pending gradients of the last coper_train_backward.  Otherwise the gradient is read from
+ *   `flat` in place (16-byte aligned, n == total; else COPER_EINVAL), every row present, and no backward is needed.  `scale`
+ *   multiplies the gradient before the clip: the norm, and what coper_train_grad reports as global_norm afterwards, is that of
+ *   scale * g; the element factor scale * clip / max(norm, clip) is formed once, in double (scale == 1: the bits of the fused step).
+ *   The mean over M accumulated micro-batches on W replicas is scale = 1 / (M W) on the all-reduced sum.
+ * State: apply consumes the pending gradients.  coper_train_apply(flat == NULL) without a coper_train_backward since the last
+ *   coper_train_apply, coper_train_step*, coper_train_forward* or coper_train_init is COPER_ESTATE: those calls zero the gradient
+ *   buffers (a half-zeroed gradient is never applied).  coper_train_powers' `step` counts backward passes (the dropout counter), the
+ *   beta powers count updates.
+ * Deterministic mode: every launch these calls add has one defined order, and coper_train_backward + coper_train_apply(NULL, 1), or
+ *   + coper_train_grads_export + coper_train_apply(flat, 1), leave the bits of coper_train_step in every output.  In the default mode
+ *   the split step's norm is summed in another order than the fused step's (whose GEMM epilogues add the dense weights' squares). */
+COPER_API int coper_train_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup,
+                                   const float* labels, int64_t B, int64_t L, float* loss_out, void* stream);
+COPER_API int coper_train_backward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr,
+                                       const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out,
+                                       void* stream);
+COPER_API int coper_train_grads_layout(coper_handle* h, const char* leaf_name, int64_t* offset, int64_t* n, int64_t* total);
+COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap, int32_t accumulate, void* stream);
+COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, double scale, void* stream);
+/* Diagnostics: 1 when the next step will scale the dense weights' operand packing by the maximum the last optimizer pass recorded as
+ * it wrote them (no pass over the weights), 0 when it will scan them (before the first update; after coper_set_param of a TRAINABLE
+ * leaf -- registering a BN moving statistic again leaves it at 1: it says nothing about the weights; looked-up dense tables, which
+ * are not packed, report 0); -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle. */
+COPER_API int coper_train_wmax_carried(const coper_handle* h);
 /* Diagnostics: copies the (unclipped) gradient of the last step for a trainable leaf into `out` (device float
  * buffer of `cap` elements; may be NULL), returns its length in *n, and in *global_norm (optional, host) the
  * global gradient norm of the last step (synchronises).  The looked-up dense table's rows of relations the last batch did not hold are
