@@ -1176,18 +1176,41 @@ __global__ __launch_bounds__(256) void k_band_excess_bf16x3(const uint4* __restr
 // place band_exact_body decodes the band bits from: tile q / 128, row of a wave f / (32 MB), lane 16 ((f / 4) & 3) + (q & 15),
 // value V = 4 MB ((q & 127) / 16) + 4 ((f / 16) & (MB - 1)) + (f & 3) of block M = (f / (16 MB)) & 1: word MB M + (V >> 5), bit
 // 31 - (V & 31).  Set bits are taken back from ranks[q].  Entries inside the band are not gt: the band walk passes them over as
-// known answers, as it always did.  A wave owns BL_QW consecutive queries -- their entries are contiguous, 64 per round, each lane
-// finds its entry's query by binary lifting over the first entries the lanes hold -- and every run of one query subtracts once.
+// known answers, as it always did.  A wave owns BL_WQ = 32 consecutive queries, two ranges of BL_QW = 16 -- their entries are
+// contiguous, 64 per round, each lane finds its entry's query by binary lifting over the first entries the lanes hold -- and every
+// run of one query subtracts once.  (Two ranges a wave: 160 workgroups of the role at 20,480 queries, which with the 290 of the
+// band walk are resident at once, two to a CU; one range a wave made 610, and the last 98 waited for a CU.)
 // Long rows (real KGs hold (e1, rel) pairs with thousands of known tails: the reason for the excess role above): a wave takes back
-// the first BL_OWN entries of its 16 queries itself; what lies beyond is dealt, 64 entries at a time, over ALL waves of the role.
-// No list and no hand-over between workgroups: every wave reads the first entry of every 16-query range of the launch (one indptr
-// word in 16: 1,281 words at 20,480 queries, independent loads) and finds the long ranges itself; tile t of the excess of range r
-// belongs to wave (t + 61 r) mod G, as the excess role deals its tiles.
+// the first BL_OWN entries of each of its two ranges itself; what lies beyond is dealt, 64 entries at a time, over ALL waves of the
+// role: tile t of the excess of range r belongs to wave (t + 61 r) mod G, as the excess role deals its tiles.  No list and no
+// hand-over between workgroups: every WORKGROUP finds the long ranges of the launch itself, from the first entry of every range
+// (one indptr word in 16: 1,281 words at 20,480 queries).  It scans in batches of BL_SCAN_N = 2,048 ranges, chunk c (64 ranges, one
+// a lane) of a batch by wave c & 3: a wave issues the BL_SCAN_R loads of its chunks -- a lane takes its range's end from the lane
+// above, lane 63 from one more load per chunk, the end of the chunk's last range -- BEFORE its own entries, so that the scan of a
+// launch of up to 32,768 queries is one round trip that the wave's own work hides (it was a round trip per 64 ranges in every
+// wave: twenty, one after the other, behind the own entries); the ballots go through 2 x 32 words of LDS and one barrier a batch
+// (the batches alternate between the two halves: a wave that writes batch b + 2 has passed the barrier of b + 1, which every wave
+// reaches with batch b's words in registers).  Every loop is bounded by its trip count.
 constexpr int BL_QW = 16;
+constexpr int BL_WQ = 2 * BL_QW;                                      // queries of a wave
 constexpr int64_t BL_OWN = 256;
-// one round: entries [pb, min(pb + 64, p_lim)) of the range whose queries start at qw0 (lane j < nq: my_lo = the first entry of
-// query qw0 + j, my_e2 its target; lanes beyond: my_lo = the range's end)
-template <int PL>
+constexpr int BL_SCAN_R = 8;                                          // chunks of 64 ranges a wave scans per batch
+constexpr int BL_SCAN_N = 4 * 64 * BL_SCAN_R;                         // ranges of a batch
+#ifdef COPER_DBG_BL_CLOCK
+// diagnostic build (tools/ab_build.py, tools/ab_band_lookup.py): s_memrealtime (100 MHz) of thread 0 of every workgroup of the
+// launch; g_bl_clk[blockIdx.x] = {start, own entries done, scan for long ranges done, end} in a look-up workgroup, {start, -, -,
+// end} in a band workgroup.  No output depends on them.
+constexpr int BL_NSTAMP = 4;
+__device__ unsigned long long g_bl_clk[BL_NSTAMP * 1024];
+__device__ int g_bl_grid[2];                                          // {n_band, workgroups of the launch}
+#define BL_STAMP(i_)                                                                                         \
+  if (threadIdx.x == 0 && blockIdx.x < 1024) g_bl_clk[BL_NSTAMP * blockIdx.x + (i_)] = __builtin_amdgcn_s_memrealtime();
+#else
+#define BL_STAMP(i_)
+#endif
+// one round: entries [pb, min(pb + 64, p_lim)) of the NQ queries (16: a range, 32: a wave's two) that start at qw0 (lane j < nq:
+// my_lo = the first entry of query qw0 + j, my_e2 its target; lanes beyond: my_lo = the end of the last query's entries)
+template <int PL, int NQ>
 __device__ __forceinline__ void band_lookup_round(const unsigned* __restrict__ words, const unsigned rows4, const BandArgs& A, const int64_t qw0,
                                                   const int64_t my_lo, const int64_t my_e2, const int64_t pb, const int64_t p_lim, const int lane) {
   constexpr int MB = SC3_MB;
@@ -1196,7 +1219,7 @@ __device__ __forceinline__ void band_lookup_round(const unsigned* __restrict__ w
   const bool valid = p < p_lim;
   int qi = 0;                                                         // the last j with first entry <= p
 #pragma unroll
-  for (int step = BL_QW / 2; step >= 1; step >>= 1) {
+  for (int step = NQ / 2; step >= 1; step >>= 1) {
     const int64_t first = __shfl(my_lo, qi + step);
     qi = (valid && first <= p) ? qi + step : qi;
   }
@@ -1226,56 +1249,144 @@ __device__ __forceinline__ void band_lookup_round(const unsigned* __restrict__ w
   }
 }
 
+// the scan's loads of batch b in this wave: v[k] = the first entry of range b BL_SCAN_N + 64 (4 k + wave) + lane, e[k] the end of
+// the chunk's last range (one address for the wave; a load under `lane == 63` made the compiler wait for each before the next);
+// ranges beyond the launch read indptr[Bc] on both sides and are not long
+__device__ __forceinline__ void band_lookup_scan_loads(const BandArgs& A, const int64_t b, const int wave, const int lane,
+                                                       int64_t (&v)[BL_SCAN_R], int64_t (&e)[BL_SCAN_R]) {
+#pragma unroll
+  for (int k = 0; k < BL_SCAN_R; ++k) {
+    const int64_t r0 = b * BL_SCAN_N + 64 * (4 * k + wave);           // (wave-uniform)
+    const int64_t qa = (r0 + lane) * BL_QW, qe = (r0 + 64) * BL_QW;
+    v[k] = A.indptr[qa < A.Bc ? qa : A.Bc];
+    e[k] = A.indptr[qe < A.Bc ? qe : A.Bc];
+  }
+}
+
 template <int PL>
 __device__ __forceinline__ void band_lookup_body(const unsigned* __restrict__ words, const unsigned rows4, const BandArgs& A, const int64_t wg,
-                                                 const int64_t n_wg) {
+                                                 const int64_t n_wg, unsigned long long (&s_long)[2][4 * BL_SCAN_R]) {
+  static_assert(4 * BL_SCAN_R <= 64, "a lane reads one chunk's word");
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int64_t me = wg * 4 + wave, G = n_wg * 4;
-  // ---- the wave's own 16 queries: the first BL_OWN of their entries
-  const int64_t qw0 = me * BL_QW;
+  BL_STAMP(0);
+  const int64_t n_ranges = (A.Bc + BL_QW - 1) / BL_QW;
+  int64_t v[BL_SCAN_R], e[BL_SCAN_R];
+  band_lookup_scan_loads(A, 0, wave, lane, v, e);                     // in flight while the wave takes its own entries
+  // ---- the wave's own 32 queries: the first BL_OWN entries of each of their two ranges
+  const int64_t qw0 = me * BL_WQ;
   if (qw0 < A.Bc) {
-    const int64_t qw1 = qw0 + BL_QW < A.Bc ? qw0 + BL_QW : A.Bc;
+    const int64_t qw1 = qw0 + BL_WQ < A.Bc ? qw0 + BL_WQ : A.Bc;
     const int nq = (int)(qw1 - qw0);
     const int64_t p_end = A.indptr[qw1];
     const int64_t my_lo = lane < nq ? A.indptr[qw0 + lane] : p_end;
     const int64_t my_e2 = lane < nq ? A.e2[qw0 + lane] : -1;
-    const int64_t p_begin = __shfl(my_lo, 0);
-    const int64_t p_lim = p_end - p_begin > BL_OWN ? p_begin + BL_OWN : p_end;
-    for (int64_t pb = p_begin; pb < p_lim; pb += 64)                  // (wave-uniform)
-      band_lookup_round<PL>(words, rows4, A, qw0, my_lo, my_e2, pb, p_lim, lane);
+    const int64_t p_begin = __shfl(my_lo, 0), p_mid = __shfl(my_lo, BL_QW);       // (one range only: p_mid = p_end)
+    const int64_t lim_a = p_mid - p_begin > BL_OWN ? p_begin + BL_OWN : p_mid;
+    const int64_t lim_b = p_end - p_mid > BL_OWN ? p_mid + BL_OWN : p_end;
+    // The first range is not long (every pass of the benchmark): its entries and the second range's own share are contiguous in
+    // the CSR and are taken as ONE run, [p_begin, lim_b) -- a round of 64 entries may then hold entries of both ranges, and the
+    // round's search over the 32 lanes' row starts (band_lookup_round) finds each entry's query across the ranges' border as it
+    // does within a range.  The first range is long: its own share ends at lim_a, and the second range's is a run of its own.
+    const int64_t lim0 = lim_a == p_mid ? lim_b : lim_a;
+    for (int64_t pb = p_begin; pb < lim0; pb += 64)                                // (wave-uniform)
+      band_lookup_round<PL, BL_WQ>(words, rows4, A, qw0, my_lo, my_e2, pb, lim0, lane);
+    if (lim_a != p_mid)
+      for (int64_t pb = p_mid; pb < lim_b; pb += 64)
+        band_lookup_round<PL, BL_WQ>(words, rows4, A, qw0, my_lo, my_e2, pb, lim_b, lane);
   }
-  // ---- the excess of long ranges, found by every wave for itself
-  const int64_t n_ranges = (A.Bc + BL_QW - 1) / BL_QW;
-  for (int64_t r0 = 0; r0 < n_ranges; r0 += 64) {
-    const int64_t r = r0 + lane;
-    bool is_long = false;
-    if (r < n_ranges) {
-      const int64_t qa = r * BL_QW, qb = qa + BL_QW < A.Bc ? qa + BL_QW : A.Bc;
-      is_long = A.indptr[qb] - A.indptr[qa] > BL_OWN;
+  BL_STAMP(1);
+  // ---- the excess of long ranges, found by the workgroup
+  for (int64_t b = 0;;) {                                             // (block-uniform: ceil(n_ranges / BL_SCAN_N) trips)
+    const int par = (int)(b & 1);
+#pragma unroll
+    for (int k = 0; k < BL_SCAN_R; ++k) {
+      int64_t hi = __shfl_down(v[k], 1);
+      if (lane == 63) hi = e[k];
+      const unsigned long long m = __ballot(hi - v[k] > BL_OWN);
+      if (lane == 0) s_long[par][4 * k + wave] = m;
     }
-    unsigned long long longs = __ballot(is_long);
-    while (longs) {                                                   // (wave-uniform)
-      const int64_t rr = r0 + __builtin_ctzll(longs);
-      longs &= longs - 1;
-      const int64_t qa = rr * BL_QW, qb = qa + BL_QW < A.Bc ? qa + BL_QW : A.Bc;
-      const int nq = (int)(qb - qa);
-      const int64_t p_end = A.indptr[qb];
-      const int64_t my_lo = lane < nq ? A.indptr[qa + lane] : p_end;
-      const int64_t my_e2 = lane < nq ? A.e2[qa + lane] : -1;
-      const int64_t p0 = __shfl(my_lo, 0) + BL_OWN;
-      const int64_t t0 = ((me - 61 * rr) % G + G) % G;
-      for (int64_t pb = p0 + 64 * t0; pb < p_end; pb += 64 * G)
-        band_lookup_round<PL>(words, rows4, A, qa, my_lo, my_e2, pb, p_end, lane);
+    __syncthreads();
+    const unsigned long long word = lane < 4 * BL_SCAN_R ? s_long[par][lane] : 0ull;
+    unsigned long long chunks = __ballot(word != 0ull);
+#ifdef COPER_DBG_BL_CLOCK
+    if ((b + 1) * BL_SCAN_N >= n_ranges) BL_STAMP(2);
+#endif
+    while (chunks) {                                                  // (wave-uniform)
+      const int c = __builtin_ctzll(chunks);
+      chunks &= chunks - 1;
+      unsigned long long longs = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)word, c) |
+                                 (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(word >> 32), c) << 32;
+      while (longs) {
+        const int64_t rr = b * BL_SCAN_N + 64 * c + __builtin_ctzll(longs);
+        longs &= longs - 1;
+        const int64_t qa = rr * BL_QW, qb = qa + BL_QW < A.Bc ? qa + BL_QW : A.Bc;
+        const int nq = (int)(qb - qa);
+        const int64_t p_end = A.indptr[qb];
+        const int64_t my_lo = lane < nq ? A.indptr[qa + lane] : p_end;
+        const int64_t my_e2 = lane < nq ? A.e2[qa + lane] : -1;
+        const int64_t p0 = __shfl(my_lo, 0) + BL_OWN;
+        const int64_t t0 = ((me - 61 * rr) % G + G) % G;
+        for (int64_t pb = p0 + 64 * t0; pb < p_end; pb += 64 * G)
+          band_lookup_round<PL, BL_QW>(words, rows4, A, qa, my_lo, my_e2, pb, p_end, lane);
+      }
     }
+    if (++b * BL_SCAN_N >= n_ranges) break;
+    band_lookup_scan_loads(A, b, wave, lane, v, e);
   }
+  BL_STAMP(3);
 }
 
 // the band walk of a count launch that stored its gt plane, with the look-up role in further workgroups of the same launch
 __global__ __launch_bounds__(256) void k_band_lookup_bf16x3(const uint4* __restrict__ mask, const unsigned long long* __restrict__ summ,
                                                             int64_t n_units, unsigned rows4, BandArgs A, int n_band) {
-  if ((int)blockIdx.x < n_band) band_exact_body<COPER_CHAIN_CB, sc3_planes(SC3_GT)>(mask, summ, n_units, rows4, A, blockIdx.x);
-  else band_lookup_body<sc3_planes(SC3_GT)>((const unsigned*)mask, rows4, A, (int64_t)blockIdx.x - n_band, (int64_t)gridDim.x - n_band);
+  __shared__ unsigned long long s_long[2][4 * BL_SCAN_R];
+#ifdef COPER_DBG_BL_CLOCK
+  if (blockIdx.x == 0 && threadIdx.x == 0) { g_bl_grid[0] = n_band; g_bl_grid[1] = (int)gridDim.x; }
+#endif
+  if ((int)blockIdx.x < n_band) {
+    BL_STAMP(0);
+    band_exact_body<COPER_CHAIN_CB, sc3_planes(SC3_GT)>(mask, summ, n_units, rows4, A, blockIdx.x);
+    BL_STAMP(3);
+  } else band_lookup_body<sc3_planes(SC3_GT)>((const unsigned*)mask, rows4, A, (int64_t)blockIdx.x - n_band, (int64_t)gridDim.x - n_band, s_long);
 }
+
+#ifdef COPER_DBG_BL_CLOCK
+// out[0..3] medians over the look-up workgroups of the four stamps, out[4..7] the latest of each (us from the earliest start of any
+// workgroup of the launch); [8], [9] first / last start of a look-up workgroup; [10] the launch's last end; [11] median end of a
+// band workgroup; [12], [13] band / look-up workgroups; [14], [15] median / longest scan (stamp 2 - stamp 1)
+extern "C" __attribute__((visibility("default"))) int coper_dbg_bl_clock(double* out) {
+  static unsigned long long hbuf[BL_NSTAMP * 1024];
+  int grid[2];
+  if (hipMemcpyFromSymbol(hbuf, HIP_SYMBOL(g_bl_clk), sizeof hbuf) != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(grid, HIP_SYMBOL(g_bl_grid), sizeof grid) != hipSuccess) return 1;
+  const int n_band = grid[0], n_wg = std::min(grid[1], 1024);
+  if (n_wg <= n_band) return 2;
+  unsigned long long t0 = ~0ull, t1 = 0;
+  for (int i = 0; i < n_wg; ++i) { t0 = std::min(t0, hbuf[BL_NSTAMP * i]); t1 = std::max(t1, hbuf[BL_NSTAMP * i + 3]); }
+  auto us = [&](unsigned long long t) { return (double)(t - t0) * 0.01; };
+  std::vector<double> v;
+  for (int j = 0; j < BL_NSTAMP; ++j) {
+    v.clear();
+    for (int i = n_band; i < n_wg; ++i) v.push_back(us(hbuf[BL_NSTAMP * i + j]));
+    std::sort(v.begin(), v.end());
+    out[j] = v[v.size() / 2];
+    out[BL_NSTAMP + j] = v.back();
+    if (j == 0) out[8] = v.front(), out[9] = v.back();
+  }
+  out[10] = us(t1);
+  v.clear();
+  for (int i = 0; i < n_band; ++i) v.push_back(us(hbuf[BL_NSTAMP * i + 3]));
+  std::sort(v.begin(), v.end());
+  out[11] = v.empty() ? 0.0 : v[v.size() / 2];
+  out[12] = n_band; out[13] = n_wg - n_band;
+  v.clear();
+  for (int i = n_band; i < n_wg; ++i) v.push_back((double)(hbuf[BL_NSTAMP * i + 2] - hbuf[BL_NSTAMP * i + 1]) * 0.01);
+  std::sort(v.begin(), v.end());
+  out[14] = v[v.size() / 2]; out[15] = v.back();
+  return 0;
+}
+#endif
 
 static FilterArgs filter_args(coper_handle* h, const float* hvec, const int64_t* e2, const int64_t* indptr, const int64_t* idx,
                               const float2* tband, int64_t B, int32_t* ranks) {
@@ -1444,7 +1555,7 @@ int score_count3_chunk_bf16x3(coper_handle* h, PassCtx& ctx, int64_t q0, int64_t
     const unsigned n_band = (unsigned)((n_units + BE_UPW - 1) / BE_UPW);
     const unsigned long long* summ = (const unsigned long long*)((const char*)h->mask_ws + (gt ? 2 : 1) * score_count3_mask_words_bytes(h, Bc));
     if (gt) {
-      const unsigned n_look = (unsigned)((Bc + 4 * BL_QW - 1) / (4 * BL_QW));
+      const unsigned n_look = (unsigned)((Bc + 4 * BL_WQ - 1) / (4 * BL_WQ));
       if (h->profile) h->timers["band_lookup"].launches += 1;     // (coper_profile_read("band_lookup"): how many band launches carried the role; no time of its own)
       hipLaunchKernelGGL(k_band_lookup_bf16x3, dim3(n_band + n_look), dim3(256), 0, s, (const uint4*)h->mask_ws, summ, n_units,
                          (unsigned)(rows_per_tile * 4), A, (int)n_band);

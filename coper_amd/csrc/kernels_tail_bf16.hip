@@ -196,9 +196,10 @@ __device__ __forceinline__ float tl_entry_score(const f32x16& acc, const int qi,
   return sc;
 }
 
-// (Steps 0 - 2 have a TWIN: k_finalize_targets_bf16x3 below repeats them statement by statement, without the filter waves.  An
-// edit to the fragments, the targets or the band here has to be made there too; tests/test_gpu_filter_bits.py compares the two
-// kernels' ranks.  One body with a compile-time switch compiled THIS kernel to another schedule, so they are two functions.)
+// (Steps 0 - 2 have a TWIN: k_finalize_targets_bf16x3 below computes the same fragments, targets and bands without the filter waves,
+// with the same arithmetic in the same order but its requests issued in an order of its own.  An edit to the fragments, the targets
+// or the band here has to be made there too; tests/test_gpu_filter_bits.py compares the two kernels' ranks.  One body with a
+// compile-time switch compiled THIS kernel to another schedule, so they are two functions.)
 template <int KS>
 __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_targets_filter_bf16x3(
     int64_t B, int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3,
@@ -370,71 +371,156 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
   TL_STAMP(5);
 }
 
+// ---- pieces of k_finalize_targets_bf16x3 below
+//   x3_batch_exp (bf16x3_chain.h) in three pieces, so that the load can go out with the kernel's first loads: the same maximum over
+//   the same 1,024 slots, the same exponent
+__device__ __forceinline__ float4 tl_x3m_load(const float* __restrict__ x3m) {
+  static_assert(X3M_SLOTS == 1024, "one float4 per thread of a 256-thread block");
+  return ((const float4*)x3m)[threadIdx.x & 255];
+}
+__device__ __forceinline__ float tl_x3m_max(const float4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
+__device__ __forceinline__ int tl_batch_exp(float m /* tl_x3m_max of the thread's slots */, const int ent_exp, int32_t* __restrict__ x3s,
+                                            float* s_red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  const int e = x3_exp_for_bits(__float_as_uint(m));
+  if (blockIdx.x == 0 && threadIdx.x == 0) { x3s[0] = e; x3s[1] = e + ent_exp; }
+  return e;
+}
+//   tl_gather for the k-steps [K0, K1) of the lane's row only
+template <int KS, int K0, int K1>
+__device__ __forceinline__ void tl_gather_steps(const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo, const int64_t my_erow,
+                                                const int half, uint4 (&ah)[KS + 1], uint4 (&al)[KS + 1]) {
+  const int64_t ea = my_erow >= 0 ? my_erow : 0;
+  const uint4* pa_h = Ehi + ea * (2 * KS) + half;
+  const uint4* pa_l = Elo + ea * (2 * KS) + half;
+#pragma unroll
+  for (int k = K0; k < K1; ++k) { ah[k] = pa_h[k * 2]; al[k] = pa_l[k * 2]; }
+}
+//   tl_mma from accumulators that already hold the rows' biases: the MFMA sequence of tl_mma
+template <int KS>
+__device__ __forceinline__ f32x16 tl_mma_from(f32x16 acc, const uint4 (&ah)[KS + 1], const uint4 (&al)[KS + 1], const uint4 (*s_bh)[64],
+                                              const uint4 (*s_bl)[64], const int lane, const bool half_tail) {
+#pragma unroll
+  for (int u = 0; u < KS; u += 2) {
+    if (u + 1 < KS) {
+      const uint4 bh0 = s_bh[u][lane], bl0 = s_bl[u][lane], bh1 = s_bh[u + 1][lane], bl1 = s_bl[u + 1][lane];
+      BX3_PAIR(ah[u], al[u], bh0, bl0, ah[u + 1], al[u + 1], bh1, bl1, acc);
+    } else {
+      const uint4 bh0 = s_bh[u][lane], bl0 = s_bl[u][lane];
+      BX3_LAST_BY(half_tail, ah[u], al[u], bh0, bl0, acc);
+    }
+  }
+  return acc;
+}
+constexpr int TL_LATE_STEPS = 3;   // k-steps of the target rows requested after the fragments (see step 0 of the kernel)
+
 // k_finalize_targets_bf16x3 -- the kernel above without its step 3, for passes that take their filter correction from the count
 // kernel's own compare bits (filter_bits_supported below; kernels_score3_bf16.hip: SC3_GT and the look-up role of the band launch):
 // fragments and targets only.  No CSR entry is read, no filter tile scored, no block listed as heavy; ranks are preset to 1 (or the
-// stale value) and the look-up role takes the known answers above the band back.  Steps 1 and 2 are the statements of the kernel
-// above -- the same fragments, targets and bands, bit for bit.  (The same workgroup shape: three of the four waves only build
-// fragments now, which is most of what the launch still does.)
-template <int KS>
-__global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_targets_bf16x3(
-    int64_t B, int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3,
-    const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo, const float* __restrict__ bias_pad, int64_t n_local,
-    const int64_t* __restrict__ e2, float* __restrict__ tgt, float kappa, const unsigned* __restrict__ band_consts,
-    const float* __restrict__ x3m, int ent_exp, int32_t* __restrict__ x3s, float2* __restrict__ tband, int32_t* __restrict__ ranks,
-    const int32_t* __restrict__ stale, int32_t* __restrict__ stale_count) {
-  __shared__ uint4 s_bh[KS][64], s_bl[KS][64];   // the block's B-operand fragments (hi / lo)
-  __shared__ int64_t s_e[32];
-  __shared__ float s_n2[TL_WAVES][32];
+// stale value) and the look-up role takes the known answers above the band back.  The arithmetic of steps 1 and 2 is that of the
+// kernel above -- the same fragments, targets and bands, bit for bit; n2 is summed in the same order (a wave's chain over its
+// k-steps, then waves 0..3).  What differs is the order of the REQUESTS: this kernel has no filter waves whose first tiles must be
+// on their way early, so all four waves issue their fp32 pieces and the x3m slots at once and reach the exponent's barrier together,
+// and wave 0's target rows travel under the fragments' arithmetic (step 0 below).  Same workgroup shape: 32 queries, four waves.
+//
+// The body is compiled twice, for fp32 rows that can be loaded 16 bytes at a time (VEC: d a multiple of 4, an aligned array) and for
+// rows read float by float, and the kernel branches once between them.  As ONE body with the branch around the loads, the compiler
+// met the float-by-float path's pending loads at every join and answered with s_waitcnt vmcnt(0): in front of the vector loads, and
+// in front of the exponent's reduction, where it made wave 0 sit out its gather after all.
+template <int KS, bool VEC>
+__device__ __forceinline__ void tl_targets_body(
+    const int64_t B, const int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3, const uint4* __restrict__ Ehi,
+    const uint4* __restrict__ Elo, const float* __restrict__ bias_pad, const int64_t n_local, const int64_t* __restrict__ e2,
+    float* __restrict__ tgt, const float kappa, const unsigned* __restrict__ band_consts, const float* __restrict__ x3m, const int ent_exp,
+    int32_t* __restrict__ x3s, float2* __restrict__ tband, int32_t* __restrict__ ranks, const int32_t* __restrict__ stale,
+    int32_t* __restrict__ stale_count, uint4 (*s_bh)[64], uint4 (*s_bl)[64], int64_t* s_e, float (*s_n2)[32]) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
   const int64_t blk = blockIdx.x, q0 = blk * 32, q = q0 + i;
   const bool live = q < B;
   const int tail_kind = bx3_tail_kind(d, KS);
   const bool half_tail = tail_kind == BX3_TAIL_HALF;
   TL_STAMP(0);
-  // ---- 0. wave 0 requests the target rows (pair i = (query i, e2[query i]): the diagonal of its tile) before the fragments exist
+  // ---- 0. everything that depends on no other load goes out in ONE burst, in every wave: the targets' ids, the thread's x3m slots
+  // and the wave's pieces of the fp32 rows.  Wave 0's target rows follow as soon as the ids have landed, so the
+  // gather travels while the fragments are built.  (The first form requested the target rows first: wave 0 then sat out the ids,
+  // the gather -- with a spill's s_waitcnt vmcnt(0) in the middle of it -- and only then its fp32 pieces, three round trips behind
+  // waves 1 - 3, which waited for it at the barrier of the exponent's reduction.)
+  static_assert(TL_WAVES == 4, "tl_x3m_load / tl_batch_exp: 256 threads");
   const int64_t my_e2 = live ? e2[q] : -1;
+  const float4 xm = tl_x3m_load(x3m);
+  constexpr int NKW = (KS + TL_WAVES - 1) / TL_WAVES;      // k-steps of a wave
+  float yv[NKW][8];
+  // (VEC has no branch at all: a lane whose four floats lie outside its row, or whose query or k-step does not exist, loads the
+  // array's first 16 bytes, and step 1 replaces them by zeros.  A branch per lane or per k-step splits the burst: the compiler waits
+  // in front of loads that write registers another path's pending loads might, and behind each pair for the values' first use.)
+  bool in_a[NKW], in_b[NKW];
+#pragma unroll
+  for (int u = 0; u < NKW; ++u) {
+    const int ks = wave + TL_WAVES * u;
+    const int k0 = 16 * ks + 8 * half;
+    if (VEC) {
+      in_a[u] = live && ks < KS && k0 + 4 <= d;
+      in_b[u] = live && ks < KS && k0 + 8 <= d;
+      const float4 a = *(const float4*)(h_rows + (in_a[u] ? q * d + k0 : 0)), b = *(const float4*)(h_rows + (in_b[u] ? q * d + k0 + 4 : 0));
+      yv[u][0] = a.x; yv[u][1] = a.y; yv[u][2] = a.z; yv[u][3] = a.w; yv[u][4] = b.x; yv[u][5] = b.y; yv[u][6] = b.z; yv[u][7] = b.w;
+    } else {
+      in_a[u] = in_b[u] = true;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) yv[u][c] = (ks < KS && live && k0 + c < d) ? h_rows[q * d + k0 + c] : 0.f;
+    }
+  }
+  // |h_q|^2 and the zeros, HERE: the first use of the pieces has to stand before wave 0 branches off to its gather.  Behind it the
+  // compiler counts the gather's loads as pending in every wave and makes wave 0 sit out half of them for a piece it already has.
+  // (Everything of the burst lands together, and 32 FMAs are nothing beside a round trip.)
+  float n2 = 0.f;
+#pragma unroll
+  for (int u = 0; u < NKW; ++u) {     // (no `if (ks < KS)`, for the same reason: a k-step that does not exist holds zeros, and
+#pragma unroll                        //  fmaf(0, 0, n2) is n2 -- the sum is never -0)
+    for (int c = 0; c < 8; ++c) {
+      yv[u][c] = (c < 4 ? in_a[u] : in_b[u]) ? yv[u][c] : 0.f;
+      n2 = fmaf(yv[u][c], yv[u][c], n2);
+    }
+  }
+  float xmax = tl_x3m_max(xm);
+  asm volatile("" : "+v"(n2), "+v"(xmax));   // (pins both -- and with them the waits for the burst -- here, in front of the branch)
+  // the target rows (pair i = (query i, e2[query i]): the diagonal of wave 0's tile).  The tile consumes its k-steps in order, so
+  // the last TL_LATE_STEPS of them are requested only when the fp32 pieces have left their registers (after step 1): with all 2 KS
+  // pieces in flight beside them the kernel spilled at 168 registers a lane.
+  constexpr int KS_EARLY = KS - TL_LATE_STEPS;
   int64_t erow = my_e2;
   if (erow < 0 || erow >= n_local) erow = -1;
   uint4 ah[KS + 1], al[KS + 1];
+  float bias16[16];
   if (wave == 0) {
     if (half == 0) s_e[i] = erow;
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
-    tl_gather<KS>(Ehi, Elo, erow, half, ah, al);
+    // the biases of the tile's 16 rows of this lane, all in flight ahead of the rows (row 0's where there is no target: step 2
+    // keeps a zero).  tl_mma loads them one by one behind the fragments' barrier, each a round trip of its own.
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t er = s_e[(r & 3) + 8 * (r >> 2) + 4 * half];
+      bias16[r] = bias_pad[er >= 0 ? er : 0];
+    }
+    tl_gather_steps<KS, 0, KS_EARLY>(Ehi, Elo, erow, half, ah, al);
   }
   // ---- 1. the block's fragments: wave w takes k-steps w, w + 4, ...
-  static_assert(TL_WAVES == 4, "x3_batch_exp: 256 threads");
   int eh, sexp;
   int32_t x3l[2];
   {
-    const bool vec_ok = (d & 3) == 0 && (((uintptr_t)h_rows) & 15) == 0;
-    constexpr int NKW = (KS + TL_WAVES - 1) / TL_WAVES;      // k-steps of a wave
-    float yv[NKW][8];
-#pragma unroll
-    for (int u = 0; u < NKW; ++u) {
-      const int ks = wave + TL_WAVES * u;
-      const int k0 = 16 * ks + 8 * half;
-      if (ks < KS) {
-        if (live && k0 + 8 <= d && vec_ok) {
-          const float4 a = *(const float4*)(h_rows + q * d + k0), b = *(const float4*)(h_rows + q * d + k0 + 4);
-          yv[u][0] = a.x; yv[u][1] = a.y; yv[u][2] = a.z; yv[u][3] = a.w; yv[u][4] = b.x; yv[u][5] = b.y; yv[u][6] = b.z; yv[u][7] = b.w;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 8; ++c) yv[u][c] = (live && k0 + c < d) ? h_rows[q * d + k0 + c] : 0.f;
-        }
-      }
-    }
-    eh = x3_batch_exp(x3m, ent_exp, x3s, &s_n2[0][0]); sexp = eh + ent_exp; x3l[0] = eh; x3l[1] = sexp;
+    eh = tl_batch_exp(xmax, ent_exp, x3s, &s_n2[0][0]); sexp = eh + ent_exp; x3l[0] = eh; x3l[1] = sexp;
     __syncthreads();                        // (s_n2 served as the reduction's scratch)
-    float n2 = 0.f;
 #pragma unroll
     for (int u = 0; u < NKW; ++u) {
       const int ks = wave + TL_WAVES * u;
       if (ks < KS) {
         float y[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) { n2 = fmaf(yv[u][c], yv[u][c], n2); y[c] = x3_scale(yv[u][c], eh); }
+        for (int c = 0; c < 8; ++c) y[c] = x3_scale(yv[u][c], eh);
         uint4 h4, l4;
         split8_bf16(y, h4, l4);
         f3_store_piece(hf3, KS, tail_kind, q, ks, half, h4, l4, true);   // rows past B: zero pieces (the count kernel's tile is whole)
@@ -445,12 +531,22 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
     n2 += __shfl_xor(n2, 32);
     if (half == 0) s_n2[wave][i] = n2;
   }
+  if (wave == 0) {
+    tl_gather_steps<KS, KS_EARLY, KS>(Ehi, Elo, erow, half, ah, al);
+    ah[KS] = ah[KS - 1]; al[KS] = al[KS - 1];     // (never used, as in tl_gather)
+  }
   TL_STAMP(1);
   __syncthreads();
   TL_STAMP(2);
   // ---- 2. the targets: the diagonal of wave 0's tile against the fragments in LDS; tau_q and the band
   if (wave == 0) {
-    const f32x16 acc = tl_mma<KS>(bias_pad, s_e, ah, al, s_bh, s_bl, lane, half, sexp, half_tail);
+    f32x16 acc0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {       // (tl_mma's first statement, on the biases loaded in step 0)
+      const int64_t er = s_e[(r & 3) + 8 * (r >> 2) + 4 * half];
+      acc0[r] = er >= 0 ? x3_scale(bias16[r], sexp) : 0.f;
+    }
+    const f32x16 acc = tl_mma_from<KS>(acc0, ah, al, s_bh, s_bl, lane, half_tail);
     // D[i][i] sits in lane i + 32 * ((i >> 2) & 1), register (i & 3) + 4 * (i >> 3)
     float diag = 0.f;
     const int reg = (i & 3) + 4 * (i >> 3);
@@ -459,10 +555,10 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
     float t0 = __shfl(diag, i + 32 * ((i >> 2) & 1));   // lane i (both halves): the target of query i
     t0 = erow >= 0 ? t0 : 0.f;
     if (half == 0) {
-      float n2 = 0.f;
+      float n2q = 0.f;
 #pragma unroll
-      for (int w2 = 0; w2 < TL_WAVES; ++w2) n2 += s_n2[w2][i];
-      const float tau = x3_scale(x3_band_tau(n2, kappa, band_consts, d, x3l), sexp);
+      for (int w2 = 0; w2 < TL_WAVES; ++w2) n2q += s_n2[w2][i];
+      const float tau = x3_scale(x3_band_tau(n2q, kappa, band_consts, d, x3l), sexp);
       if (live) { tgt[q] = x3_scale(t0, -sexp); tband[q] = make_float2(t0 - tau, t0 + tau); }
     }
   }
@@ -473,6 +569,24 @@ __global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_ta
   if (wave == 0 && half == 0 && live) ranks[q] = is_stale ? COPER_RANK_STALE : 1;
   if (is_stale && blk == 0 && threadIdx.x == 0) atomicAdd(stale_count, 1);
   TL_STAMP(5);
+}
+
+template <int KS>
+__global__ __launch_bounds__(64 * TL_WAVES, KS <= 13 ? 3 : 2) void k_finalize_targets_bf16x3(
+    int64_t B, int d, const float* __restrict__ h_rows, uint4* __restrict__ hf3,
+    const uint4* __restrict__ Ehi, const uint4* __restrict__ Elo, const float* __restrict__ bias_pad, int64_t n_local,
+    const int64_t* __restrict__ e2, float* __restrict__ tgt, float kappa, const unsigned* __restrict__ band_consts,
+    const float* __restrict__ x3m, int ent_exp, int32_t* __restrict__ x3s, float2* __restrict__ tband, int32_t* __restrict__ ranks,
+    const int32_t* __restrict__ stale, int32_t* __restrict__ stale_count) {
+  __shared__ uint4 s_bh[KS][64], s_bl[KS][64];   // the block's B-operand fragments (hi / lo)
+  __shared__ int64_t s_e[32];
+  __shared__ float s_n2[TL_WAVES][32];
+  if ((d & 3) == 0 && (((uintptr_t)h_rows) & 15) == 0)
+    tl_targets_body<KS, true>(B, d, h_rows, hf3, Ehi, Elo, bias_pad, n_local, e2, tgt, kappa, band_consts, x3m, ent_exp, x3s, tband, ranks,
+                              stale, stale_count, s_bh, s_bl, s_e, s_n2);
+  else
+    tl_targets_body<KS, false>(B, d, h_rows, hf3, Ehi, Elo, bias_pad, n_local, e2, tgt, kappa, band_consts, x3m, ent_exp, x3s, tband, ranks,
+                               stale, stale_count, s_bh, s_bl, s_e, s_n2);
 }
 
 #ifdef COPER_DBG_TL_CLOCK
