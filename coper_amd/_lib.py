@@ -133,6 +133,10 @@ PROTOTYPES = {
     "coper_train_slot": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, _I64, C.c_int32, C.POINTER(_I64), _P]),
     "coper_train_powers": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I64), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(_I64)]),
+    "coper_train_defer_rows": (C.c_int, [_P, C.c_int32, _P]),
+    "coper_train_rows_deferred": (C.c_int, [_P]),
+    "coper_train_sync_rows": (C.c_int, [_P, _P]),
+    "coper_train_row_stats": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P]),
 }
 
 _lib = None

@@ -470,6 +470,9 @@ COPER_API int coper_set_param(coper_handle* h, const char* leaf_name, const void
              (long long)prod(got), (long long)prod(lf->spec_shape));
     return fail(h, COPER_ESHAPE, buf);
   }
+  // (deferred rows: the table being replaced, its twin and their slots are brought current through the pointers registered so far)
+  if (lf->set && (lf == h->lv.ent_emb || lf == h->lv.pred_bias))
+    if (int rc = train_rows_sync(h, nullptr, true)) return rc;
   lf->ptr = (const float*)dev_ptr;
   lf->shape = got;
   lf->set = true;
@@ -734,6 +737,7 @@ COPER_API int coper_prepare(coper_handle* h, void* stream) {
   int rc;
   if ((rc = prepare_check_set(h))) return rc;
   COPER_HIP_TRY(h, hipSetDevice(cfg.device));
+  if ((rc = train_rows_sync(h, stream, false))) return rc;      // (deferred rows: the images below are built from rows that are current)
   h->prepared = false;          // (until every derived buffer below exists again: a prepare that fails leaves a handle that refuses passes)
   h->gcur = 0;                  // (x3m of the home set is re-allocated below; a grouping done ahead does not survive a prepare)
   h->pipe.invalidate_grouping();

@@ -419,6 +419,9 @@ struct PassCtx {
 int fail(coper_handle* h, int code, const std::string& msg);
 void train_destroy(coper_handle* h);   // coper_train.hip
 int train_params_changed(coper_handle* h, const char* leaf_name);   // coper_set_param: the training state resolves its variables again
+// deferred rows (coper_train_defer_rows): every row of ent_emb / pred_bias and their slots current before a call reads or replaces the
+// tables whole; device_wide: for a call without a stream (null stream between two device synchronisations).  No-op with the mode off.
+int train_rows_sync(coper_handle* h, void* stream, bool device_wide);
 int hip_fail(coper_handle* h, hipError_t e, const char* what);
 
 #define COPER_HIP_TRY(h, expr)                                    \

@@ -25,6 +25,10 @@
 //   order -- per-workgroup partial sums in TrainState::det_slab folded by k_tr_fold_det, one writer per embedding / relation row
 //   (k_tr_rows_by_key_det), S rows built in ascending lookup position (k_tr_build_S_det) -- chosen where the launch is made (`det`);
 //   the step is one chain on the caller's stream there.  With the mode off every launch is the one it was.
+//   Deferred rows (coper_train_defer_rows): the sampled step touches only the rows of ent_emb / pred_bias its batch names --
+//   claim, catch up (the closed form of the skipped zero-gradient updates), norm and update over that list, the list before re-zeroed --
+//   in phases of their own beside the ones above (Step::rows_*; kernels in train_rows.h); k_tr_zero_list, k_tr_sumsq and k_tr_amsgrad
+//   leave the two tables out.  With the mode off every launch is the one it was.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 #include <algorithm>
@@ -35,6 +39,7 @@
 #include "train_common.h"
 #include "train_gemm.h"
 #include "train_kernels.h"
+#include "train_rows.h"
 
 namespace coper {
 
@@ -169,6 +174,18 @@ struct TrainState {
   RedLayout red_layout() const { return RedLayout{red, (size_t)mx}; }
   float* bn_row(BnRow k) const { return bnst + (size_t)k * mx; }
   TrainLeaves lv;            // where the variables are (resolve_leaves)
+  // deferred rows (coper_train_defer_rows; kernels in train_rows.h).  rows_word[e]: row e of ent_emb / pred_bias and their
+  // slots is current as of update number rows_word[e] of rows_now (updates since the mode was enabled); rows_claim: a bit per row, set
+  // while the row is on a list; rows_list[rows_prev]: the rows of the call before (their gradient rows are the only non-zero ones of
+  // the two buffers, their claim bits the only ones set), rows_list[rows_prev ^ 1]: free for the next call; rows_count: their lengths
+  bool rows_deferred = false;
+  int32_t rows_now = 0;
+  double rows_l2b1p = 0, rows_l2b2p = 0;   // log2 of b1p / b2p, advanced by addition: a catch-up divides the powers by beta^gap (train_rows.h, RowCatchUp)
+  int rows_prev = 0;
+  int64_t rows_cap = 0;
+  DevBuf<int32_t> rows_word, rows_list[2], rows_count;
+  DevBuf<unsigned> rows_claim;
+  DevBuf<unsigned long long> rows_stats;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -456,13 +473,59 @@ struct SideJoin {
   ~SideJoin() { for (int i = 0; i < 3; ++i) join(i); }
 };
 
+// ---- deferred rows: what the row kernels take (train_rows.h)
+static RowTables row_tables(const coper_handle* h, const TrainState* T) {
+  const TrainParam &e = *T->lv.ent_emb, &b = *T->lv.pred_bias;
+  RowTables t;
+  t.p = e.p; t.g = e.g; t.m = e.m; t.v = e.v; t.vh = e.vh;
+  t.bp = b.p; t.bg = b.g; t.bm = b.m; t.bv = b.v; t.bvh = b.vh;
+  t.word = T->rows_word;
+  t.E = h->dm.E;
+  t.d = h->dm.d;
+  t.vec = (h->dm.d & 3) == 0 && ((((uintptr_t)t.p) | ((uintptr_t)t.g) | ((uintptr_t)t.m) | ((uintptr_t)t.v) | ((uintptr_t)t.vh)) & 15) == 0;
+  return t;
+}
+// terms of C = sum_j lr(.) beta1^j worth keeping: lr(t) <= lr / (1 - beta1) and the first term is >= lr beta1 sqrt(1 - beta2) -- so
+// everything beyond j, at most lr beta1^j / (1 - beta1)^2, is below 2^-53 of the sum once beta1^(j-1) < 2^-53 (1 - beta1)^2 sqrt(1 - beta2)
+static int32_t rows_jmax(double b1, double b2) {
+  if (!(b1 > 0.0) || !(b1 < 1.0)) return 1;      // (beta1 = 0: every term is 0)
+  const double j = 1.0 + (53.0 * std::log(2.0) - 2.0 * std::log(1.0 - b1) - 0.5 * std::log(b2 < 1.0 ? 1.0 - b2 : 1.0)) / -std::log(b1);
+  return j < 1.0 ? 1 : j > 1e9 ? 1000000000 : (int32_t)std::ceil(j);
+}
+static RowCatchUp row_catch_up_args(const TrainState* T) {
+  const coper_train_config& tc = T->cfg;
+  RowCatchUp cu;
+  cu.lr = tc.learning_rate; cu.b1 = tc.beta1; cu.b2 = tc.beta2; cu.eps = tc.epsilon;
+  cu.l2b1 = cu.b1 > 0.0 ? std::log2(cu.b1) : 0.0; cu.l2b2 = cu.b2 > 0.0 ? std::log2(cu.b2) : 0.0;   // (a beta of 0: its powers are 0 at every gap)
+  cu.l2b1p = T->rows_l2b1p; cu.l2b2p = T->rows_l2b2p;
+  cu.b2f = tc.beta2;
+  cu.now = T->rows_now;
+  cu.jmax = rows_jmax(cu.b1, cu.b2);
+  return cu;
+}
+// a wave per row, four per workgroup, at most 8,192 workgroups (the kernels stride)
+inline dim3 rows_grid(int64_t rows) { return dim3((unsigned)std::min<int64_t>(std::max<int64_t>((rows + 3) / 4, 1), 8192)); }
+// coper_profile_read of the training step's structure (counts, no times -- as "band_lookup"): "train.zero.<leaf>" per whole-buffer zeroing
+// of a leaf's gradient, "train.sumsq.leaves" / "train.amsgrad.leaves" the tensors k_tr_sumsq / k_tr_amsgrad were launched over,
+// "train.rows.<kernel>" per launch of a row kernel
+inline void prof_count(coper_handle* h, const std::string& what, int64_t n = 1) { if (h->profile) h->timers[what].launches += n; }
+
+// One pass over E: every row of ent_emb / pred_bias and their slots current (k_rows_sync; a row with gap 0 is not written).
+static int rows_sync_launch(coper_handle* h, TrainState* T, hipStream_t s) {
+  hipLaunchKernelGGL(k_rows_sync, rows_grid(h->dm.E), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T));
+  prof_count(h, "train.rows.sync");
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
+}
+
 // clip + AMSGrad over every trainable tensor: the squared norm (k_tr_sumsq; deterministic mode: through the slab and its fold), then
-// k_tr_amsgrad.  The caller has zeroed the squared-norm slots and wmax[wmax_cur ^ 1].  flat: the gradients are read from the flat
-// gradient vector in place (each leaf at its flat_off) instead of the gradient buffers.  sumsq_done: the leaf whose squares a GEMM of
+// k_tr_amsgrad.  Deferred rows: ent_emb and pred_bias are left out of both launches, and the rows of `rows_list` (its length on the
+// device, `rows_count`) go through k_rows_sumsq / k_rows_update between and behind them.  The caller has zeroed the squared-norm slots
+// and wmax[wmax_cur ^ 1].  flat: the gradients are read from the flat gradient vector in place (each leaf at its flat_off) instead of the gradient buffers.  sumsq_done: the leaf whose squares a GEMM of
 // the same step already added to the slots.  table_counts: the relation counts that say which rows of the looked-up dense table
 // exist.  gs: coper_train_apply's scale (1: the fused step).  Returns whether the pass carried the dense weights' maximum.
 static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, const float* flat, const TrainParam* sumsq_done,
-                             const int32_t* table_counts, double gs) {
+                             const int32_t* table_counts, double gs, const int32_t* rows_list = nullptr, const int32_t* rows_count = nullptr) {
   const Dims& dm = h->dm;
   const coper_train_config& tc = T->cfg;
   const TrainLeaves& lv = T->lv;
@@ -470,12 +533,13 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
   const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
   const RedLayout red = T->red_layout();
   TrainTensors tt;
-  const int np = (int)T->tp.size();
+  int np = 0;      // tensors of the two launches: every leaf, or every leaf but the two tables
   int skip = -1;
   // the dense weights' largest |p_new| for the next step's packs (k_tr_amsgrad's 16-byte path only: it is the one that carries it)
   tt.wmax = nullptr; tt.wmax_of = -1;
-  for (int i = 0; i < np; ++i) {
-    const TrainParam& t = T->tp[i];
+  for (const TrainParam& t : T->tp) {
+    if (rows_list && (&t == lv.ent_emb || &t == lv.pred_bias)) continue;
+    const int i = np++;
     tt.p[i] = t.p; tt.g[i] = flat ? const_cast<float*>(flat) + t.flat_off : t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
     tt.n[i] = t.n;
     const bool table = lk && &t == lv.fc_weights;
@@ -493,9 +557,20 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
     hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, ssq, 0);
   } else
     hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
+  prof_count(h, "train.sumsq.leaves", np);
+  if (rows_list) {
+    hipLaunchKernelGGL(k_rows_sumsq, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, ssq);
+    prof_count(h, "train.rows.sumsq");
+  }
   const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
   hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, ssq, red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1, tc.beta2,
                      tc.epsilon, gs);
+  prof_count(h, "train.amsgrad.leaves", np);
+  if (rows_list) {      // (behind k_tr_amsgrad on the same stream: both read the slots, neither writes them)
+    hipLaunchKernelGGL(k_rows_update, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, (const double*)ssq,
+                       tc.clip_norm, lr_t, tc.beta1, tc.beta2, tc.epsilon, gs, T->rows_now + 1);
+    prof_count(h, "train.rows.update");
+  }
   return tt.wmax != nullptr;
 }
 
@@ -530,7 +605,9 @@ struct Step {
   float *const mean1 = T->bn_row(BN1_MEAN), *const inv1 = T->bn_row(BN1_INV), *const mean2 = T->bn_row(FCBN_MEAN), *const inv2 = T->bn_row(FCBN_INV);
   SideJoin sj{T, s};
   // the scorer's backward through the dense d(loss)/d(logits) matrix S and one GEMM (else by float atomics)
-  const bool dense_scorer_bwd = (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
+  // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE)
+  const bool rows = T->rows_deferred;
+  const bool dense_scorer_bwd = !rows && (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
   // ---- from phase to phase
   float *Tf = nullptr, *dTf = nullptr;                // generated dense: T[rho][b][k] | dT (in T->A, once grow_workspaces has seen to it)
   const float *K_ps = nullptr, *kb_ps = nullptr;      // per-sample conv filters / biases (T->Kt, T->Kbv; null where they are static)
@@ -545,6 +622,7 @@ struct Step {
   int t_slices = 1, dx_slices = 1;   // K slices the T and dx products left for k_tr_fc_post_slices / k_tr_bn1_bwd_sums to add
   bool score_dh_fused = false;   // scores, loss, ds and dh came from one pass over the rows (k_tr_score_loss_dh)
   const TrainParam* sumsq_done = nullptr;   // the leaf whose squared gradient norm its own GEMM accumulated
+  const int32_t *rows_list = nullptr, *rows_count = nullptr;   // deferred rows: the rows this call claimed (rows_claim_catch_up)
   bool scorer_bwd_on_side() const { return two_streams && score_dh_fused && tg_split_k(dm.E, d, B) == 1; }
 
   int grow_workspaces() {
@@ -645,9 +723,10 @@ struct Step {
     ZeroList zl;
     zl.n = 0;
     auto add = [&](void* p, size_t bytes) { if (p && bytes && zl.n < TR_ZERO_MAX) { zl.p[zl.n] = p; zl.bytes[zl.n] = bytes; ++zl.n; } };
-    auto grad = [&](const TrainParam* t) { if (t) add(t->g, sizeof(float) * t->n); };
+    auto grad = [&](const TrainParam* t) { if (t) { add(t->g, sizeof(float) * t->n); if (h->profile) prof_count(h, "train.zero." + t->name); } };
     add(red.base, sizeof(double) * red.doubles());
-    for (const TrainParam* t : {lv.ent_emb, lv.rel_emb, lv.conv1_weights, lv.conv1_bias, lv.pred_bias}) grad(t);
+    // (deferred rows: the two tables' gradients are zero but for the rows of the call before, which rows_rezero clears)
+    for (const TrainParam* t : {rows ? nullptr : lv.ent_emb, lv.rel_emb, lv.conv1_weights, lv.conv1_bias, rows ? nullptr : lv.pred_bias}) grad(t);
     if (lk) grad(lv.fc_bias);
     else if (gen) add(lv.gen[1].proj[nh]->g, sizeof(float) * rc_b * d);
     else add(lv.fc_bias->g, sizeof(float) * d);
@@ -659,6 +738,41 @@ struct Step {
     w_slots = T->wmax_valid ? T->wmax[T->wmax_cur].get() : nullptr;
     // (a coper_group_next registration, or a grouping prepared ahead, was for an evaluation pass: a training step drops both)
     h->pipe.invalidate_grouping();
+  }
+  // ---- deferred rows, in front of every forward kernel: the id lists hold B (L + 1) entries
+  int rows_grow() {
+    const int64_t need = B * (L + 1);
+    if (need <= T->rows_cap) return COPER_OK;
+    int rc;
+    // the list of the call before is still owed its re-zero: pay it from the old buffers, then replace both
+    if (T->rows_cap) rows_rezero();
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    T->rows_cap = 0;
+    if ((rc = T->rows_list[0].alloc(h, (size_t)need, "deferred-row list")) || (rc = T->rows_list[1].alloc(h, (size_t)need, "deferred-row list"))) return rc;
+    COPER_HIP_TRY(h, hipMemsetAsync(T->rows_count, 0, 2 * sizeof(int32_t), s));
+    T->rows_cap = need;
+    return COPER_OK;
+  }
+  // 5. the rows of the call before: their gradient rows, their claim bits; the other list's count (the claim appends from 0)
+  void rows_rezero() {
+    const int pv = T->rows_prev;
+    hipLaunchKernelGGL(k_rows_rezero, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), T->rows_list[pv].get(), T->rows_count + pv,
+                       T->rows_claim.get(), T->rows_count + (pv ^ 1));
+    prof_count(h, "train.rows.rezero");
+  }
+  // 1. + 2. claim the batch's rows into the free list and bring them current.  The list is the handle's "list of the call before" from
+  // here on, whatever becomes of the call: the next one re-zeroes it.
+  void rows_claim_catch_up() {
+    const int cur = T->rows_prev ^ 1;
+    const int64_t n = B * (L + 1);
+    hipLaunchKernelGGL(k_rows_claim, grid1d(n), dim3(256), 0, s, e1, B, lookup, n, (int64_t)dm.E, T->rows_claim.get(), T->rows_list[cur].get(),
+                       T->rows_count + cur);
+    T->rows_prev = cur;
+    rows_list = T->rows_list[cur];
+    rows_count = T->rows_count + cur;
+    hipLaunchKernelGGL(k_rows_catch_up, rows_grid(n), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T), rows_list, rows_count);
+    prof_count(h, "train.rows.claim");
+    prof_count(h, "train.rows.catch_up");
   }
   // looked-up dense table: group the batch by relation (perm / rel_offset / rel_count of the inference path): the table gradient is
   // written per present relation, never zero-filled (1.75 GB at FB15k-237 shapes)
@@ -1118,10 +1232,23 @@ struct Step {
         hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * r), dim3(256), 0, s, T->chain[g].dv[0], rel, dm.R, r, B * r, lv.rel_emb->g);
   }
   // ---- clip + AMSGrad
-  bool optimizer() { return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0); }
+  bool optimizer() { return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0, rows_list, rows_count); }
 };
 
 }  // namespace
+
+// coper_prepare, coper_set_param of ent_emb / pred_bias (coper_abi.hip) and the calls here that read or replace the tables whole: with
+// deferred rows on, every row current first.  device_wide: for a caller without a stream -- the pass runs on the null stream between two
+// device synchronisations.  Nothing to do without a training state or with the mode off.
+int coper::train_rows_sync(coper_handle* h, void* stream, bool device_wide) {
+  TrainState* T = (TrainState*)h->train;
+  if (!T || !T->rows_deferred) return COPER_OK;
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  if (device_wide) COPER_HIP_TRY(h, hipDeviceSynchronize());
+  if (int rc = rows_sync_launch(h, T, device_wide ? nullptr : (hipStream_t)stream)) return rc;
+  if (device_wide) COPER_HIP_TRY(h, hipDeviceSynchronize());
+  return COPER_OK;
+}
 
 static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                            int64_t B, int64_t L, float* loss_out, void* stream, const int apply, float* pred_out, float* h_out,
@@ -1141,6 +1268,13 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
   }
+  if (T->rows_deferred) {      // what has a gradient in every row, or hands the dense gradient on, is refused
+    if (csr.indptr || !lookup)
+      return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deferred-rows mode (coper_train_defer_rows): a 1-vs-all step has a gradient in every row");
+    if (apply == 2)
+      return fail(h, COPER_EUNSUPPORTED, "coper_train_backward: deferred-rows mode (coper_train_defer_rows): the split step's flat gradient is dense");
+    if (B * (L + 1) > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_train_step: deferred-rows mode: B * (L + 1) ids do not fit the row lists");
+  }
   if (T->det) {      // what the mode does not put in order is refused, never served unordered
     if (lookup && !((double)B * (double)h->dm.E * 4.0 <= 512.0 * 1024 * 1024 && h->dm.E <= 0x7fffffff))
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: sampled labels at B*num_ent*4 > 512 MiB take the atomic scorer backward");
@@ -1154,8 +1288,20 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply, csr};
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
+  if (st.rows) {
+    if (T->rows_now >= 0x7ffffff0) {      // (the step words are int32: start counting again from a table that is current)
+      if ((rc = rows_sync_launch(h, T, st.s))) return rc;
+      COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * (size_t)h->dm.E, st.s));
+      T->rows_now = 0;
+    }
+    if ((rc = st.rows_grow())) return rc;
+  }
   T->pending = false;      // (the gradient buffers are zeroed next: what a coper_train_backward left in them is gone)
   st.zero_accumulators();
+  if (st.rows) {
+    st.rows_rezero();
+    st.rows_claim_catch_up();
+  }
   if (st.lk && (rc = st.group_for_lookup())) return rc;
 
   st.fwd_conv_filters();
@@ -1190,6 +1336,11 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   const bool wmax_carried = st.optimizer();
   COPER_HIP_TRY(h, hipGetLastError());
+  if (st.rows) {      // (k_rows_update wrote the listed rows' words: current as of this update)
+    T->rows_now += 1;
+    T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
+    T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
+  }
   T->b1p *= T->cfg.beta1;
   T->b2p *= T->cfg.beta2;
   T->step += 1;
@@ -1255,6 +1406,8 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
+  if (T->rows_deferred)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: deferred-rows mode (coper_train_defer_rows): the flat gradient vector is dense by contract");
   if (!flat || ((uintptr_t)flat & 15) != 0) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat must be a 16-byte aligned device buffer");
   if (cap < T->flat_total) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat holds fewer than coper_train_grads_layout's total");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1278,6 +1431,8 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
+  if (T->rows_deferred)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: deferred-rows mode (coper_train_defer_rows): an update from the dense flat gradient touches every row");
   if (!flat && !T->pending)
     return fail(h, COPER_ESTATE, "coper_train_apply: no gradients pending (no coper_train_backward since the last update, step, forward or init)");
   if (flat && (n != T->flat_total || ((uintptr_t)flat & 15) != 0))
@@ -1326,6 +1481,79 @@ COPER_API int coper_train_deterministic(const coper_handle* h) {
   return T ? (T->det ? 1 : 0) : -COPER_ESTATE;
 }
 
+// ---- deferred rows (include/coper_hip.h, "Deferred rows")
+COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_defer_rows: call coper_train_init first");
+  if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_defer_rows: enable is 0 or 1");
+  if (enable && T->det)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: a deterministic state: the unique-row list and the atomic scorer backward are unordered");
+  if ((enable != 0) == T->rows_deferred) return COPER_OK;
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  if (!enable) {      // every row current, then the dense path again (it zeroes the gradient buffers whole; the row state is rebuilt at the next enable)
+    if (int rc = rows_sync_launch(h, T, s)) return rc;
+    T->rows_deferred = false;
+    return COPER_OK;
+  }
+  const size_t E = (size_t)h->dm.E;
+  int rc;
+  if ((rc = T->rows_word.ensure(h, E, "deferred-row step words")) || (rc = T->rows_claim.ensure(h, (E + 31) / 32, "deferred-row claim bits")) ||
+      (rc = T->rows_count.ensure(h, 2, "deferred-row counts")) || (rc = T->rows_stats.ensure(h, 2, "deferred-row statistics")))
+    return rc;
+  // every row is current now; no row is listed; the two gradient buffers are zero everywhere (from here on: but for the listed rows)
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * E, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_claim, 0, sizeof(unsigned) * ((E + 31) / 32), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_count, 0, 2 * sizeof(int32_t), s));
+  COPER_HIP_TRY(h, hipMemsetAsync(T->lv.ent_emb->g, 0, sizeof(float) * (size_t)T->lv.ent_emb->n, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(T->lv.pred_bias->g, 0, sizeof(float) * (size_t)T->lv.pred_bias->n, s));
+  T->rows_now = 0;
+  T->rows_prev = 0;
+  T->rows_l2b1p = std::log2(T->b1p);      // (log2(0) = -inf: the power is 0 at every gap, as the dense step has it)
+  T->rows_l2b2p = std::log2(T->b2p);
+  T->pending = false;      // (a pending backward's gradient is gone with the zeroing)
+  T->rows_deferred = true;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_deferred(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->rows_deferred ? 1 : 0) : -COPER_ESTATE;
+}
+
+COPER_API int coper_train_sync_rows(coper_handle* h, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (!h->train) return fail(h, COPER_ESTATE, "coper_train_sync_rows: call coper_train_init first");
+  return train_rows_sync(h, stream, false);
+}
+
+COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, int64_t* rows_behind, int64_t* max_gap, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_row_stats: call coper_train_init first");
+  if (rows_last_step) *rows_last_step = 0;
+  if (rows_behind) *rows_behind = 0;
+  if (max_gap) *max_gap = 0;
+  if (!T->rows_deferred) return COPER_OK;      // (the dense step: every row current, nothing listed)
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_stats, 0, 2 * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(k_rows_stats, dim3((unsigned)std::min<int64_t>((h->dm.E + 255) / 256, 4096)), dim3(256), 0, s, T->rows_word.get(), (int64_t)h->dm.E,
+                     T->rows_now, T->rows_stats.get());
+  COPER_HIP_TRY(h, hipGetLastError());
+  unsigned long long st[2] = {0, 0};
+  int32_t counts[2] = {0, 0};
+  COPER_HIP_TRY(h, hipMemcpyAsync(st, T->rows_stats, sizeof st, hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipMemcpyAsync(counts, T->rows_count, sizeof counts, hipMemcpyDeviceToHost, s));
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  if (rows_last_step) *rows_last_step = counts[T->rows_prev];
+  if (rows_behind) *rows_behind = (int64_t)st[0];
+  if (max_gap) *max_gap = (int64_t)st[1];
+  return COPER_OK;
+}
+
 COPER_API int coper_train_grad(coper_handle* h, const char* leaf_name, float* out, int64_t cap, int64_t* n, double* global_norm,
                                void* stream) {
   if (!h || !leaf_name) return COPER_EINVAL;
@@ -1365,6 +1593,12 @@ COPER_API int coper_train_slot(coper_handle* h, const char* leaf_name, int32_t w
   if (n) *n = t->n;
   if (!buf) return COPER_OK;
   if (cap < t->n) return fail(h, COPER_EINVAL, "coper_train_slot: buffer too small");
+  // (deferred rows: a slot of the two tables is read or replaced whole -- every row current first, so that what is read is the dense
+  //  optimizer's slot and what is planted belongs to the update count the powers stand at)
+  if (T->rows_deferred && (t == T->lv.ent_emb || t == T->lv.pred_bias)) {
+    COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = rows_sync_launch(h, T, (hipStream_t)stream)) return rc;
+  }
   COPER_HIP_TRY(h, hipMemcpyAsync(set ? slot : buf, set ? buf : slot, sizeof(float) * t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return COPER_OK;
 }
@@ -1374,8 +1608,12 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_powers: call coper_train_init first");
-  if (set_beta1_power) T->b1p = *set_beta1_power;
-  if (set_beta2_power) T->b2p = *set_beta2_power;
+  // (deferred rows: a catch-up reads the gap's learning rates off the CURRENT powers -- every row current under the old ones first.  The
+  //  call has no stream: the device is synchronised around the pass)
+  if (T->rows_deferred && (set_beta1_power || set_beta2_power))
+    if (int rc = train_rows_sync(h, nullptr, true)) return rc;
+  if (set_beta1_power) { T->b1p = *set_beta1_power; T->rows_l2b1p = std::log2(T->b1p); }
+  if (set_beta2_power) { T->b2p = *set_beta2_power; T->rows_l2b2p = std::log2(T->b2p); }
   if (set_step) T->step = (uint32_t)*set_step;
   if (beta1_power) *beta1_power = T->b1p;
   if (beta2_power) *beta2_power = T->b2p;

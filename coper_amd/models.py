@@ -160,6 +160,10 @@ class ConvE(object):
         """Sets parameters by the reference's leaf names.  `global_rows`: ent_emb / pred_bias are given
         for all |E| entities and sliced to the shard here."""
         lo, hi = self.shard
+        if getattr(self, "_rows_deferred", False) and ("ent_emb" in params or "pred_bias" in params):
+            # deferred rows: the tensors registered so far are brought current while this model still holds them (coper_set_param syncs
+            # through the pointers registered before it, include/coper_hip.h)
+            self.train_sync_rows()
         for name, want in self._specs.items():
             if name not in params:
                 continue
@@ -200,7 +204,8 @@ class ConvE(object):
         """Registers again every tensor whose version counter moved since it was registered: the tensors ARE the variables, and an
         in-place edit of one leaves the prepared caches, the entity maximum and the training step's record of the dense weights'
         magnitude stale.  (The library's own writes -- the training step, BN moving statistics -- go through raw pointers and do not
-        move the counters.)"""
+        move the counters.)  Deferred rows (train_init(deferred_rows=True)): ent_emb / pred_bias are brought current first whenever one
+        of them is registered again (load_parameters)."""
         vs = self._versions
         changed = [n for n, t in self._tensors.items() if _version(t) != vs[n]]
         if changed:
@@ -209,7 +214,9 @@ class ConvE(object):
     @property
     def variables(self):
         """Dict with the keys of models.py:316-325; generated parameters are holder objects like the
-        reference's generator objects."""
+        reference's generator objects.  Deferred rows (train_init(deferred_rows=True)): the tables are brought current first; the
+        tensors handed out are the registered ones and go stale again with the next training step, until the next sync."""
+        self.train_sync_rows()
         T = self._tensors
         out = {"ent_emb": T.get("ent_emb"), "pred_bias": T.get("pred_bias")}
         if not self.is_parameter_lookup:
@@ -860,12 +867,19 @@ class ConvE(object):
         return ms.value, n.value
 
     # ---------------------------------------------------------------- training
-    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, **overrides):
+    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, deferred_rows=False, **overrides):
         """Allocates gradients and AMSGrad slots (amsgrad.py:112-118).  Hyper-parameters come from
         model_descriptors (models.py:99-130) unless overridden.  The tensors passed to load_parameters ARE the
         variables: train_step updates them in place (BN moving statistics included).
         deterministic=True: bit-reproducible steps (coper_train_config.deterministic in include/coper_hip.h has the contract): the same
-        state and the same batch give the same bits in every output, across calls, handles, processes and streams."""
+        state and the same batch give the same bits in every output, across calls, handles, processes and streams.
+        deferred_rows=True (coper_train_defer_rows in include/coper_hip.h has the contract): a sampled train_step / train_forward touches
+        only the rows of ent_emb / pred_bias its batch names; every other row's dense AMSGrad update is applied exactly, in closed form,
+        when the row is next read.  The registered ent_emb / pred_bias tensors (`load_parameters`' arguments, `_tensors`) are the
+        caller's own and are CURRENT ONLY AFTER A SYNC: train_sync_rows(), or any of prepare() / encode() and the other inference calls,
+        `variables`, session fetches of the tables, optimizer_state() and the checkpoint writers fed from them, which sync themselves.
+        A raw read of the tensors in between is the caller's risk.  Not with deterministic=True; 1-vs-all batches and the split step
+        (train_backward / train_grads_export / train_apply) are refused in the mode."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -885,7 +899,45 @@ class ConvE(object):
             _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
         self._grads_layout = None
+        self._rows_deferred = False      # (a new training state starts dense)
+        if deferred_rows:
+            self.train_defer_rows(True)
         return self
+
+    def train_defer_rows(self, enable=True):
+        """coper_train_defer_rows: the deferred-rows mode on or off (train_init's docstring).  Turning it off brings every row current."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        enable = int(enable) if not isinstance(enable, bool) else (1 if enable else 0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_defer_rows(self._h, enable, self._stream()))
+        self._rows_deferred = bool(enable)
+        return self
+
+    @property
+    def train_rows_deferred(self):
+        """The mode in force (coper_train_rows_deferred): 1 or 0."""
+        v = self._lib.coper_train_rows_deferred(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
+
+    def train_sync_rows(self):
+        """coper_train_sync_rows: every row of ent_emb, pred_bias and their slots current (one pass over num_ent on the current stream).
+        Idempotent; nothing to do without a training state or with the mode off."""
+        if getattr(self, "_rows_deferred", False):
+            with torch.cuda.device(self.device):
+                _lib.check(self._h, self._lib.coper_train_sync_rows(self._h, self._stream()))
+        return self
+
+    def train_row_stats(self):
+        """coper_train_row_stats: dict(rows_last_step, rows_behind, max_gap).  Synchronises: tests and diagnostics."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_row_stats(self._h, C.byref(a), C.byref(b), C.byref(c), self._stream()))
+        return dict(rows_last_step=a.value, rows_behind=b.value, max_gap=c.value)
 
     @property
     def train_deterministic(self):
@@ -1067,6 +1119,7 @@ class ConvE(object):
     def optimizer_state(self):
         """AMSGrad state for a checkpoint: ({leaf: (m, v, v_hat) numpy}, {"beta1_power", "beta2_power", "step"}) --
         what `tf.train.Saver` keeps as `<var>/AMSGrad{,_1,_2}` and beta1_power / beta2_power (amsgrad.py:108-119)."""
+        self.train_sync_rows()      # (deferred rows: the slots are read whole; coper_train_slot would sync per call)
         slots = {}
         for leaf in self.trainable_leaves():
             parts = []
@@ -1150,6 +1203,7 @@ class Session(object):
         # variables fetched directly, `session.run([model.variables['rel_emb'], model.variables['ent_emb']])`
         # (run_cpg.py:244-248): device tensors -> host arrays; no batch is consumed
         if all(isinstance(f, torch.Tensor) for f in fl):
+            m.train_sync_rows()      # (deferred rows: a fetched table is current)
             out = [f.detach().cpu().numpy() for f in fl]
             return out[0] if single else (out if isinstance(fetches, list) else tuple(out))
         handle = feed_dict.get(m.input_iterator_handle)

@@ -46,6 +46,10 @@ def main(argv=None):
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible training steps (coper_train_config.deterministic): two runs of this loop with the same "
                          "arguments and the same batches reach the same variables bit for bit")
+    ap.add_argument("--deferred-rows", action="store_true",
+                    help="sampled steps touch only the entity rows their batch names (coper_train_defer_rows): every other row's dense "
+                         "AMSGrad update is applied exactly, in closed form, when the row is next read; not with --sparse-labels or "
+                         "--deterministic")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--dense", choices=("cached", "factored"), default="cached",
                     help="generated dense layer at inference: the per-relation weight cache, or the factored path whose prepare after "
@@ -65,7 +69,7 @@ def main(argv=None):
               batch_norm_momentum=0.1)
     model = ConvE(md, device="cuda:0", score_mode="bf16x3", dense=args.dense)
     model.load_parameters(cdata.synthetic_params(md, seed=0))      # random init of the named architecture
-    model.train_init(seed=0, deterministic=args.deterministic)
+    model.train_init(seed=0, deterministic=args.deterministic, deferred_rows=args.deferred_rows)
 
     # device=: the negative sampler runs on the GPU (coper_amd.data.DeviceTrainDataset; ~40 x the host sampler at FB15k-237 sizes)
     if args.sparse_labels:
@@ -95,6 +99,7 @@ def main(argv=None):
 
     # checkpoint in the reference's format (run_cpg.py:252) and restore into a fresh model (run_cpg.py:206)
     prefix = os.path.join(work, "checkpoints", "model_weights.ckpt")
+    model.train_sync_rows()                                        # (--deferred-rows: the tensors read below are current after a sync)
     slots, powers = model.optimizer_state()
     weights.save_tf_checkpoint(prefix, {k: v.cpu().numpy() for k, v in model._tensors.items()}, slots, powers)
     restored = ConvE(md, device="cuda:0", score_mode="bf16x3", dense=args.dense).load_parameters(weights.load_tf_checkpoint(prefix))

@@ -681,6 +681,52 @@ COPER_API int coper_train_slot(coper_handle* h, const char* leaf_name, int32_t w
 COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power, const double* set_beta2_power,
                                  const int64_t* set_step, double* beta1_power, double* beta2_power, int64_t* step);
 
+/* Deferred rows: an opt-in mode of the SAMPLED step (coper_train_step / coper_train_forward with a lookup) in which every launch touches
+ * O(B L d) bytes of ent_emb, pred_bias, their gradients and their slots, and none that scale with num_ent.  The optimizer stays the
+ * reference's dense AMSGrad (utils/amsgrad.py:161-189 decays m and v of every row every step): for a row with zero gradient that update
+ * is a closed form -- a row (p, m, v, v_hat) current at update t0 and without gradient at updates t0+1 .. t0+k becomes
+ *     v_hat' = max(v_hat, beta2 v)      m' = beta1^k m      v' = beta2^k v      p' = p - C m / (sqrt(v_hat') + epsilon)
+ *     C = sum_{j=1..k} lr(t0+j) beta1^j,   lr(t) = learning_rate sqrt(1 - beta2^t) / (1 - beta1^t)
+ * (C and the powers in double, from the state's beta powers; terms below 2^-53 of the sum are dropped, by a bound that follows beta1)
+ * -- so a row is brought current only when something reads it: the rows a batch names, in front of its forward pass; every row before
+ * inference, export or a checkpoint.  This is a deferred, EXACT row update, not the "lazy" optimizer of other libraries (which skips
+ * the decay).  Against the dense step the results differ by float32 rounding only: p is rounded once per gap instead of once per
+ * update, m and v take one rounded power, and the scorer's backward always takes the float-atomic route (the one large tables take).
+ * With the mode off every launch and every bit is what it was.
+ *
+ * coper_train_defer_rows(h, enable, stream): after coper_train_init (COPER_ESTATE without a training state); enable is 0 or 1
+ *   (COPER_EINVAL otherwise); COPER_EUNSUPPORTED on a deterministic = 1 state (the unique-row list and the atomic scorer backward are
+ *   unordered).  Enabling allocates the row state -- an int32 "current as of update" word per row, a claim bitmap of num_ent bits, two id
+ *   lists of B (L + 1) int32 that grow with the batch -- and zeroes d(ent_emb) / d(pred_bias) whole, once.  Disabling first brings every
+ *   row current on `stream`; the next step is the dense one.
+ * coper_train_rows_deferred(h): 1 or 0; -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle.
+ * coper_train_sync_rows(h, stream): one pass over num_ent that brings every row of ent_emb, pred_bias and their three slots current.
+ *   Idempotent (a row that is current is not written: a second call changes no bit); a no-op with the mode off.
+ * coper_train_row_stats(h, &rows_last_step, &rows_behind, &max_gap, stream): the unique (clamped) rows the last coper_train_step /
+ *   coper_train_forward named; the rows that are not current and the largest number of updates one is behind, from one scan of the step
+ *   words.  Any output may be NULL; zeros with the mode off.  Synchronises `stream`: for tests and diagnostics.
+ *
+ * With the mode on
+ *   - these calls bring every row current themselves before they read or replace the tables, so explicit syncing is only ever an
+ *     optimisation: coper_prepare; coper_train_slot (get and set) of ent_emb / pred_bias; coper_set_param of those two leaves and
+ *     coper_train_powers when it sets a power (neither has a stream: the pass runs on the null stream between two device
+ *     synchronisations, so not under stream capture; coper_set_param syncs through the pointers registered BEFORE the call, which must
+ *     still be live).  coper_train_grad needs nothing: the dense gradient buffers stay and hold the whole gradient of the last step
+ *     (the rows of the step before are re-zeroed at the start of the next call instead of the whole buffers).
+ *   - these are refused with COPER_EUNSUPPORTED, coper_last_error says why, the handle stays usable: 1-vs-all steps, dense or CSR (every
+ *     row has a gradient); coper_train_backward*, coper_train_grads_export, coper_train_apply (the flat vector is dense by contract).
+ *   - the registered ent_emb / pred_bias TENSORS are current only after a sync (or one of the calls above): a raw read of them in
+ *     between sees rows as of their last use.  Rows named by a step are current when it returns.
+ *   - coper_train_forward brings the rows of its batch current too (it reads them) and advances nothing.
+ *   - with the profile enabled (coper_profile_enable) the training step files counts, no times, under these names for
+ *     coper_profile_read: "train.zero.<leaf>" per whole-buffer zeroing of a leaf's gradient (ent_emb, pred_bias, rel_emb and the static
+ *     conv leaves), "train.sumsq.leaves" / "train.amsgrad.leaves" the tensors k_tr_sumsq / k_tr_amsgrad ran over, and
+ *     "train.rows.rezero|claim|catch_up|sumsq|update|sync" per launch of a row kernel. */
+COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stream);
+COPER_API int coper_train_rows_deferred(const coper_handle* h);
+COPER_API int coper_train_sync_rows(coper_handle* h, void* stream);
+COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, int64_t* rows_behind, int64_t* max_gap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
