@@ -137,6 +137,11 @@ PROTOTYPES = {
     "coper_train_rows_deferred": (C.c_int, [_P]),
     "coper_train_sync_rows": (C.c_int, [_P, _P]),
     "coper_train_row_stats": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P]),
+    "coper_train_rows_layout": (C.c_int, [_P, C.c_char_p, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "coper_train_rows_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    "coper_train_rows_export": (C.c_int, [_P, _P, _I64, C.c_int32, _P, _P, _I64, _P, _P]),
+    "coper_train_rows_import": (C.c_int, [_P, _P, _P, _I64, C.c_int32, _P]),
+    "coper_train_rows_apply": (C.c_int, [_P, _P, _I64, C.c_double, _P]),
 }
 
 _lib = None

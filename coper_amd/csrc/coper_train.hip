@@ -28,7 +28,8 @@
 //   Deferred rows (coper_train_defer_rows): the sampled step touches only the rows of ent_emb / pred_bias its batch names --
 //   claim, catch up (the closed form of the skipped zero-gradient updates), norm and update over that list, the list before re-zeroed --
 //   in phases of their own beside the ones above (Step::rows_*; kernels in train_rows.h); k_tr_zero_list, k_tr_sumsq and k_tr_amsgrad
-//   leave the two tables out.  With the mode off every launch is the one it was.
+//   leave the two tables out.  With the mode off every launch is the one it was.  The mode's split step (coper_train_rows_backward |
+//   _export | _import | _apply) exchanges a small flat vector and row blocks: k_rows_export / k_rows_import (train_rows.h).
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 #include <algorithm>
@@ -51,6 +52,7 @@ struct TrainParam {
   int64_t n = 0;
   DevBuf<float> g;      // gradient of the last step
   int64_t flat_off = 0; // where the leaf starts in the flat gradient vector (coper_train_grads_layout)
+  int64_t small_off = -1; // ... and in the small flat vector of the deferred-rows split step (coper_train_rows_layout; -1: ent_emb, pred_bias)
   DevBuf<float> m;      // AMSGrad slots
   DevBuf<float> v;
   DevBuf<float> vh;
@@ -186,6 +188,14 @@ struct TrainState {
   DevBuf<int32_t> rows_word, rows_list[2], rows_count;
   DevBuf<unsigned> rows_claim;
   DevBuf<unsigned long long> rows_stats;
+  // the step in calls in the mode (coper_train_rows_*).  small_total: the small flat vector's length.  rows_pending_small:
+  // the gradient buffers of every leaf but the two tables hold a coper_train_rows_backward that nothing has consumed or zeroed;
+  // rows_pending_table: rows_list[rows_prev] and the listed rows of d(ent_emb) / d(pred_bias) hold such a backward, or the imports since
+  // the last `first`; rows_bound: what the host knows about that list's length (min(B (L + 1), E); min(E, entries imported))
+  int64_t small_total = 0;
+  bool rows_pending_small = false, rows_pending_table = false;
+  int64_t rows_bound = 0;
+  void rows_pending_clear() { rows_pending_small = rows_pending_table = false; rows_bound = 0; }
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -399,6 +409,10 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
     if (TrainParam* t = T->find(lf.name.c_str())) {
       t->flat_off = T->flat_total;
       T->flat_total += (t->n + 63) / 64 * 64;
+      if (t != T->lv.ent_emb && t != T->lv.pred_bias) {      // the small flat vector: the same rules without the two tables
+        t->small_off = T->small_total;
+        T->small_total += (t->n + 63) / 64 * 64;
+      }
     }
   T->mx = dm.C > dm.d ? dm.C : dm.d;
   for (int i = 0; i < T->nh; ++i) T->mx = h->cfg.ctx_out[i] > T->mx ? h->cfg.ctx_out[i] : T->mx;
@@ -517,15 +531,25 @@ static int rows_sync_launch(coper_handle* h, TrainState* T, hipStream_t s) {
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
+// the step words are int32: close to the end, start counting again from a table that is current (every word 0 = rows_now)
+static int rows_wrap_guard(coper_handle* h, TrainState* T, hipStream_t s) {
+  if (T->rows_now < 0x7ffffff0) return COPER_OK;
+  if (int rc = rows_sync_launch(h, T, s)) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * (size_t)h->dm.E, s));
+  T->rows_now = 0;
+  return COPER_OK;
+}
 
 // clip + AMSGrad over every trainable tensor: the squared norm (k_tr_sumsq; deterministic mode: through the slab and its fold), then
 // k_tr_amsgrad.  Deferred rows: ent_emb and pred_bias are left out of both launches, and the rows of `rows_list` (its length on the
 // device, `rows_count`) go through k_rows_sumsq / k_rows_update between and behind them.  The caller has zeroed the squared-norm slots
 // and wmax[wmax_cur ^ 1].  flat: the gradients are read from the flat gradient vector in place (each leaf at its flat_off) instead of the gradient buffers.  sumsq_done: the leaf whose squares a GEMM of
 // the same step already added to the slots.  table_counts: the relation counts that say which rows of the looked-up dense table
-// exist.  gs: coper_train_apply's scale (1: the fused step).  Returns whether the pass carried the dense weights' maximum.
+// exist.  gs: coper_train_apply's scale (1: the fused step).  flat_small: `flat` is the small flat vector of coper_train_rows_apply (each
+// leaf at its small_off; with rows_list).  Returns whether the pass carried the dense weights' maximum.
 static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, const float* flat, const TrainParam* sumsq_done,
-                             const int32_t* table_counts, double gs, const int32_t* rows_list = nullptr, const int32_t* rows_count = nullptr) {
+                             const int32_t* table_counts, double gs, const int32_t* rows_list = nullptr, const int32_t* rows_count = nullptr,
+                             bool flat_small = false) {
   const Dims& dm = h->dm;
   const coper_train_config& tc = T->cfg;
   const TrainLeaves& lv = T->lv;
@@ -540,7 +564,7 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
   for (const TrainParam& t : T->tp) {
     if (rows_list && (&t == lv.ent_emb || &t == lv.pred_bias)) continue;
     const int i = np++;
-    tt.p[i] = t.p; tt.g[i] = flat ? const_cast<float*>(flat) + t.flat_off : t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
+    tt.p[i] = t.p; tt.g[i] = flat ? const_cast<float*>(flat) + (flat_small ? t.small_off : t.flat_off) : t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
     tt.n[i] = t.n;
     const bool table = lk && &t == lv.fc_weights;
     tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
@@ -583,7 +607,8 @@ struct Step {
   hipStream_t const s;
   const int64_t *const e1, *const rel; const int32_t* const lookup; const float* const labels; const int64_t B, L;
   float *const loss_out, *const pred_out, *const h_out;
-  const int apply;                  // 0: coper_train_forward; 1: coper_train_step; 2: coper_train_backward (everything but the optimizer)
+  const int apply;                  // 0: coper_train_forward; 1: coper_train_step; 2: coper_train_backward (everything but the optimizer);
+                                    // 3: coper_train_rows_backward (the same in the deferred-rows mode)
   const CsrLabels csr;              // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
   const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
   const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
@@ -1268,11 +1293,14 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
   }
+  if (apply == 3 && !T->rows_deferred)      // coper_train_rows_backward: the mode's own backward
+    return fail(h, COPER_ESTATE, "coper_train_rows_backward: the deferred-rows mode is off (coper_train_defer_rows; coper_train_backward is the dense call)");
   if (T->rows_deferred) {      // what has a gradient in every row, or hands the dense gradient on, is refused
     if (csr.indptr || !lookup)
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deferred-rows mode (coper_train_defer_rows): a 1-vs-all step has a gradient in every row");
     if (apply == 2)
-      return fail(h, COPER_EUNSUPPORTED, "coper_train_backward: deferred-rows mode (coper_train_defer_rows): the split step's flat gradient is dense");
+      return fail(h, COPER_EUNSUPPORTED, "coper_train_backward: deferred-rows mode (coper_train_defer_rows): the split step's flat gradient is dense "
+                                         "(the mode's split step: coper_train_rows_backward / _export / _import / _apply)");
     if (B * (L + 1) > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_train_step: deferred-rows mode: B * (L + 1) ids do not fit the row lists");
   }
   if (T->det) {      // what the mode does not put in order is refused, never served unordered
@@ -1289,14 +1317,10 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
   if (st.rows) {
-    if (T->rows_now >= 0x7ffffff0) {      // (the step words are int32: start counting again from a table that is current)
-      if ((rc = rows_sync_launch(h, T, st.s))) return rc;
-      COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * (size_t)h->dm.E, st.s));
-      T->rows_now = 0;
-    }
-    if ((rc = st.rows_grow())) return rc;
+    if ((rc = rows_wrap_guard(h, T, st.s)) || (rc = st.rows_grow())) return rc;
   }
   T->pending = false;      // (the gradient buffers are zeroed next: what a coper_train_backward left in them is gone)
+  T->rows_pending_clear();      // (... and what a coper_train_rows_backward or the imports left: rows_rezero below)
   st.zero_accumulators();
   if (st.rows) {
     st.rows_rezero();
@@ -1328,10 +1352,14 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   st.sj.join(SJ_DP);      // (dP and its squared norm)
   st.sj.join(SJ_SCORER_BWD);
   if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_step: an event call of the side streams failed");
-  if (apply == 2) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
+  if (apply >= 2) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
     COPER_HIP_TRY(h, hipGetLastError());
     T->step += 1;
-    T->pending = true;
+    if (apply == 2) T->pending = true;
+    else {               // coper_train_rows_backward: ... for coper_train_rows_export / coper_train_rows_apply; the table part is the claimed list
+      T->rows_pending_small = T->rows_pending_table = true;
+      T->rows_bound = std::min<int64_t>(B * (L + 1), h->dm.E);
+    }
     return COPER_OK;
   }
   const bool wmax_carried = st.optimizer();
@@ -1407,7 +1435,8 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
   if (T->rows_deferred)
-    return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: deferred-rows mode (coper_train_defer_rows): the flat gradient vector is dense by contract");
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: deferred-rows mode (coper_train_defer_rows): the flat gradient vector is dense by contract "
+                                       "(the mode's export: coper_train_rows_export)");
   if (!flat || ((uintptr_t)flat & 15) != 0) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat must be a 16-byte aligned device buffer");
   if (cap < T->flat_total) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat holds fewer than coper_train_grads_layout's total");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1432,7 +1461,8 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
   if (T->rows_deferred)
-    return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: deferred-rows mode (coper_train_defer_rows): an update from the dense flat gradient touches every row");
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: deferred-rows mode (coper_train_defer_rows): an update from the dense flat gradient touches every row "
+                                       "(the mode's update: coper_train_rows_apply)");
   if (!flat && !T->pending)
     return fail(h, COPER_ESTATE, "coper_train_apply: no gradients pending (no coper_train_backward since the last update, step, forward or init)");
   if (flat && (n != T->flat_total || ((uintptr_t)flat & 15) != 0))
@@ -1495,6 +1525,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   if (!enable) {      // every row current, then the dense path again (it zeroes the gradient buffers whole; the row state is rebuilt at the next enable)
     if (int rc = rows_sync_launch(h, T, s)) return rc;
     T->rows_deferred = false;
+    T->rows_pending_clear();      // (the dense step zeroes the two buffers whole: a pending row gradient is gone)
     return COPER_OK;
   }
   const size_t E = (size_t)h->dm.E;
@@ -1513,6 +1544,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   T->rows_l2b1p = std::log2(T->b1p);      // (log2(0) = -inf: the power is 0 at every gap, as the dense step has it)
   T->rows_l2b2p = std::log2(T->b2p);
   T->pending = false;      // (a pending backward's gradient is gone with the zeroing)
+  T->rows_pending_clear();
   T->rows_deferred = true;
   return COPER_OK;
 }
@@ -1551,6 +1583,165 @@ COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, in
   if (rows_last_step) *rows_last_step = counts[T->rows_prev];
   if (rows_behind) *rows_behind = (int64_t)st[0];
   if (max_gap) *max_gap = (int64_t)st[1];
+  return COPER_OK;
+}
+
+// ---- deferred rows: the step in calls (include/coper_hip.h, "Deferred rows: the step in calls")
+static inline int rows_block_stride(int d) { return (d + 1 + 3) & ~3; }
+
+// The id lists at `need` entries or more WITH what they hold (Step::rows_grow re-zeroes the listed rows and drops the list: a step is
+// about to do that anyway; an import adds to the list).  Doubles, up to E, so that the imports of one update grow it a few times at most.
+static int rows_grow_keep(coper_handle* h, TrainState* T, int64_t need, hipStream_t s) {
+  if (need <= T->rows_cap) return COPER_OK;
+  const int64_t cap = std::max<int64_t>(need, std::min<int64_t>(2 * T->rows_cap, h->dm.E));
+  DevBuf<int32_t> grown[2];
+  int rc;
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  for (int i = 0; i < 2; ++i) {
+    if ((rc = grown[i].alloc(h, (size_t)cap, "deferred-row list"))) return rc;      // (nothing has changed: the old lists stand)
+    if (T->rows_cap)
+      COPER_HIP_TRY(h, hipMemcpyAsync(grown[i], T->rows_list[i], sizeof(int32_t) * (size_t)T->rows_cap, hipMemcpyDeviceToDevice, s));
+  }
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  for (int i = 0; i < 2; ++i) T->rows_list[i] = std::move(grown[i]);
+  T->rows_cap = cap;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_layout(coper_handle* h, const char* leaf_name, int64_t* offset, int64_t* n, int64_t* total, int64_t* row_stride) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_layout: call coper_train_init first");
+  if (total) *total = T->small_total;
+  if (row_stride) *row_stride = rows_block_stride(h->dm.d);
+  if (!leaf_name) return COPER_OK;
+  const TrainParam* t = T->find(leaf_name);
+  if (!t) return fail(h, COPER_EINVAL, std::string("coper_train_rows_layout: not a trainable leaf: ") + leaf_name);
+  if (t->small_off < 0)
+    return fail(h, COPER_EINVAL, std::string("coper_train_rows_layout: ") + leaf_name + " travels as row blocks, not in the small flat vector");
+  if (offset) *offset = t->small_off;
+  if (n) *n = t->n;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
+                                        int64_t B, int64_t L, float* loss_out, void* stream) {
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 3, nullptr, nullptr);
+}
+
+COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t small_cap, int32_t accumulate, int32_t* ids, float* vals,
+                                      int64_t row_cap, int32_t* count, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_export: call coper_train_init first");
+  if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_export: the deferred-rows mode is off (coper_train_grads_export is the dense call)");
+  if ((ids == nullptr) != (vals == nullptr)) return fail(h, COPER_EINVAL, "coper_train_rows_export: ids and vals are given or NULL together");
+  if (!small && !ids) return fail(h, COPER_EINVAL, "coper_train_rows_export: nothing to export into");
+  if (small && !T->rows_pending_small)
+    return fail(h, COPER_ESTATE, "coper_train_rows_export: no gradients pending (no coper_train_rows_backward since the last update, step, forward or init)");
+  if (ids && !T->rows_pending_table)
+    return fail(h, COPER_ESTATE, "coper_train_rows_export: no row gradients pending (no coper_train_rows_backward or import since the last update, step, forward or init)");
+  if (small && (((uintptr_t)small & 15) != 0 || small_cap < T->small_total))
+    return fail(h, COPER_EINVAL, "coper_train_rows_export: small must be 16-byte aligned and hold coper_train_rows_layout's total");
+  if (ids && (row_cap < T->rows_bound || row_cap > 0x7fffffff))
+    return fail(h, COPER_EINVAL, "coper_train_rows_export: row_cap is below the bound of the pending rows (min(B (L + 1), num_ent) of the backward; min(num_ent, entries imported))");
+  if (ids && (((uintptr_t)ids & 3) != 0 || ((uintptr_t)vals & 3) != 0)) return fail(h, COPER_EINVAL, "coper_train_rows_export: misaligned ids / vals");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  if (small) {      // k_tr_grads_export over every leaf but the two tables, at their offsets in the small vector
+    ExportList el;
+    int np = 0;
+    el.table = -1; el.rowlen = 1; el.rowcnt = nullptr;
+    for (const TrainParam& t : T->tp) {
+      if (t.small_off < 0) continue;
+      const int i = np++;
+      el.g[i] = t.g; el.off[i] = t.small_off; el.n[i] = t.n; el.span[i] = (t.n + 63) / 64 * 64;
+      if (h->dm.lookup && h->dm.gen_fc && &t == T->lv.fc_weights) {      // rows of relations absent from the backward's batch: zeros
+        el.table = i; el.rowlen = h->dm.F * (int64_t)h->dm.d; el.rowcnt = T->step_rel_count;
+      }
+    }
+    if (accumulate) hipLaunchKernelGGL(k_tr_grads_export<true>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, small);
+    else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, small);
+  }
+  if (ids) {
+    const RowTables t = row_tables(h, T);
+    const int pv = T->rows_prev;
+    hipLaunchKernelGGL(k_rows_export, rows_grid(row_cap), dim3(256), 0, s, t, (const int32_t*)T->rows_list[pv].get(), (const int32_t*)(T->rows_count + pv),
+                       ids, vals, rows_block_stride(h->dm.d), (t.vec && ((uintptr_t)vals & 15) == 0) ? 1 : 0, row_cap, count);
+    prof_count(h, "train.rows.export");
+  }
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const float* vals, int64_t n, int32_t first, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_import: call coper_train_init first");
+  if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_import: the deferred-rows mode is off (coper_train_defer_rows)");
+  if (n < 0 || n > 0x7fffffff || (n > 0 && (!ids || !vals)) || ((uintptr_t)ids & 3) != 0 || ((uintptr_t)vals & 3) != 0)
+    return fail(h, COPER_EINVAL, "coper_train_rows_import: bad argument");
+  if (!first && !T->rows_pending_table)
+    return fail(h, COPER_ESTATE, "coper_train_rows_import: no row gradients pending to add to: the first import of an update passes first != 0");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  const int64_t bound = std::min<int64_t>(h->dm.E, (first ? 0 : T->rows_bound) + n);
+  int rc;
+  // (at least one entry: the optimizer takes "a list exists" for "the mode is on")
+  if ((rc = rows_wrap_guard(h, T, s)) || (rc = rows_grow_keep(h, T, std::max<int64_t>(bound, 1), s))) return rc;
+  const RowTables t = row_tables(h, T);
+  if (first) {      // a new pending gradient: what a step does to the list of the call before (k_rows_rezero), and the free list becomes the current one
+    const int pv = T->rows_prev;
+    if (T->rows_cap) {
+      hipLaunchKernelGGL(k_rows_rezero, rows_grid(T->rows_cap), dim3(256), 0, s, t, (const int32_t*)T->rows_list[pv].get(), (const int32_t*)(T->rows_count + pv),
+                         T->rows_claim.get(), T->rows_count + (pv ^ 1));
+      prof_count(h, "train.rows.rezero");
+    }
+    T->rows_prev = pv ^ 1;      // (a backward's small gradients stay pending: the import replaces the table part alone)
+  }
+  if (n > 0) {
+    const int cur = T->rows_prev;
+    hipLaunchKernelGGL(k_rows_import, grid1d(n), dim3(256), 0, s, t, row_catch_up_args(T), ids, vals, rows_block_stride(h->dm.d),
+                       (t.vec && ((uintptr_t)vals & 15) == 0) ? 1 : 0, n, T->rows_claim.get(), T->rows_list[cur].get(), T->rows_count + cur, T->rows_cap);
+    prof_count(h, "train.rows.import");
+  }
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->rows_pending_table = true;
+  T->rows_bound = bound;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_t n, double scale, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_apply: call coper_train_init first");
+  if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_apply: the deferred-rows mode is off (coper_train_apply is the dense call)");
+  if (!T->rows_pending_table || (!small && !T->rows_pending_small))
+    return fail(h, COPER_ESTATE, "coper_train_rows_apply: no gradients pending (no coper_train_rows_backward or import since the last update, step, forward or init)");
+  if (small && (n != T->small_total || ((uintptr_t)small & 15) != 0))
+    return fail(h, COPER_EINVAL, "coper_train_rows_apply: small must be 16-byte aligned and n coper_train_rows_layout's total");
+  if (!std::isfinite(scale)) return fail(h, COPER_EINVAL, "coper_train_rows_apply: scale is not finite");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
+  T->rows_pending_clear();
+  const RedLayout red = T->red_layout();
+  ZeroList zl;           // as coper_train_apply: the slots hold the backward's epilogue squares, wmax[wmax_cur ^ 1] what the update before last left
+  zl.n = 2;
+  zl.p[0] = red.sumsq_slots(); zl.bytes[0] = sizeof(double) * TG_SUMSQ_SLOTS;
+  zl.p[1] = T->wmax[T->wmax_cur ^ 1].get(); zl.bytes[1] = sizeof(unsigned) * TG_MAX_SLOTS;
+  hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
+  const int pv = T->rows_prev;
+  const bool wmax_carried = optimizer_launch(h, T, s, small, nullptr, small ? nullptr : T->step_rel_count.get(), scale, T->rows_list[pv].get(),
+                                             T->rows_count + pv, small != nullptr);
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->rows_now += 1;      // (k_rows_update wrote the listed rows' words: current as of this update -- as the mode's fused step)
+  T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
+  T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
+  T->b1p *= T->cfg.beta1;
+  T->b2p *= T->cfg.beta2;
+  T->wmax_cur ^= 1;
+  T->wmax_valid = wmax_carried;
   return COPER_OK;
 }
 

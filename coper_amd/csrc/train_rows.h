@@ -251,5 +251,154 @@ __global__ __launch_bounds__(256) void k_rows_stats(const int32_t* __restrict__ 
   if ((threadIdx.x & 63) == 0 && behind) { atomicAdd(out, behind); atomicMax(out + 1, gap); }
 }
 
+// ---- the step in calls (include/coper_hip.h, "Deferred rows: the step in calls").  What crosses the boundary for the two
+// tables is a ROW BLOCK: ids int32 [row_cap] and vals float [row_cap, rs], rs = (d + 1 + 3) & ~3 -- columns [0, d) the row of d(ent_emb),
+// column d the row's d(pred_bias), the pad columns 0.  vec: d % 4 == 0, the tables' pointers (RowTables::vec) and vals 16-byte aligned.
+constexpr int ROWS_BLOCK_INFLIGHT = 4;      // rows of a wave whose loads are issued before the first store
+
+// 7. Export: a wave per listed row (grid-stride, ROWS_BLOCK_INFLIGHT rows of a wave in flight): ids[i] = the row, vals[i] = its gradient
+// row and bias gradient, copied; ids[count .. row_cap) = -1 by all threads behind; *count_out = count.  A gather of 2 rows rs 4 bytes.
+// The host has checked row_cap against its bound of the list's length; the kernel takes the smaller of the two all the same.
+__global__ __launch_bounds__(256) void k_rows_export(RowTables t, const int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                     int32_t* __restrict__ ids, float* __restrict__ vals, int rs, int vec, int64_t row_cap,
+                                                     int32_t* __restrict__ count_out) {
+  const int64_t n = (int64_t)*count < row_cap ? (int64_t)*count : row_cap;
+  const int lane = threadIdx.x & 63;
+  const int64_t W = (int64_t)gridDim.x * 4;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && count_out) *count_out = (int32_t)n;
+  for (int64_t i0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i0 < n; i0 += ROWS_BLOCK_INFLIGHT * W) {
+    int64_t row[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+    for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u) row[u] = i0 + u * W < n ? (int64_t)list[i0 + u * W] : -1;
+    if (vec) {
+      const int d4 = t.d >> 2;
+      for (int q = lane; q < d4; q += 64) {
+        float4 v[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (row[u] >= 0) v[u] = ((const float4*)(t.g + row[u] * t.d))[q];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (row[u] >= 0) ((float4*)(vals + (i0 + u * W) * rs))[q] = v[u];
+      }
+    } else {
+      for (int q = lane; q < t.d; q += 64) {
+        float v[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (row[u] >= 0) v[u] = t.g[row[u] * t.d + q];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (row[u] >= 0) vals[(i0 + u * W) * rs + q] = v[u];
+      }
+    }
+    if (lane == 0) {      // the id, the bias column, the pad columns
+      float b[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+      for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+        if (row[u] >= 0) b[u] = t.bg[row[u]];
+#pragma unroll
+      for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u) {
+        if (row[u] < 0) continue;
+        const int64_t i = i0 + u * W;
+        ids[i] = (int32_t)row[u];
+        if (vec) ((float4*)(vals + i * rs))[t.d >> 2] = make_float4(b[u], 0.f, 0.f, 0.f);
+        else {
+          vals[i * rs + t.d] = b[u];
+          for (int c = t.d + 1; c < rs; ++c) vals[i * rs + c] = 0.f;
+        }
+      }
+    }
+  }
+  for (int64_t j = n + (int64_t)blockIdx.x * 256 + threadIdx.x; j < row_cap; j += (int64_t)gridDim.x * 256) ids[j] = -1;
+}
+
+// 8. Import: a thread per block entry, a wave per 64 of them, three jobs in one launch -- no job of one wave waits for another wave.
+//   claim + append: k_rows_claim's form; an entry outside [0, E) is padding and does not vote.  The thread that sets a row's claim bit is
+//     the one that writes its list entry (list_cap: the host's bound holds; the kernel does not rely on it for its stores).
+//   catch-up: the rows this wave appended, one after the other by the whole wave (rows_catch_up; a current row has gap 0 and is skipped,
+//     so a row is brought current once however often it is imported).  Rows that were listed already are current: whoever listed them
+//     brought them current.
+//   add: g[row] += vals[i], d(pred_bias)[row] += vals[i][d], entry after entry of the wave, ROWS_BLOCK_INFLIGHT entries' loads in
+//     flight.  Plain loads and stores: the ids of a block are distinct, so an element has one writer per launch, and launches on a stream
+//     add in call order.  The gradient row of a row that was not listed is zero (the mode's invariant), so the add is right for rows
+//     appended by this very launch too, whichever wave appended them.  (A block that names a row twice: two waves read, add and
+//     write -- some sum of the two, nothing else.)
+__global__ __launch_bounds__(256) void k_rows_import(RowTables t, RowCatchUp cu, const int32_t* __restrict__ ids, const float* __restrict__ vals,
+                                                     int rs, int vec, int64_t n, unsigned* __restrict__ claim, int32_t* __restrict__ list,
+                                                     int32_t* __restrict__ count, int64_t list_cap) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, i_wave = i - lane;
+  int row = -1;
+  if (i < n) {
+    row = ids[i];
+    if (row < 0 || (int64_t)row >= t.E) row = -1;
+  }
+  bool mine = false;
+  if (row >= 0) {
+    const unsigned bit = 1u << (row & 31);
+    mine = (atomicOr(claim + (row >> 5), bit) & bit) == 0u;
+  }
+  const unsigned long long valid = __ballot(row >= 0);
+  if (valid == 0ull) return;      // (the whole wave)
+  const unsigned long long fresh = __ballot(mine);
+  if (fresh != 0ull) {
+    const int leader = __ffsll((long long)fresh) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(count, (int)__popcll(fresh));
+    base = __shfl(base, leader, 64);
+    if (mine) {
+      const int64_t at = (int64_t)base + (int64_t)__popcll(fresh & ((1ull << lane) - 1ull));
+      if (at < list_cap) list[at] = row;
+    }
+    for (unsigned long long mm = fresh; mm != 0ull; mm &= mm - 1ull) {
+      const int64_t r = __shfl(row, __ffsll((long long)mm) - 1, 64);
+      const int k = cu.now - t.word[r];
+      if (k > 0) rows_catch_up(t, cu, r, k, lane);
+    }
+  }
+  unsigned long long mm = valid;
+  while (mm != 0ull) {
+    int64_t r[ROWS_BLOCK_INFLIGHT], e[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+    for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u) {
+      r[u] = -1; e[u] = 0;
+      if (mm != 0ull) {
+        const int j = __ffsll((long long)mm) - 1;
+        mm &= mm - 1ull;
+        r[u] = __shfl(row, j, 64);
+        e[u] = i_wave + j;
+      }
+    }
+    if (vec) {
+      const int d4 = t.d >> 2;
+      for (int q = lane; q < d4; q += 64) {
+        float4 a[ROWS_BLOCK_INFLIGHT], g[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (r[u] >= 0) { a[u] = ((const float4*)(vals + e[u] * rs))[q]; g[u] = ((const float4*)(t.g + r[u] * t.d))[q]; }
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (r[u] >= 0) ((float4*)(t.g + r[u] * t.d))[q] = make_float4(g[u].x + a[u].x, g[u].y + a[u].y, g[u].z + a[u].z, g[u].w + a[u].w);
+      }
+    } else {
+      for (int q = lane; q < t.d; q += 64) {
+        float a[ROWS_BLOCK_INFLIGHT], g[ROWS_BLOCK_INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (r[u] >= 0) { a[u] = vals[e[u] * rs + q]; g[u] = t.g[r[u] * t.d + q]; }
+#pragma unroll
+        for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+          if (r[u] >= 0) t.g[r[u] * t.d + q] = g[u] + a[u];
+      }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int u = 0; u < ROWS_BLOCK_INFLIGHT; ++u)
+        if (r[u] >= 0) t.bg[r[u]] += vals[e[u] * rs + t.d];
+    }
+  }
+}
+
 }  // namespace
 }  // namespace coper

@@ -879,7 +879,8 @@ class ConvE(object):
         caller's own and are CURRENT ONLY AFTER A SYNC: train_sync_rows(), or any of prepare() / encode() and the other inference calls,
         `variables`, session fetches of the tables, optimizer_state() and the checkpoint writers fed from them, which sync themselves.
         A raw read of the tensors in between is the caller's risk.  Not with deterministic=True; 1-vs-all batches and the split step
-        (train_backward / train_grads_export / train_apply) are refused in the mode."""
+        (train_backward / train_grads_export / train_apply) are refused in the mode, whose own split step is train_rows_backward /
+        train_rows_export / train_rows_import / train_rows_apply (`coper_amd.parallel.DataParallelTrainer` takes it by itself)."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -899,6 +900,8 @@ class ConvE(object):
             _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
         self._grads_layout = None
+        self._rows_layout = None
+        self._rows_bound = 0             # the block size train_rows_export allocates by: the bound of the pending rows
         self._rows_deferred = False      # (a new training state starts dense)
         if deferred_rows:
             self.train_defer_rows(True)
@@ -1066,6 +1069,97 @@ class ConvE(object):
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_apply(self._h, _ptr(flat), flat.numel() if flat is not None else 0, float(scale),
                                                             self._stream()))
+        self._after_update()
+        return self
+
+    # ---- deferred rows: the step in calls (include/coper_hip.h: rows_backward | rows_export | rows_import | rows_apply)
+    def train_rows_layout(self):
+        """coper_train_rows_layout: ({leaf: (offset, n)} of the SMALL flat vector -- every trainable leaf but ent_emb / pred_bias, the
+        rules of train_grads_layout --, its total length in floats, the row block's stride rs = (ent_emb_size + 4) & ~3 in floats)."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        if getattr(self, "_rows_layout", None) is None:      # (fixed at train_init)
+            off, n, total, rs = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+            out = {}
+            for leaf in self._specs:
+                if leaf.endswith(("moving_mean", "moving_variance")) or leaf in ("ent_emb", "pred_bias"):
+                    continue
+                _lib.check(self._h, self._lib.coper_train_rows_layout(self._h, leaf.encode(), C.byref(off), C.byref(n), None, None))
+                out[leaf] = (off.value, n.value)
+            _lib.check(self._h, self._lib.coper_train_rows_layout(self._h, None, None, None, C.byref(total), C.byref(rs)))
+            self._rows_layout = (out, total.value, rs.value)
+        return dict(self._rows_layout[0]), self._rows_layout[1], self._rows_layout[2]
+
+    def train_rows_backward(self, batch):
+        """coper_train_rows_backward: the deferred-rows mode's sampled train_step without the update.  The loss, the BN moving
+        statistics and the dropout counter move; the gradients stay on the handle for train_rows_export / train_rows_apply (the tables'
+        as the list of rows the batch named).  1-vs-all batches are refused.  Returns the loss as a 1-element device tensor."""
+        if "e2_multi" not in batch and "lab_indptr" in batch:
+            raise _lib.CoperError(7, "train_rows_backward: deferred-rows mode: a 1-vs-all step has a gradient in every row")
+        self._train_dispatch(batch, self._lib.coper_train_rows_backward, None)
+        B = int(len(batch["e1"]))
+        L = int(batch["e2_multi"].shape[1])
+        self._rows_bound = min(B * (L + 1), self.num_ent)
+        return self._train_loss
+
+    def _rows_block(self, ids, vals, what):
+        dev = torch.device(self.device)
+        rs = self.train_rows_layout()[2]
+        if (ids.dtype != torch.int32 or vals.dtype != torch.float32 or not ids.is_contiguous() or not vals.is_contiguous() or ids.device != dev
+                or vals.device != dev or ids.dim() != 1 or tuple(vals.shape) != (ids.numel(), rs)):
+            raise ValueError("%s: ids int32 [n] and vals float32 [n, %d], contiguous, on the model's device" % (what, rs))
+
+    def train_rows_export(self, small=None, accumulate=False, ids=None, vals=None):
+        """coper_train_rows_export: the pending gradients as (small, ids, vals, count) device tensors.  `small` = g or += g over the
+        small flat vector (None allocates it; zeros when accumulating; False: the block alone); the block ids int32 [cap] / vals float32 [cap, rs] takes the
+        rows of the pending list -- ids[:count] the rows, vals their gradient rows and bias gradients, ids[count:] = -1.  ids = vals =
+        None allocates the block at the bound of the last train_rows_backward, min(B (L + 1), num_ent).  count: a 1-element int32 device
+        tensor (no synchronisation).  Nothing is consumed."""
+        total = self.train_rows_layout()[1]
+        rs = self._rows_layout[2]
+        if small is False:      # the block alone (after imports no backward's small gradients need be pending): None is returned for it
+            small = None
+        elif small is None:
+            small = (torch.zeros if accumulate else torch.empty)(total, device=self.device, dtype=torch.float32)
+        if small is not None and (small.dtype != torch.float32 or not small.is_contiguous() or small.device != torch.device(self.device)):
+            raise ValueError("train_rows_export: small must be a contiguous float32 tensor on the model's device")
+        if (ids is None) != (vals is None):
+            raise ValueError("train_rows_export: ids and vals are given or None together")
+        if ids is None:
+            cap = max(int(getattr(self, "_rows_bound", 0)), 1)
+            ids = torch.empty(cap, device=self.device, dtype=torch.int32)
+            vals = torch.empty((cap, rs), device=self.device, dtype=torch.float32)
+        self._rows_block(ids, vals, "train_rows_export")
+        count = torch.zeros(1, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_rows_export(self._h, _ptr(small), small.numel() if small is not None else 0,
+                                                                  1 if accumulate else 0, _ptr(ids), _ptr(vals),
+                                                                  ids.numel(), _ptr(count), self._stream()))
+        return small, ids, vals, count
+
+    def train_rows_import(self, ids, vals, first=False):
+        """coper_train_rows_import: adds a row block (ids int32 [n], vals float32 [n, rs]; entries outside [0, num_ent) are padding) to
+        the pending table gradient; first=True starts a new one.  Blocks add up in call order, one writer per element, no atomics."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        self._rows_block(ids, vals, "train_rows_import")
+        self._sync_parameters()      # (rows the block brings onto the list are brought current: through the registered tensors)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_rows_import(self._h, _ptr(ids), _ptr(vals), ids.numel(), 1 if first else 0, self._stream()))
+        self._rows_bound = min(self.num_ent, (0 if first else int(getattr(self, "_rows_bound", 0))) + ids.numel())
+        return self
+
+    def train_rows_apply(self, small=None, scale=1.0):
+        """coper_train_rows_apply: clip + AMSGrad from the pending row gradients (a train_rows_backward's, or the imports') and the
+        small flat vector (read in place; None: the pending gradients of the last train_rows_backward).  `scale` as in train_apply."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        if small is not None and (small.dtype != torch.float32 or not small.is_contiguous() or small.device != torch.device(self.device)):
+            raise ValueError("train_rows_apply: small must be a contiguous float32 tensor on the model's device")
+        self._sync_parameters()
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_rows_apply(self._h, _ptr(small), small.numel() if small is not None else 0, float(scale),
+                                                                 self._stream()))
         self._after_update()
         return self
 

@@ -6,6 +6,9 @@ export that ADDS its gradient into one flat vector, ONE all-reduce (sum) of that
 scaled by 1 / (ranks * micro-batches).  The replicas start equal (rank 0's state is broadcast) and stay equal, because every rank
 applies the same bytes.  Entity-sharded (model-parallel) training is not built, the all-reduce does not overlap the backward pass,
 and there is no SyncBN.
+
+In the deferred-rows mode (coper_train_defer_rows) the same update is made from coper_train_rows_backward | _export | _import | _apply:
+a small flat vector for everything but ent_emb / pred_bias, and row blocks (ids, gradient rows) for those two.
 """
 import ctypes as C
 
@@ -62,7 +65,26 @@ class DataParallelTrainer(object):
 
     The averaged moving statistics are written into the caller's tensors in place.  That moves their version counters, and the
     model registers them again (coper_set_param); registering a moving statistic again does not discard what the optimizer's
-    last pass recorded about the dense weights (their largest magnitude, which the next step's operand packing scales by)."""
+    last pass recorded about the dense weights (their largest magnitude, which the next step's operand packing scales by).
+
+    THE SPARSE ROUTE.  A model in the deferred-rows mode (`train_init(deferred_rows=True)`, `model.train_rows_deferred == 1` at
+    construction) never forms the dense gradient of ent_emb / pred_bias, so there is no flat vector to all-reduce.  `step` then makes
+    the update from the mode's own split step (include/coper_hip.h, "Deferred rows: the step in calls"):
+
+      * per micro-batch i `train_rows_backward` + `train_rows_export`: the SMALL flat vector (every leaf but the two tables)
+        accumulates in `flat`, the batch's rows and their gradient rows go into slot i of an [M, cap] / [M, cap, rs] pair of buffers;
+      * ONE `all_reduce(SUM)` of the small vector;
+      * one `all_gather` of the M block lengths and ONE HOST READ of their maximum `mx` -- the only host synchronisation of an update.
+        It buys gathering `ids[:, :mx]` / `vals[:, :mx]` instead of cap = B (L + 1) rows per rank and micro-batch every time;
+      * every rank imports ALL world * M blocks, its own included, from the gathered buffers in ascending (rank, micro-batch) order,
+        the first with `first=True`: every replica adds the same bytes in the same order, one writer per element, no float atomics --
+        the replicas' table gradients are equal byte for byte (`gathered` keeps the last update's buffers);
+      * `train_rows_apply(flat, 1 / (world * micro_batches))`; moving statistics and loss as above.
+
+    The replicas' VARIABLES are not claimed equal to the bit on this route: the mode's squared norm is summed by unordered atomics.
+    Construction brings every row current (`train_sync_rows`) before the raw tables are broadcast.  Over gloo, which gathers host
+    tensors only, the blocks are staged through the host: ranks sharing a GPU are a correctness run, and multi-GPU scaling of this route
+    has not been measured.  Sampled batches only (the mode refuses 1-vs-all)."""
 
     def __init__(self, model, group=None, micro_batches=1):
         import torch.distributed as dist
@@ -78,7 +100,14 @@ class DataParallelTrainer(object):
         self.group = group
         self.world = self._dist.get_world_size(group) if self._dist else 1
         self.rank = self._dist.get_rank(group) if self._dist else 0
-        self.layout, total = model.train_grads_layout()
+        self.sparse = model.train_rows_deferred == 1      # the deferred-rows mode: the sparse route (class docstring)
+        if self.sparse:
+            self.layout, total, self.row_stride = model.train_rows_layout()
+            self._ids = self._vals = None                 # [M, cap] / [M, cap, rs]: micro-batch i's row block in slot i
+            self._counts = torch.zeros(self.micro_batches, device=model.device, dtype=torch.int32)
+            self.gathered = None                          # the last update's (ids [W, M, mx], vals [W, M, mx, rs]) as every rank imported them
+        else:
+            self.layout, total = model.train_grads_layout()
         self.flat = torch.zeros(total, device=model.device, dtype=torch.float32)
         self._stat_names = [k for k in model._tensors if k.endswith(("moving_mean", "moving_variance"))]
         n_stats = sum(model._tensors[k].numel() for k in self._stat_names)
@@ -92,6 +121,7 @@ class DataParallelTrainer(object):
 
     def _broadcast_state(self):
         m, dist, src = self.model, self._dist, self._src()
+        m.train_sync_rows()      # (deferred rows: the raw ent_emb / pred_bias tensors are current only after a sync)
         for t in m._tensors.values():
             dist.broadcast(t, src=src, group=self.group)
         # (whether a collective into a tensor moves its version counter is the backend's business: register every tensor again --
@@ -123,6 +153,8 @@ class DataParallelTrainer(object):
             batches = [batches]
         if len(batches) != self.micro_batches:
             raise ValueError("step: %d local batches, micro_batches = %d" % (len(batches), self.micro_batches))
+        if self.sparse:
+            return self._step_rows(batches)
         small = self._small
         loss = small[-1:]
         for i, b in enumerate(batches):
@@ -135,6 +167,15 @@ class DataParallelTrainer(object):
         if self.world > 1:
             dist = self._dist
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
+        self._average_stats()
+        m.train_apply(self.flat, 1.0 / (self.world * self.micro_batches))
+        return loss / float(self.world * self.micro_batches)
+
+    def _average_stats(self):
+        """The BN moving statistics averaged over the ranks in one small all-reduce, written back in place; the loss rides in it."""
+        m, small = self.model, self._small
+        if self.world > 1:
+            dist = self._dist
             at = 0
             for k in self._stat_names:
                 t = m._tensors[k]
@@ -147,5 +188,50 @@ class DataParallelTrainer(object):
                 t = m._tensors[k]
                 t.copy_(small[at:at + t.numel()].reshape(t.shape))
                 at += t.numel()
-        m.train_apply(self.flat, 1.0 / (self.world * self.micro_batches))
-        return loss / float(self.world * self.micro_batches)
+
+    # ---- one update in the deferred-rows mode
+    def _gather(self, t):
+        """`t` of every rank, stacked [world, ...] in rank order, on the model's device.  gloo gathers host tensors only: there the
+        tensor is staged through the host (ranks sharing a GPU over gloo are a correctness run)."""
+        dist = self._dist
+        if dist.get_backend(self.group) == "nccl":
+            out = torch.empty((self.world,) + tuple(t.shape), device=t.device, dtype=t.dtype)
+            dist.all_gather_into_tensor(out, t.contiguous(), group=self.group)
+            return out
+        host = t.cpu().contiguous()
+        parts = [torch.empty_like(host) for _ in range(self.world)]
+        dist.all_gather(parts, host, group=self.group)
+        return torch.stack(parts).to(t.device)
+
+    def _step_rows(self, batches):
+        """The sparse route (class docstring): the small flat vector is all-reduced, the tables' gradients travel as row blocks."""
+        m, M, rs = self.model, self.micro_batches, self.row_stride
+        small = self._small
+        loss = small[-1:]
+        # the bound of a backward's row list, min(B (L + 1), num_ent) (a batch without sampled labels: train_rows_backward refuses it)
+        cap = max(min(len(b["e1"]) * (int(b["e2_multi"].shape[1]) + 1), m.num_ent) if "e2_multi" in b else 1 for b in batches)
+        if self._ids is None or self._ids.shape[1] < cap:
+            self._ids = torch.full((M, cap), -1, device=m.device, dtype=torch.int32)
+            self._vals = torch.zeros((M, cap, rs), device=m.device, dtype=torch.float32)
+        for i, b in enumerate(batches):
+            li = m.train_rows_backward(b)
+            cnt = m.train_rows_export(self.flat, accumulate=i > 0, ids=self._ids[i], vals=self._vals[i])[3]
+            self._counts[i:i + 1].copy_(cnt)
+            if i:
+                loss += li
+            else:
+                loss.copy_(li)
+        if self.world > 1:
+            dist = self._dist
+            dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
+            mx = int(self._gather(self._counts).max().item())      # the ONE host synchronisation of an update
+            ids, vals = self._gather(self._ids[:, :mx]), self._gather(self._vals[:, :mx])
+            self.gathered = (ids, vals)
+            blocks = [(ids[r, i], vals[r, i]) for r in range(self.world) for i in range(M)]
+        else:
+            blocks = [(self._ids[i], self._vals[i]) for i in range(M)]      # (whole slots: entries behind a block's count are padding)
+        for j, (bi, bv) in enumerate(blocks):      # ascending (rank, micro-batch) on every rank: the same bytes in the same order
+            m.train_rows_import(bi, bv, first=j == 0)
+        self._average_stats()
+        m.train_rows_apply(self.flat, 1.0 / (self.world * M))
+        return loss / float(self.world * M)

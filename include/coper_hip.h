@@ -714,7 +714,8 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
  *     still be live).  coper_train_grad needs nothing: the dense gradient buffers stay and hold the whole gradient of the last step
  *     (the rows of the step before are re-zeroed at the start of the next call instead of the whole buffers).
  *   - these are refused with COPER_EUNSUPPORTED, coper_last_error says why, the handle stays usable: 1-vs-all steps, dense or CSR (every
- *     row has a gradient); coper_train_backward*, coper_train_grads_export, coper_train_apply (the flat vector is dense by contract).
+ *     row has a gradient); coper_train_backward*, coper_train_grads_export, coper_train_apply (the flat vector is dense by contract:
+ *     the mode's split step is coper_train_rows_backward / _export / _import / _apply, "Deferred rows: the step in calls" below).
  *   - the registered ent_emb / pred_bias TENSORS are current only after a sync (or one of the calls above): a raw read of them in
  *     between sees rows as of their last use.  Rows named by a step are current when it returns.
  *   - coper_train_forward brings the rows of its batch current too (it reads them) and advances nothing.
@@ -726,6 +727,61 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
 COPER_API int coper_train_rows_deferred(const coper_handle* h);
 COPER_API int coper_train_sync_rows(coper_handle* h, void* stream);
 COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, int64_t* rows_behind, int64_t* max_gap, void* stream);
+
+/* Deferred rows: the step in calls.  The split step of the mode: backward | export | import | apply, for gradient accumulation and
+ * data-parallel replicas of a model whose tables are too large to exchange whole.  Two objects cross the boundary:
+ *   the SMALL FLAT VECTOR: the rules of coper_train_grads_layout (coper_param_spec order, every leaf at a multiple of 64 floats, pads 0)
+ *     over the trainable leaves EXCEPT ent_emb and pred_bias;
+ *   the ROW BLOCK for those two: ids int32 [row_cap] and vals float [row_cap, rs], rs = (ent_emb_size + 1 + 3) & ~3 floats.  Columns
+ *     [0, d) of vals[i] hold row ids[i] of d(ent_emb), column d holds d(pred_bias)[ids[i]], the pad columns are 0.  With vals 16-byte
+ *     aligned every row is, and ent_emb_size % 4 == 0 then takes 16-byte accesses (anything else: the scalar route, same results).
+ *     The ids of a block are distinct and lie in [0, num_ent).  An entry < 0 or >= num_ent is PADDING: never dereferenced, written
+ *     through or listed.  A block that carries an id twice gets an unspecified sum of the two for that row, nothing worse.
+ *
+ * coper_train_rows_layout(h, leaf_name, &offset, &n, &total, &row_stride): where `leaf_name` lies in the small vector, the vector's
+ *   length and rs.  leaf_name == NULL: *total and *row_stride alone; "ent_emb" / "pred_bias": COPER_EINVAL (they travel as blocks).
+ *   Any output may be NULL.  A function of the model: the same with the mode on or off (after coper_train_init: COPER_ESTATE before).
+ * coper_train_rows_backward: the arguments of coper_train_step, and the mode's sampled step up to the optimizer -- re-zero, claim,
+ *   catch-up, forward, backward.  The loss, the BN moving statistics and the dropout counter move; no variable, slot or beta power is
+ *   touched; the handle stays prepared (as coper_train_backward).  The gradients stay PENDING on the handle: the small leaves in their
+ *   gradient buffers, the tables as the claimed row list plus the rows of the dense gradient buffers, as after a step.
+ *   lookup == NULL (1-vs-all): COPER_EUNSUPPORTED.  Mode off: COPER_ESTATE.
+ * coper_train_rows_export(h, small, small_cap, accumulate, ids, vals, row_cap, count, stream): small = g or small += g (accumulate != 0)
+ *   over the small leaves in one launch (no atomics; 16-byte aligned, small_cap >= total); the pending list's rows gathered into the
+ *   block: ids[i] the row, vals[i] a bit-for-bit copy of its gradient row and bias gradient, ids[count .. row_cap) = -1, *count (a
+ *   DEVICE int32; may be NULL) the list's length.  row_cap below the host-known bound of the pending rows -- min(B (L + 1), num_ent)
+ *   after a backward, min(num_ent, entries imported since `first`) after imports -- is COPER_EINVAL before anything is launched; the
+ *   host is never synchronised.  ids / vals may be NULL together (the small vector alone), small may be NULL (the block alone).
+ *   Nothing is consumed: the pending state stays.  Nothing pending for a part that is asked for: COPER_ESTATE.
+ * coper_train_rows_import(h, ids, vals, n, first, stream): adds a block of n entries to the handle's pending TABLE gradient.
+ *   first != 0 starts a new pending gradient: the rows of the current list are re-zeroed, their claim bits cleared, the list emptied
+ *   (what a step does to the list of the call before).  Rows the list does not hold yet are claimed, appended and brought current
+ *   (once: a current row is skipped).  vals are added to the rows of the dense gradient buffers with one writer per element per call and
+ *   no float atomics: blocks add up in call order, the sum of an element has one defined order.  The list grows by the host-known bound
+ *   and keeps its content (a host synchronisation of `stream` when it grows, as a step that grows it).  first == 0 with no table
+ *   gradient pending: COPER_ESTATE.  n == 0 is allowed.
+ * coper_train_rows_apply(h, small, n, scale, stream): the optimizer alone.  The squared norm from the small leaves and the listed
+ *   rows; AMSGrad on the small leaves (read from `small` in place: 16-byte aligned, n == total, else COPER_EINVAL; small == NULL: the
+ *   pending gradients of the last coper_train_rows_backward) and on the listed rows; the update counter of the rows, the beta powers
+ *   and their log2 advance as in the mode's fused step.  The table part always comes from the handle's pending rows, left there by
+ *   the backward or by imports.  `scale` as in coper_train_apply.  Nothing pending: COPER_ESTATE.  Consumes what is pending.
+ *
+ * State (as "The step in three calls"): coper_train_step*, coper_train_forward*, coper_train_init, coper_train_defer_rows that
+ *   switches the mode, and coper_train_rows_apply clear what is pending; a refused call clears nothing.  coper_prepare between backward
+ *   and apply is allowed and changes nothing the apply reads.  coper_train_grad after a backward or after imports returns the dense
+ *   pending gradient as it stands; coper_train_row_stats' rows_last_step the length of the pending list (after imports: the union of
+ *   the blocks' rows).  With the profile enabled the new launches file counts under "train.rows.export" and "train.rows.import".
+ *   Deterministic states cannot enable the mode, so these calls are COPER_ESTATE there.  The replicas of a data-parallel run add the
+ *   same blocks in the same order and so hold the same table gradient byte for byte; the mode's norm is summed by unordered atomics, so
+ *   their variables agree to rounding, not to the bit. */
+COPER_API int coper_train_rows_layout(coper_handle* h, const char* leaf_name, int64_t* offset, int64_t* n, int64_t* total,
+                                      int64_t* row_stride);
+COPER_API int coper_train_rows_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup,
+                                        const float* labels, int64_t B, int64_t L, float* loss_out, void* stream);
+COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t small_cap, int32_t accumulate, int32_t* ids, float* vals,
+                                      int64_t row_cap, int32_t* count, void* stream);
+COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const float* vals, int64_t n, int32_t first, void* stream);
+COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_t n, double scale, void* stream);
 
 #ifdef __cplusplus
 }
