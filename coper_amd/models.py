@@ -1244,8 +1244,10 @@ class ConvE(object):
             b1 = C.c_double(powers["beta1_power"]) if "beta1_power" in powers else None
             b2 = C.c_double(powers["beta2_power"]) if "beta2_power" in powers else None
             st = C.c_int64(int(powers["step"])) if "step" in powers else None
-            _lib.check(self._h, self._lib.coper_train_powers(self._h, C.byref(b1) if b1 else None, C.byref(b2) if b2 else None,
-                                                            C.byref(st) if st else None, None, None, None))
+            # (`is not None`: a ctypes number that holds 0 is falsy, and beta1^t IS 0.0 from t = 8,000 on)
+            _lib.check(self._h, self._lib.coper_train_powers(self._h, C.byref(b1) if b1 is not None else None,
+                                                            C.byref(b2) if b2 is not None else None,
+                                                            C.byref(st) if st is not None else None, None, None, None))
         return self
 
     def trainable_leaves(self):

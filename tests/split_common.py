@@ -77,10 +77,10 @@ def oracle_update(ref, opt, grads_list):
     return mean, gn
 
 
-def new_oracle(md, p0):
+def new_oracle(md, p0, clip=CLIP):
     from oracle import coper_train_oracle as T
     ref = {k: np.array(v, np.float64) for k, v in p0.items()}
-    return ref, T.AMSGrad(T.trainable_names(md), ref, lr=md["learning_rate"], clip=CLIP)
+    return ref, T.AMSGrad(T.trainable_names(md), ref, lr=md["learning_rate"], clip=clip)
 
 
 def check_grads(got, want, gn_o, what=""):

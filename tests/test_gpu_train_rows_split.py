@@ -266,11 +266,11 @@ UPDATES = 3
 
 
 @functools.lru_cache(maxsize=None)
-def _trajectory(name, micro):
-    """The float64 oracle over UPDATES updates of `micro` gap batches each (computed once per model and micro-batch count) ->
-    ([(mean loss, mean gradients, their norm)] per update, the final state)."""
+def _trajectory(name, micro, clip=S.CLIP):
+    """The float64 oracle over UPDATES updates of `micro` gap batches each, clipping at `clip` (computed once per model, micro-batch
+    count and clip) -> ([(mean loss, mean gradients, their norm)] per update, the final state)."""
     md = _md(name)
-    ref, opt = S.new_oracle(md, _p0(md))
+    ref, opt = S.new_oracle(md, _p0(md), clip)
     out = []
     for u in range(UPDATES):
         losses, grads = [], []
@@ -321,8 +321,9 @@ def _route_update(m, route, md, u):
     return loss, grads
 
 
-@pytest.mark.parametrize("name", ["cpg_linear", "plain"])
-def test_the_routes_agree_with_the_oracle(name):
+@pytest.mark.parametrize("name,clip", [pytest.param("cpg_linear", S.CLIP, id="cpg_linear"), pytest.param("plain", S.CLIP, id="plain"),
+                                       pytest.param("cpg_linear", 0.1, id="cpg_linear-clip0.1")])
+def test_the_routes_agree_with_the_oracle(name, clip):
     """Three free-running updates on the gap batches of G.2, dropout on: rows_backward + rows_apply(NULL, 1); rows_backward + export +
     import(first) + rows_apply(small, 1); two micro-batches accumulated and applied with scale 0.5 -- each against the float64 oracle of
     the same updates (split_common.oracle_backward / oracle_update: the mean of the micro-batch gradients through one AMSGrad.step), with
@@ -330,16 +331,23 @@ def test_the_routes_agree_with_the_oracle(name):
     update: the loss by the non-tight law, the gradients by check_grads (2e-4 by _rel_err), the norm to 1e-4.  After the last update and
     a train_sync_rows(): every variable by check_variables, whose gradient term takes the sum of the three updates' gradient deviations
     (each update moves a variable by its own deviation's worth, and they add), and every slot of every row by G.2's law: within twice
-    the dense twin's deviation plus the absolute floor."""
+    the dense twin's deviation plus the absolute floor.
+    clip0.1: the same with clip_norm = 0.1 on every side, below half the oracle's global norm in every update (asserted) -- at 5.0 the
+    clip factor is 1 whatever k_rows_sumsq adds, and so is |scale| sqrt(ss) of k_rows_update under the micro-batch route's scale 0.5.
+    There the slots are held WITHOUT the absolute floor, dev <= 2 dev_twin + 1e-4 max|w| (the law of
+    tests/test_gpu_train_rows_edges.py): v is around 1e-9 and m around 1e-4, and the first AMSGrad updates move p by lr_t sign(g)
+    whatever the scale, so a wrong clip factor shows in the slots or nowhere."""
     md = _md(name)
     p0 = _p0(md)
     final = {}
     for route, micro in (("dense", 1), ("rows", 1), ("rows_block", 1), ("dense_m2", 2), ("rows_m2", 2)):
-        traj, ref, want_state = _trajectory(name, micro)
-        m = _model(md, p0, deferred_rows=route.startswith("rows"))
+        traj, ref, want_state = _trajectory(name, micro, clip)
+        m = _model(md, p0, deferred_rows=route.startswith("rows"), clip_norm=clip)
         dg_sum = {}
         for u in range(UPDATES):
             loss_o, mean_o, gn_o = traj[u]
+            if clip != S.CLIP:
+                assert gn_o > 2.0 * clip, (micro, u, gn_o)
             loss, grads = _route_update(m, route, md, u)
             _loss_close(loss, loss_o)
             dg = S.check_grads(grads, mean_o, gn_o, "%s update %d" % (route, u))
@@ -360,8 +368,8 @@ def test_the_routes_agree_with_the_oracle(name):
                 continue
             dev = float(np.abs(got[key].reshape(w.shape) - w).max())
             dev_twin = float(np.abs(final[twin][0][key].reshape(w.shape) - w).max())
-            floor = 2e-5 + 1e-5 * float(np.abs(w).max())
-            print("S.4 %s %s %s/%s: %.3e dense %.3e floor %.3e" % (name, route, key[0], key[1], dev, dev_twin, floor))
+            floor = 2e-5 + 1e-5 * float(np.abs(w).max()) if clip == S.CLIP else 1e-4 * float(np.abs(w).max())
+            print("S.4 %s clip %g %s %s/%s: %.3e dense %.3e floor %.3e" % (name, clip, route, key[0], key[1], dev, dev_twin, floor))
             assert dev <= 2.0 * dev_twin + floor, (route, key, dev, dev_twin, floor)
 
 
