@@ -135,6 +135,8 @@ PROTOTYPES = {
                                      C.POINTER(C.c_double), C.POINTER(_I64)]),
     "coper_train_defer_rows": (C.c_int, [_P, C.c_int32, _P]),
     "coper_train_rows_deferred": (C.c_int, [_P]),
+    "coper_train_order_rows": (C.c_int, [_P, C.c_int32, _P]),
+    "coper_train_rows_ordered": (C.c_int, [_P]),
     "coper_train_sync_rows": (C.c_int, [_P, _P]),
     "coper_train_row_stats": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P]),
     "coper_train_rows_layout": (C.c_int, [_P, C.c_char_p, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),

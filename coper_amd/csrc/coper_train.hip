@@ -30,6 +30,9 @@
 //   in phases of their own beside the ones above (Step::rows_*; kernels in train_rows.h); k_tr_zero_list, k_tr_sumsq and k_tr_amsgrad
 //   leave the two tables out.  With the mode off every launch is the one it was.  The mode's split step (coper_train_rows_backward |
 //   _export | _import | _apply) exchanges a small flat vector and row blocks: k_rows_export / k_rows_import (train_rows.h).
+//   Ordered rows (coper_train_order_rows; a switch on a deterministic state): the sampled scorer's table gradient by a stable
+//   sort of the batch's ids, their segment heads and one wave per segment (Step::order_rows / bwd_scorer; kernels in train_order.h) at any
+//   num_ent; the heads are the deferred-rows mode's row list, in ascending id, and its norm goes through the slab.  Off: nothing changes.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 #include <algorithm>
@@ -41,6 +44,7 @@
 #include "train_gemm.h"
 #include "train_kernels.h"
 #include "train_rows.h"
+#include "train_order.h"
 
 namespace coper {
 
@@ -196,6 +200,14 @@ struct TrainState {
   bool rows_pending_small = false, rows_pending_table = false;
   int64_t rows_bound = 0;
   void rows_pending_clear() { rows_pending_small = rows_pending_table = false; rows_bound = 0; }
+  // ordered rows (coper_train_order_rows; kernels in train_order.h): the sort's ping-pong buffers ord_key / ord_val and the
+  // segment offsets ord_seg hold ord_cap = B (L + 1) entries (+ 1), ord_hist 256 words per sort tile (+ the tiles' head counts behind
+  // them), ord_scan their exclusive scan; ord_list / ord_count: the unique rows of a step with deferred rows off (with it on they are rows_list / rows_count).
+  // rows_list_unsorted: imports appended to the pending list since it was last in ascending id (sorted before the norm and an export).
+  bool rows_ordered = false;
+  int64_t ord_cap = 0;
+  DevBuf<int32_t> ord_key[2], ord_val[2], ord_seg, ord_hist, ord_scan, ord_list, ord_count;
+  bool rows_list_unsorted = false;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -517,6 +529,14 @@ static RowCatchUp row_catch_up_args(const TrainState* T) {
   cu.jmax = rows_jmax(cu.b1, cu.b2);
   return cu;
 }
+// Ordered rows, behind an update's advance of the powers and of their log2: the log2 a catch-up reads is that of the power itself for
+// as long as the power is a normal double -- a function of the powers (what coper_train_powers restores), not of how many additions
+// led there, so handles with different histories catch rows up to the same bits.  Once a power has underflowed the sum carries on.
+static void rows_log2_from_powers(TrainState* T) {
+  if (!T->rows_ordered) return;
+  if (T->b1p >= 1e-290) T->rows_l2b1p = std::log2(T->b1p);
+  if (T->b2p >= 1e-290) T->rows_l2b2p = std::log2(T->b2p);
+}
 // a wave per row, four per workgroup, at most 8,192 workgroups (the kernels stride)
 inline dim3 rows_grid(int64_t rows) { return dim3((unsigned)std::min<int64_t>(std::max<int64_t>((rows + 3) / 4, 1), 8192)); }
 // coper_profile_read of the training step's structure (counts, no times -- as "band_lookup"): "train.zero.<leaf>" per whole-buffer zeroing
@@ -540,6 +560,66 @@ static int rows_wrap_guard(coper_handle* h, TrainState* T, hipStream_t s) {
   return COPER_OK;
 }
 
+// ---- ordered rows (kernels in train_order.h)
+inline int64_t ord_tiles(int64_t n) { return std::max<int64_t>((n + ORD_TILE - 1) / ORD_TILE, 1); }
+// 8-bit digit passes that cover the ids of [0, E)
+inline int ord_passes(int64_t E) {
+  int bits = 0;
+  while (bits < 32 && ((int64_t)1 << bits) < E) ++bits;
+  return std::max((bits + 7) / 8, 1);
+}
+// the sort's workspace at `n` entries or more (a host synchronisation of `s` when it grows, as every workspace of the step)
+static int ord_grow(coper_handle* h, TrainState* T, int64_t n, hipStream_t s) {
+  if (n <= T->ord_cap) return COPER_OK;
+  int rc;
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  T->ord_cap = 0;
+  for (int i = 0; i < 2; ++i)
+    if ((rc = T->ord_key[i].alloc(h, (size_t)n, "ordered-rows sort")) || (rc = T->ord_val[i].alloc(h, (size_t)n, "ordered-rows sort"))) return rc;
+  if ((rc = T->ord_seg.alloc(h, (size_t)n + 1, "ordered-rows segments")) || (rc = T->ord_list.alloc(h, (size_t)n, "ordered-rows list")) ||
+      (rc = T->ord_hist.alloc(h, (size_t)257 * ord_tiles(n), "ordered-rows histograms")) ||
+      (rc = T->ord_scan.alloc(h, (size_t)256 * ord_tiles(n), "ordered-rows histograms")) || (rc = T->ord_count.ensure(h, 1, "ordered-rows count")))
+    return rc;
+  T->ord_cap = n;
+  return COPER_OK;
+}
+// The stable LSD sort of `n` entries (n_dev, when given: the device-side count, at most n) by key.  src: the first pass's input
+// (OrdSrc).  with_vals: carry the entry indices.  Returns which of ord_key[] / ord_val[] holds the result.
+static int ord_sort_launch(coper_handle* h, TrainState* T, hipStream_t s, OrdSrc src, const int32_t* n_dev, int64_t n, bool with_vals) {
+  const int passes = ord_passes(h->dm.E);
+  const unsigned tiles = (unsigned)ord_tiles(n);
+  int cur = 0;
+  for (int p = 0; p < passes; ++p) {
+    cur = p & 1;
+    hipLaunchKernelGGL(k_ord_hist, dim3(tiles), dim3(256), 0, s, src, n_dev, n, 8 * p, T->ord_hist.get());
+    hipLaunchKernelGGL(k_ord_scan, dim3(256), dim3(256), 0, s, (const int32_t*)T->ord_hist.get(), (int)tiles, T->ord_scan.get());
+    hipLaunchKernelGGL(k_ord_scatter, dim3(tiles), dim3(256), 0, s, src, n_dev, n, 8 * p, (const int32_t*)T->ord_scan.get(), T->ord_key[cur].get(),
+                       with_vals ? T->ord_val[cur].get() : nullptr);
+    prof_count(h, "train.order.sort", 3);
+    src.keys = T->ord_key[cur];
+    src.vals = with_vals ? T->ord_val[cur].get() : nullptr;
+  }
+  return cur;
+}
+// The pending list of the deferred-rows mode in ascending id again, after imports appended to it (k_rows_import: wave-arrival order):
+// a keys-only sort of the listed ids, copied back.  In front of what reads the list in order: the norm of coper_train_rows_apply,
+// coper_train_rows_export.
+static int ord_sort_pending_list(coper_handle* h, TrainState* T, hipStream_t s) {
+  if (!T->rows_ordered || !T->rows_list_unsorted) return COPER_OK;
+  const int64_t n = T->rows_bound;
+  if (n > 0) {
+    if (int rc = ord_grow(h, T, n, s)) return rc;
+    const int pv = T->rows_prev;
+    OrdSrc src{T->rows_list[pv].get(), nullptr, nullptr, nullptr, 0, (int64_t)h->dm.E};
+    const int at = ord_sort_launch(h, T, s, src, T->rows_count + pv, n, false);
+    // (entries behind the count are whatever the buffers held: nothing reads them)
+    COPER_HIP_TRY(h, hipMemcpyAsync(T->rows_list[pv], T->ord_key[at], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    COPER_HIP_TRY(h, hipGetLastError());
+  }
+  T->rows_list_unsorted = false;
+  return COPER_OK;
+}
+
 // clip + AMSGrad over every trainable tensor: the squared norm (k_tr_sumsq; deterministic mode: through the slab and its fold), then
 // k_tr_amsgrad.  Deferred rows: ent_emb and pred_bias are left out of both launches, and the rows of `rows_list` (its length on the
 // device, `rows_count`) go through k_rows_sumsq / k_rows_update between and behind them.  The caller has zeroed the squared-norm slots
@@ -549,7 +629,7 @@ static int rows_wrap_guard(coper_handle* h, TrainState* T, hipStream_t s) {
 // leaf at its small_off; with rows_list).  Returns whether the pass carried the dense weights' maximum.
 static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, const float* flat, const TrainParam* sumsq_done,
                              const int32_t* table_counts, double gs, const int32_t* rows_list = nullptr, const int32_t* rows_count = nullptr,
-                             bool flat_small = false) {
+                             bool flat_small = false, int64_t rows_n = 0 /* ordered rows: the host's bound of the list's length */) {
   const Dims& dm = h->dm;
   const coper_train_config& tc = T->cfg;
   const TrainLeaves& lv = T->lv;
@@ -582,7 +662,14 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
   } else
     hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
   prof_count(h, "train.sumsq.leaves", np);
-  if (rows_list) {
+  if (rows_list && T->rows_ordered) {
+    // the listed rows' share in partial sums of ORD_SUMSQ_ROWS list positions (the slab is free again behind the fold above), folded
+    // into slot 1: the small leaves' share in slot 0, the rows' in slot 1, and every reader adds the slots in index order
+    const int64_t parts = std::max<int64_t>((rows_n + ORD_SUMSQ_ROWS - 1) / ORD_SUMSQ_ROWS, 1);
+    hipLaunchKernelGGL(k_rows_sumsq_ord, dim3((unsigned)parts), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, T->det_slab.get());
+    hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, parts, ssq + 1, 0);
+    prof_count(h, "train.order.sumsq");
+  } else if (rows_list) {
     hipLaunchKernelGGL(k_rows_sumsq, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, ssq);
     prof_count(h, "train.rows.sumsq");
   }
@@ -632,7 +719,9 @@ struct Step {
   // the scorer's backward through the dense d(loss)/d(logits) matrix S and one GEMM (else by float atomics)
   // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE)
   const bool rows = T->rows_deferred;
-  const bool dense_scorer_bwd = !rows && (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
+  // (ordered rows: the sorted-segment route at every |E| -- one arithmetic for every table size)
+  const bool ordered = T->rows_ordered && lookup != nullptr;
+  const bool dense_scorer_bwd = !rows && !ordered && (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
   // ---- from phase to phase
   float *Tf = nullptr, *dTf = nullptr;                // generated dense: T[rho][b][k] | dT (in T->A, once grow_workspaces has seen to it)
   const float *K_ps = nullptr, *kb_ps = nullptr;      // per-sample conv filters / biases (T->Kt, T->Kbv; null where they are static)
@@ -648,6 +737,8 @@ struct Step {
   bool score_dh_fused = false;   // scores, loss, ds and dh came from one pass over the rows (k_tr_score_loss_dh)
   const TrainParam* sumsq_done = nullptr;   // the leaf whose squared gradient norm its own GEMM accumulated
   const int32_t *rows_list = nullptr, *rows_count = nullptr;   // deferred rows: the rows this call claimed (rows_claim_catch_up)
+  // ordered rows: the sorted entry indices, and the batch's unique rows with their segment offsets (order_rows; null until it ran)
+  const int32_t *ord_vals = nullptr, *ord_rows = nullptr, *ord_rows_count = nullptr;
   bool scorer_bwd_on_side() const { return two_streams && score_dh_fused && tg_split_k(dm.E, d, B) == 1; }
 
   int grow_workspaces() {
@@ -701,9 +792,10 @@ struct Step {
       const int64_t cwid = csr.indptr ? ova_chunk(B, dm.E, tc.one_vs_all_chunk) : 0;
       size_t need = (size_t)DET_CS_WGS * 2 * T->mx;
       // (as floats: the 64-row stretches of a column sum over |E|, the filter taps or d columns, or of the [rc_b, d] bias-projection product)
-      const size_t widest = std::max({(size_t)(one_vs_all ? 0 : dm.E), (size_t)NT * C, (size_t)d, (size_t)rc_b * d});
+      // (ordered rows: no column sum over |E|; the partial sums of the listed rows' norm instead)
+      const size_t widest = std::max({(size_t)((one_vs_all || ordered) ? 0 : dm.E), (size_t)NT * C, (size_t)d, (size_t)rc_b * d});
       for (size_t n : {(size_t)2048, (size_t)B, (size_t)(B * ((cwid + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH)), (size_t)512 * TR_MAX_PARAMS,
-                       (size_t)((B + 63) / 64) * widest / 2 + 1})
+                       (size_t)((B + 63) / 64) * widest / 2 + 1, (size_t)(ordered ? (B * (L + 1) + ORD_SUMSQ_ROWS - 1) / ORD_SUMSQ_ROWS + 1 : 0)})
         need = n > need ? n : need;
       if (need > T->det_slab.size()) {
         COPER_HIP_TRY(h, hipStreamSynchronize(s));
@@ -790,14 +882,36 @@ struct Step {
   void rows_claim_catch_up() {
     const int cur = T->rows_prev ^ 1;
     const int64_t n = B * (L + 1);
-    hipLaunchKernelGGL(k_rows_claim, grid1d(n), dim3(256), 0, s, e1, B, lookup, n, (int64_t)dm.E, T->rows_claim.get(), T->rows_list[cur].get(),
-                       T->rows_count + cur);
+    // (ordered rows: the list is the sort's segment heads -- ascending id -- and the heads set the claim bits)
+    if (ordered) order_rows(T->rows_list[cur].get(), T->rows_count + cur, T->rows_claim.get());
+    else {
+      hipLaunchKernelGGL(k_rows_claim, grid1d(n), dim3(256), 0, s, e1, B, lookup, n, (int64_t)dm.E, T->rows_claim.get(), T->rows_list[cur].get(),
+                         T->rows_count + cur);
+      prof_count(h, "train.rows.claim");
+    }
     T->rows_prev = cur;
+    T->rows_list_unsorted = false;
     rows_list = T->rows_list[cur];
     rows_count = T->rows_count + cur;
     hipLaunchKernelGGL(k_rows_catch_up, rows_grid(n), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T), rows_list, rows_count);
-    prof_count(h, "train.rows.claim");
     prof_count(h, "train.rows.catch_up");
+  }
+  // ---- ordered rows: the B L lookup ids and the B e1 ids in ascending (id, b, l) -- the stable sort -- then the segment
+  // heads: the batch's unique rows ascending into `list` / `count`, their segment offsets into T->ord_seg, their claim bits when asked.
+  // Once per call: in front of the forward pass with deferred rows (the list is what is caught up), else in front of the reduce.
+  void order_rows(int32_t* list, int32_t* count, unsigned* claim) {
+    const int64_t n = B * (L + 1);
+    OrdSrc src{nullptr, nullptr, e1, lookup, B * L, (int64_t)dm.E};
+    const int at = ord_sort_launch(h, T, s, src, nullptr, n, true);
+    const unsigned tiles = (unsigned)ord_tiles(n);
+    int32_t* const tile_heads = T->ord_hist + (size_t)256 * tiles;
+    hipLaunchKernelGGL(k_ord_head_count, dim3(tiles), dim3(256), 0, s, (const int32_t*)T->ord_key[at].get(), n, tile_heads);
+    hipLaunchKernelGGL(k_ord_heads, dim3(tiles), dim3(256), 0, s, (const int32_t*)T->ord_key[at].get(), n, (const int32_t*)tile_heads, list,
+                       T->ord_seg.get(), count, claim);
+    prof_count(h, "train.order.heads", 2);
+    ord_vals = T->ord_val[at];
+    ord_rows = list;
+    ord_rows_count = count;
   }
   // looked-up dense table: group the batch by relation (perm / rel_offset / rel_count of the inference path): the table gradient is
   // written per present relation, never zero-filled (1.75 GB at FB15k-237 shapes)
@@ -937,7 +1051,7 @@ struct Step {
     const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
     // a training step over a sampled lookup whose dE goes through the dense S matrix: scores, loss, ds and dh from one pass over the rows
     // (coper_train_forward takes the same kernel: its loss is the step's, bit for bit; the dh it leaves in the workspace is not used)
-    score_dh_fused = !one_vs_all && dense_scorer_bwd && (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
+    score_dh_fused = !one_vs_all && (dense_scorer_bwd || ordered) && (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
                      (((uintptr_t)ent | (uintptr_t)T->dh.get() | (uintptr_t)T->hv.get()) & 15) == 0;
     if (one_vs_all) {
       if ((size_t)(B * dm.E) > T->Sd.size()) {
@@ -1052,6 +1166,22 @@ struct Step {
       // dh[B,d] = S E: 8 output tiles, K = |E| cut into slices
       return tg_matmul(h, T, s, MmView{T->Sd, tg_idx(dm.E), tg_idx(1), false}, B, MmView{ent, tg_idx(1), tg_idx(d), true}, d, dm.E, T->dh,
                        tg_idx(d), tg_idx(1));
+    }
+    if (ordered) {
+      // one writer per named row, its addends in ascending (b, l): `=` onto the zeroed rows (the conv backward adds the e1 rows behind it)
+      if (!ord_vals) order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
+      const int vec = (d & 3) == 0 && (((uintptr_t)T->hv.get() | (uintptr_t)dE) & 15) == 0;
+      hipLaunchKernelGGL(k_ord_reduce, rows_grid(std::min<int64_t>(B * (L + 1), dm.E)), dim3(256), 0, s, ord_rows, (const int32_t*)T->ord_seg.get(),
+                         ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, dE, dbias);
+      prof_count(h, "train.order.reduce");
+      // dh by the gather, in its own fixed order (as behind the dense S route)
+      if (score_dh_fused) {
+      } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
+        hipLaunchKernelGGL(k_tr_dh_gather4, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
+                           T->ds, dm.E, d, L, T->dh);
+      else
+        hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
+      return COPER_OK;
     }
     if (!dense_scorer_bwd) {
       hipLaunchKernelGGL(k_tr_score_bwd<true>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, dE, dbias);
@@ -1257,7 +1387,10 @@ struct Step {
         hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * r), dim3(256), 0, s, T->chain[g].dv[0], rel, dm.R, r, B * r, lv.rel_emb->g);
   }
   // ---- clip + AMSGrad
-  bool optimizer() { return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0, rows_list, rows_count); }
+  bool optimizer() {
+    return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0, rows_list, rows_count, false,
+                            std::min<int64_t>(B * (L + 1), dm.E));
+  }
 };
 
 }  // namespace
@@ -1304,8 +1437,11 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
     if (B * (L + 1) > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_train_step: deferred-rows mode: B * (L + 1) ids do not fit the row lists");
   }
   if (T->det) {      // what the mode does not put in order is refused, never served unordered
-    if (lookup && !((double)B * (double)h->dm.E * 4.0 <= 512.0 * 1024 * 1024 && h->dm.E <= 0x7fffffff))
+    // (ordered rows: the sampled scorer's backward is the sorted-segment route at every num_ent)
+    if (lookup && !T->rows_ordered && !((double)B * (double)h->dm.E * 4.0 <= 512.0 * 1024 * 1024 && h->dm.E <= 0x7fffffff))
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: sampled labels at B*num_ent*4 > 512 MiB take the atomic scorer backward");
+    if (lookup && T->rows_ordered && (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff))
+      return fail(h, COPER_EINVAL, "coper_train_step: ordered rows: B * (L + 1) ids and num_ent must fit 31 bits");
     // (routes chosen by pointer alignment -- the fused scorer, the 16-byte loss stream of the CSR chunks -- sum in another order)
     if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
@@ -1316,6 +1452,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply, csr};
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
+  if (st.ordered && (rc = ord_grow(h, T, B * (L + 1), st.s))) return rc;
   if (st.rows) {
     if ((rc = rows_wrap_guard(h, T, st.s)) || (rc = st.rows_grow())) return rc;
   }
@@ -1371,6 +1508,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   T->b1p *= T->cfg.beta1;
   T->b2p *= T->cfg.beta2;
+  if (st.rows) rows_log2_from_powers(T);
   T->step += 1;
   T->wmax_cur ^= 1;
   T->wmax_valid = wmax_carried;
@@ -1517,7 +1655,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_defer_rows: call coper_train_init first");
   if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_defer_rows: enable is 0 or 1");
-  if (enable && T->det)
+  if (enable && T->det && !T->rows_ordered)      // (ordered rows put both in order: coper_train_order_rows)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: a deterministic state: the unique-row list and the atomic scorer backward are unordered");
   if ((enable != 0) == T->rows_deferred) return COPER_OK;
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1553,6 +1691,31 @@ COPER_API int coper_train_rows_deferred(const coper_handle* h) {
   if (!h) return -COPER_EINVAL;
   const TrainState* T = (const TrainState*)h->train;
   return T ? (T->rows_deferred ? 1 : 0) : -COPER_ESTATE;
+}
+
+// ---- ordered rows (include/coper_hip.h, "Ordered rows")
+COPER_API int coper_train_order_rows(coper_handle* h, int32_t enable, void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_order_rows: call coper_train_init first");
+  if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_order_rows: enable is 0 or 1");
+  if (!T->det)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_order_rows: a deterministic = 0 state: the rest of its step is unordered, so nothing could be promised");
+  if (!enable && T->rows_deferred)
+    return fail(h, COPER_ESTATE, "coper_train_order_rows: deferred rows is on and needs the ordered list on this state: disable deferred rows first");
+  if ((enable != 0) == T->rows_ordered) return COPER_OK;
+  (void)stream;      // (nothing is launched: the workspace grows with the first batch)
+  T->rows_ordered = enable != 0;
+  T->rows_list_unsorted = false;
+  T->pending = false;      // (as switching deferred rows: what a split step left pending is dropped, never applied by another route)
+  T->rows_pending_clear();
+  return COPER_OK;
+}
+
+COPER_API int coper_train_rows_ordered(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->rows_ordered ? 1 : 0) : -COPER_ESTATE;
 }
 
 COPER_API int coper_train_sync_rows(coper_handle* h, void* stream) {
@@ -1664,6 +1827,7 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
     else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, small);
   }
   if (ids) {
+    if (int rc = ord_sort_pending_list(h, T, s)) return rc;      // (ordered rows: the block in ascending row id, after imports too)
     const RowTables t = row_tables(h, T);
     const int pv = T->rows_prev;
     hipLaunchKernelGGL(k_rows_export, rows_grid(row_cap), dim3(256), 0, s, t, (const int32_t*)T->rows_list[pv].get(), (const int32_t*)(T->rows_count + pv),
@@ -1704,6 +1868,7 @@ COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const
     hipLaunchKernelGGL(k_rows_import, grid1d(n), dim3(256), 0, s, t, row_catch_up_args(T), ids, vals, rows_block_stride(h->dm.d),
                        (t.vec && ((uintptr_t)vals & 15) == 0) ? 1 : 0, n, T->rows_claim.get(), T->rows_list[cur].get(), T->rows_count + cur, T->rows_cap);
     prof_count(h, "train.rows.import");
+    T->rows_list_unsorted = true;      // (appended in wave-arrival order; ordered rows sort the list before anything reads it in order)
   }
   COPER_HIP_TRY(h, hipGetLastError());
   T->rows_pending_table = true;
@@ -1723,6 +1888,16 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   if (!std::isfinite(scale)) return fail(h, COPER_EINVAL, "coper_train_rows_apply: scale is not finite");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
+  const int64_t rows_n = T->rows_bound;
+  if (T->rows_ordered) {      // the norm reads the list in ascending id, through the slab (an apply on a handle whose slab no backward has sized)
+    int rc;
+    if ((rc = ord_sort_pending_list(h, T, s))) return rc;
+    const size_t need = std::max<size_t>((size_t)512 * TR_MAX_PARAMS, (size_t)(rows_n / ORD_SUMSQ_ROWS + 2));
+    if (need > T->det_slab.size()) {
+      COPER_HIP_TRY(h, hipStreamSynchronize(s));
+      if ((rc = T->det_slab.alloc(h, need, "deterministic slabs"))) return rc;
+    }
+  }
   h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   T->rows_pending_clear();
   const RedLayout red = T->red_layout();
@@ -1733,13 +1908,14 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
   const int pv = T->rows_prev;
   const bool wmax_carried = optimizer_launch(h, T, s, small, nullptr, small ? nullptr : T->step_rel_count.get(), scale, T->rows_list[pv].get(),
-                                             T->rows_count + pv, small != nullptr);
+                                             T->rows_count + pv, small != nullptr, rows_n);
   COPER_HIP_TRY(h, hipGetLastError());
   T->rows_now += 1;      // (k_rows_update wrote the listed rows' words: current as of this update -- as the mode's fused step)
   T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
   T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
   T->b1p *= T->cfg.beta1;
   T->b2p *= T->cfg.beta2;
+  rows_log2_from_powers(T);
   T->wmax_cur ^= 1;
   T->wmax_valid = wmax_carried;
   return COPER_OK;

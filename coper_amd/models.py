@@ -867,7 +867,8 @@ class ConvE(object):
         return ms.value, n.value
 
     # ---------------------------------------------------------------- training
-    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, deferred_rows=False, **overrides):
+    def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, deferred_rows=False,
+                   ordered_rows=False, **overrides):
         """Allocates gradients and AMSGrad slots (amsgrad.py:112-118).  Hyper-parameters come from
         model_descriptors (models.py:99-130) unless overridden.  The tensors passed to load_parameters ARE the
         variables: train_step updates them in place (BN moving statistics included).
@@ -878,9 +879,14 @@ class ConvE(object):
         when the row is next read.  The registered ent_emb / pred_bias tensors (`load_parameters`' arguments, `_tensors`) are the
         caller's own and are CURRENT ONLY AFTER A SYNC: train_sync_rows(), or any of prepare() / encode() and the other inference calls,
         `variables`, session fetches of the tables, optimizer_state() and the checkpoint writers fed from them, which sync themselves.
-        A raw read of the tensors in between is the caller's risk.  Not with deterministic=True; 1-vs-all batches and the split step
+        A raw read of the tensors in between is the caller's risk.  With deterministic=True only together with ordered_rows=True (below);
+        1-vs-all batches and the split step
         (train_backward / train_grads_export / train_apply) are refused in the mode, whose own split step is train_rows_backward /
-        train_rows_export / train_rows_import / train_rows_apply (`coper_amd.parallel.DataParallelTrainer` takes it by itself)."""
+        train_rows_export / train_rows_import / train_rows_apply (`coper_amd.parallel.DataParallelTrainer` takes it by itself).
+        ordered_rows=True (coper_train_order_rows in include/coper_hip.h has the contract; needs deterministic=True): the table gradient
+        of a sampled batch is built from a stable sort of the batch's ids, one writer per row -- bit-reproducible sampled steps at any
+        number of entities, and deferred_rows=True on a deterministic state, whose row blocks then come in ascending row id and whose
+        data-parallel replicas stay byte-identical.  Its bits are not those of deterministic=True without it."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -903,9 +909,29 @@ class ConvE(object):
         self._rows_layout = None
         self._rows_bound = 0             # the block size train_rows_export allocates by: the bound of the pending rows
         self._rows_deferred = False      # (a new training state starts dense)
+        if ordered_rows:                 # (before deferred_rows: a deterministic state takes that mode only with the ordered list)
+            self.train_order_rows(True)
         if deferred_rows:
             self.train_defer_rows(True)
         return self
+
+    def train_order_rows(self, enable=True):
+        """coper_train_order_rows: the ordered-rows switch of a deterministic training state on or off (train_init's docstring)."""
+        if getattr(self, "_train_loss", None) is None:
+            raise _lib.CoperError(5, "call train_init() first")
+        enable = int(enable) if not isinstance(enable, bool) else (1 if enable else 0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_order_rows(self._h, enable, self._stream()))
+        self._rows_bound = 0             # (switching drops what a split step left pending)
+        return self
+
+    @property
+    def train_rows_ordered(self):
+        """The switch in force (coper_train_rows_ordered): 1 or 0."""
+        v = self._lib.coper_train_rows_ordered(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
 
     def train_defer_rows(self, enable=True):
         """coper_train_defer_rows: the deferred-rows mode on or off (train_init's docstring).  Turning it off brings every row current."""

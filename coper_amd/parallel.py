@@ -82,6 +82,10 @@ class DataParallelTrainer(object):
       * `train_rows_apply(flat, 1 / (world * micro_batches))`; moving statistics and loss as above.
 
     The replicas' VARIABLES are not claimed equal to the bit on this route: the mode's squared norm is summed by unordered atomics.
+    When `model.train_rows_ordered` is 1 (`train_init(deterministic=True, ordered_rows=True, deferred_rows=True)`; include/coper_hip.h,
+    "Ordered rows") they ARE: the blocks come in ascending row id, the pending list is sorted before the norm reads it and the norm is
+    summed in one fixed order, so replicas that import the same blocks in the same order and apply the same small vector end
+    byte-identical in every variable, slot, power and row word.  No new route: the one above, chosen by `train_rows_deferred`.
     Construction brings every row current (`train_sync_rows`) before the raw tables are broadcast.  Over gloo, which gathers host
     tensors only, the blocks are staged through the host: ranks sharing a GPU are a correctness run, and multi-GPU scaling of this route
     has not been measured.  Sampled batches only (the mode refuses 1-vs-all)."""

@@ -728,6 +728,54 @@ COPER_API int coper_train_rows_deferred(const coper_handle* h);
 COPER_API int coper_train_sync_rows(coper_handle* h, void* stream);
 COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, int64_t* rows_behind, int64_t* max_gap, void* stream);
 
+/* Ordered rows: an opt-in switch on a deterministic = 1 training state that builds the sparse table gradient of a SAMPLED batch
+ *     dE[lookup[b,l]] += ds[b,l] h[b]        dbias[lookup[b,l]] += ds[b,l]
+ * with one writer per row and one order of addends, at any num_ent: the B L lookup ids (clamped as everywhere: outside [0, num_ent) is
+ * row 0) are sorted by a stable radix sort into ascending (id, b, l); the sorted run of an id is its segment; one wave per segment forms
+ *     acc = fmaf(ds[b,l], h[b][k], acc)   from acc = 0.f, over the segment's entries in ascending (b, l)
+ * per element k -- and acc = fmaf(ds[b,l], 1.f, acc) for dbias -- and stores it with `=` onto the zeroed row.  ent_emb_size % 4 == 0 takes
+ * 16-byte accesses, anything else the scalar route with the same results.  A segment is never split, so its sum is a function of the
+ * batch alone: not of a grid, a capacity or an occupancy.  The segment heads are the batch's unique rows (the e1 ids included) in
+ * ascending id.  The sort tile (COPER_ORDER_SORT_TILE entries) and the stretch of the ordered norm (COPER_ORDER_SUMSQ_ROWS list
+ * positions per partial sum) are constants of the kernels; neither reaches a result.
+ *
+ * coper_train_order_rows(h, enable, stream): after coper_train_init (COPER_ESTATE without a training state; coper_train_init clears the
+ *   switch); enable is 0 or 1 (COPER_EINVAL otherwise); COPER_EUNSUPPORTED on a deterministic = 0 state (the rest of that step is
+ *   unordered, so nothing could be promised); disabling while deferred rows is on is COPER_ESTATE (disable deferred rows first).
+ *   Switching clears what a split step left pending, as coper_train_defer_rows does.  Nothing is launched; the sort's workspace
+ *   (four int32 arrays of B (L + 1), the segment offsets and the tile histograms) grows with the batch.
+ * coper_train_rows_ordered(h): 1 or 0; -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle.
+ *
+ * With the switch on (and for this switch only, the three sentences of the sections around it read as follows)
+ *   - SAMPLED steps, backwards and forwards (coper_train_step, coper_train_backward, coper_train_forward with a lookup) are served at
+ *     any B * num_ent: the 512 MiB refusal of the deterministic mode does not apply.  The scorer backward of a sampled batch ALWAYS takes
+ *     the route above, whatever num_ent is -- one arithmetic for every table size.  Its bits are NOT those of the dense-S route that
+ *     deterministic = 1 takes without the switch (a GEMM on split operands): the promise is reproducibility, not equality with the
+ *     other route.  1-vs-all batches (dense or CSR labels) keep the launches and the bits of deterministic = 1.  The 16-byte alignment
+ *     refusal stays.
+ *   - coper_train_defer_rows(h, 1, ...) is accepted on the deterministic state: the row list of a call is the segment heads -- ascending
+ *     id, not an unordered append -- the scorer backward is the route above instead of float atomics, and the norm of the listed rows is
+ *     summed in partial sums of COPER_ORDER_SUMSQ_ROWS list positions that a fold adds in a fixed order, beside the small leaves'
+ *     share.  Every call of the mode then runs under the determinism contract of the deterministic mode: step, forward, sync, slot
+ *     reads, coper_train_rows_backward | _export | _import | _apply.  From the same build, configuration, variables, slots, powers, step
+ *     counter, row words and batch arrays every output has the same bits: call after call, between handles, and between handles with
+ *     different histories (a row list or workspace that grew earlier from a larger batch).
+ *   - coper_train_rows_export writes its block in ascending row id; after imports the pending list is sorted ascending again before
+ *     anything order-sensitive reads it (the norm of coper_train_rows_apply, an export).  The replicas of a data-parallel run import the
+ *     same blocks in the same order and apply the same small vector: they end byte-identical in every variable, slot, power and row word,
+ *     not merely equal to rounding.
+ *   - not promised: equality across permutations of a batch, across builds, or across GPU models.
+ *   - cost, as measured on an MI355X at B = 512, L = 1000 (profiles/train_ordered.json): the sort is 29 us per digit pass,
+ *     heads 17 us, the reduce 44 us at FB15k-237 (135 us at 1M entities), the ordered norm 22 - 72 us; a sampled step is 1.00 (FB15k-237)
+ *     / 0.89 (WN18RR) of deterministic = 1 without the switch and 1.22 / 1.25 of the default mode; with deferred rows 0.73 - 0.83 of the
+ *     default mode's deferred step (no float atomics).  A segment is one wave's serial chain: a hub id in every position costs B L fmas.
+ *   - with the profile enabled the launches file counts under "train.order.sort" (three per digit pass), "train.order.heads" (two),
+ *     "train.order.reduce" and, with deferred rows, "train.order.sumsq"; a sampled step files none under "train.rows.claim". */
+#define COPER_ORDER_SORT_TILE 2048
+#define COPER_ORDER_SUMSQ_ROWS 64
+COPER_API int coper_train_order_rows(coper_handle* h, int32_t enable, void* stream);
+COPER_API int coper_train_rows_ordered(const coper_handle* h);
+
 /* Deferred rows: the step in calls.  The split step of the mode: backward | export | import | apply, for gradient accumulation and
  * data-parallel replicas of a model whose tables are too large to exchange whole.  Two objects cross the boundary:
  *   the SMALL FLAT VECTOR: the rules of coper_train_grads_layout (coper_param_spec order, every leaf at a multiple of 64 floats, pads 0)
