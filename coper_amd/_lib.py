@@ -144,6 +144,13 @@ PROTOTYPES = {
     "coper_train_rows_export": (C.c_int, [_P, _P, _I64, C.c_int32, _P, _P, _I64, _P, _P]),
     "coper_train_rows_import": (C.c_int, [_P, _P, _P, _I64, C.c_int32, _P]),
     "coper_train_rows_apply": (C.c_int, [_P, _P, _I64, C.c_double, _P]),
+    "coper_train_init_sharded": (C.c_int, [_P, C.POINTER(coper_train_config)]),
+    "coper_train_sharded": (C.c_int, [_P]),
+    "coper_train_shard_gather": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "coper_train_shard_forward": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P]),
+    "coper_train_shard_score_csr": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "coper_train_shard_backward": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
+    "coper_train_shard_apply": (C.c_int, [_P, _P, C.c_int32, _P]),
 }
 
 _lib = None

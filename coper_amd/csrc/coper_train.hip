@@ -33,6 +33,10 @@
 //   Ordered rows (coper_train_order_rows; a switch on a deterministic state): the sampled scorer's table gradient by a stable
 //   sort of the batch's ids, their segment heads and one wave per segment (Step::order_rows / bwd_scorer; kernels in train_order.h) at any
 //   num_ent; the heads are the deferred-rows mode's row list, in ascending id, and its norm goes through the slab.  Off: nothing changes.
+//   Entity-sharded 1-vs-all (coper_train_init_sharded): the handle holds rows [shard_lo, shard_hi) of the two tables with their
+//   gradients and slots; the step is four calls -- coper_train_shard_forward | _score_csr | _backward | _apply -- over the phases below,
+//   with the caller's exchanges between them (input rows, the shards' shares of dh and the loss, their squared norms).  A deterministic
+//   state only; kernels of its own in train_shard.h.  Every other entry point behaves as it did.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 #include <algorithm>
@@ -45,6 +49,7 @@
 #include "train_kernels.h"
 #include "train_rows.h"
 #include "train_order.h"
+#include "train_shard.h"
 
 namespace coper {
 
@@ -208,6 +213,20 @@ struct TrainState {
   int64_t ord_cap = 0;
   DevBuf<int32_t> ord_key[2], ord_val[2], ord_seg, ord_hist, ord_scan, ord_list, ord_count;
   bool rows_list_unsorted = false;
+  // entity-sharded 1-vs-all (coper_train_init_sharded).  shard_phase: the call the state machine expects next (ShardPhase).
+  // sh_e1 / sh_rel: the batch's ids as the forward call saw them (the backward call has no id arguments); sh_iota: 0 .. B - 1, the row
+  // numbers of the gathered input rows.  shard_carry: what the forward phases hand to the backward ones across the calls.
+  bool sharded = false;
+  int shard_phase = 0;
+  int64_t sh_B = 0, sh_cap = 0;
+  DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
+  struct ShardCarry {
+    const unsigned *w_slots = nullptr, *x_slots = nullptr;
+    const float *ccw = nullptr, *ccb = nullptr, *cw = nullptr, *cbv = nullptr, *xin = nullptr;
+    float* dxin = nullptr;
+    const TrainParam* W = nullptr;
+    bool p3_packed = false;
+  } shard_carry;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -371,15 +390,18 @@ void train_destroy(coper_handle* h) {
 
 using namespace coper;
 
-extern "C" {
-
-COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
+// coper_train_init, and coper_train_init_sharded (`sharded`: any [shard_lo, shard_hi); the leaves ent_emb / pred_bias are the handle's own
+// rows, so their gradients and slots below are too)
+static int train_init_impl(coper_handle* h, const coper_train_config* cfg, const bool sharded) {
   if (!h || !cfg) return COPER_EINVAL;
   if (cfg->abi_version != COPER_ABI_VERSION) return fail(h, COPER_EINVAL, "coper_train_init: ABI version mismatch");
   if (h->cfg.role != COPER_ROLE_BOTH) return fail(h, COPER_ESTATE, "coper_train_init: training needs a COPER_ROLE_BOTH handle");
   const Dims& dm = h->dm;
-  if (h->cfg.shard_lo != 0 || h->cfg.shard_hi != dm.E)
+  if (!sharded && (h->cfg.shard_lo != 0 || h->cfg.shard_hi != dm.E))
     return fail(h, COPER_EUNSUPPORTED, "coper_train_init: training needs the whole entity table on the handle");
+  if (sharded && cfg->deterministic != 1)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_init_sharded: needs deterministic = 1 (the replicated encoders stay equal only because the mode makes "
+                                       "every small-leaf gradient a function of its inputs; the default mode would need an all-reduce of them)");
   if (dm.C > 256)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_init: at most 256 conv channels");
   if (!(cfg->learning_rate > 0) || cfg->hidden_dropout < 0 || cfg->hidden_dropout >= 1 || cfg->output_dropout < 0 ||
@@ -395,6 +417,7 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   h->train = T;
   T->cfg = *cfg;
   T->det = cfg->deterministic == 1;
+  T->sharded = sharded;
   T->b1p = cfg->beta1;   // the beta powers start at beta (amsgrad.py:108-113)
   T->b2p = cfg->beta2;
   T->nh = (dm.gen_fc && !dm.lookup) ? h->cfg.n_ctx_out : 0;
@@ -458,6 +481,12 @@ COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) {
   }
   return COPER_OK;
 }
+
+extern "C" {
+
+COPER_API int coper_train_init(coper_handle* h, const coper_train_config* cfg) { return train_init_impl(h, cfg, false); }
+
+COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg) { return train_init_impl(h, cfg, true); }
 
 }  // extern "C"
 
@@ -697,6 +726,11 @@ struct Step {
   const int apply;                  // 0: coper_train_forward; 1: coper_train_step; 2: coper_train_backward (everything but the optimizer);
                                     // 3: coper_train_rows_backward (the same in the deferred-rows mode)
   const CsrLabels csr;              // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
+  // the entity-sharded step: the tables are rows [sh_lo, sh_lo + sh_n) of num_ent; the input images are the rows of
+  // img_rows [B, d] (the gathered e1 rows), never the table's
+  const bool shard = false;
+  const float* const img_rows = nullptr;
+  const int64_t sh_lo = 0, sh_n = dm.E;
   const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
   const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
   const bool cat = dm.concat_rel, two_streams = T->side[0] != nullptr;
@@ -789,7 +823,7 @@ struct Step {
     if (det) {
       // the slab of the widest reducing launch: DET_CS_WGS workgroups of column sums (2 mx doubles each), a loss kernel's grid (B, 2048,
       // or B x the stretches of a chunk), k_tr_sumsq's 512 x tensors
-      const int64_t cwid = csr.indptr ? ova_chunk(B, dm.E, tc.one_vs_all_chunk) : 0;
+      const int64_t cwid = (csr.indptr || shard) ? ova_chunk(B, sh_n, tc.one_vs_all_chunk) : 0;
       size_t need = (size_t)DET_CS_WGS * 2 * T->mx;
       // (as floats: the 64-row stretches of a column sum over |E|, the filter taps or d columns, or of the [rc_b, d] bias-projection product)
       // (ordered rows: no column sum over |E|; the partial sums of the listed rows' norm instead)
@@ -919,7 +953,7 @@ struct Step {
     int rc;
     if ((rc = coper_reserve(h, B, 0, (void*)s))) return rc;
     h->gcur = 0;
-    if ((rc = launch_group_by_relation(h, e1, rel, false, B, 32, s))) return rc;
+    if ((rc = launch_group_by_relation(h, e1, rel, shard /* no table row is looked up by e1 there */, B, 32, s))) return rc;
     if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->grouping().rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
     // (the grouping's order inside a relation is arrival order, and the order k_tr_lookup_dW sums in: a sorted copy for it)
     if (det && apply)
@@ -967,8 +1001,10 @@ struct Step {
   // the conv, Conv1BN, ReLU, dropout -> x [B, F_conv]; concat_rel: [x | c]
   void fwd_conv_bn1() {
     const size_t lds_conv = sizeof(float) * (size_t)(isz + (NT + 1) * C);
-    hipLaunchKernelGGL(k_tr_conv_fwd, dim3((unsigned)B), dim3(256), lds_conv, s, e1, rel, lv.ent_emb->p, lv.rel_emb ? lv.rel_emb->p : nullptr,
-                       dm.gen_conv ? nullptr : lv.conv1_weights->p, dm.gen_conv ? nullptr : lv.conv1_bias->p, dm.E, dm.R, d, r, dm.in_h, dm.in_w,
+    // (sharded: the image of sample b is row b of the gathered rows)
+    hipLaunchKernelGGL(k_tr_conv_fwd, dim3((unsigned)B), dim3(256), lds_conv, s, img_rows ? T->sh_iota.get() : e1, rel, img_rows ? img_rows : lv.ent_emb->p,
+                       lv.rel_emb ? lv.rel_emb->p : nullptr,
+                       dm.gen_conv ? nullptr : lv.conv1_weights->p, dm.gen_conv ? nullptr : lv.conv1_bias->p, img_rows ? B : (int64_t)dm.E, dm.R, d, r, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->img, ((gen || cat) && !genc) ? T->c.get() : nullptr, T->y, K_ps, kb_ps, dm.fh, dm.fw);
     double* const cs = red.cs_slots(CSS_BN1_FWD);
     if (use_batch && det) det_col_sums(T->y, B * (int64_t)P, C, cs, DET_CS_WGS);
@@ -1108,7 +1144,8 @@ struct Step {
     const float* const pred_bias = lv.pred_bias->p;
     float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
     const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
-    const int64_t E = dm.E, cw = ova_chunk(B, E, tc.one_vs_all_chunk);
+    // (sharded: E is the handle's own rows -- local columns c0, entity sh_lo + c0; inv_E above stays that of the whole table)
+    const int64_t E = sh_n, cw = ova_chunk(B, E, tc.one_vs_all_chunk);
     if ((size_t)(B * cw) > T->Sd.size() || (apply && cw < E && (size_t)nBd > T->dhc.size())) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
       if ((rc = T->Sd.ensure(h, (size_t)(B * cw), "training workspace")) || (apply && cw < E && (rc = T->dhc.ensure(h, (size_t)nBd, "training workspace"))))
@@ -1121,16 +1158,16 @@ struct Step {
       if ((rc = tg_matmul(h, T, s, MmView{T->hv, tg_idx(d), tg_idx(1), false}, B, MmView{ent_c, tg_idx(d), tg_idx(1), false}, w, d, T->Sd,
                           tg_idx(w), tg_idx(1))))
         return rc;
-      if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);
+      if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);      // (never sharded)
       const int64_t n_stretch = (w + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH;
       const int vec = (w & 3) == 0 && (((uintptr_t)T->Sd.get() | (uintptr_t)(pred_bias + c0)) & 15) == 0;
       if (det) {      // (a later chunk's shares onto the earlier chunks' sum: chunk order)
         hipLaunchKernelGGL(k_tr_csr_loss<true>, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
-                           csr.n_rows, c0, w, n_stretch, vec, eps, inv_E, inv_BL, T->det_slab.get());
+                           csr.n_rows, sh_lo + c0, w, n_stretch, vec, eps, inv_E, inv_BL, T->det_slab.get());
         det_fold(1, B * n_stretch, red.loss(), 1);
       } else
       hipLaunchKernelGGL(k_tr_csr_loss<false>, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
-                         csr.n_rows, c0, w, n_stretch, vec, eps, inv_E, inv_BL, red.loss());
+                         csr.n_rows, sh_lo + c0, w, n_stretch, vec, eps, inv_E, inv_BL, red.loss());
       if (apply) {
         hipLaunchKernelGGL(k_tr_col_sum_f32, grid1d(w), dim3(256), 0, s, T->Sd, B, w, dbias + c0);
         if ((rc = tg_matmul(h, T, s, MmView{T->Sd, tg_idx(1), tg_idx(w), true}, w, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE + c0 * d,
@@ -1346,6 +1383,12 @@ struct Step {
       hipLaunchKernelGGL(k_tr_conv_bwd<true>, dim3((unsigned)B), dim3(256), lds_cb, s, T->dx, T->img, dm.gen_conv ? nullptr : lv.conv1_weights->p, e1, rel,
                          dm.E, dm.R, d, r, dm.in_h, dm.in_w, dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->dimg.get(),
                          (float*)nullptr, K_ps, T->dKs, T->dkbs, dm.fh, dm.fw);
+      if (shard) {      // the owned e1 rows alone; a row of another shard is that rank's to write
+        float* const dE = lv.ent_emb->g;
+        const int vec = (d & 3) == 0 && (isz & 3) == 0 && (((uintptr_t)T->dimg.get() | (uintptr_t)dE) & 15) == 0;
+        hipLaunchKernelGGL(k_shard_rows_by_key, dim3((unsigned)B), dim3(256), 0, s, (const float*)T->dimg.get(), (int64_t)isz, (int64_t)0, d, e1, (int64_t)dm.E, B,
+                           sh_lo, sh_n, vec, dE);
+      } else
       det_rows_by_key(T->dimg, isz, 0, d, e1, dm.E, lv.ent_emb->g);
       if (dm.stacked) det_rows_by_key(T->dimg, isz, d, r, rel, dm.R, lv.rel_emb->g);
       return;
@@ -1426,6 +1469,9 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
   }
+  if (T->sharded)      // (the entity-sharded state has its own four calls and no other step)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_step / _backward / _forward: an entity-sharded state (coper_train_init_sharded) steps through "
+                                       "coper_train_shard_forward | _score_csr | _backward | _apply");
   if (apply == 3 && !T->rows_deferred)      // coper_train_rows_backward: the mode's own backward
     return fail(h, COPER_ESTATE, "coper_train_rows_backward: the deferred-rows mode is off (coper_train_defer_rows; coper_train_backward is the dense call)");
   if (T->rows_deferred) {      // what has a gradient in every row, or hands the dense gradient on, is refused
@@ -1572,6 +1618,8 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
+  if (T->sharded)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: an entity-sharded state (coper_train_init_sharded): no table gradient leaves its shard");
   if (T->rows_deferred)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: deferred-rows mode (coper_train_defer_rows): the flat gradient vector is dense by contract "
                                        "(the mode's export: coper_train_rows_export)");
@@ -1598,6 +1646,8 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
+  if (T->sharded)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: an entity-sharded state (coper_train_init_sharded): its update is coper_train_shard_apply");
   if (T->rows_deferred)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: deferred-rows mode (coper_train_defer_rows): an update from the dense flat gradient touches every row "
                                        "(the mode's update: coper_train_rows_apply)");
@@ -1655,6 +1705,8 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_defer_rows: call coper_train_init first");
   if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_defer_rows: enable is 0 or 1");
+  if (T->sharded)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: an entity-sharded state (coper_train_init_sharded) trains 1-vs-all, a gradient in every row");
   if (enable && T->det && !T->rows_ordered)      // (ordered rows put both in order: coper_train_order_rows)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: a deterministic state: the unique-row list and the atomic scorer backward are unordered");
   if ((enable != 0) == T->rows_deferred) return COPER_OK;
@@ -1699,6 +1751,8 @@ COPER_API int coper_train_order_rows(coper_handle* h, int32_t enable, void* stre
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_order_rows: call coper_train_init first");
   if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_order_rows: enable is 0 or 1");
+  if (T->sharded)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_order_rows: an entity-sharded state (coper_train_init_sharded) takes no sampled labels");
   if (!T->det)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_order_rows: a deterministic = 0 state: the rest of its step is unordered, so nothing could be promised");
   if (!enable && T->rows_deferred)
@@ -1985,6 +2039,218 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
   if (beta1_power) *beta1_power = T->b1p;
   if (beta2_power) *beta2_power = T->b2p;
   if (step) *step = (int64_t)T->step;
+  return COPER_OK;
+}
+
+}  // extern "C"
+
+// ---- entity-sharded 1-vs-all training (include/coper_hip.h, "Entity-sharded training")
+namespace {
+
+enum ShardPhase { SHP_FORWARD = 0, SHP_SCORE = 1, SHP_BACKWARD = 2, SHP_APPLY = 3 };
+const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr", "coper_train_shard_backward", "coper_train_shard_apply"};
+
+// the sharded state of a call `what` that the state machine expects at `phase`; null (with the status in *rc) otherwise
+static TrainState* shard_state(coper_handle* h, const char* what, int phase, int* rc) {
+  TrainState* T = (TrainState*)h->train;
+  if (!T) { *rc = fail(h, COPER_ESTATE, std::string(what) + ": call coper_train_init_sharded first"); return nullptr; }
+  if (!T->sharded) { *rc = fail(h, COPER_ESTATE, std::string(what) + ": not an entity-sharded state (coper_train_init_sharded)"); return nullptr; }
+  if (phase >= 0 && T->shard_phase != phase) {
+    *rc = fail(h, COPER_ESTATE, std::string(what) + ": out of order: the next call of this step is " + kShardCall[T->shard_phase]);
+    return nullptr;
+  }
+  return T;
+}
+
+// a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (apply = 1) with the
+// handle's own rows for the tables
+static Step shard_step(coper_handle* h, TrainState* T, hipStream_t s, float* h_out, const CsrLabels& csr, const float* img_rows) {
+  return Step{h, T, h->dm, T->cfg, T->lv, s, T->sh_e1.get(), T->sh_rel.get(), nullptr, nullptr, T->sh_B, (int64_t)h->dm.E, nullptr, nullptr, h_out, 1,
+              csr, true, img_rows, (int64_t)h->cfg.shard_lo, (int64_t)h->dm.n_local};
+}
+static void shard_carry_save(TrainState* T, const Step& st) {
+  T->shard_carry = TrainState::ShardCarry{st.w_slots, st.x_slots, st.ccw, st.ccb, st.cw, st.cbv, st.xin, st.dxin, st.W, st.p3_packed};
+}
+static void shard_carry_load(const TrainState* T, Step& st) {
+  const TrainState::ShardCarry& c = T->shard_carry;
+  st.w_slots = c.w_slots; st.x_slots = c.x_slots; st.ccw = c.ccw; st.ccb = c.ccb; st.cw = c.cw; st.cbv = c.cbv; st.xin = c.xin; st.dxin = c.dxin;
+  st.W = c.W; st.p3_packed = c.p3_packed;
+}
+// the tensor table of k_tr_sumsq / k_tr_amsgrad over the two tables (tables = 1), every other leaf (0) or all of them (-1)
+static int shard_tensors(coper_handle* h, TrainState* T, int tables, TrainTensors& tt) {
+  const Dims& dm = h->dm;
+  const TrainLeaves& lv = T->lv;
+  const bool lk = dm.lookup && dm.gen_fc, gen = dm.gen_fc && !dm.lookup;
+  const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
+  int np = 0;
+  tt.wmax = nullptr; tt.wmax_of = -1;
+  for (const TrainParam& t : T->tp) {
+    const bool is_table = &t == lv.ent_emb || &t == lv.pred_bias;
+    if (tables >= 0 && is_table != (tables != 0)) continue;
+    const int i = np++;
+    tt.p[i] = t.p; tt.g[i] = t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
+    tt.n[i] = t.n;
+    const bool table = lk && &t == lv.fc_weights;
+    tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
+    tt.rowcnt[i] = table ? T->step_rel_count.get() : nullptr;      // (the forward call's snapshot: an evaluation may have grouped since)
+    if (tables < 0 && !lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
+      tt.wmax = T->wmax[T->wmax_cur ^ 1];      // (as optimizer_launch: the dense weights' largest |p_new| for the next step's packs)
+      tt.wmax_of = i;
+    }
+  }
+  return np;
+}
+
+}  // namespace
+
+extern "C" {
+
+COPER_API int coper_train_sharded(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->sharded ? 1 : 0) : -COPER_ESTATE;
+}
+
+// out[b] = ent_emb[e1[b]] for the ids this handle holds, a zero row for every other: an addend of the all-reduce that forms e1_rows.
+// Reads the registered table as it stands (no coper_prepare needed: the step before has just changed it).
+COPER_API int coper_train_shard_gather(coper_handle* h, const int64_t* e1, int64_t B, float* rows_out, void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  if (!shard_state(h, "coper_train_shard_gather", -1, &rc)) return rc;
+  if (!e1 || !rows_out || B <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_gather: bad argument");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  return launch_gather_entities(h, e1, B, rows_out, (hipStream_t)stream);
+}
+
+COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, float* h_out,
+                                        void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, "coper_train_shard_forward", SHP_FORWARD, &rc);
+  if (!T) return rc;
+  if (!e1 || !rel || !e1_rows || B <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_forward: bad argument");
+  if (B * ((h->dm.n_local + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff)
+    return fail(h, COPER_EINVAL, "coper_train_shard_forward: batch too large for the loss kernel's grid");
+  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_shard_forward: batch too large for the dropout counter");
+  // (routes chosen by pointer alignment sum in another order: as the deterministic step)
+  if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_forward: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  if (B > T->sh_cap) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    T->sh_cap = 0;
+    if ((rc = T->sh_e1.alloc(h, (size_t)B, "sharded step ids")) || (rc = T->sh_rel.alloc(h, (size_t)B, "sharded step ids")) ||
+        (rc = T->sh_iota.alloc(h, (size_t)B, "sharded step ids")))
+      return rc;
+    T->sh_cap = B;
+    hipLaunchKernelGGL(k_shard_iota, grid1d(B), dim3(256), 0, s, T->sh_iota.get(), B);
+  }
+  COPER_HIP_TRY(h, hipMemcpyAsync(T->sh_e1, e1, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipMemcpyAsync(T->sh_rel, rel, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToDevice, s));
+  T->sh_B = B;
+  Step st = shard_step(h, T, s, h_out, CsrLabels(), e1_rows);
+  if ((rc = st.grow_workspaces())) return rc;
+  T->pending = false;
+  st.zero_accumulators();
+  if (st.lk && (rc = st.group_for_lookup())) return rc;
+  st.fwd_conv_filters();
+  st.fwd_conv_bn1();
+  if ((rc = st.fwd_dense())) return rc;
+  st.fwd_fcbn();
+  if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipGetLastError());
+  shard_carry_save(T, st);
+  T->shard_phase = SHP_SCORE;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_indptr, const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows,
+                                          int64_t B, float* dh_part, double* loss_part, void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, "coper_train_shard_score_csr", SHP_SCORE, &rc);
+  if (!T) return rc;
+  if (!lab_indptr || !lab_idx || !dh_part || !loss_part || B <= 0 || n_rows < 0 || (!lab_row && n_rows != B))
+    return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: bad argument (lab_row == NULL needs n_rows == B)");
+  if (B != T->sh_B) return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: B is not the forward call's");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  Step st = shard_step(h, T, s, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows}, nullptr);
+  if ((rc = st.grow_workspaces())) return rc;
+  shard_carry_load(T, st);
+  // the chunk loop over the own rows: d(pred_bias), d(ent_emb), the chunk shares of dh in ascending chunk order, the loss shares onto the zeroed sum
+  if ((rc = st.score_csr())) return rc;
+  COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->shard_phase = SHP_BACKWARD;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts, const double* loss_parts, int32_t G, float* loss_out,
+                                         double* sumsq_part, void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, "coper_train_shard_backward", SHP_BACKWARD, &rc);
+  if (!T) return rc;
+  if (!dh_parts || !loss_parts || !sumsq_part || G < 1) return fail(h, COPER_EINVAL, "coper_train_shard_backward: bad argument");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr);
+  if ((rc = st.grow_workspaces())) return rc;
+  shard_carry_load(T, st);
+  // dh and the loss: the ranks' shares in ascending rank
+  const int64_t nBd = st.nBd;
+  const int vec = (nBd & 3) == 0 && (((uintptr_t)dh_parts | (uintptr_t)T->dh.get()) & 15) == 0;
+  hipLaunchKernelGGL(k_shard_fold_parts, dim3((unsigned)std::min<int64_t>(((vec ? nBd / 4 : nBd) + 255) / 256, 2048)), dim3(256), 0, s, dh_parts, (int)G, nBd,
+                     vec, T->dh.get(), loss_parts, st.red.loss());
+  if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, st.red.loss(), 1.0 / ((double)st.B * (double)st.L), loss_out);
+  st.bwd_fcbn();
+  if ((rc = st.bwd_dense())) return rc;
+  if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
+  st.bwd_bn1();
+  st.bwd_conv();      // (the owned e1 rows onto what the score call stored in d(ent_emb))
+  st.bwd_conv_filters();
+  // the squared norm of this shard's table gradients, in the fixed order of the slab's fold, into its own double
+  TrainTensors tt;
+  const int np = shard_tensors(h, T, 1, tt);
+  hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, -1, T->det_slab.get());
+  hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, sumsq_part, 0);
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->step += 1;
+  T->shard_phase = SHP_APPLY;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts, int32_t G, void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, "coper_train_shard_apply", SHP_APPLY, &rc);
+  if (!T) return rc;
+  if (!sumsq_parts || G < 1) return fail(h, COPER_EINVAL, "coper_train_shard_apply: bad argument");
+  if (G > TG_SUMSQ_SLOTS - 1) return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_apply: more shards than squared-norm slots (63)");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  const coper_train_config& tc = T->cfg;
+  h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
+  // (the slots are zero since the forward call's zero list: nothing of a deterministic step adds to them)
+  double* const ssq = T->red_layout().sumsq_slots();
+  TrainTensors tt;
+  int np = shard_tensors(h, T, 0, tt);
+  hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, -1, T->det_slab.get());
+  hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, ssq, 0);
+  hipLaunchKernelGGL(k_shard_place_sumsq, dim3(1), dim3(64), 0, s, sumsq_parts, (int)G, ssq);
+  np = shard_tensors(h, T, -1, tt);
+  const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
+  hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, (const double*)ssq, T->red_layout().total_sumsq(), tc.clip_norm, lr_t,
+                     tc.beta1, tc.beta2, tc.epsilon, 1.0);
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->b1p *= tc.beta1;
+  T->b2p *= tc.beta2;
+  T->wmax_cur ^= 1;
+  T->wmax_valid = tt.wmax != nullptr;
+  T->shard_phase = SHP_FORWARD;
   return COPER_OK;
 }
 

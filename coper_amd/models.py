@@ -868,7 +868,7 @@ class ConvE(object):
 
     # ---------------------------------------------------------------- training
     def train_init(self, seed=0, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=5.0, deterministic=False, deferred_rows=False,
-                   ordered_rows=False, **overrides):
+                   ordered_rows=False, entity_sharded=False, **overrides):
         """Allocates gradients and AMSGrad slots (amsgrad.py:112-118).  Hyper-parameters come from
         model_descriptors (models.py:99-130) unless overridden.  The tensors passed to load_parameters ARE the
         variables: train_step updates them in place (BN moving statistics included).
@@ -886,7 +886,11 @@ class ConvE(object):
         ordered_rows=True (coper_train_order_rows in include/coper_hip.h has the contract; needs deterministic=True): the table gradient
         of a sampled batch is built from a stable sort of the batch's ids, one writer per row -- bit-reproducible sampled steps at any
         number of entities, and deferred_rows=True on a deterministic state, whose row blocks then come in ascending row id and whose
-        data-parallel replicas stay byte-identical.  Its bits are not those of deterministic=True without it."""
+        data-parallel replicas stay byte-identical.  Its bits are not those of deterministic=True without it.
+        entity_sharded=True (coper_train_init_sharded in include/coper_hip.h has the contract; needs deterministic=True): the model may
+        hold any shard of the entity table (`ConvE(..., shard=(lo, hi))`); gradients and slots of ent_emb / pred_bias exist for its rows
+        only, and the step is the four train_shard_* calls, which `coper_amd.parallel.EntityShardedTrainer` drives.  1-vs-all batches
+        with sparse labels only; train_step and the split steps are refused on such a state."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -902,9 +906,14 @@ class ConvE(object):
         cfg.seed = int(seed) & 0xFFFFFFFF
         cfg.deterministic = int(deterministic)      # (True / False -> 1 / 0; any other integer reaches the library's COPER_EINVAL)
         cfg.one_vs_all_chunk = int(md.get("one_vs_all_chunk", 0) or 0)     # entity columns per chunk of the sparse-label step; 0: the library's
+        init = self._lib.coper_train_init_sharded if entity_sharded else self._lib.coper_train_init
         with torch.cuda.device(self.device):
-            _lib.check(self._h, self._lib.coper_train_init(self._h, C.byref(cfg)))
+            _lib.check(self._h, init(self._h, C.byref(cfg)))
         self._train_loss = torch.zeros(1, device=self.device, dtype=torch.float32)
+        # (what the ranks of an EntityShardedTrainer must agree on)
+        self._train_cfg = (cfg.learning_rate, cfg.beta1, cfg.beta2, cfg.epsilon, cfg.clip_norm, cfg.label_smoothing_epsilon, cfg.hidden_dropout,
+                           cfg.output_dropout, cfg.context_rel_dropout, cfg.batch_norm_momentum, cfg.batch_norm_train_stats, cfg.seed,
+                           cfg.deterministic, cfg.one_vs_all_chunk)
         self._grads_layout = None
         self._rows_layout = None
         self._rows_bound = 0             # the block size train_rows_export allocates by: the bound of the pending rows
@@ -975,6 +984,64 @@ class ConvE(object):
         if v < 0:
             raise _lib.CoperError(-v, "call train_init() first")
         return v
+
+    # ---- the entity-sharded step (include/coper_hip.h: "Entity-sharded training"; coper_amd.parallel.EntityShardedTrainer drives it)
+    @property
+    def train_sharded(self):
+        """1 after train_init(entity_sharded=True), else 0 (coper_train_sharded)."""
+        v = self._lib.coper_train_sharded(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
+
+    def train_shard_gather(self, e1, out=None):
+        """coper_train_shard_gather: [B, d] rows of the ids this shard holds, zero rows for the others."""
+        e1 = self._ids(e1)
+        self._sync_parameters()
+        if out is None:
+            out = torch.empty((e1.numel(), self.ent_emb_size), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_gather(self._h, _ptr(e1), e1.numel(), _ptr(out), self._stream()))
+        return out
+
+    def train_shard_forward(self, e1, rel, e1_rows, want_h=False):
+        """coper_train_shard_forward: the replicated train-mode encoder on the whole batch, its input images from `e1_rows` [B, d]."""
+        e1, rel = self._ids(e1), self._ids(rel)
+        B = e1.numel()
+        if rel.numel() != B or tuple(e1_rows.shape) != (B, self.ent_emb_size) or e1_rows.dtype != torch.float32 or not e1_rows.is_contiguous():
+            raise ValueError("train_shard_forward: e1, rel [B]; e1_rows a contiguous float32 [B, ent_emb_size]")
+        self._sync_parameters()
+        hv = torch.empty((B, self.ent_emb_size), device=self.device, dtype=torch.float32) if want_h else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_forward(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), B, _ptr(hv), self._stream()))
+        return hv
+
+    def train_shard_score(self, batch, B, dh_part, loss_part):
+        """coper_train_shard_score_csr: this shard's chunk loop; dh_part float32 [B, d] and loss_part float64 [1] are written."""
+        ip, ix, row, n_rows = self._csr_labels(batch, B)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_score_csr(self._h, _ptr(ip), _ptr(ix), _ptr(row), n_rows, B, _ptr(dh_part),
+                                                                      _ptr(loss_part), self._stream()))
+
+    def train_shard_backward(self, dh_parts, loss_parts, sumsq_part):
+        """coper_train_shard_backward: dh_parts float32 [G, B, d] and loss_parts float64 [G] folded in rank order, the encoder's
+        backward, the owned e1 rows; sumsq_part float64 [1] is written.  Returns the loss as a 1-element device tensor."""
+        G = int(loss_parts.numel())
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_backward(self._h, _ptr(dh_parts), _ptr(loss_parts), G, _ptr(self._train_loss),
+                                                                     _ptr(sumsq_part), self._stream()))
+        return self._train_loss
+
+    def train_shard_apply(self, sumsq_parts):
+        """coper_train_shard_apply: clip by the global norm (the small leaves' share + sumsq_parts float64 [G] in index order), AMSGrad."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_apply(self._h, _ptr(sumsq_parts), int(sumsq_parts.numel()), self._stream()))
+        self._after_update()
+        if self.score_mode == "bf16x3" and getattr(self, "_x3_absmax", None) is not None:
+            # the rows moved: a table-wide maximum agreed for the old ones may no longer cover them (as load_parameters with new rows
+            # for this shard alone).  Back to the shard's own; an EntityShardedRanker re-agrees on the table-wide one when it is built
+            _lib.check(self._h, self._lib.coper_set_x3_ent_absmax(self._h, 0.0))
+            self._x3_absmax = None
 
     def _csr_labels(self, batch, B):
         """The sparse 1-vs-all labels of a batch (`lab_indptr`, `lab_idx`, optional `lab_row`) as device int64 tensors + the table's

@@ -4,8 +4,10 @@ coper_train_grads_export | coper_train_apply).
 Every rank holds a full replica of the model (`ConvE` after `train_init`).  An update is: per micro-batch a backward pass and an
 export that ADDS its gradient into one flat vector, ONE all-reduce (sum) of that vector over the ranks, then the optimizer on the sum
 scaled by 1 / (ranks * micro-batches).  The replicas start equal (rank 0's state is broadcast) and stay equal, because every rank
-applies the same bytes.  Entity-sharded (model-parallel) training is not built, the all-reduce does not overlap the backward pass,
-and there is no SyncBN.
+applies the same bytes.  The all-reduce does not overlap the backward pass, and there is no SyncBN.
+
+Entity-sharded (model-parallel) 1-vs-all training is `EntityShardedTrainer` below: the entity table, its gradients and
+slots split over the ranks, the encoder replicated; sampled labels on a sharded table are not built.
 
 In the deferred-rows mode (coper_train_defer_rows) the same update is made from coper_train_rows_backward | _export | _import | _apply:
 a small flat vector for everything but ent_emb / pred_bias, and row blocks (ids, gradient rows) for those two.
@@ -239,3 +241,149 @@ class DataParallelTrainer(object):
         self._average_stats()
         m.train_rows_apply(self.flat, 1.0 / (self.world * M))
         return loss / float(self.world * M)
+
+
+class EntityShardedTrainer(object):
+    """Entity-sharded (model-parallel) 1-vs-all training from sparse labels (include/coper_hip.h, "Entity-sharded training";
+    DESIGN.md 6.7).  Rank g of G holds rows [lo_g, hi_g) of ent_emb / pred_bias with their gradients and AMSGrad slots
+    (`ConvE(md, shard=(lo, hi))` + `train_init(deterministic=True, entity_sharded=True)`); every other leaf is replicated and stays
+    byte-identical on every rank WITHOUT an exchange, because the deterministic mode makes the encoder a function of its inputs.
+
+      * `EntityShardedTrainer(model, group=None)`: one shard per process of a `torch.distributed` group;
+      * `EntityShardedTrainer(models=[m_0, ..., m_{G-1}])`: the G shards in one process; the exchanges are torch ops in rank order.
+
+    Both forms leave the same bytes.  Construction checks that the shards' bounds tile [0, num_ent) in rank order and that seed,
+    hyper-parameters, dropout counter and beta powers are equal on every rank, and raises ValueError otherwise.
+
+    `step(batch)` takes the SAME batch on every rank -- `e1`, `rel` [B], `lab_indptr`, `lab_idx` (+ `lab_row`), as
+    `ConvE.train_step` takes sparse 1-vs-all labels -- and makes one update:
+
+      1. each rank gathers the e1 rows it holds (zero rows for the others); all-reduce: the [B, d] input rows (one non-zero addend
+         per element: exact);
+      2. `train_shard_forward`: the replicated encoder up to h;
+      3. `train_shard_score`: the scorer over the own rows -- this shard's table gradients, its share of dh and of the loss;
+      4. all-gather of the [B, d] shares and of the loss doubles;
+      5. `train_shard_backward`: the shares folded in rank order, the encoder's backward, the owned e1 rows, this shard's squared norm;
+      6. all-gather of the G doubles;
+      7. `train_shard_apply`: clip by the global norm, AMSGrad over the small leaves and the own rows.
+
+    Nothing table-sized or logit-sized moves.  Returns the batch loss as a 1-element device tensor (per rank; a list in the
+    in-process form would hold G equal values, so rank 0's is returned).  gloo, which moves host tensors only, is staged through the
+    host as `DataParallelTrainer._gather` does.  Not built: sampled or dense labels, the default (non-deterministic) mode, a batch
+    split over ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not been measured."""
+
+    def __init__(self, model=None, group=None, models=None):
+        import torch.distributed as dist
+        if (model is None) == (models is None):
+            raise ValueError("EntityShardedTrainer(model, group) or EntityShardedTrainer(models=[...])")
+        self.local = list(models) if models is not None else [model]
+        if not self.local:
+            raise ValueError("EntityShardedTrainer: no models")
+        for m in self.local:
+            if getattr(m, "_train_loss", None) is None:
+                raise _lib.CoperError(5, "call train_init(deterministic=True, entity_sharded=True) first")
+            if m.train_sharded != 1:
+                raise ValueError("EntityShardedTrainer: a model whose training state is not entity-sharded (train_init(entity_sharded=True))")
+        self._dist = None
+        self.group = group
+        if models is None:
+            self._dist = dist if dist.is_available() and dist.is_initialized() else None
+            if self._dist is None and group is not None:
+                raise ValueError("a process group needs torch.distributed to be initialised")
+        elif group is not None:
+            raise ValueError("EntityShardedTrainer(models=[...]) takes no process group")
+        self.world = self._dist.get_world_size(group) if self._dist else len(self.local)
+        self.rank = self._dist.get_rank(group) if self._dist else 0
+        self._check_ranks()
+
+    # ---- construction
+    @staticmethod
+    def _describe(m):
+        """What must agree across ranks, and the bounds, as float64: [lo, hi, num_ent, hyper-parameters ..., beta powers, counter]."""
+        b1, b2, st = C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(m._h, m._lib.coper_train_powers(m._h, None, None, None, C.byref(b1), C.byref(b2), C.byref(st)))
+        return [float(m.shard[0]), float(m.shard[1]), float(m.num_ent)] + [float(v) for v in m._train_cfg] + [b1.value, b2.value, float(st.value)]
+
+    def _check_ranks(self):
+        mine = torch.tensor([self._describe(m) for m in self.local], dtype=torch.float64)
+        if self._dist is not None:
+            parts = [torch.empty_like(mine) for _ in range(self.world)]
+            if self._dist.get_backend(self.group) == "nccl":
+                dev = self.local[0].device
+                parts = [p.to(dev) for p in parts]
+                self._dist.all_gather(parts, mine.to(dev), group=self.group)
+                parts = [p.cpu() for p in parts]
+            else:
+                self._dist.all_gather(parts, mine, group=self.group)
+            mine = torch.cat(parts)
+        rows = mine.tolist()
+        at = 0.0
+        for g, r in enumerate(rows):
+            if r[0] != at or r[1] <= r[0]:
+                raise ValueError("EntityShardedTrainer: the shards do not tile [0, num_ent) in rank order (rank %d holds [%d, %d))" % (g, r[0], r[1]))
+            at = r[1]
+            if r[2:] != rows[0][2:]:
+                raise ValueError("EntityShardedTrainer: rank %d differs from rank 0 in seed, hyper-parameters, dropout counter or beta powers" % g)
+        if at != rows[0][2]:
+            raise ValueError("EntityShardedTrainer: the shards end at %d of %d entities" % (at, rows[0][2]))
+
+    # ---- the exchanges
+    def _gather(self, t):
+        """`t` of every rank stacked [world, ...] in rank order on t's device (process form)."""
+        dist = self._dist
+        if dist.get_backend(self.group) == "nccl":
+            out = torch.empty((self.world,) + tuple(t.shape), device=t.device, dtype=t.dtype)
+            dist.all_gather_into_tensor(out, t.contiguous(), group=self.group)
+            return out
+        host = t.cpu().contiguous()
+        parts = [torch.empty_like(host) for _ in range(self.world)]
+        dist.all_gather(parts, host, group=self.group)
+        return torch.stack(parts).to(t.device)
+
+    def _sum(self, t):
+        """The sum of `t` over the ranks (process form; every element has one non-zero addend: exact in any order)."""
+        dist = self._dist
+        if dist.get_backend(self.group) == "nccl":
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            return t
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
+        return host.to(t.device)
+
+    def _exchange(self, parts, reduce=False):
+        """parts[i]: local model i's tensor.  Returns per local model the stacked [world, ...] tensor (or the sum) on its device."""
+        if self._dist is not None and self.world > 1:
+            return [self._sum(parts[0]) if reduce else self._gather(parts[0])]
+        out = []
+        for m in self.local:
+            mine = [p.to(m.device) for p in parts]      # rank order
+            if reduce:
+                acc = mine[0].clone()
+                for p in mine[1:]:
+                    acc += p
+                out.append(acc)
+            else:
+                out.append(torch.stack(mine))
+        return out
+
+    # ---- one update
+    def step(self, batch):
+        ms = self.local
+        if "lab_indptr" not in batch or "e2_multi" in batch:
+            raise ValueError("EntityShardedTrainer.step: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row])")
+        B = len(batch["e1"])
+        d = ms[0].ent_emb_size
+        rows = self._exchange([m.train_shard_gather(batch["e1"]) for m in ms], reduce=True)                      # 1
+        dh, ls, sq = [], [], []
+        for m, r in zip(ms, rows):
+            m.train_shard_forward(batch["e1"], batch["rel"], r)                                                   # 2
+            dh.append(torch.empty((B, d), device=m.device, dtype=torch.float32))
+            ls.append(torch.empty(1, device=m.device, dtype=torch.float64))
+            sq.append(torch.empty(1, device=m.device, dtype=torch.float64))
+            m.train_shard_score(batch, B, dh[-1], ls[-1])                                                         # 3
+        dh_all, ls_all = self._exchange(dh), self._exchange(ls)                                                   # 4
+        losses = [m.train_shard_backward(a, l.reshape(-1), s) for m, a, l, s in zip(ms, dh_all, ls_all, sq)]      # 5
+        sq_all = self._exchange(sq)                                                                               # 6
+        for m, s in zip(ms, sq_all):
+            m.train_shard_apply(s.reshape(-1))                                                                    # 7
+        return losses[0]

@@ -831,6 +831,58 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
 COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const float* vals, int64_t n, int32_t first, void* stream);
 COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_t n, double scale, void* stream);
 
+/* Entity-sharded training: 1-vs-all from sparse labels with the entity table split over G handles.  Rank g holds rows
+ * [shard_lo, shard_hi) of ent_emb / pred_bias (coper_config), their gradients and their AMSGrad slots, and nothing of the other rows.
+ * The encoder runs replicated on the whole batch; the scorer (the chunk loop of coper_train_step_csr over the handle's own rows), the
+ * table's optimizer pass and the table's memory divide by G.  The caller moves three small things per step between the ranks: the
+ * [B, d] input rows, the [G, B, d] shares of dh with G doubles of loss, and G doubles of squared norm.
+ *
+ * coper_train_init_sharded(h, cfg): coper_train_init, but any [shard_lo, shard_hi) of a COPER_ROLE_BOTH handle is accepted ([0, num_ent):
+ *   a world of one); gradients and slots of the two tables are allocated for the handle's rows only.  Needs cfg->deterministic == 1
+ *   (COPER_EUNSUPPORTED otherwise): the replicas of the encoder stay equal with no exchange only because that mode makes h, every
+ *   small-leaf gradient and the BN moving statistics a function of their inputs.  coper_train_init itself still refuses shard handles.
+ * coper_train_sharded(h): 1 or 0; -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle.
+ * coper_train_shard_gather(h, e1, B, rows_out, stream): rows_out [B, d] = the table rows of the ids this handle holds, zero rows for
+ *   the others -- one addend of e1_rows below (each element has one non-zero addend: the sum over ranks is exact).  Reads the
+ *   registered table as it stands, prepared or not; no part of the state machine.
+ * The step, four calls in this order (any other order: COPER_ESTATE, the text names the call expected next):
+ * coper_train_shard_forward(h, e1, rel, e1_rows, B, h_out, stream): the train-mode encoder up to h on the whole batch.  The input
+ *   images are the rows of e1_rows (device float [B, d]: the sum over ranks of coper_train_shard_gather / coper_gather_entities),
+ *   never the table's.  e1 and rel (device int64 [B]) are copied: the later calls name no ids.  h_out: optional device float [B, d].
+ *   Zeroes the gradients, moves the BN moving statistics as a step does.
+ * coper_train_shard_score_csr(h, lab_indptr, lab_idx, lab_row, n_rows, B, dh_part, loss_part, stream): labels as coper_train_step_csr
+ *   (global ids; entries outside the shard are absent for this rank).  Walks the own rows in chunks of one_vs_all_chunk columns (local
+ *   column c is entity shard_lo + c; the label-smoothing term uses the global num_ent), stores this shard's d(pred_bias) and
+ *   d(ent_emb) rows, and hands out dh_part (device float [B, d]: the chunk shares added in ascending chunk order) and loss_part
+ *   (device double [1]: the unnormalised sum).
+ * coper_train_shard_backward(h, dh_parts, loss_parts, G, loss_out, sumsq_part, stream): dh = dh_parts[0] + dh_parts[1] + ... in
+ *   ascending g (device float [G, B, d]), the loss the same way in double (device double [G]; loss_out: optional device float [1], the
+ *   batch loss).  Then the encoder's backward; the conv backward's d(img) rows are added to the OWNED e1 rows only (one writer per row,
+ *   ascending b, onto what the score call stored; a row of another shard is dropped without a store).  Advances the dropout counter.
+ *   sumsq_part: device double [1], the squared norm of this shard's d(ent_emb) and d(pred_bias), summed in one fixed order.
+ * coper_train_shard_apply(h, sumsq_parts, G, stream): global squared norm = the small leaves' + sumsq_parts[0 .. G) in index order
+ *   (device double [G], G <= 63); clip and AMSGrad over the small leaves and the own rows; the beta powers advance, inference caches
+ *   go stale.
+ * Bits: every output of a sharded step is the same across runs, handles and processes; the replicated leaves and their slots are
+ *   byte-identical on every rank.  Where every shard is exactly one chunk (the last one ragged) and the global norm is <= clip_norm,
+ *   loss, variables, slots and BN statistics are those of coper_train_step_csr on a deterministic whole-table handle with the same
+ *   one_vs_all_chunk; otherwise only the association of a float / double sum differs.
+ * On a sharded state coper_train_step*, coper_train_backward*, coper_train_forward*, coper_train_grads_export, coper_train_apply,
+ *   coper_train_defer_rows and coper_train_order_rows return COPER_EUNSUPPORTED; coper_train_grad / coper_train_slot of the two tables
+ *   hand out the local rows, global_norm the global one.  Null pointers, G < 1, B <= 0: COPER_EINVAL.
+ * Not built: sampled labels on a sharded table; the default (non-deterministic) mode; splitting the encoder's batch over ranks (needs
+ *   a synchronised BN); dense [B, num_ent] labels; a forward-only sharded call; overlap of the exchanges with compute. */
+COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg);
+COPER_API int coper_train_sharded(const coper_handle* h);
+COPER_API int coper_train_shard_gather(coper_handle* h, const int64_t* e1, int64_t B, float* rows_out, void* stream);
+COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B,
+                                        float* h_out, void* stream);
+COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_indptr, const int64_t* lab_idx, const int64_t* lab_row,
+                                          int64_t n_rows, int64_t B, float* dh_part, double* loss_part, void* stream);
+COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts, const double* loss_parts, int32_t G, float* loss_out,
+                                         double* sumsq_part, void* stream);
+COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts, int32_t G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

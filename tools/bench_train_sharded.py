@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""What one rank of an entity-sharded 1-vs-all training step costs, phase by phase, on ONE GPU:
+
+    python tools/bench_train_sharded.py [--shapes fb15k237_b512,synth1m_b128] [--worlds 1,2,4,8] [--reps 20] [--parent-root DIR]
+                                        [--rounds 3] [--out profiles/train_sharded.json]
+
+Shapes: FB15k-237 CoPER at B = 512, and its layers over a 1,048,583 x 200 table at B = 128; sparse 1-vs-all labels (about five
+positives per row), ids uniform over the table.  Each configuration runs in a fresh child process:
+    single             (a) the deterministic whole-table handle, `train_step` on the CSR batch: host clock around the step + a device
+                       synchronisation.  With --parent-root DIR (a checkout of the parent commit with its library built) the same on
+                       that build, in the same run, the two builds ALTERNATING for --rounds rounds (a process apart, the same code
+                       differs by a per cent or two): the path is untouched, so each build's median of medians should lie inside the
+                       other's pooled [min, max].
+    shard G            (b) rank 0 of G, emulated without the other ranks: a handle that holds rows shard_bounds(E, G, 0), the four
+                       calls of a step timed by device events, the exchanges replaced by buffers of the right shape ([B, d] input
+                       rows, [G, B, d] shares of dh, G doubles) -- the values mean nothing, the work is the rank's own.  G = 1 is the
+                       whole table in the four calls: its score and apply phases are (a)'s scorer and optimizer share.
+5 warm steps, then --reps repetitions: median [min, max].  The summary gives, per shape and G, the score and apply phases as a fraction
+of G = 1's, the encoder phases, and the projected step of one rank before collectives (the sum of its four phases).  Multi-GPU scaling
+with real RCCL exchanges is NOT measured here.  One JSON document; no threshold is set on these times."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.environ.get("COPER_BENCH_ROOT") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+SHAPES = {"fb15k237_b512": dict(B=512), "synth1m_b128": dict(B=128, num_ent=1048583)}
+PHASES = ("forward", "score", "backward", "apply")
+
+
+def _stats(ms):
+    import numpy as np
+    a = np.sort(np.asarray(ms))
+    return {"min": float(a[0]), "median": float(np.median(a)), "max": float(a[-1]), "n": int(len(a))}
+
+
+def _md(shape):
+    from coper_amd import data as cdata
+    over = {k: v for k, v in SHAPES[shape].items() if k != "B"}
+    md = cdata.model_descriptors("fb15k237_cpg", **over)
+    md.update(batch_norm_train_stats=True, batch_norm_momentum=0.1, hidden_dropout=0.3, output_dropout=0.2, label_smoothing_epsilon=0.1,
+              learning_rate=1e-3)
+    return md
+
+
+def _batches(md, B, n=4):
+    import numpy as np
+    import torch
+    E, R = md["num_ent"], md["num_rel"]
+    rng = np.random.default_rng(0)
+    dev = lambda a: torch.as_tensor(a).cuda()
+    out = []
+    for _ in range(n):
+        idx = np.sort(rng.integers(0, E, (B, 5)), axis=1)
+        idx[:, 1:][idx[:, 1:] == idx[:, :-1]] = E      # (a repeated id: past the table, absent by contract)
+        idx = np.sort(idx, axis=1)
+        out.append(dict(e1=dev(rng.integers(0, E, B)), rel=dev(rng.integers(0, R, B)), lab_indptr=dev(np.arange(0, 5 * B + 1, 5, dtype=np.int64)),
+                        lab_idx=dev(idx.reshape(-1).astype(np.int64))))
+    return out
+
+
+def child(shape, world, reps):
+    import time
+    import torch
+    from coper_amd import data as cdata
+    from coper_amd.models import ConvE
+    md = _md(shape)
+    B, E, d = SHAPES[shape]["B"], md["num_ent"], md["ent_emb_size"]
+    rec = {"shape": shape, "num_ent": E, "d": d, "B": B, "world": world}
+    if world:
+        from coper_amd.sharding import shard_bounds
+        lo, hi = shard_bounds(E, world, 0)
+    else:
+        lo, hi = 0, E
+    rec["rows"] = hi - lo
+    small = cdata.synthetic_params(md, 0, skip=("ent_emb", "pred_bias"))
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    p = {k: torch.as_tensor(v) for k, v in small.items()}
+    p.update(ent_emb=torch.randn((hi - lo, d), device="cuda", generator=gen) * 0.1, pred_bias=torch.randn((hi - lo,), device="cuda", generator=gen) * 0.1)
+    m = ConvE(md, device="cuda:0", shard=(lo, hi)).load_parameters(p, global_rows=False)
+    bs = _batches(md, B)
+    rec["device"] = torch.cuda.get_device_name(0)
+    if not world:
+        m.train_init(seed=1, deterministic=True)
+        for i in range(5):
+            m.train_step(bs[i % 4])
+        ms = []
+        for i in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.train_step(bs[i % 4])
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        rec["step_ms"] = _stats(ms)
+    else:
+        m.train_init(seed=1, deterministic=True, entity_sharded=True)
+        rows = torch.randn((B, d), device="cuda", generator=gen) * 0.1
+        dh, ls, sq = torch.empty((B, d), device="cuda"), torch.empty(1, device="cuda", dtype=torch.float64), torch.empty(1, device="cuda", dtype=torch.float64)
+        dh_all = torch.randn((world, B, d), device="cuda", generator=gen) * 1e-4
+        ls_all = torch.ones(world, device="cuda", dtype=torch.float64)
+        sq_all = torch.full((world,), 1e-3, device="cuda", dtype=torch.float64)
+        times = {k: [] for k in PHASES + ("step",)}
+        for i in range(5 + reps):
+            b = bs[i % 4]
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            m.train_shard_forward(b["e1"], b["rel"], rows)
+            ev[1].record()
+            m.train_shard_score(b, B, dh, ls)
+            ev[2].record()
+            m.train_shard_backward(dh_all, ls_all, sq)
+            ev[3].record()
+            m.train_shard_apply(sq_all)
+            ev[4].record()
+            torch.cuda.synchronize()
+            if i >= 5:
+                for j, k in enumerate(PHASES):
+                    times[k].append(ev[j].elapsed_time(ev[j + 1]))
+                times["step"].append(ev[0].elapsed_time(ev[4]))
+        rec["phase_ms"] = {k: _stats(v) for k, v in times.items()}
+    m.close()
+    print(json.dumps(rec))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--worlds", default="1,2,4,8")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_sharded.json"))
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--world", type=int, default=0)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.world, a.reps)
+    res, stop = [], False
+    for shape in a.shapes.split(","):
+        runs = ([(0, None)] + ([(0, a.parent_root)] if a.parent_root else [])) * (a.rounds if a.parent_root else 1)
+        runs += [(int(g), None) for g in a.worlds.split(",")]
+        for world, root in runs:
+            env = dict(os.environ)
+            if root:      # the parent commit's package and library, this file's child
+                env["COPER_BENCH_ROOT"] = os.path.abspath(root)
+                env.pop("COPER_HIP_LIB", None)
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", shape, "--world", str(world), "--reps", str(a.reps)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+            rec = json.loads(line[-1]) if r.returncode == 0 and line else {"shape": shape, "world": world, "failed": r.returncode,
+                                                                          "stderr": r.stderr[-400:]}
+            rec["build"] = "parent" if root else "this"
+            res.append(rec)
+            print(json.dumps(rec), flush=True)
+            if r.returncode not in (0, 1):      # (a child that died of a signal: nothing more is started on the device)
+                stop = True
+                break
+        if stop:
+            break
+    summary = []
+    for shape in a.shapes.split(","):
+        s = {"shape": shape}
+        single = {}
+        for build in ("this", "parent"):      # pooled over the alternating rounds: the median of the processes' medians, their extremes
+            rs = [r["step_ms"] for r in res if r["shape"] == shape and "step_ms" in r and r["build"] == build]
+            if rs:
+                meds = sorted(x["median"] for x in rs)
+                single[build] = {"min": min(x["min"] for x in rs), "median": meds[len(meds) // 2], "max": max(x["max"] for x in rs),
+                                 "process_medians": [x["median"] for x in rs]}
+        if "this" in single:
+            s["single_step_ms"] = single["this"]
+        if "this" in single and "parent" in single:
+            t, p = single["this"], single["parent"]
+            s["parent_step_ms"] = p
+            s["medians_inside_each_others_range"] = bool(p["min"] <= t["median"] <= p["max"] and t["min"] <= p["median"] <= t["max"])
+        ph = {r["world"]: r["phase_ms"] for r in res if r["shape"] == shape and "phase_ms" in r}
+        for g in sorted(ph):
+            e = {k: ph[g][k]["median"] for k in PHASES}
+            e["projected_step_before_collectives_ms"] = sum(e[k] for k in PHASES)
+            if 1 in ph:
+                e["score_over_world1"] = ph[g]["score"]["median"] / ph[1]["score"]["median"]
+                e["apply_over_world1"] = ph[g]["apply"]["median"] / ph[1]["apply"]["median"]
+            s["world_%d" % g] = e
+        summary.append(s)
+    doc = {"tool": "tools/bench_train_sharded.py", "reps": a.reps,
+           "clock": "single: host perf_counter around train_step + a device synchronisation; shard: device events around each of the four calls; "
+                    "warm (5 steps); one process per configuration; one GPU, exchanges emulated by buffers (no collective is timed)",
+           "results": res, "summary": summary}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    open(a.out, "w").write(json.dumps(doc, indent=1) + "\n")
+    print(json.dumps(summary))
+
+
+if __name__ == "__main__":
+    main()
