@@ -34,7 +34,8 @@
 //   sort of the batch's ids, their segment heads and one wave per segment (Step::order_rows / bwd_scorer; kernels in train_order.h) at any
 //   num_ent; the heads are the deferred-rows mode's row list, in ascending id, and its norm goes through the slab.  Off: nothing changes.
 //   Entity-sharded 1-vs-all (coper_train_init_sharded): the handle holds rows [shard_lo, shard_hi) of the two tables with their
-//   gradients and slots; the step is four calls -- coper_train_shard_forward | _score_csr | _backward | _apply -- over the phases below,
+//   gradients and slots; the step is four calls -- coper_train_shard_forward | _score_csr or _score_lookup (sampled labels, DESIGN 6.8:
+//   Step::score_lookup_shard) | _backward | _apply -- over the phases below,
 //   with the caller's exchanges between them (input rows, the shards' shares of dh and the loss, their squared norms).  A deterministic
 //   state only; kernels of its own in train_shard.h.  Every other entry point behaves as it did.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
@@ -215,10 +216,12 @@ struct TrainState {
   bool rows_list_unsorted = false;
   // entity-sharded 1-vs-all (coper_train_init_sharded).  shard_phase: the call the state machine expects next (ShardPhase).
   // sh_e1 / sh_rel: the batch's ids as the forward call saw them (the backward call has no id arguments); sh_iota: 0 .. B - 1, the row
-  // numbers of the gathered input rows.  shard_carry: what the forward phases hand to the backward ones across the calls.
+  // numbers of the gathered input rows.  shard_carry: what the forward phases hand to the backward ones across the calls.  sh_labels: the
+  // labels the step's loss is a mean over, as the score call that ran counts them (B num_ent: 1-vs-all; B L: sampled).
   bool sharded = false;
   int shard_phase = 0;
   int64_t sh_B = 0, sh_cap = 0;
+  double sh_labels = 1.0;
   DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
   struct ShardCarry {
     const unsigned *w_slots = nullptr, *x_slots = nullptr;
@@ -754,7 +757,8 @@ struct Step {
   // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE)
   const bool rows = T->rows_deferred;
   // (ordered rows: the sorted-segment route at every |E| -- one arithmetic for every table size)
-  const bool ordered = T->rows_ordered && lookup != nullptr;
+  // (a sharded state's sampled score call, DESIGN 6.8: always that route)
+  const bool ordered = (T->rows_ordered || shard) && lookup != nullptr;
   const bool dense_scorer_bwd = !rows && !ordered && (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
   // ---- from phase to phase
   float *Tf = nullptr, *dTf = nullptr;                // generated dense: T[rho][b][k] | dT (in T->A, once grow_workspaces has seen to it)
@@ -790,7 +794,7 @@ struct Step {
           (rc = ws(T->c, (size_t)cb * r)) || (rc = ws(T->dc, (size_t)cb * r)) ||
           (rc = ws(T->z0, (size_t)cb * d)) || (rc = ws(T->z1, (size_t)cb * d)) ||
           (rc = ws(T->hv, (size_t)cb * d)) || (rc = ws(T->dh, (size_t)cb * d)) ||
-          (rc = ws(T->dz, (size_t)cb * d)) || (rc = ws(T->ds, (size_t)cb * (one_vs_all ? 1 : cl))))
+          (rc = ws(T->dz, (size_t)cb * d)) || (rc = ws(T->ds, (size_t)cb * cl)))      // (capL entries per sample whatever this call's label form: capL is what the next sampled call compares its L with)
         return rc;
       if (cat && ((rc = ws(T->xc, (size_t)cb * F)) || (rc = ws(T->dxc, (size_t)cb * F)))) return rc;
       if (gen) {
@@ -1186,6 +1190,45 @@ struct Step {
     if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)nBd, hipMemcpyDeviceToDevice, s));
     return COPER_OK;
   }
+  // The sampled scorer of a sharded step, forward AND backward, over the entries (b, l) whose clamped id this handle holds:
+  // the launches fwd_score_loss + bwd_scorer make on an ordered-rows state, each in its SHARD form -- the same route by the same
+  // conditions, so a shard that is the whole table leaves the whole-table step's bits.  ds is written at the owned entries only; the
+  // sort runs over all B (L + 1) ids (a segment's addends and their order do not depend on what else is sorted) and k_ord_reduce
+  // skips the segments of other shards.  Leaves this shard's share of dh in T->dh and of the loss in red.loss().
+  int score_lookup_shard() {
+    float* const ent = lv.ent_emb->p;
+    const float* const pred_bias = lv.pred_bias->p;
+    float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
+    const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
+    score_dh_fused = (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
+                     (((uintptr_t)ent | (uintptr_t)T->dh.get() | (uintptr_t)T->hv.get()) & 15) == 0;
+    if (score_dh_fused) {
+      const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
+      // (k_tr_score_loss_dh's LDS and the compacted entries' positions: int [L] more)
+      const size_t lds_sf = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + 2 * sizeof(int) * (size_t)L;
+      if (lds_sf > 64 * 1024)
+        COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_score_loss_dh<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sf));
+      hipLaunchKernelGGL((k_tr_score_loss_dh<true, true>), dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d,
+                         (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get(), sh_lo, sh_n);
+    } else
+      hipLaunchKernelGGL((k_tr_score_loss<true, true>), dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E,
+                         d, L, eps, inv_E, inv_BL, T->ds, T->det_slab.get(), sh_lo, sh_n);
+    det_fold(1, B, red.loss(), 1);      // (the B workgroups' loss shares, in sample order, onto the sum the forward call zeroed)
+    order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
+    const int vec = (d & 3) == 0 && (((uintptr_t)T->hv.get() | (uintptr_t)dE) & 15) == 0;
+    hipLaunchKernelGGL(k_ord_reduce, rows_grid(std::min<int64_t>(B * (L + 1), dm.E)), dim3(256), 0, s, ord_rows, (const int32_t*)T->ord_seg.get(),
+                       ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, sh_lo, sh_n, dE, dbias);
+    prof_count(h, "train.order.reduce");
+    if (score_dh_fused) {
+      // (dh came with the scores)
+    } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
+      hipLaunchKernelGGL(k_tr_dh_gather4<true>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
+                         T->ds, dm.E, d, L, T->dh, sh_lo, sh_n);
+    else
+      hipLaunchKernelGGL((k_tr_score_bwd<false, true>), dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh,
+                         (float*)nullptr, (float*)nullptr, sh_lo, sh_n);
+    return COPER_OK;
+  }
   // ---- backward
   // d(loss)/d(logits) -> dh [B, d], d(pred_bias), d(ent_emb): through a GEMM on the dense S where B * |E| is small, else by float atomics.
   // Behind the caller's fork (scorer_bwd_on_side) S, dbias and dE = S^T h (~70 us that need ds and h only) run on side[0] beside the dense
@@ -1209,12 +1252,12 @@ struct Step {
       if (!ord_vals) order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
       const int vec = (d & 3) == 0 && (((uintptr_t)T->hv.get() | (uintptr_t)dE) & 15) == 0;
       hipLaunchKernelGGL(k_ord_reduce, rows_grid(std::min<int64_t>(B * (L + 1), dm.E)), dim3(256), 0, s, ord_rows, (const int32_t*)T->ord_seg.get(),
-                         ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, dE, dbias);
+                         ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, (int64_t)0, (int64_t)dm.E, dE, dbias);
       prof_count(h, "train.order.reduce");
       // dh by the gather, in its own fixed order (as behind the dense S route)
       if (score_dh_fused) {
       } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
-        hipLaunchKernelGGL(k_tr_dh_gather4, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
+        hipLaunchKernelGGL(k_tr_dh_gather4<>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
                            T->ds, dm.E, d, L, T->dh);
       else
         hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
@@ -1243,7 +1286,7 @@ struct Step {
     if (score_dh_fused) {
       // (dh came with the scores: k_tr_score_loss_dh)
     } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
-      hipLaunchKernelGGL(k_tr_dh_gather4, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
+      hipLaunchKernelGGL(k_tr_dh_gather4<>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
                          T->ds, dm.E, d, L, T->dh);
     else
       hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
@@ -2044,11 +2087,12 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
 
 }  // extern "C"
 
-// ---- entity-sharded 1-vs-all training (include/coper_hip.h, "Entity-sharded training")
+// ---- entity-sharded training (include/coper_hip.h, "Entity-sharded training")
 namespace {
 
 enum ShardPhase { SHP_FORWARD = 0, SHP_SCORE = 1, SHP_BACKWARD = 2, SHP_APPLY = 3 };
-const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr", "coper_train_shard_backward", "coper_train_shard_apply"};
+const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr or coper_train_shard_score_lookup",
+                                   "coper_train_shard_backward", "coper_train_shard_apply"};
 
 // the sharded state of a call `what` that the state machine expects at `phase`; null (with the status in *rc) otherwise
 static TrainState* shard_state(coper_handle* h, const char* what, int phase, int* rc) {
@@ -2064,9 +2108,11 @@ static TrainState* shard_state(coper_handle* h, const char* what, int phase, int
 
 // a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (apply = 1) with the
 // handle's own rows for the tables
-static Step shard_step(coper_handle* h, TrainState* T, hipStream_t s, float* h_out, const CsrLabels& csr, const float* img_rows) {
-  return Step{h, T, h->dm, T->cfg, T->lv, s, T->sh_e1.get(), T->sh_rel.get(), nullptr, nullptr, T->sh_B, (int64_t)h->dm.E, nullptr, nullptr, h_out, 1,
-              csr, true, img_rows, (int64_t)h->cfg.shard_lo, (int64_t)h->dm.n_local};
+// (lookup / labels [B, L]: the sampled score call; every other phase names no labels and L is num_ent)
+static Step shard_step(coper_handle* h, TrainState* T, hipStream_t s, float* h_out, const CsrLabels& csr, const float* img_rows,
+                       const int32_t* lookup = nullptr, const float* labels = nullptr, int64_t L = 0) {
+  return Step{h, T, h->dm, T->cfg, T->lv, s, T->sh_e1.get(), T->sh_rel.get(), lookup, labels, T->sh_B, lookup ? L : (int64_t)h->dm.E, nullptr, nullptr,
+              h_out, 1, csr, true, img_rows, (int64_t)h->cfg.shard_lo, (int64_t)h->dm.n_local};
 }
 static void shard_carry_save(TrainState* T, const Step& st) {
   T->shard_carry = TrainState::ShardCarry{st.w_slots, st.x_slots, st.ccw, st.ccb, st.cw, st.cbv, st.xin, st.dxin, st.W, st.p3_packed};
@@ -2184,6 +2230,37 @@ COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_in
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
+  T->sh_labels = (double)B * (double)h->dm.E;
+  T->shard_phase = SHP_BACKWARD;
+  return COPER_OK;
+}
+
+COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* lookup, const float* labels, int64_t B, int64_t L, float* dh_part,
+                                             double* loss_part, void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, "coper_train_shard_score_lookup", SHP_SCORE, &rc);
+  if (!T) return rc;
+  if (!lookup || !labels || !dh_part || !loss_part || B <= 0 || L <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: bad argument");
+  if (B != T->sh_B) return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: B is not the forward call's");
+  if (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff)
+    return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: ordered rows: B * (L + 1) ids and num_ent must fit 31 bits");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  // d(loss)/d(scores) [B, L]: grown here, alone -- the other workspaces hold what the forward call left for the backward call
+  if ((size_t)T->capB * (size_t)L > T->ds.size()) {
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = T->ds.alloc(h, (size_t)T->capB * (size_t)L, "training workspace"))) return rc;
+  }
+  if (L > T->capL) T->capL = L;
+  Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr, lookup, labels, L);
+  if ((rc = st.grow_workspaces()) || (rc = ord_grow(h, T, B * (L + 1), s))) return rc;
+  shard_carry_load(T, st);
+  if ((rc = st.score_lookup_shard())) return rc;
+  COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->sh_labels = (double)B * (double)L;
   T->shard_phase = SHP_BACKWARD;
   return COPER_OK;
 }
@@ -2205,7 +2282,8 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   const int vec = (nBd & 3) == 0 && (((uintptr_t)dh_parts | (uintptr_t)T->dh.get()) & 15) == 0;
   hipLaunchKernelGGL(k_shard_fold_parts, dim3((unsigned)std::min<int64_t>(((vec ? nBd / 4 : nBd) + 255) / 256, 2048)), dim3(256), 0, s, dh_parts, (int)G, nBd,
                      vec, T->dh.get(), loss_parts, st.red.loss());
-  if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, st.red.loss(), 1.0 / ((double)st.B * (double)st.L), loss_out);
+  // (the mean is over the labels of the score call that ran: B num_ent of a 1-vs-all step, B L of a sampled one)
+  if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, st.red.loss(), 1.0 / T->sh_labels, loss_out);
   st.bwd_fcbn();
   if ((rc = st.bwd_dense())) return rc;
   if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }

@@ -289,12 +289,16 @@ __global__ __launch_bounds__(256) void k_tr_fcbn_fwd(const float* __restrict__ z
 
 // sampled scorer + loss + d(loss)/ds.  One workgroup per query; h[b] in LDS; one lookup entry per thread.
 // DET (here and in the other loss kernels): the workgroup's loss share is STORED at loss_acc[blockIdx.x], a slab k_tr_fold_det adds
-template <bool DET>
+// SHARD (here and in the other sampled-scorer kernels): ent / pred_bias hold rows [sh_lo, sh_lo + sh_n) of the E-row
+// table, and only an entry whose (clamped) id lies there is served -- the same chain per entry; an entry of another shard costs no
+// row read, no store and no loss term.  Without SHARD the two bounds are not read.
+template <bool DET, bool SHARD = false>
 __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__ hv, const float* __restrict__ ent,
                                                        const float* __restrict__ pred_bias,
                                                        const int32_t* __restrict__ lookup, const float* __restrict__ labels,
                                                        int64_t E, int d, int64_t L, float ls_eps, float inv_E, float inv_BL,
-                                                       float* __restrict__ ds, double* __restrict__ loss_acc) {
+                                                       float* __restrict__ ds, double* __restrict__ loss_acc, int64_t sh_lo = 0,
+                                                       int64_t sh_n = 0) {
   extern __shared__ float hl[];
   __shared__ double part[256];
   const int64_t b = blockIdx.x;
@@ -304,6 +308,10 @@ __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__
   for (int64_t l = threadIdx.x; l < L; l += 256) {
     int64_t row = lookup[b * L + l];
     if (row < 0 || row >= E) row = 0;
+    if constexpr (SHARD) {
+      row -= sh_lo;
+      if (row < 0 || row >= sh_n) continue;
+    }
     const float* er = ent + row * d;
     float s = 0.f;
     if ((d & 3) == 0) {   // 16-byte loads of the gathered row; the fma chain keeps its order
@@ -348,12 +356,17 @@ __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__
 #endif
 constexpr int SF_U = COPER_SF_U;      // rows per slot and batch
 constexpr int SF_MAX_L = 8192;       // lookup entries of a query held in LDS (32 KB)
-template <bool DET>
+// SHARD (k_tr_score_loss's comment): the sample's owned entries are compacted in LDS -- stable, ascending l: ids[j] the
+// local row of the j-th owned entry, pos[j] its l -- and the batch loop below runs over the compacted count Ln in place of L, so the
+// rows of other shards are never requested.  A row's score chain does not depend on where in a batch the row sits, so ds[b, l] is
+// the whole-table launch's value; dh and the loss share add the owned terms in the order this kernel gives Ln entries.  A shard
+// that owns every entry compacts to the identity.  (LDS: int pos[L] behind ids.)
+template <bool DET, bool SHARD = false>
 __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restrict__ hv, const float* __restrict__ ent,
                                                           const float* __restrict__ pred_bias, const int32_t* __restrict__ lookup,
                                                           const float* __restrict__ labels, int64_t E, int d, int L, float ls_eps,
                                                           float inv_E, float inv_BL, float* __restrict__ ds, float* __restrict__ dh,
-                                                          double* __restrict__ loss_acc) {
+                                                          double* __restrict__ loss_acc, int64_t sh_lo = 0, int64_t sh_n = 0) {
   extern __shared__ float4 sf_lds[];   // float4 [slots][d4] (the slots' dh shares at the end) | float part[RB][d4 + 1] | float g[RB] | int ids[L]
   __shared__ double red[256];
   const int64_t b = blockIdx.x;
@@ -366,10 +379,48 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
   const int slot = threadIdx.x / d4, q4 = threadIdx.x - slot * d4;
   const bool live = slot < slots;
   // the query's rows, range-checked once (a row id is read by the thread that loads the row, by the thread that scores it, ...)
+  int Ln = L;      // the entries the batch loop walks
+  [[maybe_unused]] int* const pos = ids + L;
+  if constexpr (SHARD) {
+    __shared__ int wown[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int base = 0;      // owned entries in front of this round (uniform)
+    for (int l0 = 0; l0 < L; l0 += 256) {
+      const int l = l0 + (int)threadIdx.x;
+      int64_t row = -1;
+      if (l < L) {
+        row = lookup[b * L + l];
+        row = ((row < 0 || row >= E) ? 0 : row) - sh_lo;
+      }
+      const bool own = row >= 0 && row < sh_n;
+      const unsigned long long om = __ballot(own);
+      if (lane == 0) wown[w] = (int)__popcll(om);
+      __syncthreads();
+      int at = base + (int)__popcll(om & ((1ull << lane) - 1ull));
+      for (int q = 0; q < w; ++q) at += wown[q];
+      if (own) {      // (at <= l < L)
+        ids[at] = (int)row;
+        pos[at] = l;
+      }
+      base += wown[0] + wown[1] + wown[2] + wown[3];
+      __syncthreads();
+    }
+    Ln = base;
+    if (Ln == 0) {      // (uniform) nothing of this sample lives here: an exact zero row, a zero loss share
+      for (int k = threadIdx.x; k < d; k += 256) dh[b * d + k] = 0.f;
+      if (threadIdx.x == 0) {
+        if constexpr (DET) loss_acc[blockIdx.x] = 0.0;
+      }
+      return;
+    }
+  } else {
   for (int l = threadIdx.x; l < L; l += 256) {
     const int32_t row = lookup[b * L + l];
     ids[l] = (row < 0 || row >= E) ? 0 : row;
   }
+  }
+  // where entry j of the walk sits in the sample's [L] arrays
+  auto at_l = [&](int j) { if constexpr (SHARD) return pos[j]; else return j; };
   const float4 h4 = live ? *(const float4*)(hv + b * d + 4 * q4) : make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -382,7 +433,7 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
   {                                                                                           \
     _Pragma("unroll") for (int u = 0; u < SF_U; ++u) {                                        \
       const int l = (l0_) + u * slots + slot;                                                 \
-      const int64_t row = ids[l < L ? l : L - 1];                                             \
+      const int64_t row = ids[l < Ln ? l : Ln - 1];                                           \
       dst_[u] = *(const float4*)(ent + row * d + 4 * qc);                                     \
     }                                                                                         \
   }
@@ -392,9 +443,9 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
 #define SF_BATCH(l0_, cur_, nxt_)                                                             \
   {                                                                                           \
     const int lb = (l0_);                                                                     \
-    const bool on = sr < RB && lb + sr < L;    /* (uniform over the tpr neighbours of a row) */ \
-    const int lc = lb + sr < L ? lb + sr : L - 1;                                             \
-    const float lab = labels[b * L + lc], pb = pred_bias[ids[lc]];                            \
+    const bool on = sr < RB && lb + sr < Ln;   /* (uniform over the tpr neighbours of a row) */ \
+    const int lc = lb + sr < Ln ? lb + sr : Ln - 1;                                           \
+    const float lab = labels[b * L + at_l(lc)], pb = pred_bias[ids[lc]];                      \
     SF_FETCH(lb + RB, nxt_);                                                                  \
     if (live) {                                                                               \
       _Pragma("unroll") for (int u = 0; u < SF_U; ++u) {                                      \
@@ -417,13 +468,13 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
       lacc += (double)(fmaxf(sc, 0.f) - sc * t + log1pf(expf(-as)));   /* sigmoid cross-entropy with logits */ \
       const float sg = 1.f / (1.f + expf(-sc));                                               \
       const float g = (sg - t) * inv_BL;                                                      \
-      ds[b * L + lb + sr] = g;                                                                \
+      ds[b * L + at_l(lb + sr)] = g;                                                          \
       gsh[sr] = g;                                                                            \
     }                                                                                         \
     __syncthreads();                                                                          \
     if (live) {                                                                               \
       _Pragma("unroll") for (int u = 0; u < SF_U; ++u)                                        \
-        if (lb + u * slots + slot < L) {                                                      \
+        if (lb + u * slots + slot < Ln) {                                                     \
           const float g = gsh[u * slots + slot];                                              \
           acc.x = fmaf(g, cur_[u].x, acc.x); acc.y = fmaf(g, cur_[u].y, acc.y);               \
           acc.z = fmaf(g, cur_[u].z, acc.z); acc.w = fmaf(g, cur_[u].w, acc.w);               \
@@ -431,9 +482,9 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
     }                                                                                         \
   }
   SF_FETCH(0, va);
-  for (int l0 = 0; l0 < L; l0 += 2 * RB) {
+  for (int l0 = 0; l0 < Ln; l0 += 2 * RB) {
     SF_BATCH(l0, va, vb);
-    if (l0 + RB < L) SF_BATCH(l0 + RB, vb, va);      // (uniform)
+    if (l0 + RB < Ln) SF_BATCH(l0 + RB, vb, va);      // (uniform)
   }
 #undef SF_BATCH
 #undef SF_FETCH
@@ -460,11 +511,15 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
 // ------------------------------------------------------------------------------------------------
 // dh[b,k] = sum_l ds[b,l] E[lookup[b,l], k];  SCATTER: also dE[lookup, k] += ds h[b,k], dbias[lookup] += ds by
 // float atomics (the route for entity tables too large for the dense S matrix below)
-template <bool SCATTER>
+// SHARD (k_tr_score_loss's comment; without SCATTER only): an entry of another shard is a (0, 0) addend with nothing loaded -- acc
+// starts at +0 and no sum of this chain is -0, so fmaf(0, 0, acc) returns acc: the owned entries' chain in ascending l.
+template <bool SCATTER, bool SHARD = false>
 __global__ __launch_bounds__(256) void k_tr_score_bwd(const float* __restrict__ hv, const float* __restrict__ ent,
                                                       const int32_t* __restrict__ lookup, const float* __restrict__ ds,
                                                       int64_t E, int d, int64_t L, float* __restrict__ dh,
-                                                      float* __restrict__ dE, float* __restrict__ dbias) {
+                                                      float* __restrict__ dE, float* __restrict__ dbias, int64_t sh_lo = 0,
+                                                      int64_t sh_n = 0) {
+  static_assert(!(SCATTER && SHARD), "the sharded step scatters nothing: its table gradient is k_ord_reduce's");
   const int64_t b = blockIdx.x;
   for (int k0 = 0; k0 < d; k0 += 256) {   // a thread per feature, 256 features at a time (d <= 256: one trip; 640: three)
   const int k = k0 + threadIdx.x;
@@ -479,10 +534,15 @@ __global__ __launch_bounds__(256) void k_tr_score_bwd(const float* __restrict__ 
     for (int u = 0; u < 8; ++u) {
       row[u] = lookup[b * L + l + u];
       if (row[u] < 0 || row[u] >= E) row[u] = 0;
+      if constexpr (SHARD) {
+        row[u] -= sh_lo;
+        if (row[u] < 0 || row[u] >= sh_n) row[u] = -1;
+        g[u] = row[u] >= 0 ? ds[b * L + l + u] : 0.f;
+      } else
       g[u] = ds[b * L + l + u];
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) ev[u] = k < d ? ent[row[u] * d + k] : 0.f;
+    for (int u = 0; u < 8; ++u) ev[u] = (k < d && (!SHARD || row[u] >= 0)) ? ent[row[u] * d + k] : 0.f;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {   // same summation order as the plain loop
       acc = fmaf(g[u], ev[u], acc);
@@ -495,6 +555,10 @@ __global__ __launch_bounds__(256) void k_tr_score_bwd(const float* __restrict__ 
   for (; l < L; ++l) {
     int64_t row = lookup[b * L + l];
     if (row < 0 || row >= E) row = 0;
+    if constexpr (SHARD) {
+      row -= sh_lo;
+      if (row < 0 || row >= sh_n) continue;
+    }
     const float g = ds[b * L + l];
     if (k < d) {
       acc = fmaf(g, ent[row * d + k], acc);
@@ -511,9 +575,11 @@ __global__ __launch_bounds__(256) void k_tr_score_bwd(const float* __restrict__ 
 // four features (16-byte loads) of one of 256 / (d / 4) row slots, eight rows ahead, so a workgroup keeps 8 * slots rows
 // (32 KB at d = 200) in flight; the slots' partial sums meet in LDS.  (The per-feature form with eight 4-byte loads in
 // flight per thread read at 3.1 TB/s.)
+// SHARD: as k_tr_score_bwd -- an entry of another shard is a (0, 0) addend with nothing loaded.
+template <bool SHARD = false>
 __global__ __launch_bounds__(256) void k_tr_dh_gather4(const float* __restrict__ ent, const int32_t* __restrict__ lookup,
                                                        const float* __restrict__ ds, int64_t E, int d, int64_t L,
-                                                       float* __restrict__ dh) {
+                                                       float* __restrict__ dh, int64_t sh_lo = 0, int64_t sh_n = 0) {
   extern __shared__ float4 sh4[];   // [slots][d / 4]
   const int64_t b = blockIdx.x;
   const int d4 = d >> 2, slots = 256 / d4;
@@ -531,10 +597,18 @@ __global__ __launch_bounds__(256) void k_tr_dh_gather4(const float* __restrict__
       for (int u = 0; u < 8; ++u) {
         row[u] = lk[l + u * slots];
         if (row[u] < 0 || row[u] >= E) row[u] = 0;
+        if constexpr (SHARD) {
+          row[u] -= sh_lo;
+          if (row[u] < 0 || row[u] >= sh_n) row[u] = -1;
+          g[u] = row[u] >= 0 ? gs[l + u * slots] : 0.f;
+        } else
         g[u] = gs[l + u * slots];
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *(const float4*)(ent + row[u] * d + 4 * q4);
+      for (int u = 0; u < 8; ++u) {
+        if constexpr (SHARD) v[u] = row[u] >= 0 ? *(const float4*)(ent + row[u] * d + 4 * q4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        else v[u] = *(const float4*)(ent + row[u] * d + 4 * q4);
+      }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         acc.x = fmaf(g[u], v[u].x, acc.x); acc.y = fmaf(g[u], v[u].y, acc.y);
@@ -544,6 +618,10 @@ __global__ __launch_bounds__(256) void k_tr_dh_gather4(const float* __restrict__
     for (; l < L; l += slots) {
       int64_t row = lk[l];
       if (row < 0 || row >= E) row = 0;
+      if constexpr (SHARD) {
+        row -= sh_lo;
+        if (row < 0 || row >= sh_n) continue;
+      }
       const float g = gs[l];
       const float4 v = *(const float4*)(ent + row * d + 4 * q4);
       acc.x = fmaf(g, v.x, acc.x); acc.y = fmaf(g, v.y, acc.y); acc.z = fmaf(g, v.z, acc.z); acc.w = fmaf(g, v.w, acc.w);

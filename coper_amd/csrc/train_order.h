@@ -230,6 +230,8 @@ __global__ __launch_bounds__(256) void k_ord_heads(const int32_t* __restrict__ k
 }
 
 // ---- ordered segment reduce: a wave per segment (grid-stride over the segments: a row's sum does not depend on which wave forms it).
+// dE / dbias hold rows [row_lo, row_lo + row_n) of the table (the whole table: 0, num_ent; a shard: DESIGN 6.8): a segment whose row
+// lies outside is skipped whole.
 //   dE[row][k] = fmaf(ds[e], h[b(e)][k], acc) over the segment's lookup entries e = b L + l in ascending e, acc from 0.f;
 //   dbias[row] = acc + ds[e] the same way.  Entries >= BL (the e1 ids) end the segment and add nothing.
 // Sixty-four entries' indices and ds are fetched by the lanes together and handed round by shuffles; eight rows of h are in flight
@@ -300,10 +302,12 @@ __device__ __forceinline__ void ord_reduce_segment(const int32_t* __restrict__ v
 __global__ __launch_bounds__(256) void k_ord_reduce(const int32_t* __restrict__ list, const int32_t* __restrict__ seg,
                                                     const int32_t* __restrict__ count, const int32_t* __restrict__ vals,
                                                     const float* __restrict__ ds, const float* __restrict__ hv, int64_t L, int64_t BL, int d,
-                                                    int vec, float* __restrict__ dE, float* __restrict__ dbias) {
+                                                    int vec, int64_t row_lo, int64_t row_n, float* __restrict__ dE,
+                                                    float* __restrict__ dbias) {
   const int n = *count, lane = threadIdx.x & 63;
   for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < n; s += gridDim.x * 4) {
-    const int64_t row = list[s];
+    const int64_t row = (int64_t)list[s] - row_lo;
+    if (row < 0 || row >= row_n) continue;      // (wave-uniform: a segment of another shard -- nothing of it is read)
     const int lo = seg[s], hi = seg[s + 1];
     if (vec) ord_reduce_segment<true>(vals, lo, hi, ds, hv, L, BL, d, lane, dE + row * d, dbias + row);
     else ord_reduce_segment<false>(vals, lo, hi, ds, hv, L, BL, d, lane, dE + row * d, dbias + row);

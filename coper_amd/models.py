@@ -890,7 +890,8 @@ class ConvE(object):
         entity_sharded=True (coper_train_init_sharded in include/coper_hip.h has the contract; needs deterministic=True): the model may
         hold any shard of the entity table (`ConvE(..., shard=(lo, hi))`); gradients and slots of ent_emb / pred_bias exist for its rows
         only, and the step is the four train_shard_* calls, which `coper_amd.parallel.EntityShardedTrainer` drives.  1-vs-all batches
-        with sparse labels only; train_step and the split steps are refused on such a state."""
+        with sparse labels and sampled batches (which always take the ordered-rows route there); train_step and the split steps are
+        refused on such a state."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -1022,6 +1023,20 @@ class ConvE(object):
         with torch.cuda.device(self.device):
             _lib.check(self._h, self._lib.coper_train_shard_score_csr(self._h, _ptr(ip), _ptr(ix), _ptr(row), n_rows, B, _ptr(dh_part),
                                                                       _ptr(loss_part), self._stream()))
+
+    def train_shard_score_lookup(self, batch, B, dh_part, loss_part):
+        """coper_train_shard_score_lookup: the sampled scorer over the entries of `lookup_values` int32 [B, L] (global ids) this shard
+        holds, labels `e2_multi` float [B, L] -- both as train_step takes them; dh_part float32 [B, d] and loss_part float64 [1] are
+        written."""
+        lookup = self._ids(batch["lookup_values"], torch.int32)
+        labels = batch["e2_multi"]
+        labels = (labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(labels)))
+        labels = labels.to(device=self.device, dtype=torch.float32).contiguous()
+        if labels.dim() != 2 or tuple(lookup.shape) != tuple(labels.shape) or labels.shape[0] != B:
+            raise ValueError("training batch: e1, rel [B]; lookup_values and e2_multi [B, L]")
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_shard_score_lookup(self._h, _ptr(lookup), _ptr(labels), B, labels.shape[1], _ptr(dh_part),
+                                                                         _ptr(loss_part), self._stream()))
 
     def train_shard_backward(self, dh_parts, loss_parts, sumsq_part):
         """coper_train_shard_backward: dh_parts float32 [G, B, d] and loss_parts float64 [G] folded in rank order, the encoder's

@@ -244,8 +244,8 @@ class DataParallelTrainer(object):
 
 
 class EntityShardedTrainer(object):
-    """Entity-sharded (model-parallel) 1-vs-all training from sparse labels (include/coper_hip.h, "Entity-sharded training";
-    DESIGN.md 6.7).  Rank g of G holds rows [lo_g, hi_g) of ent_emb / pred_bias with their gradients and AMSGrad slots
+    """Entity-sharded (model-parallel) training, 1-vs-all from sparse labels or from sampled batches (include/coper_hip.h,
+    "Entity-sharded training").  Rank g of G holds rows [lo_g, hi_g) of ent_emb / pred_bias with their gradients and AMSGrad slots
     (`ConvE(md, shard=(lo, hi))` + `train_init(deterministic=True, entity_sharded=True)`); every other leaf is replicated and stays
     byte-identical on every rank WITHOUT an exchange, because the deterministic mode makes the encoder a function of its inputs.
 
@@ -255,13 +255,16 @@ class EntityShardedTrainer(object):
     Both forms leave the same bytes.  Construction checks that the shards' bounds tile [0, num_ent) in rank order and that seed,
     hyper-parameters, dropout counter and beta powers are equal on every rank, and raises ValueError otherwise.
 
-    `step(batch)` takes the SAME batch on every rank -- `e1`, `rel` [B], `lab_indptr`, `lab_idx` (+ `lab_row`), as
-    `ConvE.train_step` takes sparse 1-vs-all labels -- and makes one update:
+    `step(batch)` takes the SAME batch on every rank -- `e1`, `rel` [B] and either `lab_indptr`, `lab_idx` (+ `lab_row`), as
+    `ConvE.train_step` takes sparse 1-vs-all labels, or a sampled batch, `lookup_values` int32 [B, L] of global ids with `e2_multi`
+    float [B, L] -- and makes one update (a step may use another label form than the step before):
 
       1. each rank gathers the e1 rows it holds (zero rows for the others); all-reduce: the [B, d] input rows (one non-zero addend
          per element: exact);
       2. `train_shard_forward`: the replicated encoder up to h;
-      3. `train_shard_score`: the scorer over the own rows -- this shard's table gradients, its share of dh and of the loss;
+      3. `train_shard_score` (sparse 1-vs-all: the scorer over the own rows) or `train_shard_score_lookup` (sampled: the scorer over
+         the batch's entries whose row this shard holds, the table gradient by the ordered-rows route) -- this shard's table
+         gradients, its share of dh and of the loss;
       4. all-gather of the [B, d] shares and of the loss doubles;
       5. `train_shard_backward`: the shares folded in rank order, the encoder's backward, the owned e1 rows, this shard's squared norm;
       6. all-gather of the G doubles;
@@ -269,8 +272,9 @@ class EntityShardedTrainer(object):
 
     Nothing table-sized or logit-sized moves.  Returns the batch loss as a 1-element device tensor (per rank; a list in the
     in-process form would hold G equal values, so rank 0's is returned).  gloo, which moves host tensors only, is staged through the
-    host as `DataParallelTrainer._gather` does.  Not built: sampled or dense labels, the default (non-deterministic) mode, a batch
-    split over ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not been measured."""
+    host as `DataParallelTrainer._gather` does.  Not built: dense [B, num_ent] labels, deferred rows on a shard, the default
+    (non-deterministic) mode, a batch split over ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not
+    been measured."""
 
     def __init__(self, model=None, group=None, models=None):
         import torch.distributed as dist
@@ -369,8 +373,11 @@ class EntityShardedTrainer(object):
     # ---- one update
     def step(self, batch):
         ms = self.local
-        if "lab_indptr" not in batch or "e2_multi" in batch:
-            raise ValueError("EntityShardedTrainer.step: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row])")
+        lv = batch.get("lookup_values", None)
+        sampled = "e2_multi" in batch and lv is not None and np.ndim(lv) == 2 and np.shape(lv)[1] > 0      # (data.py: [B, 0] means 1-vs-all)
+        if not sampled and ("lab_indptr" not in batch or "e2_multi" in batch):
+            raise ValueError("EntityShardedTrainer.step: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row]) or a sampled "
+                             "batch (lookup_values, e2_multi [B, L]); dense e2_multi [B, num_ent] is not served")
         B = len(batch["e1"])
         d = ms[0].ent_emb_size
         rows = self._exchange([m.train_shard_gather(batch["e1"]) for m in ms], reduce=True)                      # 1
@@ -380,7 +387,7 @@ class EntityShardedTrainer(object):
             dh.append(torch.empty((B, d), device=m.device, dtype=torch.float32))
             ls.append(torch.empty(1, device=m.device, dtype=torch.float64))
             sq.append(torch.empty(1, device=m.device, dtype=torch.float64))
-            m.train_shard_score(batch, B, dh[-1], ls[-1])                                                         # 3
+            (m.train_shard_score_lookup if sampled else m.train_shard_score)(batch, B, dh[-1], ls[-1])            # 3
         dh_all, ls_all = self._exchange(dh), self._exchange(ls)                                                   # 4
         losses = [m.train_shard_backward(a, l.reshape(-1), s) for m, a, l, s in zip(ms, dh_all, ls_all, sq)]      # 5
         sq_all = self._exchange(sq)                                                                               # 6

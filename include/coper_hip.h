@@ -831,7 +831,8 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
 COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const float* vals, int64_t n, int32_t first, void* stream);
 COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_t n, double scale, void* stream);
 
-/* Entity-sharded training: 1-vs-all from sparse labels with the entity table split over G handles.  Rank g holds rows
+/* Entity-sharded training: 1-vs-all from sparse labels, or sampled batches, with the entity table split over G handles (DESIGN 6.7,
+ * 6.8).  Rank g holds rows
  * [shard_lo, shard_hi) of ent_emb / pred_bias (coper_config), their gradients and their AMSGrad slots, and nothing of the other rows.
  * The encoder runs replicated on the whole batch; the scorer (the chunk loop of coper_train_step_csr over the handle's own rows), the
  * table's optimizer pass and the table's memory divide by G.  The caller moves three small things per step between the ranks: the
@@ -845,7 +846,8 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  * coper_train_shard_gather(h, e1, B, rows_out, stream): rows_out [B, d] = the table rows of the ids this handle holds, zero rows for
  *   the others -- one addend of e1_rows below (each element has one non-zero addend: the sum over ranks is exact).  Reads the
  *   registered table as it stands, prepared or not; no part of the state machine.
- * The step, four calls in this order (any other order: COPER_ESTATE, the text names the call expected next):
+ * The step, four calls in this order -- forward | score_csr OR score_lookup | backward | apply; a step may use another label form
+ * than the step before (any other order: COPER_ESTATE, the text names the call, or the two calls, expected next):
  * coper_train_shard_forward(h, e1, rel, e1_rows, B, h_out, stream): the train-mode encoder up to h on the whole batch.  The input
  *   images are the rows of e1_rows (device float [B, d]: the sum over ranks of coper_train_shard_gather / coper_gather_entities),
  *   never the table's.  e1 and rel (device int64 [B]) are copied: the later calls name no ids.  h_out: optional device float [B, d].
@@ -855,9 +857,22 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  *   column c is entity shard_lo + c; the label-smoothing term uses the global num_ent), stores this shard's d(pred_bias) and
  *   d(ent_emb) rows, and hands out dh_part (device float [B, d]: the chunk shares added in ascending chunk order) and loss_part
  *   (device double [1]: the unnormalised sum).
+ * coper_train_shard_score_lookup(h, lookup, labels, B, L, dh_part, loss_part, stream): the sampled form, valid exactly where
+ *   coper_train_shard_score_csr is.  lookup (device int32 [B, L], GLOBAL ids) and labels (device float [B, L]) are the arrays
+ *   coper_train_step takes, the same on every rank; ids outside [0, num_ent) count as row 0 and so belong to the shard that holds it.
+ *   B must be the forward call's, L >= 1, B (L + 1) and num_ent must fit 31 bits (COPER_EINVAL).  An entry (b, l) is OWNED when
+ *   shard_lo <= id < shard_hi after the clamp.  For the owned entries, and only for them: s = h[b] . E[id - lo] + pred_bias[id - lo] by
+ *   the per-row chain of the whole-table kernel of the same route (the fused scorer where d % 4 == 0, 16 <= d <= 1024, L <= 8192;
+ *   k_tr_score_loss otherwise), t = (1 - eps) label + 1 / num_ent with the GLOBAL num_ent, the loss term and
+ *   ds = (sigmoid(s) - t) / (B L): ds[b, l] is the whole-table step's value bit for bit on any sharding.  dh_part[b] = sum of
+ *   ds[b, l] E[id - lo] over the owned l in the whole-table kernel's order with the other shards' entries removed (a sample with no
+ *   owned entry: an exact zero row); loss_part[0] the unnormalised sum in double, per-sample shares in ascending b.  d(ent_emb) and
+ *   d(pred_bias) of the own rows by the ordered-rows route (coper_train_order_rows, which this call needs no switch for): a stable
+ *   sort of the batch's ids into ascending (id, b, l), a wave per owned row, fmaf from 0.f in ascending (b, l), stored with `=` onto
+ *   the rows the forward call zeroed -- no float atomics.  An entry of another shard costs no row read, no store and no loss term.
  * coper_train_shard_backward(h, dh_parts, loss_parts, G, loss_out, sumsq_part, stream): dh = dh_parts[0] + dh_parts[1] + ... in
  *   ascending g (device float [G, B, d]), the loss the same way in double (device double [G]; loss_out: optional device float [1], the
- *   batch loss).  Then the encoder's backward; the conv backward's d(img) rows are added to the OWNED e1 rows only (one writer per row,
+ *   batch loss: the mean over the labels of the score call that ran, B num_ent or B L).  Then the encoder's backward; the conv backward's d(img) rows are added to the OWNED e1 rows only (one writer per row,
  *   ascending b, onto what the score call stored; a row of another shard is dropped without a store).  Advances the dropout counter.
  *   sumsq_part: device double [1], the squared norm of this shard's d(ent_emb) and d(pred_bias), summed in one fixed order.
  * coper_train_shard_apply(h, sumsq_parts, G, stream): global squared norm = the small leaves' + sumsq_parts[0 .. G) in index order
@@ -866,12 +881,17 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  * Bits: every output of a sharded step is the same across runs, handles and processes; the replicated leaves and their slots are
  *   byte-identical on every rank.  Where every shard is exactly one chunk (the last one ragged) and the global norm is <= clip_norm,
  *   loss, variables, slots and BN statistics are those of coper_train_step_csr on a deterministic whole-table handle with the same
- *   one_vs_all_chunk; otherwise only the association of a float / double sum differs.
+ *   one_vs_all_chunk; otherwise only the association of a float / double sum differs.  Sampled steps: a shard [0, num_ent) with the
+ *   global norm <= clip_norm leaves the bits of coper_train_step on a deterministic whole-table handle with ordered rows on (the
+ *   norm itself to the last bits of a double sum), also where sampled and 1-vs-all steps alternate; on ANY sharding d(pred_bias)
+ *   and every row of d(ent_emb) that no e1 of the batch names are that handle's bit for bit (ds and the segment sums are functions
+ *   of the batch alone; the rows e1 names also take the conv backward's share, which depends on the association of dh).
  * On a sharded state coper_train_step*, coper_train_backward*, coper_train_forward*, coper_train_grads_export, coper_train_apply,
  *   coper_train_defer_rows and coper_train_order_rows return COPER_EUNSUPPORTED; coper_train_grad / coper_train_slot of the two tables
  *   hand out the local rows, global_norm the global one.  Null pointers, G < 1, B <= 0: COPER_EINVAL.
- * Not built: sampled labels on a sharded table; the default (non-deterministic) mode; splitting the encoder's batch over ranks (needs
- *   a synchronised BN); dense [B, num_ent] labels; a forward-only sharded call; overlap of the exchanges with compute. */
+ * Not built: deferred rows on a shard (the table's zeroing, norm and optimizer pass stay |E| / G per step, whatever the label form);
+ *   the default (non-deterministic) mode; splitting the encoder's batch over ranks (needs a synchronised BN); dense [B, num_ent]
+ *   labels; a forward-only sharded call; overlap of the exchanges with compute. */
 COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg);
 COPER_API int coper_train_sharded(const coper_handle* h);
 COPER_API int coper_train_shard_gather(coper_handle* h, const int64_t* e1, int64_t B, float* rows_out, void* stream);
@@ -879,6 +899,8 @@ COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, cons
                                         float* h_out, void* stream);
 COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_indptr, const int64_t* lab_idx, const int64_t* lab_row,
                                           int64_t n_rows, int64_t B, float* dh_part, double* loss_part, void* stream);
+COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* lookup, const float* labels, int64_t B, int64_t L,
+                                             float* dh_part, double* loss_part, void* stream);
 COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts, const double* loss_parts, int32_t G, float* loss_out,
                                          double* sumsq_part, void* stream);
 COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts, int32_t G, void* stream);

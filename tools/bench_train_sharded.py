@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""What one rank of an entity-sharded 1-vs-all training step costs, phase by phase, on ONE GPU:
+"""What one rank of an entity-sharded training step costs, phase by phase, on ONE GPU:
 
-    python tools/bench_train_sharded.py [--shapes fb15k237_b512,synth1m_b128] [--worlds 1,2,4,8] [--reps 20] [--parent-root DIR]
-                                        [--rounds 3] [--out profiles/train_sharded.json]
+    python tools/bench_train_sharded.py [--labels csr|sampled] [--shapes fb15k237_b512,synth1m_b128] [--worlds 1,2,4,8] [--reps 20]
+                                        [--parent-root DIR] [--rounds 3] [--out profiles/train_sharded.json]
 
-Shapes: FB15k-237 CoPER at B = 512, and its layers over a 1,048,583 x 200 table at B = 128; sparse 1-vs-all labels (about five
-positives per row), ids uniform over the table.  Each configuration runs in a fresh child process:
+Shapes: FB15k-237 CoPER at B = 512, and its layers over a 1,048,583 x 200 table at B = 128 (or B = 512); ids uniform over the table.
+--labels csr (default): sparse 1-vs-all labels, about five positives per row.  --labels sampled: L = 1000 sampled ids per sample,
+column 0 positive (coper_train_shard_score_lookup; the whole-table handle of (a) then has ordered rows on, the step a world of one
+reproduces); default shapes fb15k237_b512,synth1m_b512, default output profiles/train_sharded_sampled.json.  Each configuration runs
+in a fresh child process:
     single             (a) the deterministic whole-table handle, `train_step` on the CSR batch: host clock around the step + a device
                        synchronisation.  With --parent-root DIR (a checkout of the parent commit with its library built) the same on
                        that build, in the same run, the two builds ALTERNATING for --rounds rounds (a process apart, the same code
@@ -16,7 +19,9 @@ positives per row), ids uniform over the table.  Each configuration runs in a fr
                        rows, [G, B, d] shares of dh, G doubles) -- the values mean nothing, the work is the rank's own.  G = 1 is the
                        whole table in the four calls: its score and apply phases are (a)'s scorer and optimizer share.
 5 warm steps, then --reps repetitions: median [min, max].  The summary gives, per shape and G, the score and apply phases as a fraction
-of G = 1's, the encoder phases, and the projected step of one rank before collectives (the sum of its four phases).  Multi-GPU scaling
+of G = 1's, the encoder phases, and the projected step of one rank before collectives (the sum of its four phases); with sampled
+labels also the score phase split as c + g / G through G = 1 and the largest G (c: what does not divide, the sort over all B (L + 1)
+ids and the launches; g: what does, the row gathers and the owned segments).  Multi-GPU scaling
 with real RCCL exchanges is NOT measured here.  One JSON document; no threshold is set on these times."""
 import argparse
 import json
@@ -27,7 +32,8 @@ import sys
 ROOT = os.environ.get("COPER_BENCH_ROOT") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-SHAPES = {"fb15k237_b512": dict(B=512), "synth1m_b128": dict(B=128, num_ent=1048583)}
+SHAPES = {"fb15k237_b512": dict(B=512), "synth1m_b128": dict(B=128, num_ent=1048583), "synth1m_b512": dict(B=512, num_ent=1048583)}
+SAMPLED_L = 1000
 PHASES = ("forward", "score", "backward", "apply")
 
 
@@ -46,7 +52,7 @@ def _md(shape):
     return md
 
 
-def _batches(md, B, n=4):
+def _batches(md, B, labels, n=4):
     import numpy as np
     import torch
     E, R = md["num_ent"], md["num_rel"]
@@ -54,6 +60,12 @@ def _batches(md, B, n=4):
     dev = lambda a: torch.as_tensor(a).cuda()
     out = []
     for _ in range(n):
+        if labels == "sampled":
+            lab = np.zeros((B, SAMPLED_L), np.float32)
+            lab[:, 0] = 1.0
+            out.append(dict(e1=dev(rng.integers(0, E, B)), rel=dev(rng.integers(0, R, B)),
+                            lookup_values=dev(rng.integers(0, E, (B, SAMPLED_L)).astype(np.int32)), e2_multi=dev(lab)))
+            continue
         idx = np.sort(rng.integers(0, E, (B, 5)), axis=1)
         idx[:, 1:][idx[:, 1:] == idx[:, :-1]] = E      # (a repeated id: past the table, absent by contract)
         idx = np.sort(idx, axis=1)
@@ -62,14 +74,16 @@ def _batches(md, B, n=4):
     return out
 
 
-def child(shape, world, reps):
+def child(shape, world, reps, labels):
     import time
     import torch
     from coper_amd import data as cdata
     from coper_amd.models import ConvE
     md = _md(shape)
     B, E, d = SHAPES[shape]["B"], md["num_ent"], md["ent_emb_size"]
-    rec = {"shape": shape, "num_ent": E, "d": d, "B": B, "world": world}
+    rec = {"shape": shape, "num_ent": E, "d": d, "B": B, "world": world, "labels": labels}
+    if labels == "sampled":
+        rec["L"] = SAMPLED_L
     if world:
         from coper_amd.sharding import shard_bounds
         lo, hi = shard_bounds(E, world, 0)
@@ -81,10 +95,10 @@ def child(shape, world, reps):
     p = {k: torch.as_tensor(v) for k, v in small.items()}
     p.update(ent_emb=torch.randn((hi - lo, d), device="cuda", generator=gen) * 0.1, pred_bias=torch.randn((hi - lo,), device="cuda", generator=gen) * 0.1)
     m = ConvE(md, device="cuda:0", shard=(lo, hi)).load_parameters(p, global_rows=False)
-    bs = _batches(md, B)
+    bs = _batches(md, B, labels)
     rec["device"] = torch.cuda.get_device_name(0)
     if not world:
-        m.train_init(seed=1, deterministic=True)
+        m.train_init(seed=1, deterministic=True, **(dict(ordered_rows=True) if labels == "sampled" else {}))
         for i in range(5):
             m.train_step(bs[i % 4])
         ms = []
@@ -110,7 +124,7 @@ def child(shape, world, reps):
             ev[0].record()
             m.train_shard_forward(b["e1"], b["rel"], rows)
             ev[1].record()
-            m.train_shard_score(b, B, dh, ls)
+            (m.train_shard_score_lookup if labels == "sampled" else m.train_shard_score)(b, B, dh, ls)
             ev[2].record()
             m.train_shard_backward(dh_all, ls_all, sq)
             ev[3].record()
@@ -128,17 +142,20 @@ def child(shape, world, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--labels", choices=["csr", "sampled"], default="csr")
+    ap.add_argument("--shapes", default=None)
     ap.add_argument("--worlds", default="1,2,4,8")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_sharded.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--world", type=int, default=0)
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.world, a.reps)
+        return child(a.child, a.world, a.reps, a.labels)
+    a.shapes = a.shapes or ("fb15k237_b512,synth1m_b512" if a.labels == "sampled" else "fb15k237_b512,synth1m_b128")
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_sharded_sampled.json" if a.labels == "sampled" else "train_sharded.json")
     res, stop = [], False
     for shape in a.shapes.split(","):
         runs = ([(0, None)] + ([(0, a.parent_root)] if a.parent_root else [])) * (a.rounds if a.parent_root else 1)
@@ -148,7 +165,7 @@ def main():
             if root:      # the parent commit's package and library, this file's child
                 env["COPER_BENCH_ROOT"] = os.path.abspath(root)
                 env.pop("COPER_HIP_LIB", None)
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", shape, "--world", str(world), "--reps", str(a.reps)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", shape, "--world", str(world), "--reps", str(a.reps), "--labels", a.labels]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             rec = json.loads(line[-1]) if r.returncode == 0 and line else {"shape": shape, "world": world, "failed": r.returncode,
@@ -185,8 +202,13 @@ def main():
                 e["score_over_world1"] = ph[g]["score"]["median"] / ph[1]["score"]["median"]
                 e["apply_over_world1"] = ph[g]["apply"]["median"] / ph[1]["apply"]["median"]
             s["world_%d" % g] = e
+        if a.labels == "sampled" and 1 in ph and max(ph) > 1:      # score(G) = c + g / G through G = 1 and the largest G
+            gm = max(ph)
+            s1, sg = ph[1]["score"]["median"], ph[gm]["score"]["median"]
+            per = (s1 - sg) / (1.0 - 1.0 / gm)
+            s["score_fit_ms"] = {"through_worlds": [1, gm], "divides_by_world": per, "does_not_divide": s1 - per}
         summary.append(s)
-    doc = {"tool": "tools/bench_train_sharded.py", "reps": a.reps,
+    doc = {"tool": "tools/bench_train_sharded.py", "labels": a.labels, "reps": a.reps,
            "clock": "single: host perf_counter around train_step + a device synchronisation; shard: device events around each of the four calls; "
                     "warm (5 steps); one process per configuration; one GPU, exchanges emulated by buffers (no collective is timed)",
            "results": res, "summary": summary}
