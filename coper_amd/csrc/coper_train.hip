@@ -35,11 +35,15 @@
 //   num_ent; the heads are the deferred-rows mode's row list, in ascending id, and its norm goes through the slab.  Off: nothing changes.
 //   Entity-sharded 1-vs-all (coper_train_init_sharded): the handle holds rows [shard_lo, shard_hi) of the two tables with their
 //   gradients and slots; the step is four calls -- coper_train_shard_forward | _score_csr or _score_lookup (sampled labels, DESIGN 6.8:
-//   Step::score_lookup_shard) | _backward | _apply -- over the phases below,
+//   the sampled scorer below over the handle's row range) | _backward | _apply -- over the phases below,
 //   with the caller's exchanges between them (input rows, the shards' shares of dh and the loss, their squared norms).  A deterministic
 //   state only; kernels of its own in train_shard.h.  Every other entry point behaves as it did.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
+//   What a call is (StepKind) and which route its scorer takes (ScorerPlan: label form, table-gradient route, dh route, the owned row
+//   range) are decided ONCE per call -- plan_scorer, and ScorerPlan::resolve_dh behind the workspaces -- and read everywhere else: the
+//   refusals, the workspace sizes and the launches cannot disagree.  Every update ends in the same tail: a tensor table from
+//   train_tensors, the launches, finish_update for the host's bookkeeping.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -66,6 +70,19 @@ struct TrainParam {
   DevBuf<float> m;      // AMSGrad slots
   DevBuf<float> v;
   DevBuf<float> vh;
+};
+
+// What the forward phases of a step hand to its backward phases (a base of struct Step).  The entity-sharded step runs them in
+// different calls and keeps it on the state between them (TrainState::shard_carry): one assignment each way.
+struct StepCarry {
+  const unsigned* w_slots = nullptr;  // the dense weights' maximum as the last step's optimizer pass left it, when it describes them
+  const unsigned* x_slots = nullptr;  // the dense input's, as k_tr_bn1_fwd wrote it
+  const float *ccw = nullptr, *ccb = nullptr;   // contexts of the conv generators [B, rc_cw], [B, rc_cb]
+  const float *cw = nullptr, *cbv = nullptr;    // contexts of the dense generators [B, rc_w], [B, rc_b]
+  const float* xin = nullptr;         // the dense layer's input [B, F] and its gradient
+  float* dxin = nullptr;
+  const TrainParam* W = nullptr;      // the dense weights: row-major [rc_w * F, d] (generated), [F, d] (static) or the table (looked up)
+  bool p3_packed = false;        // the projection's second view (rows f) was packed with its first
 };
 
 // the owner of one operand plane set of the split-16 GEMMs; the GEMM helpers take the TgPlanes it hands out
@@ -223,13 +240,7 @@ struct TrainState {
   int64_t sh_B = 0, sh_cap = 0;
   double sh_labels = 1.0;
   DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
-  struct ShardCarry {
-    const unsigned *w_slots = nullptr, *x_slots = nullptr;
-    const float *ccw = nullptr, *ccb = nullptr, *cw = nullptr, *cbv = nullptr, *xin = nullptr;
-    float* dxin = nullptr;
-    const TrainParam* W = nullptr;
-    bool p3_packed = false;
-  } shard_carry;
+  StepCarry shard_carry;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -511,6 +522,63 @@ inline int64_t ova_chunk(int64_t B, int64_t E, int32_t request) {
   return c < E ? c : E;
 }
 
+// What a call of the step is: coper_train_forward; coper_train_step; coper_train_backward (everything but the optimizer);
+// coper_train_rows_backward (the same in the deferred-rows mode)
+enum class StepKind { Forward, Step, Backward, RowsBackward };
+inline bool differentiates(StepKind k) { return k != StepKind::Forward; }
+inline bool runs_optimizer(StepKind k) { return k == StepKind::Step; }
+inline bool keeps_moving_stats(StepKind k) { return k == StepKind::Forward; }      // (k_tr_bn_finish leaves the moving statistics alone)
+
+// ---- the scorer's routes, decided once per call
+// the dense d(loss)/d(logits) matrix S [B, |E|] fits: 1-vs-all trains through it, the sampled scorer's backward is a GEMM on it
+inline bool dense_S_fits(int64_t B, int64_t E) { return (double)B * (double)E * 4.0 <= 512.0 * 1024 * 1024 && E <= 0x7fffffff; }
+enum class LabelForm { Dense, Csr, Sampled };      // labels [B, |E|] (or none: a sharded call that scores nothing); id lists; [B, L] with a lookup
+// d(ent_emb) / d(pred_bias): one GEMM on the S of 1-vs-all; per chunk of entity columns (Step::score_csr); the dense S built from the
+// lookup and one GEMM; sorted segments, one writer per row (ordered rows, a sharded state); float atomics
+enum class TableGrad { OvaGemm, CsrChunks, DenseS, Ordered, Atomics };
+// dh [B, d]: a GEMM on S (1-vs-all); from the pass that formed the scores (k_tr_score_loss_dh); k_tr_dh_gather4; k_tr_score_bwd
+enum class DhRoute { Gemm, Fused, Gather4, ScoreBwd };
+struct ScorerPlan {
+  LabelForm labels = LabelForm::Dense;
+  TableGrad table = TableGrad::OvaGemm;
+  DhRoute dh = DhRoute::Gemm;
+  size_t lds_fused = 0;         // k_tr_score_loss_dh's dynamic LDS (DhRoute::Fused)
+  bool shard = false;           // an entity-sharded state: the tables are rows [lo, lo + n) of num_ent, the sampled kernels
+  int64_t lo = 0, n = 0;        //   take their SHARD forms; otherwise [0, num_ent)
+  bool sampled() const { return labels == LabelForm::Sampled; }
+  bool ordered() const { return table == TableGrad::Ordered; }
+  // The part that looks at pointers, once the workspaces exist (ent is the caller's: nothing here follows from an allocator).
+  void resolve_dh(int d, int64_t L, const float* ent, const float* dh_ws, const float* hv_ws) {
+    if (!sampled()) return;
+    dh = DhRoute::ScoreBwd;
+    if (table == TableGrad::Atomics) return;      // (k_tr_score_bwd<true>: dh beside its atomics)
+    // the gather: 16-byte rows; fused with the scores: a training step whose dE goes through S or the segments takes scores, loss, ds
+    // and dh from one pass over the rows (coper_train_forward takes the same kernel: its loss is the step's, bit for bit)
+    if (!((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)dh_ws) & 15) == 0)) return;
+    dh = DhRoute::Gather4;
+    if (!(L >= 1 && L <= SF_MAX_L && ((uintptr_t)hv_ws & 15) == 0)) return;
+    dh = DhRoute::Fused;
+    const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
+    // (SHARD: the compacted entries' positions, int [L] more)
+    lds_fused = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + (shard ? 2 : 1) * sizeof(int) * (size_t)L;
+  }
+};
+// (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE;  ordered rows: the sorted-segment route at every |E| --
+//  one arithmetic for every table size;  a sharded state's sampled score call, DESIGN 6.8: always that route)
+static ScorerPlan plan_scorer(const coper_handle* h, const TrainState* T, const int32_t* lookup, const CsrLabels& csr, int64_t B) {
+  ScorerPlan p;
+  p.shard = T->sharded;
+  p.lo = p.shard ? (int64_t)h->cfg.shard_lo : 0;
+  p.n = p.shard ? (int64_t)h->dm.n_local : (int64_t)h->dm.E;
+  if (csr.indptr) { p.labels = LabelForm::Csr; p.table = TableGrad::CsrChunks; }
+  else if (lookup) {
+    p.labels = LabelForm::Sampled;
+    p.table = (T->rows_ordered || p.shard) ? TableGrad::Ordered
+            : (!T->rows_deferred && dense_S_fits(B, h->dm.E)) ? TableGrad::DenseS : TableGrad::Atomics;
+  }
+  return p;
+}
+
 // the side streams (TrainState::side): fork(i, k) lets side[k] start behind everything queued on s so far, join(i) lets s go on
 // behind what side[k] was given since.  Whatever leaves the step early joins what it forked.
 struct SideJoin {
@@ -591,6 +659,13 @@ static int rows_wrap_guard(coper_handle* h, TrainState* T, hipStream_t s) {
   T->rows_now = 0;
   return COPER_OK;
 }
+// the rows of the call before: their gradient rows, their claim bits; the other list's count (a claim or an import appends from 0)
+static void rows_rezero_launch(coper_handle* h, TrainState* T, hipStream_t s) {
+  const int pv = T->rows_prev;
+  hipLaunchKernelGGL(k_rows_rezero, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), T->rows_list[pv].get(), T->rows_count + pv,
+                     T->rows_claim.get(), T->rows_count + (pv ^ 1));
+  prof_count(h, "train.rows.rezero");
+}
 
 // ---- ordered rows (kernels in train_order.h)
 inline int64_t ord_tiles(int64_t n) { return std::max<int64_t>((n + ORD_TILE - 1) / ORD_TILE, 1); }
@@ -652,6 +727,75 @@ static int ord_sort_pending_list(coper_handle* h, TrainState* T, hipStream_t s) 
   return COPER_OK;
 }
 
+// ---- the update: the tensor table of k_tr_sumsq / k_tr_amsgrad, their launches, the host's bookkeeping behind them
+enum class LeafSet { All, Small /* every leaf but ent_emb and pred_bias */, Tables /* those two */ };
+enum class GradSrc { Buffers /* TrainParam::g */, FlatVector /* `vec` at each leaf's flat_off */, SmallVector /* ... at its small_off */ };
+// Fills `tt` with the leaves of `which` in T->tp order and returns how many.  table_counts: the relation counts that say which rows of
+// the looked-up dense table exist.  carry_wmax: the table hands k_tr_amsgrad wmax[wmax_cur ^ 1] for the dense weights' largest |p_new|
+// (the next step's packs read it) -- on its 16-byte path only: it is the one that carries it.  found: where `find` sits in the table.
+static int train_tensors(const coper_handle* h, TrainState* T, LeafSet which, GradSrc src, const float* vec, const int32_t* table_counts,
+                         bool carry_wmax, TrainTensors& tt, const TrainParam* find = nullptr, int* found = nullptr) {
+  const Dims& dm = h->dm;
+  const TrainLeaves& lv = T->lv;
+  const bool lk = dm.lookup && dm.gen_fc, gen = dm.gen_fc && !dm.lookup;
+  const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
+  int np = 0;
+  tt.wmax = nullptr; tt.wmax_of = -1;
+  for (const TrainParam& t : T->tp) {
+    const bool is_table = &t == lv.ent_emb || &t == lv.pred_bias;
+    if (which != LeafSet::All && is_table != (which == LeafSet::Tables)) continue;
+    const int i = np++;
+    tt.p[i] = t.p; tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
+    tt.g[i] = src == GradSrc::Buffers ? t.g.get() : const_cast<float*>(vec) + (src == GradSrc::SmallVector ? t.small_off : t.flat_off);
+    tt.n[i] = t.n;
+    const bool table = lk && &t == lv.fc_weights;
+    tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
+    tt.rowcnt[i] = table ? table_counts : nullptr;
+    if (found && &t == find) *found = i;
+    if (carry_wmax && !lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
+      tt.wmax = T->wmax[T->wmax_cur ^ 1];
+      tt.wmax_of = i;
+    }
+  }
+  return np;
+}
+// deterministic mode: the squared norm of the table's tensors -- every workgroup's sum into the slab, their fold in one order into *out
+static void sumsq_det_launch(TrainState* T, hipStream_t s, const TrainTensors& tt, int np, double* out) {
+  hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, -1, T->det_slab.get());
+  hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, out, 0);
+}
+// clip by the slots' sum + AMSGrad at this update's learning rate (returned); gs: the gradients' scale
+static float amsgrad_launch(TrainState* T, hipStream_t s, const TrainTensors& tt, int np, double gs) {
+  const coper_train_config& tc = T->cfg;
+  const RedLayout red = T->red_layout();
+  const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
+  hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, red.sumsq_slots(), red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1,
+                     tc.beta2, tc.epsilon, gs);
+  return lr_t;
+}
+// In front of an update from gradients that an earlier call left: the squared-norm slots hold what that backward's GEMM epilogues added,
+// wmax[wmax_cur ^ 1] what the update before last left
+static void zero_update_slots(TrainState* T, hipStream_t s) {
+  ZeroList zl;
+  zl.n = 2;
+  zl.p[0] = T->red_layout().sumsq_slots(); zl.bytes[0] = sizeof(double) * TG_SUMSQ_SLOTS;
+  zl.p[1] = T->wmax[T->wmax_cur ^ 1].get(); zl.bytes[1] = sizeof(unsigned) * TG_MAX_SLOTS;
+  hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
+}
+// The host's bookkeeping behind an optimizer pass.  Deferred rows: k_rows_update wrote the listed rows' words -- current as of this update.
+static void finish_update(TrainState* T, bool wmax_carried) {
+  if (T->rows_deferred) {
+    T->rows_now += 1;
+    T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
+    T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
+  }
+  T->b1p *= T->cfg.beta1;
+  T->b2p *= T->cfg.beta2;
+  if (T->rows_deferred) rows_log2_from_powers(T);
+  T->wmax_cur ^= 1;
+  T->wmax_valid = wmax_carried;
+}
+
 // clip + AMSGrad over every trainable tensor: the squared norm (k_tr_sumsq; deterministic mode: through the slab and its fold), then
 // k_tr_amsgrad.  Deferred rows: ent_emb and pred_bias are left out of both launches, and the rows of `rows_list` (its length on the
 // device, `rows_count`) go through k_rows_sumsq / k_rows_update between and behind them.  The caller has zeroed the squared-norm slots
@@ -662,37 +806,15 @@ static int ord_sort_pending_list(coper_handle* h, TrainState* T, hipStream_t s) 
 static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, const float* flat, const TrainParam* sumsq_done,
                              const int32_t* table_counts, double gs, const int32_t* rows_list = nullptr, const int32_t* rows_count = nullptr,
                              bool flat_small = false, int64_t rows_n = 0 /* ordered rows: the host's bound of the list's length */) {
-  const Dims& dm = h->dm;
   const coper_train_config& tc = T->cfg;
-  const TrainLeaves& lv = T->lv;
-  const bool lk = dm.lookup && dm.gen_fc, gen = dm.gen_fc && !dm.lookup;
-  const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
   const RedLayout red = T->red_layout();
-  TrainTensors tt;
-  int np = 0;      // tensors of the two launches: every leaf, or every leaf but the two tables
+  TrainTensors tt;      // tensors of the two launches: every leaf, or every leaf but the two tables
   int skip = -1;
-  // the dense weights' largest |p_new| for the next step's packs (k_tr_amsgrad's 16-byte path only: it is the one that carries it)
-  tt.wmax = nullptr; tt.wmax_of = -1;
-  for (const TrainParam& t : T->tp) {
-    if (rows_list && (&t == lv.ent_emb || &t == lv.pred_bias)) continue;
-    const int i = np++;
-    tt.p[i] = t.p; tt.g[i] = flat ? const_cast<float*>(flat) + (flat_small ? t.small_off : t.flat_off) : t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
-    tt.n[i] = t.n;
-    const bool table = lk && &t == lv.fc_weights;
-    tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
-    tt.rowcnt[i] = table ? table_counts : nullptr;
-    if (&t == sumsq_done) skip = i;
-    if (!lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
-      tt.wmax = T->wmax[T->wmax_cur ^ 1];
-      tt.wmax_of = i;
-    }
-  }
+  const int np = train_tensors(h, T, rows_list ? LeafSet::Small : LeafSet::All, !flat ? GradSrc::Buffers : flat_small ? GradSrc::SmallVector : GradSrc::FlatVector,
+                               flat, table_counts, true, tt, sumsq_done, &skip);
   double* const ssq = red.sumsq_slots();
-  if (T->det) {      // (skip is -1: no GEMM added squares) every workgroup's sum into the slab, their fold into slot 0 of the zeroed slots
-    hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, T->det_slab.get());
-    hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, ssq, 0);
-  } else
-    hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
+  if (T->det) sumsq_det_launch(T, s, tt, np, ssq);      // (skip is -1: no GEMM added squares) into slot 0 of the zeroed slots
+  else hipLaunchKernelGGL(k_tr_sumsq<false>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, skip, ssq);
   prof_count(h, "train.sumsq.leaves", np);
   if (rows_list && T->rows_ordered) {
     // the listed rows' share in partial sums of ORD_SUMSQ_ROWS list positions (the slab is free again behind the fold above), folded
@@ -705,9 +827,7 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
     hipLaunchKernelGGL(k_rows_sumsq, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, ssq);
     prof_count(h, "train.rows.sumsq");
   }
-  const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
-  hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, ssq, red.total_sumsq(), tc.clip_norm, lr_t, tc.beta1, tc.beta2,
-                     tc.epsilon, gs);
+  const float lr_t = amsgrad_launch(T, s, tt, np, gs);
   prof_count(h, "train.amsgrad.leaves", np);
   if (rows_list) {      // (behind k_tr_amsgrad on the same stream: both read the slots, neither writes them)
     hipLaunchKernelGGL(k_rows_update, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), rows_list, rows_count, (const double*)ssq,
@@ -719,23 +839,25 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
 
 // One call of the step: the arguments, what they and the configuration decide once, the few values a phase hands to a later one, and
 // the phases themselves in the order of the header comment's schedule (train_step_impl runs them).
-struct Step {
+struct StepArgs {
+  StepKind kind = StepKind::Step;
+  hipStream_t s = nullptr;
+  const int64_t *e1 = nullptr, *rel = nullptr;
+  const int32_t* lookup = nullptr;
+  const float* labels = nullptr;
+  int64_t B = 0, L = 0;
+  float *loss_out = nullptr, *pred_out = nullptr, *h_out = nullptr;
+  CsrLabels csr;                    // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
+  const float* img_rows = nullptr;  // the entity-sharded step: the input images are the rows of img_rows [B, d] (the gathered e1 rows), never the table's
+  ScorerPlan plan;                  // plan_scorer of the same call; its dh route once grow_workspaces has run
+};
+struct Step : StepArgs, StepCarry {
   coper_handle* const h;
   TrainState* const T;
   const Dims& dm; const coper_train_config& tc; const TrainLeaves& lv;
-  hipStream_t const s;
-  const int64_t *const e1, *const rel; const int32_t* const lookup; const float* const labels; const int64_t B, L;
-  float *const loss_out, *const pred_out, *const h_out;
-  const int apply;                  // 0: coper_train_forward; 1: coper_train_step; 2: coper_train_backward (everything but the optimizer);
-                                    // 3: coper_train_rows_backward (the same in the deferred-rows mode)
-  const CsrLabels csr;              // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
-  // the entity-sharded step: the tables are rows [sh_lo, sh_lo + sh_n) of num_ent; the input images are the rows of
-  // img_rows [B, d] (the gathered e1 rows), never the table's
-  const bool shard = false;
-  const float* const img_rows = nullptr;
-  const int64_t sh_lo = 0, sh_n = dm.E;
-  const int nomov = apply ? 0 : 2, use_batch = tc.batch_norm_train_stats ? 1 : 0;   // (nomov: k_tr_bn_finish leaves the moving statistics alone)
-  const bool one_vs_all = lookup == nullptr;   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|]
+  Step(coper_handle* h_, TrainState* T_, const StepArgs& a) : StepArgs(a), h(h_), T(T_), dm(h_->dm), tc(T_->cfg), lv(T_->lv) {}
+  const int nomov = keeps_moving_stats(kind) ? 2 : 0, use_batch = tc.batch_norm_train_stats ? 1 : 0;
+  const bool one_vs_all = !plan.sampled();   // use_negative_sampling = False: labels are the dense e2_multi [B, |E|] or id lists
   const bool cat = dm.concat_rel, two_streams = T->side[0] != nullptr;
   const bool det = T->det;          // coper_train_config.deterministic: every sum in one defined order
   const bool lk = dm.lookup && dm.gen_fc;    // dense layer from g_lookup tables (otherwise static: models.py:217-228 with context_rel_out None)
@@ -753,31 +875,16 @@ struct Step {
   const RedLayout red = T->red_layout();
   float *const mean1 = T->bn_row(BN1_MEAN), *const inv1 = T->bn_row(BN1_INV), *const mean2 = T->bn_row(FCBN_MEAN), *const inv2 = T->bn_row(FCBN_INV);
   SideJoin sj{T, s};
-  // the scorer's backward through the dense d(loss)/d(logits) matrix S and one GEMM (else by float atomics)
-  // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE)
   const bool rows = T->rows_deferred;
-  // (ordered rows: the sorted-segment route at every |E| -- one arithmetic for every table size)
-  // (a sharded state's sampled score call, DESIGN 6.8: always that route)
-  const bool ordered = (T->rows_ordered || shard) && lookup != nullptr;
-  const bool dense_scorer_bwd = !rows && !ordered && (double)B * (double)dm.E * 4.0 <= 512.0 * 1024 * 1024 && dm.E <= 0x7fffffff;
-  // ---- from phase to phase
+  // ---- from phase to phase (and StepCarry)
   float *Tf = nullptr, *dTf = nullptr;                // generated dense: T[rho][b][k] | dT (in T->A, once grow_workspaces has seen to it)
   const float *K_ps = nullptr, *kb_ps = nullptr;      // per-sample conv filters / biases (T->Kt, T->Kbv; null where they are static)
-  const unsigned* w_slots = nullptr;  // the dense weights' maximum as the last step's optimizer pass left it, when it describes them
-  const unsigned* x_slots = nullptr;  // the dense input's, as k_tr_bn1_fwd wrote it
-  const float *ccw = nullptr, *ccb = nullptr;   // contexts of the conv generators [B, rc_cw], [B, rc_cb]
-  const float *cw = nullptr, *cbv = nullptr;    // contexts of the dense generators [B, rc_w], [B, rc_b]
-  const float* xin = nullptr;         // the dense layer's input [B, F] and its gradient
-  float* dxin = nullptr;
-  const TrainParam* W = nullptr;      // the dense weights: row-major [rc_w * F, d] (generated), [F, d] (static) or the table (looked up)
-  bool p3_packed = false;        // the projection's second view (rows f) was packed with its first
   int t_slices = 1, dx_slices = 1;   // K slices the T and dx products left for k_tr_fc_post_slices / k_tr_bn1_bwd_sums to add
-  bool score_dh_fused = false;   // scores, loss, ds and dh came from one pass over the rows (k_tr_score_loss_dh)
   const TrainParam* sumsq_done = nullptr;   // the leaf whose squared gradient norm its own GEMM accumulated
   const int32_t *rows_list = nullptr, *rows_count = nullptr;   // deferred rows: the rows this call claimed (rows_claim_catch_up)
   // ordered rows: the sorted entry indices, and the batch's unique rows with their segment offsets (order_rows; null until it ran)
   const int32_t *ord_vals = nullptr, *ord_rows = nullptr, *ord_rows_count = nullptr;
-  bool scorer_bwd_on_side() const { return two_streams && score_dh_fused && tg_split_k(dm.E, d, B) == 1; }
+  bool scorer_bwd_on_side() const { return two_streams && plan.dh == DhRoute::Fused && tg_split_k(dm.E, d, B) == 1; }
 
   int grow_workspaces() {
     int rc;
@@ -827,7 +934,8 @@ struct Step {
     if (det) {
       // the slab of the widest reducing launch: DET_CS_WGS workgroups of column sums (2 mx doubles each), a loss kernel's grid (B, 2048,
       // or B x the stretches of a chunk), k_tr_sumsq's 512 x tensors
-      const int64_t cwid = (csr.indptr || shard) ? ova_chunk(B, sh_n, tc.one_vs_all_chunk) : 0;
+      const bool ordered = plan.ordered();
+      const int64_t cwid = (csr.indptr || plan.shard) ? ova_chunk(B, plan.n, tc.one_vs_all_chunk) : 0;
       size_t need = (size_t)DET_CS_WGS * 2 * T->mx;
       // (as floats: the 64-row stretches of a column sum over |E|, the filter taps or d columns, or of the [rc_b, d] bias-projection product)
       // (ordered rows: no column sum over |E|; the partial sums of the listed rows' norm instead)
@@ -843,7 +951,7 @@ struct Step {
     // (Round 6 tried the sampled scorer's forward and dh in ONE pass over the gathered rows -- a wave per row, the score a butterfly
     //  sum over its lanes: 242 us against 61 + 45 for the two kernels.  Thirty-two sequential iterations per wave, each with two
     //  dependent round trips and eight six-step cross-lane sums, are latency end to end; removed.)
-    if (!one_vs_all && dense_scorer_bwd && (size_t)(B * dm.E) > T->Sd.size()) {
+    if (plan.table == TableGrad::DenseS && (size_t)(B * dm.E) > T->Sd.size()) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
       if ((rc = T->Sd.alloc(h, (size_t)(B * dm.E), "training workspace"))) return rc;
     }
@@ -851,6 +959,7 @@ struct Step {
     dTf = T->A + (size_t)rc_w * nBd;
     K_ps = dm.gen_conv ? T->Kt.get() : nullptr;
     kb_ps = dm.gen_conv ? T->Kbv.get() : nullptr;
+    plan.resolve_dh(d, L, lv.ent_emb->p, T->dh.get(), T->hv.get());
     return COPER_OK;
   }
   // ---- deterministic mode: the launches that replace an atomic site
@@ -886,7 +995,7 @@ struct Step {
     else if (gen) add(lv.gen[1].proj[nh]->g, sizeof(float) * rc_b * d);
     else add(lv.fc_bias->g, sizeof(float) * d);
     // (the dense S of the sampled scorer's backward is written whole by k_tr_build_S: nothing to zero)
-    if (apply == 1) add(T->wmax[T->wmax_cur ^ 1], sizeof(unsigned) * TG_MAX_SLOTS);      // what this step's optimizer pass fills for the next step
+    if (runs_optimizer(kind)) add(T->wmax[T->wmax_cur ^ 1], sizeof(unsigned) * TG_MAX_SLOTS);      // what this step's optimizer pass fills for the next step
     for (unsigned* slots : {T->xmax.get(), T->dtmax.get(), T->smax.get()}) add(slots, sizeof(unsigned) * TG_MAX_SLOTS);
     hipLaunchKernelGGL(k_tr_zero_list, dim3(256, (unsigned)zl.n), dim3(256), 0, s, zl);
     T->exp_cache.clear();
@@ -900,7 +1009,7 @@ struct Step {
     if (need <= T->rows_cap) return COPER_OK;
     int rc;
     // the list of the call before is still owed its re-zero: pay it from the old buffers, then replace both
-    if (T->rows_cap) rows_rezero();
+    if (T->rows_cap) rows_rezero_launch(h, T, s);
     COPER_HIP_TRY(h, hipStreamSynchronize(s));
     T->rows_cap = 0;
     if ((rc = T->rows_list[0].alloc(h, (size_t)need, "deferred-row list")) || (rc = T->rows_list[1].alloc(h, (size_t)need, "deferred-row list"))) return rc;
@@ -908,20 +1017,13 @@ struct Step {
     T->rows_cap = need;
     return COPER_OK;
   }
-  // 5. the rows of the call before: their gradient rows, their claim bits; the other list's count (the claim appends from 0)
-  void rows_rezero() {
-    const int pv = T->rows_prev;
-    hipLaunchKernelGGL(k_rows_rezero, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), T->rows_list[pv].get(), T->rows_count + pv,
-                       T->rows_claim.get(), T->rows_count + (pv ^ 1));
-    prof_count(h, "train.rows.rezero");
-  }
   // 1. + 2. claim the batch's rows into the free list and bring them current.  The list is the handle's "list of the call before" from
   // here on, whatever becomes of the call: the next one re-zeroes it.
   void rows_claim_catch_up() {
     const int cur = T->rows_prev ^ 1;
     const int64_t n = B * (L + 1);
     // (ordered rows: the list is the sort's segment heads -- ascending id -- and the heads set the claim bits)
-    if (ordered) order_rows(T->rows_list[cur].get(), T->rows_count + cur, T->rows_claim.get());
+    if (plan.ordered()) order_rows(T->rows_list[cur].get(), T->rows_count + cur, T->rows_claim.get());
     else {
       hipLaunchKernelGGL(k_rows_claim, grid1d(n), dim3(256), 0, s, e1, B, lookup, n, (int64_t)dm.E, T->rows_claim.get(), T->rows_list[cur].get(),
                          T->rows_count + cur);
@@ -957,10 +1059,10 @@ struct Step {
     int rc;
     if ((rc = coper_reserve(h, B, 0, (void*)s))) return rc;
     h->gcur = 0;
-    if ((rc = launch_group_by_relation(h, e1, rel, shard /* no table row is looked up by e1 there */, B, 32, s))) return rc;
-    if (apply) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->grouping().rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
+    if ((rc = launch_group_by_relation(h, e1, rel, plan.shard /* no table row is looked up by e1 there */, B, 32, s))) return rc;
+    if (differentiates(kind)) COPER_HIP_TRY(h, hipMemcpyAsync(T->step_rel_count, h->grouping().rel_count, sizeof(int32_t) * ((size_t)dm.R + 1), hipMemcpyDeviceToDevice, s));
     // (the grouping's order inside a relation is arrival order, and the order k_tr_lookup_dW sums in: a sorted copy for it)
-    if (det && apply)
+    if (det && differentiates(kind))
       hipLaunchKernelGGL(k_tr_sort_groups_det, dim3((unsigned)dm.R), dim3(256), 0, s, h->grouping().perm, h->grouping().rel_offset,
                          h->grouping().rel_count, T->det_perm.get());
     return COPER_OK;
@@ -1050,7 +1152,7 @@ struct Step {
       // views from one read (tg_pack_both: 118 MB read once instead of twice, one launch instead of two)
       // (round 6 also ran this pack on a side stream beside the conv / Conv1BN launches in front of it: the stream takes the memory
       //  system, k_tr_bn1_fwd beside it 38 us for 9 -- 5 us gained, not kept)
-      if (apply && (d & 3) == 0 && (((uintptr_t)W->p) & 15) == 0) {
+      if (differentiates(kind) && (d & 3) == 0 && (((uintptr_t)W->p) & 15) == 0) {
         if ((rc = tg_pack_both(h, W->p, tg_idx(d), tg_idx2(d, F * (int64_t)d, 1), F, nrk, T->pP3, T->pP1, s, T->tg_scratch, w_slots))) return rc;
         p3_packed = true;
       } else if ((rc = tg_pack(h, W->p, tg_idx2(d, F * (int64_t)d, 1), tg_idx(d), nrk, F, tg_rows_pad(nrk), true, T->pP1, s, T->tg_scratch, nullptr, w_slots)))
@@ -1089,10 +1191,6 @@ struct Step {
     float* const ent = lv.ent_emb->p;
     const float* const pred_bias = lv.pred_bias->p;
     const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
-    // a training step over a sampled lookup whose dE goes through the dense S matrix: scores, loss, ds and dh from one pass over the rows
-    // (coper_train_forward takes the same kernel: its loss is the step's, bit for bit; the dh it leaves in the workspace is not used)
-    score_dh_fused = !one_vs_all && (dense_scorer_bwd || ordered) && (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
-                     (((uintptr_t)ent | (uintptr_t)T->dh.get() | (uintptr_t)T->hv.get()) & 15) == 0;
     if (one_vs_all) {
       if ((size_t)(B * dm.E) > T->Sd.size()) {
         COPER_HIP_TRY(h, hipStreamSynchronize(s));
@@ -1110,9 +1208,20 @@ struct Step {
         det_fold(1, 2048, red.loss(), 1);
       } else
       hipLaunchKernelGGL(k_tr_dense_loss<false>, dim3(2048), dim3(256), 0, s, T->Sd, pred_bias, labels, dm.E, B * dm.E, eps, inv_E, inv_BL, red.loss());
-    } else if (score_dh_fused) {
-      const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
-      const size_t lds_sf = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + sizeof(int) * (size_t)L;
+    } else if (plan.shard) {
+      // A sharded state (always deterministic): the SHARD forms score the entries (b, l) whose clamped id this handle holds
+      // and write ds there only -- the same route by the same plan, so a shard that is the whole table leaves the whole-table step's bits.
+      if (plan.dh == DhRoute::Fused) {
+        const size_t lds_sf = plan.lds_fused;
+        if (lds_sf > 64 * 1024)
+          COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_score_loss_dh<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sf));
+        hipLaunchKernelGGL((k_tr_score_loss_dh<true, true>), dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d,
+                           (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get(), plan.lo, plan.n);
+      } else
+        hipLaunchKernelGGL((k_tr_score_loss<true, true>), dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E,
+                           d, L, eps, inv_E, inv_BL, T->ds, T->det_slab.get(), plan.lo, plan.n);
+    } else if (plan.dh == DhRoute::Fused) {
+      const size_t lds_sf = plan.lds_fused;
       if (det)
         hipLaunchKernelGGL(k_tr_score_loss_dh<true>, dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent,
                            pred_bias, lookup, labels, dm.E, d, (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get());
@@ -1149,10 +1258,11 @@ struct Step {
     float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
     const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
     // (sharded: E is the handle's own rows -- local columns c0, entity sh_lo + c0; inv_E above stays that of the whole table)
-    const int64_t E = sh_n, cw = ova_chunk(B, E, tc.one_vs_all_chunk);
-    if ((size_t)(B * cw) > T->Sd.size() || (apply && cw < E && (size_t)nBd > T->dhc.size())) {
+    const int64_t E = plan.n, sh_lo = plan.lo, cw = ova_chunk(B, E, tc.one_vs_all_chunk);
+    const bool diff = differentiates(kind);
+    if ((size_t)(B * cw) > T->Sd.size() || (diff && cw < E && (size_t)nBd > T->dhc.size())) {
       COPER_HIP_TRY(h, hipStreamSynchronize(s));
-      if ((rc = T->Sd.ensure(h, (size_t)(B * cw), "training workspace")) || (apply && cw < E && (rc = T->dhc.ensure(h, (size_t)nBd, "training workspace"))))
+      if ((rc = T->Sd.ensure(h, (size_t)(B * cw), "training workspace")) || (diff && cw < E && (rc = T->dhc.ensure(h, (size_t)nBd, "training workspace"))))
         return rc;
     }
     const size_t cached = T->exp_cache.size();
@@ -1172,7 +1282,7 @@ struct Step {
       } else
       hipLaunchKernelGGL(k_tr_csr_loss<false>, dim3((unsigned)(B * n_stretch)), dim3(256), 0, s, T->Sd, pred_bias + c0, csr.indptr, csr.idx, csr.row,
                          csr.n_rows, sh_lo + c0, w, n_stretch, vec, eps, inv_E, inv_BL, red.loss());
-      if (apply) {
+      if (diff) {
         hipLaunchKernelGGL(k_tr_col_sum_f32, grid1d(w), dim3(256), 0, s, T->Sd, B, w, dbias + c0);
         if ((rc = tg_matmul(h, T, s, MmView{T->Sd, tg_idx(1), tg_idx(w), true}, w, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE + c0 * d,
                             tg_idx(d), tg_idx(1))))
@@ -1190,54 +1300,18 @@ struct Step {
     if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)nBd, hipMemcpyDeviceToDevice, s));
     return COPER_OK;
   }
-  // The sampled scorer of a sharded step, forward AND backward, over the entries (b, l) whose clamped id this handle holds:
-  // the launches fwd_score_loss + bwd_scorer make on an ordered-rows state, each in its SHARD form -- the same route by the same
-  // conditions, so a shard that is the whole table leaves the whole-table step's bits.  ds is written at the owned entries only; the
-  // sort runs over all B (L + 1) ids (a segment's addends and their order do not depend on what else is sorted) and k_ord_reduce
-  // skips the segments of other shards.  Leaves this shard's share of dh in T->dh and of the loss in red.loss().
-  int score_lookup_shard() {
-    float* const ent = lv.ent_emb->p;
-    const float* const pred_bias = lv.pred_bias->p;
-    float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
-    const float eps = tc.label_smoothing_epsilon, inv_E = (float)(1.0 / (double)dm.E);
-    score_dh_fused = (d & 3) == 0 && d >= 16 && d <= 1024 && L >= 1 && L <= SF_MAX_L &&
-                     (((uintptr_t)ent | (uintptr_t)T->dh.get() | (uintptr_t)T->hv.get()) & 15) == 0;
-    if (score_dh_fused) {
-      const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
-      // (k_tr_score_loss_dh's LDS and the compacted entries' positions: int [L] more)
-      const size_t lds_sf = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + 2 * sizeof(int) * (size_t)L;
-      if (lds_sf > 64 * 1024)
-        COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_score_loss_dh<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sf));
-      hipLaunchKernelGGL((k_tr_score_loss_dh<true, true>), dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d,
-                         (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get(), sh_lo, sh_n);
-    } else
-      hipLaunchKernelGGL((k_tr_score_loss<true, true>), dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E,
-                         d, L, eps, inv_E, inv_BL, T->ds, T->det_slab.get(), sh_lo, sh_n);
-    det_fold(1, B, red.loss(), 1);      // (the B workgroups' loss shares, in sample order, onto the sum the forward call zeroed)
-    order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
-    const int vec = (d & 3) == 0 && (((uintptr_t)T->hv.get() | (uintptr_t)dE) & 15) == 0;
-    hipLaunchKernelGGL(k_ord_reduce, rows_grid(std::min<int64_t>(B * (L + 1), dm.E)), dim3(256), 0, s, ord_rows, (const int32_t*)T->ord_seg.get(),
-                       ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, sh_lo, sh_n, dE, dbias);
-    prof_count(h, "train.order.reduce");
-    if (score_dh_fused) {
-      // (dh came with the scores)
-    } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
-      hipLaunchKernelGGL(k_tr_dh_gather4<true>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
-                         T->ds, dm.E, d, L, T->dh, sh_lo, sh_n);
-    else
-      hipLaunchKernelGGL((k_tr_score_bwd<false, true>), dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh,
-                         (float*)nullptr, (float*)nullptr, sh_lo, sh_n);
-    return COPER_OK;
-  }
   // ---- backward
-  // d(loss)/d(logits) -> dh [B, d], d(pred_bias), d(ent_emb): through a GEMM on the dense S where B * |E| is small, else by float atomics.
+  // d(loss)/d(logits) -> dh [B, d], d(pred_bias), d(ent_emb), by the plan's routes: a GEMM on the dense S where B * |E| is small, sorted
+  // segments (ordered rows; a sharded state, over its own rows), else float atomics.
   // Behind the caller's fork (scorer_bwd_on_side) S, dbias and dE = S^T h (~70 us that need ds and h only) run on side[0] beside the dense
   // layer's backward: tg_matmul packs into a second pair of plane sets there, dE needs no K slices (the partial-sum pool is the dx product's)
   int bwd_scorer() {
     int rc;
     float* const ent = lv.ent_emb->p;
     float *const dE = lv.ent_emb->g, *const dbias = lv.pred_bias->g;
-    if (one_vs_all) {
+    switch (plan.table) {
+    case TableGrad::CsrChunks: return COPER_OK;      // (score_csr: the backward ran chunk by chunk)
+    case TableGrad::OvaGemm:
       hipLaunchKernelGGL(k_tr_col_sum_f32, grid1d(dm.E), dim3(256), 0, s, T->Sd, B, dm.E, dbias);
       // dE[E,d] = S^T h
       if ((rc = tg_matmul(h, T, s, MmView{T->Sd, tg_idx(1), tg_idx(dm.E), true}, dm.E, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE,
@@ -1246,50 +1320,52 @@ struct Step {
       // dh[B,d] = S E: 8 output tiles, K = |E| cut into slices
       return tg_matmul(h, T, s, MmView{T->Sd, tg_idx(dm.E), tg_idx(1), false}, B, MmView{ent, tg_idx(1), tg_idx(d), true}, d, dm.E, T->dh,
                        tg_idx(d), tg_idx(1));
-    }
-    if (ordered) {
-      // one writer per named row, its addends in ascending (b, l): `=` onto the zeroed rows (the conv backward adds the e1 rows behind it)
+    case TableGrad::Atomics:
+      hipLaunchKernelGGL(k_tr_score_bwd<true>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, dE, dbias);
+      return COPER_OK;
+    case TableGrad::Ordered: {
+      // one writer per named row, its addends in ascending (b, l): `=` onto the zeroed rows (the conv backward adds the e1 rows behind it).
+      // The sort runs over all B (L + 1) ids (a segment's addends and their order do not depend on what else is sorted); the reduce
+      // skips the segments outside the plan's rows.
       if (!ord_vals) order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
       const int vec = (d & 3) == 0 && (((uintptr_t)T->hv.get() | (uintptr_t)dE) & 15) == 0;
       hipLaunchKernelGGL(k_ord_reduce, rows_grid(std::min<int64_t>(B * (L + 1), dm.E)), dim3(256), 0, s, ord_rows, (const int32_t*)T->ord_seg.get(),
-                         ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, (int64_t)0, (int64_t)dm.E, dE, dbias);
+                         ord_rows_count, ord_vals, (const float*)T->ds.get(), (const float*)T->hv.get(), L, B * L, d, vec, plan.lo, plan.n, dE, dbias);
       prof_count(h, "train.order.reduce");
-      // dh by the gather, in its own fixed order (as behind the dense S route)
-      if (score_dh_fused) {
-      } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
-        hipLaunchKernelGGL(k_tr_dh_gather4<>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
-                           T->ds, dm.E, d, L, T->dh);
-      else
-        hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
-      return COPER_OK;
+      break;
     }
-    if (!dense_scorer_bwd) {
-      hipLaunchKernelGGL(k_tr_score_bwd<true>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, dE, dbias);
-      return COPER_OK;
+    case TableGrad::DenseS: {
+      hipStream_t const q = sj.on[SJ_SCORER_BWD] >= 0 ? T->side[sj.on[SJ_SCORER_BWD]] : s;
+      const size_t lds_s = sizeof(float) * (size_t)(dm.E < TR_S_CHUNK ? dm.E : TR_S_CHUNK);
+      // (the kernel also holds 16 bytes of static LDS: asking for the whole 160 KB as dynamic is refused, and so is the launch after it)
+      if (!det && lds_s > 64 * 1024) COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_build_S, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+      if (det) {      // duplicate ids of a row in ascending l; dbias[c] = the column sum of S in ascending b
+        hipLaunchKernelGGL(k_tr_build_S_det, dim3((unsigned)B), dim3(256), 0, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
+        det_col_sum_f32(T->Sd, dm.E, dbias, q);
+      } else {
+        hipLaunchKernelGGL(k_tr_build_S, dim3((unsigned)B), dim3(256), lds_s, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
+        hipLaunchKernelGGL(k_tr_col_sums_add<false>, dim3((unsigned)((dm.E + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, q, T->Sd, B, dm.E, dbias);
+      }
+      // dE[E,d] = S^T h  (overwrites the zeroed gradient; the e1-row contributions are added after it)
+      if ((rc = tg_matmul(h, T, q, MmView{T->Sd, tg_idx(1), tg_idx(dm.E), true}, dm.E, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE,
+                          tg_idx(d), tg_idx(1), nullptr, T->smax)))
+        return rc;
+      break;
     }
-    hipStream_t const q = sj.on[SJ_SCORER_BWD] >= 0 ? T->side[sj.on[SJ_SCORER_BWD]] : s;
-    const size_t lds_s = sizeof(float) * (size_t)(dm.E < TR_S_CHUNK ? dm.E : TR_S_CHUNK);
-    // (the kernel also holds 16 bytes of static LDS: asking for the whole 160 KB as dynamic is refused, and so is the launch after it)
-    if (!det && lds_s > 64 * 1024) COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_build_S, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    if (det) {      // duplicate ids of a row in ascending l; dbias[c] = the column sum of S in ascending b
-      hipLaunchKernelGGL(k_tr_build_S_det, dim3((unsigned)B), dim3(256), 0, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
-      det_col_sum_f32(T->Sd, dm.E, dbias, q);
-    } else {
-    hipLaunchKernelGGL(k_tr_build_S, dim3((unsigned)B), dim3(256), lds_s, q, lookup, T->ds, dm.E, L, T->Sd, T->smax);
-    hipLaunchKernelGGL(k_tr_col_sums_add<false>, dim3((unsigned)((dm.E + 255) / 256), (unsigned)((B + 63) / 64)), dim3(256), 0, q, T->Sd, B, dm.E, dbias);
     }
-    // dE[E,d] = S^T h  (overwrites the zeroed gradient; the e1-row contributions are added after it)
-    if ((rc = tg_matmul(h, T, q, MmView{T->Sd, tg_idx(1), tg_idx(dm.E), true}, dm.E, MmView{T->hv, tg_idx(1), tg_idx(d), true}, d, B, dE,
-                        tg_idx(d), tg_idx(1), nullptr, T->smax)))
-      return rc;
-    // dh by the gather (a [d,B] = [d,|E|] x [|E|,B] GEMM has 8 output tiles and a long K: slower than the gather)
-    if (score_dh_fused) {
-      // (dh came with the scores: k_tr_score_loss_dh)
-    } else if ((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)T->dh.get()) & 15) == 0)
-      hipLaunchKernelGGL(k_tr_dh_gather4<>, dim3((unsigned)B), dim3(256), sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2), s, ent, lookup,
-                         T->ds, dm.E, d, L, T->dh);
-    else
-      hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
+    // dh behind the segments or the dense S, on the step's own stream and in its own fixed order: by the gather (a [d,B] = [d,|E|] x
+    // [|E|,B] GEMM has 8 output tiles and a long K: slower than the gather).  The SHARD forms take the row range: an entry of another
+    // shard is a (0, 0) addend with nothing loaded.
+    if (plan.dh == DhRoute::Gather4) {
+      const size_t lds_g = sizeof(float4) * (size_t)(256 / (d >> 2)) * (d >> 2);
+      if (plan.shard) hipLaunchKernelGGL(k_tr_dh_gather4<true>, dim3((unsigned)B), dim3(256), lds_g, s, ent, lookup, T->ds, dm.E, d, L, T->dh, plan.lo, plan.n);
+      else hipLaunchKernelGGL(k_tr_dh_gather4<>, dim3((unsigned)B), dim3(256), lds_g, s, ent, lookup, T->ds, dm.E, d, L, T->dh);
+    } else if (plan.dh == DhRoute::ScoreBwd) {
+      if (plan.shard)
+        hipLaunchKernelGGL((k_tr_score_bwd<false, true>), dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh,
+                           (float*)nullptr, (float*)nullptr, plan.lo, plan.n);
+      else hipLaunchKernelGGL(k_tr_score_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, lookup, T->ds, dm.E, d, L, T->dh, nullptr, nullptr);
+    }      // (DhRoute::Fused: dh came with the scores, k_tr_score_loss_dh)
     return COPER_OK;
   }
 
@@ -1426,11 +1502,11 @@ struct Step {
       hipLaunchKernelGGL(k_tr_conv_bwd<true>, dim3((unsigned)B), dim3(256), lds_cb, s, T->dx, T->img, dm.gen_conv ? nullptr : lv.conv1_weights->p, e1, rel,
                          dm.E, dm.R, d, r, dm.in_h, dm.in_w, dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->dimg.get(),
                          (float*)nullptr, K_ps, T->dKs, T->dkbs, dm.fh, dm.fw);
-      if (shard) {      // the owned e1 rows alone; a row of another shard is that rank's to write
+      if (plan.shard) {      // the owned e1 rows alone; a row of another shard is that rank's to write
         float* const dE = lv.ent_emb->g;
         const int vec = (d & 3) == 0 && (isz & 3) == 0 && (((uintptr_t)T->dimg.get() | (uintptr_t)dE) & 15) == 0;
         hipLaunchKernelGGL(k_shard_rows_by_key, dim3((unsigned)B), dim3(256), 0, s, (const float*)T->dimg.get(), (int64_t)isz, (int64_t)0, d, e1, (int64_t)dm.E, B,
-                           sh_lo, sh_n, vec, dE);
+                           plan.lo, plan.n, vec, dE);
       } else
       det_rows_by_key(T->dimg, isz, 0, d, e1, dm.E, lv.ent_emb->g);
       if (dm.stacked) det_rows_by_key(T->dimg, isz, d, r, rel, dm.R, lv.rel_emb->g);
@@ -1495,7 +1571,7 @@ int coper::train_rows_sync(coper_handle* h, void* stream, bool device_wide) {
 }
 
 static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
-                           int64_t B, int64_t L, float* loss_out, void* stream, const int apply, float* pred_out, float* h_out,
+                           int64_t B, int64_t L, float* loss_out, void* stream, const StepKind kind, float* pred_out, float* h_out,
                            const CsrLabels csr = CsrLabels()) {
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
@@ -1509,25 +1585,29 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (!e1 || !rel || !labels || B <= 0 || L <= 0 || B * L > 0x7fffffff)
     return fail(h, COPER_EINVAL, "coper_train_step: bad argument");
   if (!lookup && L != h->dm.E) return fail(h, COPER_EINVAL, "coper_train_step: lookup == NULL needs labels of shape [B, num_ent]");
-  if (!lookup && (double)B * (double)h->dm.E * 4.0 > 512.0 * 1024 * 1024)
+  if (!lookup && !dense_S_fits(B, h->dm.E))
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step: 1-vs-all training needs B*num_ent*4 <= 512 MiB in this version");
   }
   if (T->sharded)      // (the entity-sharded state has its own four calls and no other step)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_step / _backward / _forward: an entity-sharded state (coper_train_init_sharded) steps through "
                                        "coper_train_shard_forward | _score_csr | _backward | _apply");
-  if (apply == 3 && !T->rows_deferred)      // coper_train_rows_backward: the mode's own backward
+  if (kind == StepKind::RowsBackward && !T->rows_deferred)      // coper_train_rows_backward: the mode's own backward
     return fail(h, COPER_ESTATE, "coper_train_rows_backward: the deferred-rows mode is off (coper_train_defer_rows; coper_train_backward is the dense call)");
   if (T->rows_deferred) {      // what has a gradient in every row, or hands the dense gradient on, is refused
     if (csr.indptr || !lookup)
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deferred-rows mode (coper_train_defer_rows): a 1-vs-all step has a gradient in every row");
-    if (apply == 2)
+    if (kind == StepKind::Backward)
       return fail(h, COPER_EUNSUPPORTED, "coper_train_backward: deferred-rows mode (coper_train_defer_rows): the split step's flat gradient is dense "
                                          "(the mode's split step: coper_train_rows_backward / _export / _import / _apply)");
     if (B * (L + 1) > 0x7fffffff) return fail(h, COPER_EINVAL, "coper_train_step: deferred-rows mode: B * (L + 1) ids do not fit the row lists");
   }
+  StepArgs a;
+  a.kind = kind; a.s = (hipStream_t)stream; a.e1 = e1; a.rel = rel; a.lookup = lookup; a.labels = labels; a.B = B; a.L = L;
+  a.loss_out = loss_out; a.pred_out = pred_out; a.h_out = h_out; a.csr = csr;
+  a.plan = plan_scorer(h, T, lookup, csr, B);
   if (T->det) {      // what the mode does not put in order is refused, never served unordered
-    // (ordered rows: the sampled scorer's backward is the sorted-segment route at every num_ent)
-    if (lookup && !T->rows_ordered && !((double)B * (double)h->dm.E * 4.0 <= 512.0 * 1024 * 1024 && h->dm.E <= 0x7fffffff))
+    // (the plan says atomics: no dense S for this B * num_ent.  Ordered rows: the sorted-segment route at every num_ent)
+    if (a.plan.table == TableGrad::Atomics)
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: sampled labels at B*num_ent*4 > 512 MiB take the atomic scorer backward");
     if (lookup && T->rows_ordered && (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff))
       return fail(h, COPER_EINVAL, "coper_train_step: ordered rows: B * (L + 1) ids and num_ent must fit 31 bits");
@@ -1536,12 +1616,12 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
   }
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
-  if (apply == 1) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
+  if (runs_optimizer(kind)) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_step: batch too large for the dropout counter");
-  Step st{h, T, h->dm, T->cfg, T->lv, (hipStream_t)stream, e1, rel, lookup, labels, B, L, loss_out, pred_out, h_out, apply, csr};
+  Step st(h, T, a);
   int rc;
   if ((rc = st.grow_workspaces())) return rc;
-  if (st.ordered && (rc = ord_grow(h, T, B * (L + 1), st.s))) return rc;
+  if (st.plan.ordered() && (rc = ord_grow(h, T, B * (L + 1), st.s))) return rc;
   if (st.rows) {
     if ((rc = rows_wrap_guard(h, T, st.s)) || (rc = st.rows_grow())) return rc;
   }
@@ -1549,7 +1629,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   T->rows_pending_clear();      // (... and what a coper_train_rows_backward or the imports left: rows_rezero below)
   st.zero_accumulators();
   if (st.rows) {
-    st.rows_rezero();
+    rows_rezero_launch(h, T, st.s);
     st.rows_claim_catch_up();
   }
   if (st.lk && (rc = st.group_for_lookup())) return rc;
@@ -1559,15 +1639,13 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if ((rc = st.fwd_dense())) return rc;
   st.fwd_fcbn();
   if ((rc = csr.indptr ? st.score_csr() : st.fwd_score_loss())) return rc;      // (score_csr: the scorer's backward too, chunk by chunk)
-  if (!apply) {      // coper_train_forward: nothing is differentiated, nothing updated, the step counter (dropout masks) stays
+  if (!differentiates(kind)) {      // coper_train_forward: nothing is differentiated, nothing updated, the step counter (dropout masks) stays
     COPER_HIP_TRY(h, hipGetLastError());
     return COPER_OK;
   }
 
-  if (!csr.indptr) {
-    if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
-    if ((rc = st.bwd_scorer())) return rc;
-  }
+  if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
+  if ((rc = st.bwd_scorer())) return rc;      // (nothing left to do behind score_csr)
   st.bwd_fcbn();
   if ((rc = st.bwd_dense())) return rc;      // (generated: forks SJ_DP in front of the dP product, Step::bwd_dense_dP)
   if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
@@ -1578,10 +1656,10 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   st.sj.join(SJ_DP);      // (dP and its squared norm)
   st.sj.join(SJ_SCORER_BWD);
   if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_step: an event call of the side streams failed");
-  if (apply >= 2) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
+  if (!runs_optimizer(kind)) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
     COPER_HIP_TRY(h, hipGetLastError());
     T->step += 1;
-    if (apply == 2) T->pending = true;
+    if (kind == StepKind::Backward) T->pending = true;
     else {               // coper_train_rows_backward: ... for coper_train_rows_export / coper_train_rows_apply; the table part is the claimed list
       T->rows_pending_small = T->rows_pending_table = true;
       T->rows_bound = std::min<int64_t>(B * (L + 1), h->dm.E);
@@ -1590,37 +1668,45 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   const bool wmax_carried = st.optimizer();
   COPER_HIP_TRY(h, hipGetLastError());
-  if (st.rows) {      // (k_rows_update wrote the listed rows' words: current as of this update)
-    T->rows_now += 1;
-    T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
-    T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
-  }
-  T->b1p *= T->cfg.beta1;
-  T->b2p *= T->cfg.beta2;
-  if (st.rows) rows_log2_from_powers(T);
   T->step += 1;
-  T->wmax_cur ^= 1;
-  T->wmax_valid = wmax_carried;
+  finish_update(T, wmax_carried);
   return COPER_OK;
+}
+
+// k_tr_grads_export over every leaf at its flat_off, or (small) over the leaves of the small flat vector at their small_off
+static void grads_export_launch(coper_handle* h, TrainState* T, hipStream_t s, bool small, bool accumulate, float* out) {
+  ExportList el;
+  int np = 0;
+  el.table = -1; el.rowlen = 1; el.rowcnt = nullptr;
+  for (const TrainParam& t : T->tp) {
+    if (small && t.small_off < 0) continue;
+    const int i = np++;
+    el.g[i] = t.g; el.off[i] = small ? t.small_off : t.flat_off; el.n[i] = t.n; el.span[i] = (t.n + 63) / 64 * 64;
+    if (h->dm.lookup && h->dm.gen_fc && &t == T->lv.fc_weights) {      // rows of relations absent from the backward's batch: zeros
+      el.table = i; el.rowlen = h->dm.F * (int64_t)h->dm.d; el.rowcnt = T->step_rel_count;
+    }
+  }
+  if (accumulate) hipLaunchKernelGGL(k_tr_grads_export<true>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, out);
+  else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, out);
 }
 
 extern "C" {
 
 COPER_API int coper_train_step(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                                int64_t B, int64_t L, float* loss_out, void* stream) {
-  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 1, nullptr, nullptr);
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, StepKind::Step, nullptr, nullptr);
 }
 
 COPER_API int coper_train_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                                   int64_t B, int64_t L, float* loss_out, float* pred_out, float* h_out, void* stream) {
-  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 0, pred_out, h_out);
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, StepKind::Forward, pred_out, h_out);
 }
 
 COPER_API int coper_train_step_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
                                    const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out, void* stream) {
   if (!h) return COPER_EINVAL;
   if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
-  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 1, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, StepKind::Step, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
 }
 
 COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
@@ -1628,20 +1714,20 @@ COPER_API int coper_train_forward_csr(coper_handle* h, const int64_t* e1, const 
                                       void* stream) {
   if (!h) return COPER_EINVAL;
   if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_indptr is NULL)");
-  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 0, pred_out, h_out, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, StepKind::Forward, pred_out, h_out, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
 }
 
 // ---- the split step: backward | export | apply (include/coper_hip.h, "The step in three calls")
 COPER_API int coper_train_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                                    int64_t B, int64_t L, float* loss_out, void* stream) {
-  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 2, nullptr, nullptr);
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, StepKind::Backward, nullptr, nullptr);
 }
 
 COPER_API int coper_train_backward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
                                        const int64_t* lab_row, int64_t n_rows, int64_t B, float* loss_out, void* stream) {
   if (!h) return COPER_EINVAL;
   if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_backward_csr: bad argument (lab_indptr is NULL)");
-  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, 2, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, StepKind::Backward, nullptr, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows});
 }
 
 COPER_API int coper_train_grads_layout(coper_handle* h, const char* leaf_name, int64_t* offset, int64_t* n, int64_t* total) {
@@ -1669,18 +1755,7 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   if (!flat || ((uintptr_t)flat & 15) != 0) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat must be a 16-byte aligned device buffer");
   if (cap < T->flat_total) return fail(h, COPER_EINVAL, "coper_train_grads_export: flat holds fewer than coper_train_grads_layout's total");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
-  ExportList el;
-  const int np = (int)T->tp.size();
-  el.table = -1; el.rowlen = 1; el.rowcnt = nullptr;
-  for (int i = 0; i < np; ++i) {
-    const TrainParam& t = T->tp[i];
-    el.g[i] = t.g; el.off[i] = t.flat_off; el.n[i] = t.n; el.span[i] = (t.n + 63) / 64 * 64;
-    if (h->dm.lookup && h->dm.gen_fc && &t == T->lv.fc_weights) {      // rows of relations absent from the backward's batch: zeros
-      el.table = i; el.rowlen = h->dm.F * (int64_t)h->dm.d; el.rowcnt = T->step_rel_count;
-    }
-  }
-  if (accumulate) hipLaunchKernelGGL(k_tr_grads_export<true>, dim3(1024, (unsigned)np), dim3(256), 0, (hipStream_t)stream, el, flat);
-  else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, (hipStream_t)stream, el, flat);
+  grads_export_launch(h, T, (hipStream_t)stream, false, accumulate != 0, flat);
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
 }
@@ -1708,13 +1783,7 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   }
   h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   T->pending = false;    // (whatever follows: the gradients are consumed, or describe variables that are about to change)
-  // the squared-norm slots hold what the last backward's GEMM epilogues added, wmax[wmax_cur ^ 1] what the update before last left
-  const RedLayout red = T->red_layout();
-  ZeroList zl;
-  zl.n = 2;
-  zl.p[0] = red.sumsq_slots(); zl.bytes[0] = sizeof(double) * TG_SUMSQ_SLOTS;
-  zl.p[1] = T->wmax[T->wmax_cur ^ 1].get(); zl.bytes[1] = sizeof(unsigned) * TG_MAX_SLOTS;
-  hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
+  zero_update_slots(T, s);
   // the norm over every leaf (the epilogues' squares belonged to one backward); absent rows of the looked-up table by the backward's
   // snapshot, never by the grouping workspace (an evaluation pass may have grouped since); from a flat vector every row is present:
   // no counts at all, so the table takes the 16-byte routes of every other leaf (3.0 + 4.7 ms of k_tr_sumsq + k_tr_amsgrad through
@@ -1723,10 +1792,7 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   const int32_t* const counts = flat ? (T->det ? T->all_rel_count.get() : nullptr) : T->step_rel_count.get();
   const bool wmax_carried = optimizer_launch(h, T, s, flat, nullptr, counts, scale);
   COPER_HIP_TRY(h, hipGetLastError());
-  T->b1p *= T->cfg.beta1;
-  T->b2p *= T->cfg.beta2;
-  T->wmax_cur ^= 1;
-  T->wmax_valid = wmax_carried;
+  finish_update(T, wmax_carried);
   return COPER_OK;
 }
 
@@ -1886,7 +1952,7 @@ COPER_API int coper_train_rows_layout(coper_handle* h, const char* leaf_name, in
 
 COPER_API int coper_train_rows_backward(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                                         int64_t B, int64_t L, float* loss_out, void* stream) {
-  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, 3, nullptr, nullptr);
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, StepKind::RowsBackward, nullptr, nullptr);
 }
 
 COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t small_cap, int32_t accumulate, int32_t* ids, float* vals,
@@ -1908,21 +1974,7 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
   if (ids && (((uintptr_t)ids & 3) != 0 || ((uintptr_t)vals & 3) != 0)) return fail(h, COPER_EINVAL, "coper_train_rows_export: misaligned ids / vals");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  if (small) {      // k_tr_grads_export over every leaf but the two tables, at their offsets in the small vector
-    ExportList el;
-    int np = 0;
-    el.table = -1; el.rowlen = 1; el.rowcnt = nullptr;
-    for (const TrainParam& t : T->tp) {
-      if (t.small_off < 0) continue;
-      const int i = np++;
-      el.g[i] = t.g; el.off[i] = t.small_off; el.n[i] = t.n; el.span[i] = (t.n + 63) / 64 * 64;
-      if (h->dm.lookup && h->dm.gen_fc && &t == T->lv.fc_weights) {      // rows of relations absent from the backward's batch: zeros
-        el.table = i; el.rowlen = h->dm.F * (int64_t)h->dm.d; el.rowcnt = T->step_rel_count;
-      }
-    }
-    if (accumulate) hipLaunchKernelGGL(k_tr_grads_export<true>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, small);
-    else hipLaunchKernelGGL(k_tr_grads_export<false>, dim3(1024, (unsigned)np), dim3(256), 0, s, el, small);
-  }
+  if (small) grads_export_launch(h, T, s, true, accumulate != 0, small);      // every leaf but the two tables, at their offsets in the small vector
   if (ids) {
     if (int rc = ord_sort_pending_list(h, T, s)) return rc;      // (ordered rows: the block in ascending row id, after imports too)
     const RowTables t = row_tables(h, T);
@@ -1952,13 +2004,8 @@ COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const
   if ((rc = rows_wrap_guard(h, T, s)) || (rc = rows_grow_keep(h, T, std::max<int64_t>(bound, 1), s))) return rc;
   const RowTables t = row_tables(h, T);
   if (first) {      // a new pending gradient: what a step does to the list of the call before (k_rows_rezero), and the free list becomes the current one
-    const int pv = T->rows_prev;
-    if (T->rows_cap) {
-      hipLaunchKernelGGL(k_rows_rezero, rows_grid(T->rows_cap), dim3(256), 0, s, t, (const int32_t*)T->rows_list[pv].get(), (const int32_t*)(T->rows_count + pv),
-                         T->rows_claim.get(), T->rows_count + (pv ^ 1));
-      prof_count(h, "train.rows.rezero");
-    }
-    T->rows_prev = pv ^ 1;      // (a backward's small gradients stay pending: the import replaces the table part alone)
+    if (T->rows_cap) rows_rezero_launch(h, T, s);
+    T->rows_prev ^= 1;      // (a backward's small gradients stay pending: the import replaces the table part alone)
   }
   if (n > 0) {
     const int cur = T->rows_prev;
@@ -1997,24 +2044,12 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   }
   h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   T->rows_pending_clear();
-  const RedLayout red = T->red_layout();
-  ZeroList zl;           // as coper_train_apply: the slots hold the backward's epilogue squares, wmax[wmax_cur ^ 1] what the update before last left
-  zl.n = 2;
-  zl.p[0] = red.sumsq_slots(); zl.bytes[0] = sizeof(double) * TG_SUMSQ_SLOTS;
-  zl.p[1] = T->wmax[T->wmax_cur ^ 1].get(); zl.bytes[1] = sizeof(unsigned) * TG_MAX_SLOTS;
-  hipLaunchKernelGGL(k_tr_zero_list, dim3(8, (unsigned)zl.n), dim3(256), 0, s, zl);
+  zero_update_slots(T, s);      // (as coper_train_apply)
   const int pv = T->rows_prev;
   const bool wmax_carried = optimizer_launch(h, T, s, small, nullptr, small ? nullptr : T->step_rel_count.get(), scale, T->rows_list[pv].get(),
                                              T->rows_count + pv, small != nullptr, rows_n);
   COPER_HIP_TRY(h, hipGetLastError());
-  T->rows_now += 1;      // (k_rows_update wrote the listed rows' words: current as of this update -- as the mode's fused step)
-  T->rows_l2b1p += T->cfg.beta1 > 0.f ? std::log2((double)T->cfg.beta1) : 0.0;
-  T->rows_l2b2p += T->cfg.beta2 > 0.f ? std::log2((double)T->cfg.beta2) : 0.0;
-  T->b1p *= T->cfg.beta1;
-  T->b2p *= T->cfg.beta2;
-  rows_log2_from_powers(T);
-  T->wmax_cur ^= 1;
-  T->wmax_valid = wmax_carried;
+  finish_update(T, wmax_carried);
   return COPER_OK;
 }
 
@@ -2106,45 +2141,17 @@ static TrainState* shard_state(coper_handle* h, const char* what, int phase, int
   return T;
 }
 
-// a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (apply = 1) with the
-// handle's own rows for the tables
+// a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (StepKind::Step); the
+// plan names the handle's own rows for the tables
 // (lookup / labels [B, L]: the sampled score call; every other phase names no labels and L is num_ent)
 static Step shard_step(coper_handle* h, TrainState* T, hipStream_t s, float* h_out, const CsrLabels& csr, const float* img_rows,
                        const int32_t* lookup = nullptr, const float* labels = nullptr, int64_t L = 0) {
-  return Step{h, T, h->dm, T->cfg, T->lv, s, T->sh_e1.get(), T->sh_rel.get(), lookup, labels, T->sh_B, lookup ? L : (int64_t)h->dm.E, nullptr, nullptr,
-              h_out, 1, csr, true, img_rows, (int64_t)h->cfg.shard_lo, (int64_t)h->dm.n_local};
-}
-static void shard_carry_save(TrainState* T, const Step& st) {
-  T->shard_carry = TrainState::ShardCarry{st.w_slots, st.x_slots, st.ccw, st.ccb, st.cw, st.cbv, st.xin, st.dxin, st.W, st.p3_packed};
-}
-static void shard_carry_load(const TrainState* T, Step& st) {
-  const TrainState::ShardCarry& c = T->shard_carry;
-  st.w_slots = c.w_slots; st.x_slots = c.x_slots; st.ccw = c.ccw; st.ccb = c.ccb; st.cw = c.cw; st.cbv = c.cbv; st.xin = c.xin; st.dxin = c.dxin;
-  st.W = c.W; st.p3_packed = c.p3_packed;
-}
-// the tensor table of k_tr_sumsq / k_tr_amsgrad over the two tables (tables = 1), every other leaf (0) or all of them (-1)
-static int shard_tensors(coper_handle* h, TrainState* T, int tables, TrainTensors& tt) {
-  const Dims& dm = h->dm;
-  const TrainLeaves& lv = T->lv;
-  const bool lk = dm.lookup && dm.gen_fc, gen = dm.gen_fc && !dm.lookup;
-  const TrainParam* const W = gen ? lv.gen[0].proj[T->nh] : lv.fc_weights;
-  int np = 0;
-  tt.wmax = nullptr; tt.wmax_of = -1;
-  for (const TrainParam& t : T->tp) {
-    const bool is_table = &t == lv.ent_emb || &t == lv.pred_bias;
-    if (tables >= 0 && is_table != (tables != 0)) continue;
-    const int i = np++;
-    tt.p[i] = t.p; tt.g[i] = t.g.get(); tt.m[i] = t.m; tt.v[i] = t.v; tt.vh[i] = t.vh;
-    tt.n[i] = t.n;
-    const bool table = lk && &t == lv.fc_weights;
-    tt.rowlen[i] = table ? dm.F * (int64_t)dm.d : 1;
-    tt.rowcnt[i] = table ? T->step_rel_count.get() : nullptr;      // (the forward call's snapshot: an evaluation may have grouped since)
-    if (tables < 0 && !lk && &t == W && ((((uintptr_t)tt.p[i]) | ((uintptr_t)tt.g[i]) | ((uintptr_t)tt.m[i]) | ((uintptr_t)tt.v[i]) | ((uintptr_t)tt.vh[i])) & 15) == 0) {
-      tt.wmax = T->wmax[T->wmax_cur ^ 1];      // (as optimizer_launch: the dense weights' largest |p_new| for the next step's packs)
-      tt.wmax_of = i;
-    }
-  }
-  return np;
+  StepArgs a;
+  a.kind = StepKind::Step; a.s = s; a.e1 = T->sh_e1.get(); a.rel = T->sh_rel.get(); a.lookup = lookup; a.labels = labels;
+  a.B = T->sh_B; a.L = lookup ? L : (int64_t)h->dm.E;
+  a.h_out = h_out; a.csr = csr; a.img_rows = img_rows;
+  a.plan = plan_scorer(h, T, lookup, csr, a.B);
+  return Step(h, T, a);
 }
 
 }  // namespace
@@ -2206,7 +2213,7 @@ COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, cons
   st.fwd_fcbn();
   if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
-  shard_carry_save(T, st);
+  T->shard_carry = st;      // (the StepCarry part)
   T->shard_phase = SHP_SCORE;
   return COPER_OK;
 }
@@ -2224,7 +2231,7 @@ COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_in
   hipStream_t const s = (hipStream_t)stream;
   Step st = shard_step(h, T, s, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows}, nullptr);
   if ((rc = st.grow_workspaces())) return rc;
-  shard_carry_load(T, st);
+  static_cast<StepCarry&>(st) = T->shard_carry;
   // the chunk loop over the own rows: d(pred_bias), d(ent_emb), the chunk shares of dh in ascending chunk order, the loss shares onto the zeroed sum
   if ((rc = st.score_csr())) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
@@ -2255,8 +2262,9 @@ COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* loo
   if (L > T->capL) T->capL = L;
   Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr, lookup, labels, L);
   if ((rc = st.grow_workspaces()) || (rc = ord_grow(h, T, B * (L + 1), s))) return rc;
-  shard_carry_load(T, st);
-  if ((rc = st.score_lookup_shard())) return rc;
+  static_cast<StepCarry&>(st) = T->shard_carry;
+  // the owned entries' scores, loss shares and ds, then d(pred_bias), d(ent_emb) by sorted segments over the own rows, and this shard's share of dh
+  if ((rc = st.fwd_score_loss()) || (rc = st.bwd_scorer())) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
@@ -2276,7 +2284,7 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   hipStream_t const s = (hipStream_t)stream;
   Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr);
   if ((rc = st.grow_workspaces())) return rc;
-  shard_carry_load(T, st);
+  static_cast<StepCarry&>(st) = T->shard_carry;
   // dh and the loss: the ranks' shares in ascending rank
   const int64_t nBd = st.nBd;
   const int vec = (nBd & 3) == 0 && (((uintptr_t)dh_parts | (uintptr_t)T->dh.get()) & 15) == 0;
@@ -2292,9 +2300,8 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   st.bwd_conv_filters();
   // the squared norm of this shard's table gradients, in the fixed order of the slab's fold, into its own double
   TrainTensors tt;
-  const int np = shard_tensors(h, T, 1, tt);
-  hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, -1, T->det_slab.get());
-  hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, sumsq_part, 0);
+  const int np = train_tensors(h, T, LeafSet::Tables, GradSrc::Buffers, nullptr, nullptr, false, tt);
+  sumsq_det_launch(T, s, tt, np, sumsq_part);
   COPER_HIP_TRY(h, hipGetLastError());
   T->step += 1;
   T->shard_phase = SHP_APPLY;
@@ -2310,24 +2317,18 @@ COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts
   if (G > TG_SUMSQ_SLOTS - 1) return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_apply: more shards than squared-norm slots (63)");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  const coper_train_config& tc = T->cfg;
   h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
   // (the slots are zero since the forward call's zero list: nothing of a deterministic step adds to them)
+  // (the looked-up table's rows by the forward call's snapshot: an evaluation may have grouped since)
   double* const ssq = T->red_layout().sumsq_slots();
   TrainTensors tt;
-  int np = shard_tensors(h, T, 0, tt);
-  hipLaunchKernelGGL(k_tr_sumsq<true>, dim3(512, (unsigned)np), dim3(256), 0, s, tt, -1, T->det_slab.get());
-  hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, (int64_t)512 * np, ssq, 0);
+  int np = train_tensors(h, T, LeafSet::Small, GradSrc::Buffers, nullptr, T->step_rel_count.get(), false, tt);
+  sumsq_det_launch(T, s, tt, np, ssq);
   hipLaunchKernelGGL(k_shard_place_sumsq, dim3(1), dim3(64), 0, s, sumsq_parts, (int)G, ssq);
-  np = shard_tensors(h, T, -1, tt);
-  const float lr_t = (float)((double)tc.learning_rate * std::sqrt(1.0 - T->b2p) / (1.0 - T->b1p));
-  hipLaunchKernelGGL(k_tr_amsgrad, dim3(2048, (unsigned)np), dim3(256), 0, s, tt, (const double*)ssq, T->red_layout().total_sumsq(), tc.clip_norm, lr_t,
-                     tc.beta1, tc.beta2, tc.epsilon, 1.0);
+  np = train_tensors(h, T, LeafSet::All, GradSrc::Buffers, nullptr, T->step_rel_count.get(), true, tt);      // (the only table of this call that carries wmax)
+  amsgrad_launch(T, s, tt, np, 1.0);
   COPER_HIP_TRY(h, hipGetLastError());
-  T->b1p *= tc.beta1;
-  T->b2p *= tc.beta2;
-  T->wmax_cur ^= 1;
-  T->wmax_valid = tt.wmax != nullptr;
+  finish_update(T, tt.wmax != nullptr);
   T->shard_phase = SHP_FORWARD;
   return COPER_OK;
 }

@@ -1,8 +1,8 @@
 // Entity-sharded 1-vs-all training (include/coper_hip.h "Entity-sharded training"): the kernels that only the sharded step
 // launches.  Deterministic by construction: no float atomics, one writer per element, every sum in one order that does not depend on
 // the route (16-byte or scalar) that loads its addends.  The score phase itself is Step::score_csr over the handle's own rows, or
-// (sampled labels) Step::score_lookup_shard: the SHARD forms of the sampled-scorer kernels in train_kernels.h and
-// k_ord_reduce over the own rows' range.
+// (sampled labels) the sampled scorer (Step::fwd_score_loss + bwd_scorer) on a plan that names the own rows: the SHARD forms
+// of the sampled-scorer kernels in train_kernels.h and k_ord_reduce over the own rows' range.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
