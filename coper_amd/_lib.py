@@ -135,6 +135,7 @@ PROTOTYPES = {
                                      C.POINTER(C.c_double), C.POINTER(_I64)]),
     "coper_train_defer_rows": (C.c_int, [_P, C.c_int32, _P]),
     "coper_train_rows_deferred": (C.c_int, [_P]),
+    "coper_train_rows_updates": (_I64, [_P]),
     "coper_train_order_rows": (C.c_int, [_P, C.c_int32, _P]),
     "coper_train_rows_ordered": (C.c_int, [_P]),
     "coper_train_sync_rows": (C.c_int, [_P, _P]),

@@ -38,6 +38,11 @@
 //   the sampled scorer below over the handle's row range) | _backward | _apply -- over the phases below,
 //   with the caller's exchanges between them (input rows, the shards' shares of dh and the loss, their squared norms).  A deterministic
 //   state only; kernels of its own in train_shard.h.  Every other entry point behaves as it did.
+//   Deferred rows on a shard: coper_train_defer_rows on such a state, between steps; the row state is per LOCAL row.  The
+//   four calls branch on the mode in the host code below: the gather returns rows as of the current update (k_shard_gather_current), the
+//   forward call re-zeroes the list of the step before, the sampled score call sorts first, takes the owned run of the heads as its list
+//   (k_shard_list_owned) and catches it up, the backward call's squared norm and the apply call's table update run over that list.  With
+//   the mode off a sharded step launches what it launched.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 //   What a call is (StepKind) and which route its scorer takes (ScorerPlan: label form, table-gradient route, dh route, the owned row
@@ -235,9 +240,12 @@ struct TrainState {
   // sh_e1 / sh_rel: the batch's ids as the forward call saw them (the backward call has no id arguments); sh_iota: 0 .. B - 1, the row
   // numbers of the gathered input rows.  shard_carry: what the forward phases hand to the backward ones across the calls.  sh_labels: the
   // labels the step's loss is a mean over, as the score call that ran counts them (B num_ent: 1-vs-all; B L: sampled).
+  // Deferred rows on a shard: the row state above is per LOCAL row; sh_L: the L of the sampled score call (the backward call's
+  // bound of the list, min(B (L + 1), n_local)).
   bool sharded = false;
   int shard_phase = 0;
-  int64_t sh_B = 0, sh_cap = 0;
+  int64_t sh_B = 0, sh_cap = 0, sh_L = 0;
+  bool sh_stepped = false;     // a sharded step has begun on this state: the deferred-rows mode is no longer ENABLED on it (it is chosen before the first step)
   double sh_labels = 1.0;
   DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
   StepCarry shard_carry;
@@ -508,6 +516,11 @@ namespace {
 
 inline dim3 grid1d(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// the entity-sharded step's state machine (TrainState::shard_phase): the call expected next
+enum ShardPhase { SHP_FORWARD = 0, SHP_SCORE = 1, SHP_BACKWARD = 2, SHP_APPLY = 3 };
+const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr or coper_train_shard_score_lookup",
+                                   "coper_train_shard_backward", "coper_train_shard_apply"};
+
 // 1-vs-all labels as id lists (include/coper_hip.h, coper_train_step_csr); indptr == nullptr: the dense-label call
 struct CsrLabels {
   const int64_t *indptr = nullptr, *idx = nullptr, *row = nullptr;
@@ -600,13 +613,15 @@ struct SideJoin {
 };
 
 // ---- deferred rows: what the row kernels take (train_rows.h)
+// the rows of ent_emb / pred_bias the state holds: num_ent, or the shard's own (the mode's state is per LOCAL row there)
+inline int64_t rows_held(const coper_handle* h, const TrainState* T) { return T->sharded ? (int64_t)h->dm.n_local : (int64_t)h->dm.E; }
 static RowTables row_tables(const coper_handle* h, const TrainState* T) {
   const TrainParam &e = *T->lv.ent_emb, &b = *T->lv.pred_bias;
   RowTables t;
   t.p = e.p; t.g = e.g; t.m = e.m; t.v = e.v; t.vh = e.vh;
   t.bp = b.p; t.bg = b.g; t.bm = b.m; t.bv = b.v; t.bvh = b.vh;
   t.word = T->rows_word;
-  t.E = h->dm.E;
+  t.E = rows_held(h, T);
   t.d = h->dm.d;
   t.vec = (h->dm.d & 3) == 0 && ((((uintptr_t)t.p) | ((uintptr_t)t.g) | ((uintptr_t)t.m) | ((uintptr_t)t.v) | ((uintptr_t)t.vh)) & 15) == 0;
   return t;
@@ -633,7 +648,7 @@ static RowCatchUp row_catch_up_args(const TrainState* T) {
 // as long as the power is a normal double -- a function of the powers (what coper_train_powers restores), not of how many additions
 // led there, so handles with different histories catch rows up to the same bits.  Once a power has underflowed the sum carries on.
 static void rows_log2_from_powers(TrainState* T) {
-  if (!T->rows_ordered) return;
+  if (!T->rows_ordered && !T->sharded) return;      // (a sharded state's sampled call is always ordered: the same rule, so a shard [0, num_ent) is that handle)
   if (T->b1p >= 1e-290) T->rows_l2b1p = std::log2(T->b1p);
   if (T->b2p >= 1e-290) T->rows_l2b2p = std::log2(T->b2p);
 }
@@ -644,9 +659,9 @@ inline dim3 rows_grid(int64_t rows) { return dim3((unsigned)std::min<int64_t>(st
 // "train.rows.<kernel>" per launch of a row kernel
 inline void prof_count(coper_handle* h, const std::string& what, int64_t n = 1) { if (h->profile) h->timers[what].launches += n; }
 
-// One pass over E: every row of ent_emb / pred_bias and their slots current (k_rows_sync; a row with gap 0 is not written).
+// One pass over E (a shard: its own rows): every row of ent_emb / pred_bias and their slots current (k_rows_sync; a row with gap 0 is not written).
 static int rows_sync_launch(coper_handle* h, TrainState* T, hipStream_t s) {
-  hipLaunchKernelGGL(k_rows_sync, rows_grid(h->dm.E), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T));
+  hipLaunchKernelGGL(k_rows_sync, rows_grid(rows_held(h, T)), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T));
   prof_count(h, "train.rows.sync");
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
@@ -655,7 +670,7 @@ static int rows_sync_launch(coper_handle* h, TrainState* T, hipStream_t s) {
 static int rows_wrap_guard(coper_handle* h, TrainState* T, hipStream_t s) {
   if (T->rows_now < 0x7ffffff0) return COPER_OK;
   if (int rc = rows_sync_launch(h, T, s)) return rc;
-  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * (size_t)h->dm.E, s));
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_word, 0, sizeof(int32_t) * (size_t)rows_held(h, T), s));
   T->rows_now = 0;
   return COPER_OK;
 }
@@ -1034,6 +1049,23 @@ struct Step : StepArgs, StepCarry {
     rows_list = T->rows_list[cur];
     rows_count = T->rows_count + cur;
     hipLaunchKernelGGL(k_rows_catch_up, rows_grid(n), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T), rows_list, rows_count);
+    prof_count(h, "train.rows.catch_up");
+  }
+  // The same on a shard, in front of the sampled scorer: the sort and the heads over ALL B (L + 1) ids (k_ord_reduce reads
+  // them as with the mode off), the owned run of the heads as local rows into the free list with their claim bits, those rows current.
+  void shard_rows_list_catch_up() {
+    const int cur = T->rows_prev ^ 1;
+    const int64_t n = B * (L + 1), most = std::min<int64_t>(n, plan.n);
+    order_rows(T->ord_list.get(), T->ord_count.get(), nullptr);
+    hipLaunchKernelGGL(k_shard_list_owned, dim3((unsigned)std::min<int64_t>(std::max<int64_t>((most + 255) / 256, 1), 1024)), dim3(256), 0, s,
+                       (const int32_t*)T->ord_list.get(), (const int32_t*)T->ord_count.get(), plan.lo, plan.n, T->rows_list[cur].get(), T->rows_count + cur,
+                       T->rows_claim.get());
+    prof_count(h, "train.rows.list_owned");
+    T->rows_prev = cur;
+    T->rows_list_unsorted = false;
+    rows_list = T->rows_list[cur];
+    rows_count = T->rows_count + cur;
+    hipLaunchKernelGGL(k_rows_catch_up, rows_grid(most), dim3(256), 0, s, row_tables(h, T), row_catch_up_args(T), rows_list, rows_count);
     prof_count(h, "train.rows.catch_up");
   }
   // ---- ordered rows: the B L lookup ids and the B e1 ids in ascending (id, b, l) -- the stable sort -- then the segment
@@ -1814,11 +1846,17 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_defer_rows: call coper_train_init first");
   if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_defer_rows: enable is 0 or 1");
-  if (T->sharded)
-    return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: an entity-sharded state (coper_train_init_sharded) trains 1-vs-all, a gradient in every row");
-  if (enable && T->det && !T->rows_ordered)      // (ordered rows put both in order: coper_train_order_rows)
+  // (an entity-sharded state, DESIGN 6.11: between steps only -- the list of a step is built, caught up, summed and updated across its calls)
+  if (T->sharded && T->shard_phase != SHP_FORWARD)
+    return fail(h, COPER_ESTATE, std::string("coper_train_defer_rows: inside an entity-sharded step: the next call of this step is ") + kShardCall[T->shard_phase]);
+  if (enable && T->det && !T->rows_ordered && !T->sharded)      // (ordered rows put both in order: coper_train_order_rows; a sharded state's sampled call is always ordered)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: a deterministic state: the unique-row list and the atomic scorer backward are unordered");
   if ((enable != 0) == T->rows_deferred) return COPER_OK;
+  // (an entity-sharded state chooses the mode before its first step -- train_init's flag; leaving it is served at any step boundary.
+  //  Entering it on a state that has stepped is not built, and stays the refusal it was)
+  if (enable && T->sharded && T->sh_stepped)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: an entity-sharded state (coper_train_init_sharded) that has made a step: the mode is "
+                                       "enabled before the first step of the state (a new coper_train_init_sharded starts one)");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
   if (!enable) {      // every row current, then the dense path again (it zeroes the gradient buffers whole; the row state is rebuilt at the next enable)
@@ -1827,7 +1865,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
     T->rows_pending_clear();      // (the dense step zeroes the two buffers whole: a pending row gradient is gone)
     return COPER_OK;
   }
-  const size_t E = (size_t)h->dm.E;
+  const size_t E = (size_t)rows_held(h, T);      // (a shard: a word and a claim bit per OWNED row)
   int rc;
   if ((rc = T->rows_word.ensure(h, E, "deferred-row step words")) || (rc = T->rows_claim.ensure(h, (E + 31) / 32, "deferred-row claim bits")) ||
       (rc = T->rows_count.ensure(h, 2, "deferred-row counts")) || (rc = T->rows_stats.ensure(h, 2, "deferred-row statistics")))
@@ -1852,6 +1890,13 @@ COPER_API int coper_train_rows_deferred(const coper_handle* h) {
   if (!h) return -COPER_EINVAL;
   const TrainState* T = (const TrainState*)h->train;
   return T ? (T->rows_deferred ? 1 : 0) : -COPER_ESTATE;
+}
+
+// the updates made since the mode was enabled (what the rows' step words count in); 0 with the mode off
+COPER_API int64_t coper_train_rows_updates(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? (T->rows_deferred ? (int64_t)T->rows_now : 0) : -COPER_ESTATE;
 }
 
 // ---- ordered rows (include/coper_hip.h, "Ordered rows")
@@ -1898,7 +1943,8 @@ COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, in
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
   COPER_HIP_TRY(h, hipMemsetAsync(T->rows_stats, 0, 2 * sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(k_rows_stats, dim3((unsigned)std::min<int64_t>((h->dm.E + 255) / 256, 4096)), dim3(256), 0, s, T->rows_word.get(), (int64_t)h->dm.E,
+  const int64_t held = rows_held(h, T);      // (a shard: over its own rows)
+  hipLaunchKernelGGL(k_rows_stats, dim3((unsigned)std::min<int64_t>((held + 255) / 256, 4096)), dim3(256), 0, s, T->rows_word.get(), held,
                      T->rows_now, T->rows_stats.get());
   COPER_HIP_TRY(h, hipGetLastError());
   unsigned long long st[2] = {0, 0};
@@ -1961,6 +2007,9 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_export: call coper_train_init first");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_export: the deferred-rows mode is off (coper_train_grads_export is the dense call)");
+  if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_export: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
+                                       "_score_lookup | _backward | _apply in the deferred-rows mode too");
   if ((ids == nullptr) != (vals == nullptr)) return fail(h, COPER_EINVAL, "coper_train_rows_export: ids and vals are given or NULL together");
   if (!small && !ids) return fail(h, COPER_EINVAL, "coper_train_rows_export: nothing to export into");
   if (small && !T->rows_pending_small)
@@ -1992,6 +2041,9 @@ COPER_API int coper_train_rows_import(coper_handle* h, const int32_t* ids, const
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_import: call coper_train_init first");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_import: the deferred-rows mode is off (coper_train_defer_rows)");
+  if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_import: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
+                                       "_score_lookup | _backward | _apply in the deferred-rows mode too");
   if (n < 0 || n > 0x7fffffff || (n > 0 && (!ids || !vals)) || ((uintptr_t)ids & 3) != 0 || ((uintptr_t)vals & 3) != 0)
     return fail(h, COPER_EINVAL, "coper_train_rows_import: bad argument");
   if (!first && !T->rows_pending_table)
@@ -2025,6 +2077,9 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_apply: call coper_train_init first");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_apply: the deferred-rows mode is off (coper_train_apply is the dense call)");
+  if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_apply: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
+                                       "_score_lookup | _backward | _apply in the deferred-rows mode too");
   if (!T->rows_pending_table || (!small && !T->rows_pending_small))
     return fail(h, COPER_ESTATE, "coper_train_rows_apply: no gradients pending (no coper_train_rows_backward or import since the last update, step, forward or init)");
   if (small && (n != T->small_total || ((uintptr_t)small & 15) != 0))
@@ -2125,10 +2180,6 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
 // ---- entity-sharded training (include/coper_hip.h, "Entity-sharded training")
 namespace {
 
-enum ShardPhase { SHP_FORWARD = 0, SHP_SCORE = 1, SHP_BACKWARD = 2, SHP_APPLY = 3 };
-const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr or coper_train_shard_score_lookup",
-                                   "coper_train_shard_backward", "coper_train_shard_apply"};
-
 // the sharded state of a call `what` that the state machine expects at `phase`; null (with the status in *rc) otherwise
 static TrainState* shard_state(coper_handle* h, const char* what, int phase, int* rc) {
   TrainState* T = (TrainState*)h->train;
@@ -2139,6 +2190,19 @@ static TrainState* shard_state(coper_handle* h, const char* what, int phase, int
     return nullptr;
   }
   return T;
+}
+
+// Deferred rows on a shard: the two row lists at `need` = B (L + 1) entries or more, in front of the score call's list.  The list of the
+// step before has had its re-zero (the forward call of this step), so nothing of the old buffers is owed anything.
+static int shard_rows_grow(coper_handle* h, TrainState* T, int64_t need, hipStream_t s) {
+  if (need <= T->rows_cap) return COPER_OK;
+  int rc;
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  T->rows_cap = 0;
+  if ((rc = T->rows_list[0].alloc(h, (size_t)need, "deferred-row list")) || (rc = T->rows_list[1].alloc(h, (size_t)need, "deferred-row list"))) return rc;
+  COPER_HIP_TRY(h, hipMemsetAsync(T->rows_count, 0, 2 * sizeof(int32_t), s));
+  T->rows_cap = need;
+  return COPER_OK;
 }
 
 // a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (StepKind::Step); the
@@ -2169,10 +2233,19 @@ COPER_API int coper_train_sharded(const coper_handle* h) {
 COPER_API int coper_train_shard_gather(coper_handle* h, const int64_t* e1, int64_t B, float* rows_out, void* stream) {
   if (!h) return COPER_EINVAL;
   int rc = COPER_OK;
-  if (!shard_state(h, "coper_train_shard_gather", -1, &rc)) return rc;
+  TrainState* T = shard_state(h, "coper_train_shard_gather", -1, &rc);
+  if (!T) return rc;
   if (!e1 || !rows_out || B <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_gather: bad argument");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
-  return launch_gather_entities(h, e1, B, rows_out, (hipStream_t)stream);
+  if (!T->rows_deferred) return launch_gather_entities(h, e1, B, rows_out, (hipStream_t)stream);
+  // deferred rows: the table may hold a row several updates behind -- the row as of the current update, formed in
+  // registers; nothing of the table, the slots or the words is written
+  const RowTables t = row_tables(h, T);
+  hipLaunchKernelGGL(k_shard_gather_current, rows_grid(B), dim3(256), 0, (hipStream_t)stream, t, row_catch_up_args(T), e1, B, (int64_t)h->cfg.shard_lo,
+                     (t.vec && ((uintptr_t)rows_out & 15) == 0) ? 1 : 0, rows_out);
+  prof_count(h, "train.rows.gather_current");
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
 }
 
 COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, int64_t B, float* h_out,
@@ -2204,8 +2277,10 @@ COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, cons
   T->sh_B = B;
   Step st = shard_step(h, T, s, h_out, CsrLabels(), e1_rows);
   if ((rc = st.grow_workspaces())) return rc;
+  if (st.rows && (rc = rows_wrap_guard(h, T, s))) return rc;
   T->pending = false;
-  st.zero_accumulators();
+  st.zero_accumulators();      // (deferred rows: the two tables' gradients are left out ...)
+  if (st.rows && T->rows_cap) rows_rezero_launch(h, T, s);      // (... the rows the step before listed are zeroed, their claim bits cleared)
   if (st.lk && (rc = st.group_for_lookup())) return rc;
   st.fwd_conv_filters();
   st.fwd_conv_bn1();
@@ -2214,6 +2289,7 @@ COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, cons
   if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
   T->shard_carry = st;      // (the StepCarry part)
+  T->sh_stepped = true;
   T->shard_phase = SHP_SCORE;
   return COPER_OK;
 }
@@ -2224,6 +2300,8 @@ COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_in
   int rc = COPER_OK;
   TrainState* T = shard_state(h, "coper_train_shard_score_csr", SHP_SCORE, &rc);
   if (!T) return rc;
+  if (T->rows_deferred)      // (the phase stays "score expected": coper_train_shard_score_lookup may follow)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_score_csr: deferred-rows mode (coper_train_defer_rows): a 1-vs-all step has a gradient in every row");
   if (!lab_indptr || !lab_idx || !dh_part || !loss_part || B <= 0 || n_rows < 0 || (!lab_row && n_rows != B))
     return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: bad argument (lab_row == NULL needs n_rows == B)");
   if (B != T->sh_B) return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: B is not the forward call's");
@@ -2262,9 +2340,13 @@ COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* loo
   if (L > T->capL) T->capL = L;
   Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr, lookup, labels, L);
   if ((rc = st.grow_workspaces()) || (rc = ord_grow(h, T, B * (L + 1), s))) return rc;
+  if (st.rows && (rc = shard_rows_grow(h, T, B * (L + 1), s))) return rc;
   static_cast<StepCarry&>(st) = T->shard_carry;
+  // (deferred rows: the sort and the heads first -- the owned rows of the list are what is caught up, in front of the scorer that reads them)
+  if (st.rows) st.shard_rows_list_catch_up();
   // the owned entries' scores, loss shares and ds, then d(pred_bias), d(ent_emb) by sorted segments over the own rows, and this shard's share of dh
   if ((rc = st.fwd_score_loss()) || (rc = st.bwd_scorer())) return rc;
+  T->sh_L = L;
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
@@ -2299,9 +2381,20 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   st.bwd_conv();      // (the owned e1 rows onto what the score call stored in d(ent_emb))
   st.bwd_conv_filters();
   // the squared norm of this shard's table gradients, in the fixed order of the slab's fold, into its own double
+  if (st.rows) {
+    // deferred rows: every row off the step's list has a zero gradient -- the listed rows' squares in partial sums of ORD_SUMSQ_ROWS list
+    // positions (exact zeros behind the list's end), folded in the slab's fixed order (the slab holds them: the score call sized it)
+    const int pv = T->rows_prev;
+    const int64_t parts = std::max<int64_t>((std::min<int64_t>(st.B * (T->sh_L + 1), rows_held(h, T)) + ORD_SUMSQ_ROWS - 1) / ORD_SUMSQ_ROWS, 1);
+    hipLaunchKernelGGL(k_rows_sumsq_ord, dim3((unsigned)parts), dim3(256), 0, s, row_tables(h, T), (const int32_t*)T->rows_list[pv].get(),
+                       (const int32_t*)(T->rows_count + pv), T->det_slab.get());
+    hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, parts, sumsq_part, 0);
+    prof_count(h, "train.order.sumsq");
+  } else {
   TrainTensors tt;
   const int np = train_tensors(h, T, LeafSet::Tables, GradSrc::Buffers, nullptr, nullptr, false, tt);
   sumsq_det_launch(T, s, tt, np, sumsq_part);
+  }
   COPER_HIP_TRY(h, hipGetLastError());
   T->step += 1;
   T->shard_phase = SHP_APPLY;
@@ -2325,8 +2418,21 @@ COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts
   int np = train_tensors(h, T, LeafSet::Small, GradSrc::Buffers, nullptr, T->step_rel_count.get(), false, tt);
   sumsq_det_launch(T, s, tt, np, ssq);
   hipLaunchKernelGGL(k_shard_place_sumsq, dim3(1), dim3(64), 0, s, sumsq_parts, (int)G, ssq);
+  if (T->rows_deferred) {
+    // deferred rows: k_tr_amsgrad over the small leaves, k_rows_update over the step's list -- both read the slots as placed above (slot
+    // 0, then the G shares in index order) -- and the listed rows' words say "current as of this update"
+    const coper_train_config& tc = T->cfg;
+    const int pv = T->rows_prev;
+    np = train_tensors(h, T, LeafSet::Small, GradSrc::Buffers, nullptr, T->step_rel_count.get(), true, tt);
+    const float lr_t = amsgrad_launch(T, s, tt, np, 1.0);
+    prof_count(h, "train.amsgrad.leaves", np);
+    hipLaunchKernelGGL(k_rows_update, rows_grid(T->rows_cap), dim3(256), 0, s, row_tables(h, T), (const int32_t*)T->rows_list[pv].get(),
+                       (const int32_t*)(T->rows_count + pv), (const double*)ssq, tc.clip_norm, lr_t, tc.beta1, tc.beta2, tc.epsilon, 1.0, T->rows_now + 1);
+    prof_count(h, "train.rows.update");
+  } else {
   np = train_tensors(h, T, LeafSet::All, GradSrc::Buffers, nullptr, T->step_rel_count.get(), true, tt);      // (the only table of this call that carries wmax)
   amsgrad_launch(T, s, tt, np, 1.0);
+  }
   COPER_HIP_TRY(h, hipGetLastError());
   finish_update(T, tt.wmax != nullptr);
   T->shard_phase = SHP_FORWARD;

@@ -2,10 +2,13 @@
 // launches.  Deterministic by construction: no float atomics, one writer per element, every sum in one order that does not depend on
 // the route (16-byte or scalar) that loads its addends.  The score phase itself is Step::score_csr over the handle's own rows, or
 // (sampled labels) the sampled scorer (Step::fwd_score_loss + bwd_scorer) on a plan that names the own rows: the SHARD forms
-// of the sampled-scorer kernels in train_kernels.h and k_ord_reduce over the own rows' range.
+// of the sampled-scorer kernels in train_kernels.h and k_ord_reduce over the own rows' range.  Deferred rows on a shard:
+// the gather that returns a row as of the current update, and the owned run of the step's ordered list -- at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+
+#include "train_rows.h"
 
 namespace coper {
 namespace {
@@ -98,6 +101,82 @@ __global__ __launch_bounds__(256) void k_shard_rows_by_key(const float* __restri
 __global__ void k_shard_place_sumsq(const double* __restrict__ parts, int G, double* __restrict__ slots) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g < G) slots[1 + g] = parts[g];
+}
+
+// ---- deferred rows on a shard
+// coper_train_shard_gather in the mode: out[b] = the owned row e1[b] AS OF THE CURRENT UPDATE, although the table may hold it several
+// updates behind -- a wave per b loads p, m, v, v_hat and the row's word, forms the gap's scalars (rows_gap_scalars) and applies
+// rows_elem_catch_up to its registers: the value k_rows_catch_up would store, bit for bit.  Only `out` is written: e1 has duplicates,
+// and two waves catching the same row up in place would race.  Gap 0: the row as it stands.  A row of another shard: a zero row.
+// t: the handle's own rows (t.E of them, the first is entity `lo`).  vec: t.vec and out 16-byte aligned.
+__global__ __launch_bounds__(256) void k_shard_gather_current(RowTables t, RowCatchUp cu, const int64_t* __restrict__ e1, int64_t B, int64_t lo,
+                                                              int vec, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < B; b += (int64_t)gridDim.x * 4) {
+    const int64_t row = e1[b] - lo;      // (wave-uniform)
+    float* const dst = out + b * t.d;
+    if (row < 0 || row >= t.E) {
+      for (int q = lane; q < t.d; q += 64) dst[q] = 0.f;
+      continue;
+    }
+    const int k = cu.now - t.word[row];
+    const int64_t o = row * t.d;
+    if (k <= 0) {
+      for (int q = lane; q < t.d; q += 64) dst[q] = t.p[o + q];
+      continue;
+    }
+    double Cs, b1k, b2k;
+    rows_gap_scalars(cu, k, lane, Cs, b1k, b2k);
+    const float b1kf = (float)b1k, b2kf = (float)b2k;
+    if (vec) {
+      const float4 *p4 = (const float4*)(t.p + o), *m4 = (const float4*)(t.m + o), *v4 = (const float4*)(t.v + o), *h4 = (const float4*)(t.vh + o);
+      for (int q = lane; q < (t.d >> 2); q += 64) {
+        float4 p = p4[q], m = m4[q], v = v4[q], h = h4[q];
+        rows_elem_catch_up(p.x, m.x, v.x, h.x, Cs, b1kf, b2kf, cu.b2f, cu.eps);
+        rows_elem_catch_up(p.y, m.y, v.y, h.y, Cs, b1kf, b2kf, cu.b2f, cu.eps);
+        rows_elem_catch_up(p.z, m.z, v.z, h.z, Cs, b1kf, b2kf, cu.b2f, cu.eps);
+        rows_elem_catch_up(p.w, m.w, v.w, h.w, Cs, b1kf, b2kf, cu.b2f, cu.eps);
+        ((float4*)dst)[q] = p;
+      }
+    } else {
+      for (int q = lane; q < t.d; q += 64) {
+        float p = t.p[o + q], m = t.m[o + q], v = t.v[o + q], h = t.vh[o + q];
+        rows_elem_catch_up(p, m, v, h, Cs, b1kf, b2kf, cu.b2f, cu.eps);
+        dst[q] = p;
+      }
+    }
+  }
+}
+
+// The step's row list on a shard: glist holds the batch's unique (clamped) ids in ascending order (k_ord_heads; *gcount of them), so
+// the ids of [lo, lo + n_local) are one contiguous run of it.  Thread 0 of every workgroup finds the run by two binary searches; the
+// run goes, as LOCAL row indices, into list[0 .. *count) with the rows' local claim bits set.  An empty run: *count = 0, nothing else
+// written.  (The list's capacity is B (L + 1) >= *gcount.)
+__global__ __launch_bounds__(256) void k_shard_list_owned(const int32_t* __restrict__ glist, const int32_t* __restrict__ gcount, int64_t lo,
+                                                          int64_t n_local, int32_t* __restrict__ list, int32_t* __restrict__ count,
+                                                          unsigned* __restrict__ claim) {
+  __shared__ int run[2];
+  if (threadIdx.x == 0) {
+    const int n = *gcount;
+    auto first_at_least = [&](int64_t id) {      // the first position whose id is >= `id` (n: none)
+      int a = 0, b = n;
+      while (a < b) {
+        const int mid = a + ((b - a) >> 1);
+        if ((int64_t)glist[mid] < id) a = mid + 1; else b = mid;
+      }
+      return a;
+    };
+    run[0] = first_at_least(lo);
+    run[1] = first_at_least(lo + n_local);
+    if (blockIdx.x == 0) *count = run[1] - run[0];
+  }
+  __syncthreads();
+  const int first = run[0], last = run[1];
+  for (int64_t i = (int64_t)first + (int64_t)blockIdx.x * 256 + threadIdx.x; i < last; i += (int64_t)gridDim.x * 256) {
+    const int32_t row = (int32_t)((int64_t)glist[i] - lo);
+    list[i - first] = row;
+    atomicOr(claim + (row >> 5), 1u << (row & 31));
+  }
 }
 
 }  // namespace

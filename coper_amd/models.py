@@ -891,7 +891,11 @@ class ConvE(object):
         hold any shard of the entity table (`ConvE(..., shard=(lo, hi))`); gradients and slots of ent_emb / pred_bias exist for its rows
         only, and the step is the four train_shard_* calls, which `coper_amd.parallel.EntityShardedTrainer` drives.  1-vs-all batches
         with sparse labels and sampled batches (which always take the ordered-rows route there); train_step and the split steps are
-        refused on such a state."""
+        refused on such a state.  With deferred_rows=True as well (no ordered_rows needed; the mode is chosen here, before
+        the state's first step -- train_defer_rows(True) on a sharded state that has stepped is refused, train_defer_rows(False) is
+        served between steps): sampled steps touch only the
+        owned rows the batch names, `train_shard_gather` hands out rows as of the current update, 1-vs-all batches are refused, and the
+        registered tables are current only after a sync, as above -- over this shard's rows."""
         md = dict(self.model_descriptors)
         md.update(overrides)
         cfg = _lib.coper_train_config()
@@ -957,6 +961,14 @@ class ConvE(object):
     def train_rows_deferred(self):
         """The mode in force (coper_train_rows_deferred): 1 or 0."""
         v = self._lib.coper_train_rows_deferred(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
+
+    @property
+    def train_rows_updates(self):
+        """coper_train_rows_updates: the updates made since the deferred-rows mode was enabled (0 with the mode off)."""
+        v = self._lib.coper_train_rows_updates(self._h)
         if v < 0:
             raise _lib.CoperError(-v, "call train_init() first")
         return v

@@ -272,9 +272,18 @@ class EntityShardedTrainer(object):
 
     Nothing table-sized or logit-sized moves.  Returns the batch loss as a 1-element device tensor (per rank; a list in the
     in-process form would hold G equal values, so rank 0's is returned).  gloo, which moves host tensors only, is staged through the
-    host as `DataParallelTrainer._gather` does.  Not built: dense [B, num_ent] labels, deferred rows on a shard, the default
-    (non-deterministic) mode, a batch split over ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not
-    been measured."""
+    host as `DataParallelTrainer._gather` does.
+
+    DEFERRED ROWS (`train_init(deterministic=True, entity_sharded=True, deferred_rows=True)` on every rank): sampled steps
+    whose table work follows the batch instead of the shard's rows.  The seven steps and the three exchanges are the same; step 1 hands
+    out rows as of the current update although the table may hold them several updates behind, step 3 lists the owned rows the batch
+    names and brings them current, steps 5 and 7 take the norm and the update over that list.  Construction also compares the mode and
+    its update counter across ranks (ValueError on a mismatch); `step` raises ValueError for a sparse 1-vs-all batch in the mode;
+    `sync_rows()` brings every owned row current (the registered tables are current only then, as on a whole-table handle).  Both
+    trainer forms leave the same bytes in the mode too.
+
+    Not built: dense [B, num_ent] labels, the row-block split step on a shard, the default (non-deterministic) mode, a batch split over
+    ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not been measured."""
 
     def __init__(self, model=None, group=None, models=None):
         import torch.distributed as dist
@@ -306,7 +315,8 @@ class EntityShardedTrainer(object):
         """What must agree across ranks, and the bounds, as float64: [lo, hi, num_ent, hyper-parameters ..., beta powers, counter]."""
         b1, b2, st = C.c_double(), C.c_double(), C.c_int64()
         _lib.check(m._h, m._lib.coper_train_powers(m._h, None, None, None, C.byref(b1), C.byref(b2), C.byref(st)))
-        return [float(m.shard[0]), float(m.shard[1]), float(m.num_ent)] + [float(v) for v in m._train_cfg] + [b1.value, b2.value, float(st.value)]
+        return ([float(m.shard[0]), float(m.shard[1]), float(m.num_ent)] + [float(v) for v in m._train_cfg] + [b1.value, b2.value, float(st.value)]
+                + [float(m.train_rows_deferred), float(m.train_rows_updates)])      # (the last two: the deferred-rows mode, its update counter)
 
     def _check_ranks(self):
         mine = torch.tensor([self._describe(m) for m in self.local], dtype=torch.float64)
@@ -326,6 +336,9 @@ class EntityShardedTrainer(object):
             if r[0] != at or r[1] <= r[0]:
                 raise ValueError("EntityShardedTrainer: the shards do not tile [0, num_ent) in rank order (rank %d holds [%d, %d))" % (g, r[0], r[1]))
             at = r[1]
+            if r[-2:] != rows[0][-2:]:
+                raise ValueError("EntityShardedTrainer: rank %d differs from rank 0 in the deferred-rows mode (train_defer_rows) or in its "
+                                 "update counter" % g)
             if r[2:] != rows[0][2:]:
                 raise ValueError("EntityShardedTrainer: rank %d differs from rank 0 in seed, hyper-parameters, dropout counter or beta powers" % g)
         if at != rows[0][2]:
@@ -378,6 +391,9 @@ class EntityShardedTrainer(object):
         if not sampled and ("lab_indptr" not in batch or "e2_multi" in batch):
             raise ValueError("EntityShardedTrainer.step: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row]) or a sampled "
                              "batch (lookup_values, e2_multi [B, L]); dense e2_multi [B, num_ent] is not served")
+        if not sampled and any(m.train_rows_deferred == 1 for m in ms):
+            raise ValueError("EntityShardedTrainer.step: the models are in the deferred-rows mode, which serves sampled batches only (a 1-vs-all "
+                             "step has a gradient in every row)")
         B = len(batch["e1"])
         d = ms[0].ent_emb_size
         rows = self._exchange([m.train_shard_gather(batch["e1"]) for m in ms], reduce=True)                      # 1
@@ -394,3 +410,10 @@ class EntityShardedTrainer(object):
         for m, s in zip(ms, sq_all):
             m.train_shard_apply(s.reshape(-1))                                                                    # 7
         return losses[0]
+
+    def sync_rows(self):
+        """Deferred rows: every owned row of every local model current (`ConvE.train_sync_rows`); nothing to do with the mode off.  A
+        rank's registered ent_emb / pred_bias tensors are current only behind this, or behind one of the calls that sync by themselves."""
+        for m in self.local:
+            m.train_sync_rows()
+        return self

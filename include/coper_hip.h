@@ -722,9 +722,22 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
  *   - with the profile enabled (coper_profile_enable) the training step files counts, no times, under these names for
  *     coper_profile_read: "train.zero.<leaf>" per whole-buffer zeroing of a leaf's gradient (ent_emb, pred_bias, rel_emb and the static
  *     conv leaves), "train.sumsq.leaves" / "train.amsgrad.leaves" the tensors k_tr_sumsq / k_tr_amsgrad ran over, and
- *     "train.rows.rezero|claim|catch_up|sumsq|update|sync" per launch of a row kernel. */
+ *     "train.rows.rezero|claim|catch_up|sumsq|update|sync" per launch of a row kernel.
+ *
+ * On an entity-sharded state ("Entity-sharded training" below) the switch is accepted BETWEEN STEPS: in any phase of the
+ *   four-call step other than "forward expected" it returns COPER_ESTATE, the text names the call expected next.  The mode is ENABLED
+ *   before the state's first step (after coper_train_init_sharded; checkpointed slots and powers may be loaded before or after): on a
+ *   sharded state that has made a step, enabling returns COPER_EUNSUPPORTED as it always did there (not built; a new
+ *   coper_train_init_sharded on the handle starts a state that can take it).  Disabling is served at any step boundary.  No ordered-rows switch
+ *   is needed (the sharded sampled call is always ordered).  The row state is per LOCAL row: a word and a claim bit per owned row, the
+ *   two lists of B (L + 1) entries; coper_train_sync_rows, coper_train_row_stats and the calls above that sync by themselves work over
+ *   the handle's own rows.  What the four calls do in the mode is said there; their two kernels of their own file
+ *   "train.rows.gather_current" and "train.rows.list_owned" per launch with the profile enabled.
+ * coper_train_rows_updates(h): the updates made since the mode was enabled (what the step words count in; ranks of one sharded table
+ *   must agree on it); 0 with the mode off; -COPER_ESTATE without a training state, -COPER_EINVAL for a null handle. */
 COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stream);
 COPER_API int coper_train_rows_deferred(const coper_handle* h);
+COPER_API int64_t coper_train_rows_updates(const coper_handle* h);
 COPER_API int coper_train_sync_rows(coper_handle* h, void* stream);
 COPER_API int coper_train_row_stats(coper_handle* h, int64_t* rows_last_step, int64_t* rows_behind, int64_t* max_gap, void* stream);
 
@@ -887,10 +900,33 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  *   and every row of d(ent_emb) that no e1 of the batch names are that handle's bit for bit (ds and the segment sums are functions
  *   of the batch alone; the rows e1 names also take the conv backward's share, which depends on the association of dh).
  * On a sharded state coper_train_step*, coper_train_backward*, coper_train_forward*, coper_train_grads_export, coper_train_apply,
- *   coper_train_defer_rows and coper_train_order_rows return COPER_EUNSUPPORTED; coper_train_grad / coper_train_slot of the two tables
+ *   coper_train_rows_backward / _export / _import / _apply and coper_train_order_rows return COPER_EUNSUPPORTED (the row calls with the
+ *   deferred-rows mode off: COPER_ESTATE, as on every state); coper_train_grad / coper_train_slot of the two tables
  *   hand out the local rows, global_norm the global one.  Null pointers, G < 1, B <= 0: COPER_EINVAL.
- * Not built: deferred rows on a shard (the table's zeroing, norm and optimizer pass stay |E| / G per step, whatever the label form);
- *   the default (non-deterministic) mode; splitting the encoder's batch over ranks (needs a synchronised BN); dense [B, num_ent]
+ * Deferred rows on a shard (coper_train_defer_rows above, enabled before the state's first step): sampled steps whose table work follows the
+ *   batch, not the shard's |E| / G rows.  The four calls keep their signatures and the exchanges stay the same three:
+ *   - coper_train_shard_gather returns every owned row AS OF THE CURRENT UPDATE although the table may hold it several updates behind:
+ *     the closed-form catch-up is applied in registers and only rows_out is written (e1 has duplicates: catching up in place would
+ *     race) -- bit for bit the row a sync would leave; the table, the slots and the words keep their bytes; a row with gap 0 is
+ *     returned as it stands, a row of another shard is a zero row.  Still no part of the state machine.
+ *   - coper_train_shard_forward re-zeroes the gradient rows the step before listed (and clears their claim bits) instead of the two
+ *     buffers whole; the small leaves are zeroed as ever.
+ *   - coper_train_shard_score_lookup sorts all B (L + 1) ids FIRST; the unique ids are ascending, so the owned ones are one contiguous
+ *     run: that run, as local rows, is the step's list (an empty run: count 0, dh_part an exact zero, no word written).  The listed
+ *     rows are brought current in the table, then the scorer and the segment sums run as with the mode off.  The owned e1 rows are on
+ *     the list (their ids are in the sort), so they are current before the backward call adds the conv share to them.
+ *   - coper_train_shard_score_csr returns COPER_EUNSUPPORTED (a 1-vs-all step has a gradient in every row); the phase stays "score
+ *     expected", coper_train_shard_score_lookup may follow.
+ *   - coper_train_shard_backward: sumsq_part is the listed rows' squared norm (every other gradient row is zero), in partial sums of
+ *     COPER_ORDER_SUMSQ_ROWS list positions folded in one fixed order.
+ *   - coper_train_shard_apply: AMSGrad over the small leaves; the listed rows by the row update, which reads the same slots (slot 0,
+ *     then the G shares in index order) and writes the rows' words; the mode's update counter advances.
+ *   A shard [0, num_ent) in the mode leaves the bits of coper_train_step on a deterministic whole-table handle with ordered rows and
+ *   deferred rows on (global norm <= clip_norm; the norm itself to the last bits of a double sum).  After a sync, a row that no step
+ *   named equals that handle's row bit for bit on any sharding (a caught-up row is a function of its own words, the gap and the powers).
+ *   With the mode off a sharded step launches what it launched before the mode existed and leaves the same bits.
+ * Not built: entering the deferred-rows mode on a state that has already stepped; the row-block split step (coper_train_rows_*) on a shard; sorting the owned entries alone; the default
+ *   (non-deterministic) mode; splitting the encoder's batch over ranks (needs a synchronised BN); dense [B, num_ent]
  *   labels; a forward-only sharded call; overlap of the exchanges with compute. */
 COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg);
 COPER_API int coper_train_sharded(const coper_handle* h);

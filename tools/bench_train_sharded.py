@@ -3,6 +3,7 @@
 
     python tools/bench_train_sharded.py [--labels csr|sampled] [--shapes fb15k237_b512,synth1m_b128] [--worlds 1,2,4,8] [--reps 20]
                                         [--parent-root DIR] [--rounds 3] [--out profiles/train_sharded.json]
+    python tools/bench_train_sharded.py --labels sampled --deferred [--parent-root DIR] [--rounds 2]
 
 Shapes: FB15k-237 CoPER at B = 512, and its layers over a 1,048,583 x 200 table at B = 128 (or B = 512); ids uniform over the table.
 --labels csr (default): sparse 1-vs-all labels, about five positives per row.  --labels sampled: L = 1000 sampled ids per sample,
@@ -22,7 +23,14 @@ in a fresh child process:
 of G = 1's, the encoder phases, and the projected step of one rank before collectives (the sum of its four phases); with sampled
 labels also the score phase split as c + g / G through G = 1 and the largest G (c: what does not divide, the sort over all B (L + 1)
 ids and the launches; g: what does, the row gathers and the owned segments).  Multi-GPU scaling
-with real RCCL exchanges is NOT measured here.  One JSON document; no threshold is set on these times."""
+with real RCCL exchanges is NOT measured here.  One JSON document; no threshold is set on these times.
+--deferred (with --labels sampled): deferred rows on a shard against the same shard with the mode off.  Configurations:
+fb15k237_b512 and synth1m_b512 as rank 0 of 1, synth10m_b512 (10,000,000 x 256) as rank 0 of 8 (1.25M rows); per configuration and
+round a process each for this build with the mode off, the parent build (--parent-root) with the mode off, and this build with the mode
+on -- the same clock and the same emulated rank as above, and the gather call (which the mode replaces by a kernel of its own) timed
+as a fifth phase in front of the four.  The summary pools the rounds (median of the processes' medians, their extremes) and says per
+configuration whether the mode-on step lies wholly below the mode-off step, the ratio of the medians, and whether this build's
+mode-off median lies inside the parent's [min, max].  Default output profiles/train_sharded_deferred.json."""
 import argparse
 import json
 import os
@@ -32,7 +40,9 @@ import sys
 ROOT = os.environ.get("COPER_BENCH_ROOT") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-SHAPES = {"fb15k237_b512": dict(B=512), "synth1m_b128": dict(B=128, num_ent=1048583), "synth1m_b512": dict(B=512, num_ent=1048583)}
+SHAPES = {"fb15k237_b512": dict(B=512), "synth1m_b128": dict(B=128, num_ent=1048583), "synth1m_b512": dict(B=512, num_ent=1048583),
+          "synth10m_b512": dict(B=512, workload="synth10m_cpg")}
+DEFERRED_CONFIGS = (("fb15k237_b512", 1), ("synth1m_b512", 1), ("synth10m_b512", 8))      # (shape, G): rank 0 of G is timed
 SAMPLED_L = 1000
 PHASES = ("forward", "score", "backward", "apply")
 
@@ -45,8 +55,8 @@ def _stats(ms):
 
 def _md(shape):
     from coper_amd import data as cdata
-    over = {k: v for k, v in SHAPES[shape].items() if k != "B"}
-    md = cdata.model_descriptors("fb15k237_cpg", **over)
+    over = {k: v for k, v in SHAPES[shape].items() if k not in ("B", "workload")}
+    md = cdata.model_descriptors(SHAPES[shape].get("workload", "fb15k237_cpg"), **over)
     md.update(batch_norm_train_stats=True, batch_norm_momentum=0.1, hidden_dropout=0.3, output_dropout=0.2, label_smoothing_epsilon=0.1,
               learning_rate=1e-3)
     return md
@@ -74,14 +84,14 @@ def _batches(md, B, labels, n=4):
     return out
 
 
-def child(shape, world, reps, labels):
+def child(shape, world, reps, labels, deferred=False, gather=False):
     import time
     import torch
     from coper_amd import data as cdata
     from coper_amd.models import ConvE
     md = _md(shape)
     B, E, d = SHAPES[shape]["B"], md["num_ent"], md["ent_emb_size"]
-    rec = {"shape": shape, "num_ent": E, "d": d, "B": B, "world": world, "labels": labels}
+    rec = {"shape": shape, "num_ent": E, "d": d, "B": B, "world": world, "labels": labels, "deferred_rows": bool(deferred)}
     if labels == "sampled":
         rec["L"] = SAMPLED_L
     if world:
@@ -110,17 +120,20 @@ def child(shape, world, reps, labels):
             ms.append((time.perf_counter() - t0) * 1e3)
         rec["step_ms"] = _stats(ms)
     else:
-        m.train_init(seed=1, deterministic=True, entity_sharded=True)
+        m.train_init(seed=1, deterministic=True, entity_sharded=True, **(dict(deferred_rows=True) if deferred else {}))
         rows = torch.randn((B, d), device="cuda", generator=gen) * 0.1
         dh, ls, sq = torch.empty((B, d), device="cuda"), torch.empty(1, device="cuda", dtype=torch.float64), torch.empty(1, device="cuda", dtype=torch.float64)
         dh_all = torch.randn((world, B, d), device="cuda", generator=gen) * 1e-4
         ls_all = torch.ones(world, device="cuda", dtype=torch.float64)
         sq_all = torch.full((world,), 1e-3, device="cuda", dtype=torch.float64)
-        times = {k: [] for k in PHASES + ("step",)}
+        times = {k: [] for k in PHASES + ("step",) + (("gather",) if gather else ())}
         for i in range(5 + reps):
             b = bs[i % 4]
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
             torch.cuda.synchronize()
+            if gather:      # (the call in front of the step: in the mode, the rows as of the current update)
+                ev[5].record()
+                m.train_shard_gather(b["e1"], out=dh)
             ev[0].record()
             m.train_shard_forward(b["e1"], b["rel"], rows)
             ev[1].record()
@@ -135,7 +148,11 @@ def child(shape, world, reps, labels):
                 for j, k in enumerate(PHASES):
                     times[k].append(ev[j].elapsed_time(ev[j + 1]))
                 times["step"].append(ev[0].elapsed_time(ev[4]))
+                if gather:
+                    times["gather"].append(ev[5].elapsed_time(ev[0]))
         rec["phase_ms"] = {k: _stats(v) for k, v in times.items()}
+        if deferred:
+            rec["row_stats_after"] = m.train_row_stats()
     m.close()
     print(json.dumps(rec))
 
@@ -151,9 +168,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--world", type=int, default=0)
+    ap.add_argument("--deferred", action="store_true")
+    ap.add_argument("--child-deferred", type=int, default=-1)      # (a child of --deferred: the mode on or off; the gather timed)
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.world, a.reps, a.labels)
+        return child(a.child, a.world, a.reps, a.labels, deferred=a.child_deferred == 1, gather=a.child_deferred >= 0)
+    if a.deferred:
+        return main_deferred(a)
     a.shapes = a.shapes or ("fb15k237_b512,synth1m_b512" if a.labels == "sampled" else "fb15k237_b512,synth1m_b128")
     a.out = a.out or os.path.join(ROOT, "profiles", "train_sharded_sampled.json" if a.labels == "sampled" else "train_sharded.json")
     res, stop = [], False
@@ -211,6 +232,65 @@ def main():
     doc = {"tool": "tools/bench_train_sharded.py", "labels": a.labels, "reps": a.reps,
            "clock": "single: host perf_counter around train_step + a device synchronisation; shard: device events around each of the four calls; "
                     "warm (5 steps); one process per configuration; one GPU, exchanges emulated by buffers (no collective is timed)",
+           "results": res, "summary": summary}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    open(a.out, "w").write(json.dumps(doc, indent=1) + "\n")
+    print(json.dumps(summary))
+
+
+def _pool(rs):
+    meds = sorted(x["median"] for x in rs)
+    return {"min": min(x["min"] for x in rs), "median": meds[len(meds) // 2], "max": max(x["max"] for x in rs), "process_medians": [x["median"] for x in rs]}
+
+
+def main_deferred(a):
+    if a.labels != "sampled":
+        raise SystemExit("--deferred needs --labels sampled (a 1-vs-all step has a gradient in every row)")
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_sharded_deferred.json")
+    a.rounds = a.rounds if a.rounds != 3 else 2
+    configs = [c for c in DEFERRED_CONFIGS if not a.shapes or c[0] in a.shapes.split(",")]
+    res, stop = [], False
+    for shape, world in configs:
+        modes = [("this", 0, None)] + ([("parent", 0, a.parent_root)] if a.parent_root else []) + [("this", 1, None)]
+        for build, on, root in modes * a.rounds:
+            env = dict(os.environ)
+            if root:      # the parent commit's package and library, this file's child
+                env["COPER_BENCH_ROOT"] = os.path.abspath(root)
+                env.pop("COPER_HIP_LIB", None)
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", shape, "--world", str(world), "--reps", str(a.reps), "--labels", "sampled",
+                   "--child-deferred", str(on)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+            rec = json.loads(line[-1]) if r.returncode == 0 and line else {"shape": shape, "world": world, "deferred_rows": bool(on), "failed": r.returncode,
+                                                                          "stderr": r.stderr[-400:]}
+            rec["build"] = build
+            res.append(rec)
+            print(json.dumps(rec), flush=True)
+            if r.returncode not in (0, 1):      # (a child that died of a signal: nothing more is started on the device)
+                stop = True
+                break
+        if stop:
+            break
+    summary = []
+    for shape, world in configs:
+        s = {"shape": shape, "world": world}
+        for key, build, on in (("mode_off", "this", False), ("parent_mode_off", "parent", False), ("mode_on", "this", True)):
+            rs = [r["phase_ms"] for r in res if r["shape"] == shape and "phase_ms" in r and r["build"] == build and r["deferred_rows"] == on]
+            if rs:
+                s[key] = {k: _pool([x[k] for x in rs]) for k in rs[0]}
+                s["rows"] = [r["rows"] for r in res if r["shape"] == shape and "rows" in r][0]
+        if "mode_on" in s and "mode_off" in s:
+            on, off = s["mode_on"]["step"], s["mode_off"]["step"]
+            s["mode_on_wholly_below_mode_off"] = bool(on["max"] < off["min"])
+            s["mode_off_over_mode_on"] = off["median"] / on["median"]
+            s["rows_listed_last_step"] = [r["row_stats_after"]["rows_last_step"] for r in res if r["shape"] == shape and "row_stats_after" in r][0]
+        if "mode_off" in s and "parent_mode_off" in s:
+            t, p = s["mode_off"]["step"], s["parent_mode_off"]["step"]
+            s["mode_off_median_inside_parents_range"] = bool(p["min"] <= t["median"] <= p["max"])
+        summary.append(s)
+    doc = {"tool": "tools/bench_train_sharded.py --labels sampled --deferred", "reps": a.reps, "rounds": a.rounds, "L": SAMPLED_L,
+           "clock": "device events around the gather and each of the four calls of rank 0 of G; step = the four calls; warm (5 steps); one process "
+                    "per configuration, mode and round; one GPU, exchanges emulated by buffers (no collective is timed)",
            "results": res, "summary": summary}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     open(a.out, "w").write(json.dumps(doc, indent=1) + "\n")
