@@ -153,6 +153,8 @@ PROTOTYPES = {
     "coper_train_shard_score_lookup": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "coper_train_shard_backward": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
     "coper_train_shard_apply": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "coper_train_shard_forward_lookup": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "coper_train_shard_forward_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
 }
 
 _lib = None

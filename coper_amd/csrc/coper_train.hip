@@ -558,6 +558,8 @@ struct ScorerPlan {
   size_t lds_fused = 0;         // k_tr_score_loss_dh's dynamic LDS (DhRoute::Fused)
   bool shard = false;           // an entity-sharded state: the tables are rows [lo, lo + n) of num_ent, the sampled kernels
   int64_t lo = 0, n = 0;        //   take their SHARD forms; otherwise [0, num_ent)
+  bool current = false;         // (with shard) the forward-only sharded call in the deferred-rows mode: the sampled kernels take
+                                //   their CURRENT forms -- every owned row as of the current update in registers, nothing written
   bool sampled() const { return labels == LabelForm::Sampled; }
   bool ordered() const { return table == TableGrad::Ordered; }
   // The part that looks at pointers, once the workspaces exist (ent is the caller's: nothing here follows from an allocator).
@@ -574,6 +576,9 @@ struct ScorerPlan {
     const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
     // (SHARD: the compacted entries' positions, int [L] more)
     lds_fused = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + (shard ? 2 : 1) * sizeof(int) * (size_t)L;
+    // (CURRENT: every compacted entry's C and whether it is behind, double [L] and a byte [L] more -- where that passes the 160 KB of a
+    //  workgroup the launch is refused by the caller, never served by another route: the route decides the bits)
+    if (current) lds_fused += (sizeof(double) + 1) * (size_t)L;
   }
 };
 // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE;  ordered rows: the sorted-segment route at every |E| --
@@ -1018,6 +1023,20 @@ struct Step : StepArgs, StepCarry {
     // (a coper_group_next registration, or a grouping prepared ahead, was for an evaluation pass: a training step drops both)
     h->pipe.invalidate_grouping();
   }
+  // The same for a forward-only call on a sharded state, which leaves the last step's gradients and its global norm where
+  // they are: the reduction scratch but for the norm's double, and the maximum slots the forward kernels fill -- no gradient buffer.
+  void zero_forward_scratch() {
+    ZeroList zl;
+    zl.n = 0;
+    auto add = [&](void* p, size_t bytes) { zl.p[zl.n] = p; zl.bytes[zl.n] = bytes; ++zl.n; };
+    add(red.loss(), sizeof(double));
+    add(red.total_sumsq() + 1, sizeof(double) * (red.doubles() - 2));
+    for (unsigned* slots : {T->xmax.get(), T->dtmax.get(), T->smax.get()}) add(slots, sizeof(unsigned) * TG_MAX_SLOTS);
+    hipLaunchKernelGGL(k_tr_zero_list, dim3(256, (unsigned)zl.n), dim3(256), 0, s, zl);
+    T->exp_cache.clear();
+    w_slots = T->wmax_valid ? T->wmax[T->wmax_cur].get() : nullptr;
+    h->pipe.invalidate_grouping();
+  }
   // ---- deferred rows, in front of every forward kernel: the id lists hold B (L + 1) entries
   int rows_grow() {
     const int64_t need = B * (L + 1);
@@ -1243,13 +1262,24 @@ struct Step : StepArgs, StepCarry {
     } else if (plan.shard) {
       // A sharded state (always deterministic): the SHARD forms score the entries (b, l) whose clamped id this handle holds
       // and write ds there only -- the same route by the same plan, so a shard that is the whole table leaves the whole-table step's bits.
+      // (CURRENT, DESIGN 6.12: the same two kernels with the row load that forms a row as of the current update in registers)
       if (plan.dh == DhRoute::Fused) {
         const size_t lds_sf = plan.lds_fused;
+        if (plan.current) {
+          if (lds_sf > 64 * 1024)
+            COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_score_loss_dh<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sf));
+          hipLaunchKernelGGL((k_tr_score_loss_dh<true, true, true>), dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d,
+                             (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get(), plan.lo, plan.n, row_tables(h, T), row_catch_up_args(T));
+        } else {
         if (lds_sf > 64 * 1024)
           COPER_HIP_TRY(h, hipFuncSetAttribute((const void*)k_tr_score_loss_dh<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sf));
         hipLaunchKernelGGL((k_tr_score_loss_dh<true, true>), dim3((unsigned)B), dim3(256), lds_sf, s, T->hv, ent, pred_bias, lookup, labels, dm.E, d,
                            (int)L, eps, inv_E, inv_BL, T->ds, T->dh, T->det_slab.get(), plan.lo, plan.n);
-      } else
+        }
+      } else if (plan.current)
+        hipLaunchKernelGGL((k_tr_score_loss<true, true, true>), dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E,
+                           d, L, eps, inv_E, inv_BL, T->ds, T->det_slab.get(), plan.lo, plan.n, row_tables(h, T), row_catch_up_args(T));
+      else
         hipLaunchKernelGGL((k_tr_score_loss<true, true>), dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->hv, ent, pred_bias, lookup, labels, dm.E,
                            d, L, eps, inv_E, inv_BL, T->ds, T->det_slab.get(), plan.lo, plan.n);
     } else if (plan.dh == DhRoute::Fused) {
@@ -1270,7 +1300,14 @@ struct Step : StepArgs, StepCarry {
     }
     if (det && !one_vs_all) det_fold(1, B, red.loss(), 1);      // (the B workgroups' loss shares, in sample order)
     if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, red.loss(), 1.0 / ((double)B * (double)L), loss_out);
-    if (!one_vs_all && pred_out)
+    if (!one_vs_all && pred_out && plan.shard) {      // (coper_train_shard_forward_lookup's pred_part: the owned entries, +0.f elsewhere)
+      if (plan.current)
+        hipLaunchKernelGGL(k_tr_scores_out_shard<true>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, pred_bias, lookup, dm.E, d, L, pred_out, plan.lo,
+                           plan.n, row_tables(h, T), row_catch_up_args(T));
+      else
+        hipLaunchKernelGGL(k_tr_scores_out_shard<false>, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, pred_bias, lookup, dm.E, d, L, pred_out, plan.lo,
+                           plan.n, RowTables(), RowCatchUp());
+    } else if (!one_vs_all && pred_out)
       hipLaunchKernelGGL(k_tr_scores_out, dim3((unsigned)B), dim3(256), 0, s, T->hv, ent, pred_bias, lookup, dm.E, d, L, pred_out);
     if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)nBd, hipMemcpyDeviceToDevice, s));
     return COPER_OK;
@@ -1304,7 +1341,7 @@ struct Step : StepArgs, StepCarry {
       if ((rc = tg_matmul(h, T, s, MmView{T->hv, tg_idx(d), tg_idx(1), false}, B, MmView{ent_c, tg_idx(d), tg_idx(1), false}, w, d, T->Sd,
                           tg_idx(w), tg_idx(1))))
         return rc;
-      if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);      // (never sharded)
+      if (pred_out) hipLaunchKernelGGL(k_tr_add_bias_out_cols, grid1d(B * w), dim3(256), 0, s, T->Sd, pred_bias + c0, w, B * w, E, pred_out + c0);      // (sharded: coper_train_shard_forward_csr's pred_local, row stride n_local)
       const int64_t n_stretch = (w + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH;
       const int vec = (w & 3) == 0 && (((uintptr_t)T->Sd.get() | (uintptr_t)(pred_bias + c0)) & 15) == 0;
       if (det) {      // (a later chunk's shares onto the earlier chunks' sum: chunk order)
@@ -2437,6 +2474,76 @@ COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts
   finish_update(T, tt.wmax != nullptr);
   T->shard_phase = SHP_FORWARD;
   return COPER_OK;
+}
+
+// ---- forward-only calls on a sharded state (include/coper_hip.h): coper_train_forward / _csr restricted to the handle's
+// rows, in one call between steps.  Nothing of the state moves: no variable, moving statistic, gradient, slot, counter, row word or list.
+static int shard_forward_only(coper_handle* h, const char* what, const bool sampled, const int64_t* e1, const int64_t* rel, const float* e1_rows, const int32_t* lookup,
+                              const float* labels, int64_t L, const CsrLabels& csr, int64_t B, double* loss_part, float* pred, float* h_out,
+                              void* stream) {
+  if (!h) return COPER_EINVAL;
+  int rc = COPER_OK;
+  TrainState* T = shard_state(h, what, SHP_FORWARD, &rc);
+  if (!T) return rc;
+  const std::string w(what);
+  if (!sampled && T->rows_deferred)
+    return fail(h, COPER_EUNSUPPORTED, w + ": deferred-rows mode (coper_train_defer_rows): 1-vs-all scores read every row; " +
+                                       "coper_train_shard_forward_lookup serves the mode");
+  if (!e1 || !rel || !e1_rows || !loss_part || B <= 0) return fail(h, COPER_EINVAL, w + ": bad argument");
+  if (sampled) {
+    if (!lookup || !labels || L <= 0) return fail(h, COPER_EINVAL, w + ": bad argument");
+    if (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff) return fail(h, COPER_EINVAL, w + ": B * (L + 1) ids and num_ent must fit 31 bits");
+  } else if (!csr.indptr || !csr.idx || csr.n_rows < 0 || (!csr.row && csr.n_rows != B))
+    return fail(h, COPER_EINVAL, w + ": bad argument (lab_row == NULL needs n_rows == B)");
+  if (B * ((h->dm.n_local + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff) return fail(h, COPER_EINVAL, w + ": batch too large for the loss kernel's grid");
+  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, w + ": batch too large for the dropout counter");
+  if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
+    return fail(h, COPER_EUNSUPPORTED, w + ": deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  if (B > T->sh_cap) {      // (the row numbers of the gathered input rows: as coper_train_shard_forward grows them)
+    COPER_HIP_TRY(h, hipStreamSynchronize(s));
+    T->sh_cap = 0;
+    if ((rc = T->sh_e1.alloc(h, (size_t)B, "sharded step ids")) || (rc = T->sh_rel.alloc(h, (size_t)B, "sharded step ids")) ||
+        (rc = T->sh_iota.alloc(h, (size_t)B, "sharded step ids")))
+      return rc;
+    T->sh_cap = B;
+    hipLaunchKernelGGL(k_shard_iota, grid1d(B), dim3(256), 0, s, T->sh_iota.get(), B);
+  }
+  StepArgs a;
+  a.kind = StepKind::Forward; a.s = s; a.e1 = e1; a.rel = rel; a.lookup = lookup; a.labels = labels;
+  a.B = B; a.L = sampled ? L : (int64_t)h->dm.E;
+  a.pred_out = pred; a.h_out = h_out; a.csr = csr; a.img_rows = e1_rows;
+  a.plan = plan_scorer(h, T, lookup, csr, B);
+  a.plan.current = sampled && T->rows_deferred;
+  Step st(h, T, a);
+  if ((rc = st.grow_workspaces())) return rc;      // (between steps the workspaces are free: scratch)
+  if (st.plan.current && st.plan.dh == DhRoute::Fused && st.plan.lds_fused > 160 * 1024)
+    return fail(h, COPER_EUNSUPPORTED, w + ": deferred-rows mode: L is too large for the fused scorer's LDS with the rows' catch-up scalars");
+  st.zero_forward_scratch();
+  if (st.lk && (rc = st.group_for_lookup())) return rc;
+  st.fwd_conv_filters();
+  st.fwd_conv_bn1();
+  if ((rc = st.fwd_dense())) return rc;
+  st.fwd_fcbn();
+  // (deferred rows: no sort, no list, no catch-up launch -- the CURRENT row loads; the list of the step before keeps its re-zero owed)
+  if ((rc = sampled ? st.fwd_score_loss() : st.score_csr())) return rc;
+  COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
+  COPER_HIP_TRY(h, hipGetLastError());
+  return COPER_OK;
+}
+
+COPER_API int coper_train_shard_forward_lookup(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const int32_t* lookup,
+                                               const float* labels, int64_t B, int64_t L, double* loss_part, float* pred_part, float* h_out,
+                                               void* stream) {
+  return shard_forward_only(h, "coper_train_shard_forward_lookup", true, e1, rel, e1_rows, lookup, labels, L, CsrLabels(), B, loss_part, pred_part, h_out, stream);
+}
+
+COPER_API int coper_train_shard_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows, const int64_t* lab_indptr,
+                                            const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, double* loss_part,
+                                            float* pred_local, float* h_out, void* stream) {
+  return shard_forward_only(h, "coper_train_shard_forward_csr", false, e1, rel, e1_rows, nullptr, nullptr, 0, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows}, B,
+                            loss_part, pred_local, h_out, stream);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include "coper_internal.h"
 #include "train_common.h"
 #include "train_gemm.h"
+#include "train_rows.h"
 
 namespace coper {
 namespace {
@@ -292,39 +293,68 @@ __global__ __launch_bounds__(256) void k_tr_fcbn_fwd(const float* __restrict__ z
 // SHARD (here and in the other sampled-scorer kernels): ent / pred_bias hold rows [sh_lo, sh_lo + sh_n) of the E-row
 // table, and only an entry whose (clamped) id lies there is served -- the same chain per entry; an entry of another shard costs no
 // row read, no store and no loss term.  Without SHARD the two bounds are not read.
-template <bool DET, bool SHARD = false>
+// CURRENT (with SHARD; the forward-only sharded call in the deferred-rows mode): the table may hold a row several updates
+// behind -- the row load forms it AS OF THE CURRENT UPDATE in registers (rows_wave_C / rows_elem_catch_up on p, m, v, v_hat and the
+// row's word: the value k_rows_catch_up would store, bit for bit) and writes nothing; a row with gap 0 is read as it stands.  The
+// waves make every trip of the entry loop whole, so that a gap's scalars are formed by 64 lanes together.
+template <bool DET, bool SHARD = false, bool CURRENT = false>
 __global__ __launch_bounds__(256) void k_tr_score_loss(const float* __restrict__ hv, const float* __restrict__ ent,
                                                        const float* __restrict__ pred_bias,
                                                        const int32_t* __restrict__ lookup, const float* __restrict__ labels,
                                                        int64_t E, int d, int64_t L, float ls_eps, float inv_E, float inv_BL,
                                                        float* __restrict__ ds, double* __restrict__ loss_acc, int64_t sh_lo = 0,
-                                                       int64_t sh_n = 0) {
+                                                       int64_t sh_n = 0, RowTables rt = RowTables(), RowCatchUp cu = RowCatchUp()) {
+  static_assert(!CURRENT || SHARD, "the CURRENT row load is a form of the SHARD kernels");
   extern __shared__ float hl[];
   __shared__ double part[256];
   const int64_t b = blockIdx.x;
   for (int k = threadIdx.x; k < d; k += 256) hl[k] = hv[b * d + k];
   __syncthreads();
   double acc = 0.0;
-  for (int64_t l = threadIdx.x; l < L; l += 256) {
-    int64_t row = lookup[b * L + l];
+  const int64_t Lw = CURRENT ? (L + 255) / 256 * 256 : L;
+  for (int64_t l = threadIdx.x; l < Lw; l += 256) {
+    int64_t row = 0;
+    [[maybe_unused]] double Cs = 0.0;
+    [[maybe_unused]] bool behind = false;
+    if constexpr (CURRENT) {
+      bool own = l < L;
+      if (own) {
+        row = lookup[b * L + l];
+        row = ((row < 0 || row >= E) ? 0 : row) - sh_lo;
+        own = row >= 0 && row < sh_n;
+      }
+      const int gap = own ? cu.now - rt.word[row] : 0;
+      behind = gap > 0;
+      Cs = rows_wave_C(cu, gap, (int)(threadIdx.x & 63));
+      if (!own) continue;
+    } else {
+    row = lookup[b * L + l];
     if (row < 0 || row >= E) row = 0;
     if constexpr (SHARD) {
       row -= sh_lo;
       if (row < 0 || row >= sh_n) continue;
+    }
     }
     const float* er = ent + row * d;
     float s = 0.f;
     if ((d & 3) == 0) {   // 16-byte loads of the gathered row; the fma chain keeps its order
       const float4* er4 = (const float4*)er;
       for (int k4 = 0; k4 < d / 4; ++k4) {
-        const float4 e = er4[k4];
+        float4 e = er4[k4];
+        if constexpr (CURRENT) { if (behind) e = rows_current4(rt, cu, row * d + 4 * k4, e, Cs); }
         s = fmaf(hl[4 * k4 + 0], e.x, s); s = fmaf(hl[4 * k4 + 1], e.y, s);
         s = fmaf(hl[4 * k4 + 2], e.z, s); s = fmaf(hl[4 * k4 + 3], e.w, s);
       }
     } else {
-      for (int k = 0; k < d; ++k) s = fmaf(hl[k], er[k], s);
+      for (int k = 0; k < d; ++k) {
+        float e = er[k];
+        if constexpr (CURRENT) { if (behind) e = rows_current1(rt, cu, row * d + k, e, Cs); }
+        s = fmaf(hl[k], e, s);
+      }
     }
-    s += pred_bias[row];
+    float pb = pred_bias[row];
+    if constexpr (CURRENT) { if (behind) pb = rows_current_bias(rt, cu, row, pb, Cs); }
+    s += pb;
     const float t = (1.f - ls_eps) * labels[b * L + l] + inv_E;                  // models.py:450
     const float as = fabsf(s);
     acc += (double)(fmaxf(s, 0.f) - s * t + log1pf(expf(-as)));                 // sigmoid cross-entropy with logits
@@ -361,12 +391,16 @@ constexpr int SF_MAX_L = 8192;       // lookup entries of a query held in LDS (3
 // rows of other shards are never requested.  A row's score chain does not depend on where in a batch the row sits, so ds[b, l] is
 // the whole-table launch's value; dh and the loss share add the owned terms in the order this kernel gives Ln entries.  A shard
 // that owns every entry compacts to the identity.  (LDS: int pos[L] behind ids.)
-template <bool DET, bool SHARD = false>
+// CURRENT (k_tr_score_loss's comment): the compaction also forms, wave by wave, C of every owned entry's gap (LDS: double
+// cnow[L] and a byte behind[L] more); the row fetch and the bias load of an entry that is behind apply it to what they loaded.
+template <bool DET, bool SHARD = false, bool CURRENT = false>
 __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restrict__ hv, const float* __restrict__ ent,
                                                           const float* __restrict__ pred_bias, const int32_t* __restrict__ lookup,
                                                           const float* __restrict__ labels, int64_t E, int d, int L, float ls_eps,
                                                           float inv_E, float inv_BL, float* __restrict__ ds, float* __restrict__ dh,
-                                                          double* __restrict__ loss_acc, int64_t sh_lo = 0, int64_t sh_n = 0) {
+                                                          double* __restrict__ loss_acc, int64_t sh_lo = 0, int64_t sh_n = 0,
+                                                          RowTables rt = RowTables(), RowCatchUp cu = RowCatchUp()) {
+  static_assert(!CURRENT || SHARD, "the CURRENT row load is a form of the SHARD kernels");
   extern __shared__ float4 sf_lds[];   // float4 [slots][d4] (the slots' dh shares at the end) | float part[RB][d4 + 1] | float g[RB] | int ids[L]
   __shared__ double red[256];
   const int64_t b = blockIdx.x;
@@ -381,6 +415,8 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
   // the query's rows, range-checked once (a row id is read by the thread that loads the row, by the thread that scores it, ...)
   int Ln = L;      // the entries the batch loop walks
   [[maybe_unused]] int* const pos = ids + L;
+  [[maybe_unused]] double* const cnow = (double*)(pos + L);      // (8-byte aligned: RB is a multiple of 4, ids and pos are 8 L bytes)
+  [[maybe_unused]] unsigned char* const behind = (unsigned char*)(cnow + L);
   if constexpr (SHARD) {
     __shared__ int wown[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -393,6 +429,12 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
         row = ((row < 0 || row >= E) ? 0 : row) - sh_lo;
       }
       const bool own = row >= 0 && row < sh_n;
+      [[maybe_unused]] int gap = 0;
+      [[maybe_unused]] double Cs = 0.0;
+      if constexpr (CURRENT) {
+        gap = own ? cu.now - rt.word[row] : 0;
+        Cs = rows_wave_C(cu, gap, lane);
+      }
       const unsigned long long om = __ballot(own);
       if (lane == 0) wown[w] = (int)__popcll(om);
       __syncthreads();
@@ -401,6 +443,10 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
       if (own) {      // (at <= l < L)
         ids[at] = (int)row;
         pos[at] = l;
+        if constexpr (CURRENT) {
+          cnow[at] = Cs;
+          behind[at] = gap > 0 ? 1 : 0;
+        }
       }
       base += wown[0] + wown[1] + wown[2] + wown[3];
       __syncthreads();
@@ -433,8 +479,12 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
   {                                                                                           \
     _Pragma("unroll") for (int u = 0; u < SF_U; ++u) {                                        \
       const int l = (l0_) + u * slots + slot;                                                 \
-      const int64_t row = ids[l < Ln ? l : Ln - 1];                                           \
+      const int lj = l < Ln ? l : Ln - 1;                                                     \
+      const int64_t row = ids[lj];                                                            \
       dst_[u] = *(const float4*)(ent + row * d + 4 * qc);                                     \
+      if constexpr (CURRENT) {                                                                \
+        if (behind[lj]) dst_[u] = rows_current4(rt, cu, row * d + 4 * qc, dst_[u], cnow[lj]); \
+      }                                                                                       \
     }                                                                                         \
   }
   const int qc = live ? q4 : 0;                                  // (threads past the last slot load, and drop, a valid address)
@@ -445,7 +495,11 @@ __global__ __launch_bounds__(256) void k_tr_score_loss_dh(const float* __restric
     const int lb = (l0_);                                                                     \
     const bool on = sr < RB && lb + sr < Ln;   /* (uniform over the tpr neighbours of a row) */ \
     const int lc = lb + sr < Ln ? lb + sr : Ln - 1;                                           \
-    const float lab = labels[b * L + at_l(lc)], pb = pred_bias[ids[lc]];                      \
+    const float lab = labels[b * L + at_l(lc)];                                               \
+    float pb = pred_bias[ids[lc]];                                                            \
+    if constexpr (CURRENT) {                                                                  \
+      if (behind[lc]) pb = rows_current_bias(rt, cu, ids[lc], pb, cnow[lc]);                  \
+    }                                                                                         \
     SF_FETCH(lb + RB, nxt_);                                                                  \
     if (live) {                                                                               \
       _Pragma("unroll") for (int u = 0; u < SF_U; ++u) {                                      \
@@ -828,7 +882,8 @@ __global__ __launch_bounds__(256) void k_tr_csr_loss(float* __restrict__ S, cons
     else atomicAdd(loss_acc, part[0]);
   }
 }
-// out[b, c0 + j] = S[b, j] + pred_bias[c0 + j]: a chunk's logits into the [B, |E|] pred_out of coper_train_forward_csr
+// out[b, c0 + j] = S[b, j] + pred_bias[c0 + j]: a chunk's logits into the [B, |E|] pred_out of coper_train_forward_csr (E: the row
+// stride of out -- the handle's own rows, n_local, on an entity shard: coper_train_shard_forward_csr's pred_local)
 __global__ __launch_bounds__(256) void k_tr_add_bias_out_cols(const float* __restrict__ S, const float* __restrict__ pred_bias_c, int64_t w,
                                                               int64_t total, int64_t E, float* __restrict__ out_c /* + c0 */) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1498,6 +1553,56 @@ __global__ __launch_bounds__(256) void k_tr_scores_out(const float* __restrict__
     float s = 0.f;
     for (int k = 0; k < d; ++k) s = fmaf(hv[b * d + k], er[k], s);
     out[b * L + l] = s + pred_bias[row];
+  }
+}
+// The SHARD form for the forward-only sharded call: the same chain for the entries (b, l) whose clamped id lies in
+// [sh_lo, sh_lo + sh_n), from the handle's own rows; an exact +0.f at every other entry -- so every element of [B, L] has one non-zero
+// addend over the ranks and their sum is exact.  CURRENT: k_tr_score_loss's comment.
+template <bool CURRENT>
+__global__ __launch_bounds__(256) void k_tr_scores_out_shard(const float* __restrict__ hv, const float* __restrict__ ent,
+                                                             const float* __restrict__ pred_bias, const int32_t* __restrict__ lookup,
+                                                             int64_t E, int d, int64_t L, float* __restrict__ out, int64_t sh_lo, int64_t sh_n,
+                                                             RowTables rt, RowCatchUp cu) {
+  const int64_t b = blockIdx.x;
+  const int64_t Lw = (L + 255) / 256 * 256;      // (CURRENT: the waves make every trip whole)
+  for (int64_t l = threadIdx.x; l < Lw; l += 256) {
+    bool own = l < L;
+    int64_t row = 0;
+    if (own) {
+      row = lookup[b * L + l];
+      row = ((row < 0 || row >= E) ? 0 : row) - sh_lo;
+      own = row >= 0 && row < sh_n;
+    }
+    [[maybe_unused]] double Cs = 0.0;
+    [[maybe_unused]] bool behind = false;
+    if constexpr (CURRENT) {
+      const int gap = own ? cu.now - rt.word[row] : 0;
+      behind = gap > 0;
+      Cs = rows_wave_C(cu, gap, (int)(threadIdx.x & 63));
+    }
+    if (l >= L) continue;
+    float s = 0.f;
+    if (own) {
+      const float* er = ent + row * d;
+      const float* hb = hv + b * d;
+      if ((d & 3) == 0) {   // 16-byte loads of the row (and of its slots); the fma chain keeps its order
+        for (int k4 = 0; k4 < d / 4; ++k4) {
+          float4 e = ((const float4*)er)[k4];
+          if constexpr (CURRENT) { if (behind) e = rows_current4(rt, cu, row * d + 4 * k4, e, Cs); }
+          const float4 h4 = ((const float4*)hb)[k4];
+          s = fmaf(h4.x, e.x, s); s = fmaf(h4.y, e.y, s); s = fmaf(h4.z, e.z, s); s = fmaf(h4.w, e.w, s);
+        }
+      } else
+      for (int k = 0; k < d; ++k) {
+        float e = er[k];
+        if constexpr (CURRENT) { if (behind) e = rows_current1(rt, cu, row * d + k, e, Cs); }
+        s = fmaf(hb[k], e, s);
+      }
+      float pb = pred_bias[row];
+      if constexpr (CURRENT) { if (behind) pb = rows_current_bias(rt, cu, row, pb, Cs); }
+      s += pb;
+    }
+    out[b * L + l] = s;
   }
 }
 __global__ __launch_bounds__(256) void k_tr_add_bias_out(const float* __restrict__ S, const float* __restrict__ pred_bias, int64_t E,

@@ -96,6 +96,45 @@ __device__ __forceinline__ void rows_elem_catch_up(float& p, float& m, float& v,
   vh = vhn;
 }
 
+// ---- a row AS OF THE CURRENT UPDATE, in registers (the CURRENT forms of the sampled scorer's row load, train_kernels.h):
+// what k_rows_catch_up would store in p, formed from p, m, v, v_hat as they stand; nothing is written.
+// C of every lane's own gap k (k <= 0: the row is current, 0 is returned and nothing is computed for it), by the wave together: the
+// gaps of the wave are served one distinct value at a time through rows_gap_scalars, so C has the bits a catch-up of the row computes.
+// EVERY lane of the wave calls this, converged.  (Rows no step has named share one gap: a wave usually serves a handful of values.)
+__device__ __forceinline__ double rows_wave_C(const RowCatchUp& cu, int k, int lane) {
+  double mine = 0.0;
+  unsigned long long todo = __ballot(k > 0);
+  while (todo != 0ull) {      // (uniform)
+    const int ku = __shfl(k, __ffsll((long long)todo) - 1, 64);
+    double Cs, b1k, b2k;
+    rows_gap_scalars(cu, ku, lane, Cs, b1k, b2k);
+    if (k == ku) mine = Cs;
+    todo &= ~__ballot(k == ku);
+  }
+  return mine;
+}
+// element(s) of a row that is behind (C from rows_wave_C of its gap): rows_elem_catch_up on copies, p kept
+__device__ __forceinline__ float rows_elem_current(float p, float m, float v, float vh, double Cs, const RowCatchUp& cu) {
+  rows_elem_catch_up(p, m, v, vh, Cs, 1.f, 1.f, cu.b2f, cu.eps);      // (the powers of the gap scale m and v only)
+  return p;
+}
+// p = four elements of ent_emb at float offset o (a multiple of 4; the slots are 16-byte aligned)
+__device__ __forceinline__ float4 rows_current4(const RowTables& t, const RowCatchUp& cu, int64_t o, float4 p, double Cs) {
+  const float4 m = *(const float4*)(t.m + o), v = *(const float4*)(t.v + o), h = *(const float4*)(t.vh + o);
+  p.x = rows_elem_current(p.x, m.x, v.x, h.x, Cs, cu);
+  p.y = rows_elem_current(p.y, m.y, v.y, h.y, Cs, cu);
+  p.z = rows_elem_current(p.z, m.z, v.z, h.z, Cs, cu);
+  p.w = rows_elem_current(p.w, m.w, v.w, h.w, Cs, cu);
+  return p;
+}
+__device__ __forceinline__ float rows_current1(const RowTables& t, const RowCatchUp& cu, int64_t o, float p, double Cs) {
+  return rows_elem_current(p, t.m[o], t.v[o], t.vh[o], Cs, cu);
+}
+// pred_bias[row] of a row that is behind
+__device__ __forceinline__ float rows_current_bias(const RowTables& t, const RowCatchUp& cu, int64_t row, float bp, double Cs) {
+  return rows_elem_current(bp, t.bm[row], t.bv[row], t.bvh[row], Cs, cu);
+}
+
 // a wave brings `row` current (gap k > 0): ent_emb's row by its lanes, pred_bias's element by lane 0; then the step word
 __device__ __forceinline__ void rows_catch_up(const RowTables& t, const RowCatchUp& cu, int64_t row, int k, int lane) {
   double Cs, b1k, b2k;

@@ -4,6 +4,8 @@
 // (sampled labels) the sampled scorer (Step::fwd_score_loss + bwd_scorer) on a plan that names the own rows: the SHARD forms
 // of the sampled-scorer kernels in train_kernels.h and k_ord_reduce over the own rows' range.  Deferred rows on a shard:
 // the gather that returns a row as of the current update, and the owned run of the step's ordered list -- at the end of this file.
+// The forward-only calls launch nothing of this file: their kernels are the SHARD / CURRENT forms in train_kernels.h
+// (k_tr_scores_out_shard among them) over the row helpers of train_rows.h (rows_wave_C, rows_current4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1070,6 +1070,43 @@ class ConvE(object):
             _lib.check(self._h, self._lib.coper_set_x3_ent_absmax(self._h, 0.0))
             self._x3_absmax = None
 
+    def train_shard_forward_only(self, batch, e1_rows, want_predictions=False, want_h=False):
+        """coper_train_shard_forward_lookup / _csr: `train_forward` restricted to this shard's rows, in one call between steps, with
+        nothing written (include/coper_hip.h, "Forward-only calls").  `batch` as `EntityShardedTrainer.step` takes it (the
+        label form is picked the same way); `e1_rows` [B, d] the summed `train_shard_gather` of every rank.  Returns
+        `(loss_part, pred or None, h or None)`: loss_part float64 [1], this shard's unnormalised sum; pred float32 [B, L] with the logits
+        of the owned entries and +0.0 elsewhere (sampled), or [B, n_local], the logits of the own columns (1-vs-all); h float32 [B, d]."""
+        e1, rel = self._ids(batch["e1"]), self._ids(batch["rel"])
+        B = e1.numel()
+        if rel.numel() != B or tuple(e1_rows.shape) != (B, self.ent_emb_size) or e1_rows.dtype != torch.float32 or not e1_rows.is_contiguous():
+            raise ValueError("train_shard_forward_only: e1, rel [B]; e1_rows a contiguous float32 [B, ent_emb_size]")
+        lv = batch.get("lookup_values", None)
+        sampled = "e2_multi" in batch and lv is not None and np.ndim(lv) == 2 and np.shape(lv)[1] > 0      # (data.py: [B, 0] means 1-vs-all)
+        if not sampled and ("lab_indptr" not in batch or "e2_multi" in batch):
+            raise ValueError("train_shard_forward_only: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row]) or a sampled "
+                             "batch (lookup_values, e2_multi [B, L]); dense e2_multi [B, num_ent] is not served")
+        self._sync_parameters()
+        loss_part = torch.empty(1, device=self.device, dtype=torch.float64)
+        hv = torch.empty((B, self.ent_emb_size), device=self.device, dtype=torch.float32) if want_h else None
+        if sampled:
+            lookup = self._ids(lv, torch.int32)
+            labels = batch["e2_multi"]
+            labels = (labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(labels)))
+            labels = labels.to(device=self.device, dtype=torch.float32).contiguous()
+            if labels.dim() != 2 or tuple(lookup.shape) != tuple(labels.shape) or labels.shape[0] != B:
+                raise ValueError("training batch: e1, rel [B]; lookup_values and e2_multi [B, L]")
+            pred = torch.empty(tuple(labels.shape), device=self.device, dtype=torch.float32) if want_predictions else None
+            with torch.cuda.device(self.device):
+                _lib.check(self._h, self._lib.coper_train_shard_forward_lookup(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), _ptr(lookup), _ptr(labels),
+                                                                               B, labels.shape[1], _ptr(loss_part), _ptr(pred), _ptr(hv), self._stream()))
+        else:
+            ip, ix, row, n_rows = self._csr_labels(batch, B)
+            pred = torch.empty((B, self.shard[1] - self.shard[0]), device=self.device, dtype=torch.float32) if want_predictions else None
+            with torch.cuda.device(self.device):
+                _lib.check(self._h, self._lib.coper_train_shard_forward_csr(self._h, _ptr(e1), _ptr(rel), _ptr(e1_rows), _ptr(ip), _ptr(ix), _ptr(row),
+                                                                            n_rows, B, _ptr(loss_part), _ptr(pred), _ptr(hv), self._stream()))
+        return loss_part, pred, hv
+
     def _csr_labels(self, batch, B):
         """The sparse 1-vs-all labels of a batch (`lab_indptr`, `lab_idx`, optional `lab_row`) as device int64 tensors + the table's
         row count.  Tensors already on the device pass through untouched: a loader's table goes up once, not per batch."""

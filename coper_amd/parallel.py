@@ -282,6 +282,10 @@ class EntityShardedTrainer(object):
     `sync_rows()` brings every owned row current (the registered tables are current only then, as on a whole-table handle).  Both
     trainer forms leave the same bytes in the mode too.
 
+    `forward(batch, want_predictions=False, want_h=False)` looks at a batch without an update: the loss, the train-mode logits and h
+    from one call per rank (`ConvE.train_shard_forward_only`) between the gather of 1. and an all-gather of G doubles, with nothing
+    written -- also in the deferred-rows mode, where the owned rows are read as of the current update and stay as they are in the table.
+
     Not built: dense [B, num_ent] labels, the row-block split step on a shard, the default (non-deterministic) mode, a batch split over
     ranks, overlap of the exchanges with compute; scaling with real RCCL exchanges has not been measured."""
 
@@ -290,6 +294,7 @@ class EntityShardedTrainer(object):
         if (model is None) == (models is None):
             raise ValueError("EntityShardedTrainer(model, group) or EntityShardedTrainer(models=[...])")
         self.local = list(models) if models is not None else [model]
+        self._in_process = models is not None
         if not self.local:
             raise ValueError("EntityShardedTrainer: no models")
         for m in self.local:
@@ -410,6 +415,48 @@ class EntityShardedTrainer(object):
         for m, s in zip(ms, sq_all):
             m.train_shard_apply(s.reshape(-1))                                                                    # 7
         return losses[0]
+
+    # ---- a batch looked at, nothing updated
+    def forward(self, batch, want_predictions=False, want_h=False):
+        """The loss (and on request the train-mode logits and h) of `batch` as a step on it would see them, with NOTHING written on any
+        rank: no variable, moving statistic, gradient, slot, dropout counter or deferred-rows word -- the held-out loss
+        of a sharded run.  Between steps only.  The same batch on every rank, as `step` takes it:
+
+          1. the gather and all-reduce of `step`'s 1: the [B, d] input rows;
+          2. `train_shard_forward_only` on every local model: the encoder, the scorer over the own rows, this shard's loss double;
+          3. all-gather of the G loss doubles;
+          4. only with `want_predictions` on a sampled batch: one all-reduce of [B, L] (one non-zero addend per element: exact).
+
+        Returns `(loss, pred or None, h or None)`.  loss: the doubles added in rank order times 1 / (B L) (sampled) or 1 / (B num_ent)
+        (1-vs-all), rounded to float32, a 1-element device tensor (rank 0's in the in-process form, as `step`).  Sampled predictions
+        are the full [B, L].  1-vs-all predictions are NOT exchanged (nothing logit-sized moves): each rank gets its own [B, n_local]
+        block, the in-process form the list of blocks in rank order.  h [B, d] is the same on every rank.  In the deferred-rows mode a
+        sampled batch is scored against every row as of the current update and no row is brought current in the table."""
+        ms = self.local
+        lv = batch.get("lookup_values", None)
+        sampled = "e2_multi" in batch and lv is not None and np.ndim(lv) == 2 and np.shape(lv)[1] > 0      # (data.py: [B, 0] means 1-vs-all)
+        if not sampled and ("lab_indptr" not in batch or "e2_multi" in batch):
+            raise ValueError("EntityShardedTrainer.forward: a 1-vs-all batch with sparse labels (lab_indptr, lab_idx [, lab_row]) or a sampled "
+                             "batch (lookup_values, e2_multi [B, L]); dense e2_multi [B, num_ent] is not served")
+        if not sampled and any(m.train_rows_deferred == 1 for m in ms):
+            raise ValueError("EntityShardedTrainer.forward: the models are in the deferred-rows mode, which serves sampled batches only (1-vs-all "
+                             "scores read every row)")
+        B = len(batch["e1"])
+        rows = self._exchange([m.train_shard_gather(batch["e1"]) for m in ms], reduce=True)                      # 1
+        outs = [m.train_shard_forward_only(batch, r, want_predictions, want_h) for m, r in zip(ms, rows)]         # 2
+        ls_all = self._exchange([o[0] for o in outs])                                                             # 3
+        n_labels = float(B) * float(np.shape(lv)[1] if sampled else ms[0].num_ent)
+        total = ls_all[0].reshape(-1)
+        acc = total[0:1].clone()
+        for g in range(1, self.world):      # rank order
+            acc += total[g:g + 1]
+        loss = (acc * (1.0 / n_labels)).to(torch.float32)
+        pred = None
+        if want_predictions and sampled:
+            pred = self._exchange([o[1] for o in outs], reduce=True)[0]                                           # 4
+        elif want_predictions:
+            pred = [o[1] for o in outs] if self._in_process else outs[0][1]
+        return loss, pred, outs[0][2]
 
     def sync_rows(self):
         """Deferred rows: every owned row of every local model current (`ConvE.train_sync_rows`); nothing to do with the mode off.  A

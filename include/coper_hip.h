@@ -925,9 +925,37 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  *   deferred rows on (global norm <= clip_norm; the norm itself to the last bits of a double sum).  After a sync, a row that no step
  *   named equals that handle's row bit for bit on any sharding (a caught-up row is a function of its own words, the gap and the powers).
  *   With the mode off a sharded step launches what it launched before the mode existed and leaves the same bits.
+ * Forward-only calls: coper_train_forward / coper_train_forward_csr restricted to the handle's rows -- the loss, the
+ *   train-mode logits and h of a batch with nothing written.  Each is ONE call, accepted only between steps (when the state machine
+ *   expects coper_train_shard_forward; in any other phase COPER_ESTATE, the text names the call expected next) and the phase does not
+ *   move.  One exchange in front (e1_rows, formed as for a step), at most two small ones behind (the G loss doubles; pred_part).
+ *   coper_train_shard_forward_lookup(h, e1, rel, e1_rows, lookup, labels, B, L, loss_part, pred_part, h_out, stream)
+ *   coper_train_shard_forward_csr(h, e1, rel, e1_rows, lab_indptr, lab_idx, lab_row, n_rows, B, loss_part, pred_local, h_out, stream)
+ *   - the arguments of coper_train_shard_forward and of the score call of the same label form, with their checks and their clamping of
+ *     ids (e1 and rel are read, not kept).  The train-mode encoder runs on the whole batch from e1_rows as coper_train_forward runs it:
+ *     the dropout masks of the NEXT step, batch statistics when batch_norm_train_stats is set, the moving statistics left alone.  The
+ *     scorer is the score call's, by the same plan: the per-row chains and loss terms of the step that would follow.
+ *   - loss_part (required): device double [1], this shard's unnormalised sum as the score calls hand it out; the batch loss is the sum
+ *     over ranks divided by B L (sampled) or B num_ent (1-vs-all).
+ *   - pred_part (optional): device float [B, L], the logit of every OWNED entry (the fma chain of coper_train_forward's pred_out) and an
+ *     exact +0.0f everywhere else: every element has one non-zero addend over the ranks, their sum is exact.
+ *   - pred_local (optional): device float [B, n_local], row stride n_local: the logits of the handle's own columns, local column c is
+ *     entity shard_lo + c.  Nothing logit-sized needs to be exchanged.
+ *   - h_out (optional): device float [B, d].
+ *   - nothing is written: no variable, BN moving statistic, gradient buffer or optimizer slot; the dropout counter, what a step left
+ *     for coper_train_grad (the global norm included), every deferred-rows word, claim bit and row list stay; the handle stays
+ *     prepared.  The workspaces are free between steps and serve as scratch.  A shard [0, num_ent) returns the bits of
+ *     coper_train_forward* on a deterministic whole-table handle with ordered rows; on any sharding the summed pred_part and h are
+ *     that handle's bit for bit, the loss to the association of a double sum.
+ *   - deferred rows: coper_train_shard_forward_csr returns COPER_EUNSUPPORTED.  coper_train_shard_forward_lookup scores every owned row
+ *     AS OF THE CURRENT UPDATE without writing the table: the scorer's row load applies the closed-form catch-up to ent_emb's row and
+ *     its pred_bias word in registers (as coper_train_shard_gather does for the input rows; gap 0: the row as it stands).  No sort, no
+ *     list, no catch-up launch: the list of the step before keeps the re-zero it is owed.  Stronger than coper_train_forward on a
+ *     whole-table handle, which catches rows up in place: a row caught up in two stages is rounded twice, and a monitoring call on a
+ *     shard changes no later bit of training.  (The fused scorer keeps 9 bytes more per entry in LDS there: L <= 8192 still fits.)
  * Not built: entering the deferred-rows mode on a state that has already stepped; the row-block split step (coper_train_rows_*) on a shard; sorting the owned entries alone; the default
  *   (non-deterministic) mode; splitting the encoder's batch over ranks (needs a synchronised BN); dense [B, num_ent]
- *   labels; a forward-only sharded call; overlap of the exchanges with compute. */
+ *   labels; overlap of the exchanges with compute. */
 COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg);
 COPER_API int coper_train_sharded(const coper_handle* h);
 COPER_API int coper_train_shard_gather(coper_handle* h, const int64_t* e1, int64_t B, float* rows_out, void* stream);
@@ -940,6 +968,12 @@ COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* loo
 COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts, const double* loss_parts, int32_t G, float* loss_out,
                                          double* sumsq_part, void* stream);
 COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts, int32_t G, void* stream);
+COPER_API int coper_train_shard_forward_lookup(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows,
+                                               const int32_t* lookup, const float* labels, int64_t B, int64_t L, double* loss_part,
+                                               float* pred_part, float* h_out, void* stream);
+COPER_API int coper_train_shard_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows,
+                                            const int64_t* lab_indptr, const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows,
+                                            int64_t B, double* loss_part, float* pred_local, float* h_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,12 @@ round a process each for this build with the mode off, the parent build (--paren
 on -- the same clock and the same emulated rank as above, and the gather call (which the mode replaces by a kernel of its own) timed
 as a fifth phase in front of the four.  The summary pools the rounds (median of the processes' medians, their extremes) and says per
 configuration whether the mode-on step lies wholly below the mode-off step, the ratio of the medians, and whether this build's
-mode-off median lies inside the parent's [min, max].  Default output profiles/train_sharded_deferred.json."""
+mode-off median lies inside the parent's [min, max].  Default output profiles/train_sharded_deferred.json.
+--forward: the forward-only call (`ConvE.train_shard_forward_only`, sampled labels) of the same emulated rank 0 of G,
+over the configurations of --deferred with the mode off and on, a process each: behind the 5 + --reps timed steps of the process, 5
+warm forward-only calls, then --reps of them by device events -- once for the loss alone, once with pred_part [B, L] -- beside the
+`forward` + `score` phases of the steps of the same process (their sum per step).  The summary says per configuration and mode
+whether the forward-only median lies at or below that sum's median, and their ratio.  Default output profiles/train_sharded_forward.json."""
 import argparse
 import json
 import os
@@ -84,7 +89,7 @@ def _batches(md, B, labels, n=4):
     return out
 
 
-def child(shape, world, reps, labels, deferred=False, gather=False):
+def child(shape, world, reps, labels, deferred=False, gather=False, forward_only=False):
     import time
     import torch
     from coper_amd import data as cdata
@@ -151,6 +156,21 @@ def child(shape, world, reps, labels, deferred=False, gather=False):
                 if gather:
                     times["gather"].append(ev[5].elapsed_time(ev[0]))
         rec["phase_ms"] = {k: _stats(v) for k, v in times.items()}
+        if forward_only:      # between steps: the loss alone, then with pred_part as well
+            rec["forward_plus_score_ms"] = _stats([f + s for f, s in zip(times["forward"], times["score"])])
+            for key, want in (("forward_only_ms", False), ("forward_only_pred_ms", True)):
+                ms = []
+                for i in range(5 + reps):
+                    b = bs[i % 4]
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                    m.train_shard_forward_only(b, rows, want)
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    if i >= 5:
+                        ms.append(ev[0].elapsed_time(ev[1]))
+                rec[key] = _stats(ms)
         if deferred:
             rec["row_stats_after"] = m.train_row_stats()
     m.close()
@@ -170,9 +190,13 @@ def main():
     ap.add_argument("--world", type=int, default=0)
     ap.add_argument("--deferred", action="store_true")
     ap.add_argument("--child-deferred", type=int, default=-1)      # (a child of --deferred: the mode on or off; the gather timed)
+    ap.add_argument("--forward", action="store_true")
+    ap.add_argument("--child-forward", action="store_true")       # (a child of --forward: the forward-only calls behind the steps)
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.world, a.reps, a.labels, deferred=a.child_deferred == 1, gather=a.child_deferred >= 0)
+        return child(a.child, a.world, a.reps, a.labels, deferred=a.child_deferred == 1, gather=a.child_deferred >= 0, forward_only=a.child_forward)
+    if a.forward:
+        return main_forward(a)
     if a.deferred:
         return main_deferred(a)
     a.shapes = a.shapes or ("fb15k237_b512,synth1m_b512" if a.labels == "sampled" else "fb15k237_b512,synth1m_b128")
@@ -291,6 +315,48 @@ def main_deferred(a):
     doc = {"tool": "tools/bench_train_sharded.py --labels sampled --deferred", "reps": a.reps, "rounds": a.rounds, "L": SAMPLED_L,
            "clock": "device events around the gather and each of the four calls of rank 0 of G; step = the four calls; warm (5 steps); one process "
                     "per configuration, mode and round; one GPU, exchanges emulated by buffers (no collective is timed)",
+           "results": res, "summary": summary}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    open(a.out, "w").write(json.dumps(doc, indent=1) + "\n")
+    print(json.dumps(summary))
+
+
+def main_forward(a):
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_sharded_forward.json")
+    configs = [c for c in DEFERRED_CONFIGS if not a.shapes or c[0] in a.shapes.split(",")]
+    res, stop = [], False
+    for shape, world in configs:
+        for on in (0, 1):
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", shape, "--world", str(world), "--reps", str(a.reps), "--labels", "sampled",
+                   "--child-deferred", str(on), "--child-forward"]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+            rec = json.loads(line[-1]) if r.returncode == 0 and line else {"shape": shape, "world": world, "deferred_rows": bool(on), "failed": r.returncode,
+                                                                          "stderr": r.stderr[-400:]}
+            res.append(rec)
+            print(json.dumps(rec), flush=True)
+            if r.returncode not in (0, 1):      # (a child that died of a signal: nothing more is started on the device)
+                stop = True
+                break
+        if stop:
+            break
+    summary = []
+    for r in res:
+        if "forward_only_ms" not in r:
+            continue
+        fo, fs = r["forward_only_ms"], r["forward_plus_score_ms"]
+        s = {"shape": r["shape"], "world": r["world"], "rows": r["rows"], "deferred_rows": r["deferred_rows"], "forward_only_ms": fo,
+             "forward_only_pred_ms": r["forward_only_pred_ms"], "step_forward_plus_score_ms": fs,
+             "step_forward_ms": r["phase_ms"]["forward"], "step_score_ms": r["phase_ms"]["score"],
+             "forward_only_over_forward_plus_score": fo["median"] / fs["median"],
+             "forward_only_median_at_or_below_forward_plus_score": bool(fo["median"] <= fs["median"])}
+        if "row_stats_after" in r:
+            s["row_stats"] = r["row_stats_after"]
+        summary.append(s)
+    doc = {"tool": "tools/bench_train_sharded.py --forward", "reps": a.reps, "L": SAMPLED_L,
+           "clock": "device events around one forward-only call (ConvE.train_shard_forward_only) of rank 0 of G, warm (5 calls) behind the timed steps "
+                    "of the same process; beside it the steps' forward + score phases, summed per step; one process per configuration and mode; one "
+                    "GPU, exchanges emulated by buffers (no collective is timed)",
            "results": res, "summary": summary}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     open(a.out, "w").write(json.dumps(doc, indent=1) + "\n")
