@@ -155,6 +155,12 @@ PROTOTYPES = {
     "coper_train_shard_apply": (C.c_int, [_P, _P, C.c_int32, _P]),
     "coper_train_shard_forward_lookup": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "coper_train_shard_forward_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    # synchronised batch statistics: the backward in phases
+    "coper_train_sync_begin": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, C.c_int32, _P, _I64, C.POINTER(_I64), _P, _P]),
+    "coper_train_sync_begin_csr": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I64, C.POINTER(_I64), _P, _P]),
+    "coper_train_sync_next": (C.c_int, [_P, _P, C.c_int32, _P, _I64, C.POINTER(_I64), _P]),
+    "coper_train_sync_phase": (C.c_int, [_P]),
+    "coper_train_sync_part_len": (_I64, [_P]),
 }
 
 _lib = None

@@ -43,6 +43,10 @@
 //   forward call re-zeroes the list of the step before, the sampled score call sorts first, takes the owned run of the heads as its list
 //   (k_shard_list_owned) and catches it up, the backward call's squared norm and the apply call's table update run over that list.  With
 //   the mode off a sharded step launches what it launched.
+//   Synchronised batch statistics (coper_train_sync_begin | _next): the backward of a data-parallel rank whose Conv1BN / FCBN
+//   statistics span every rank's shard of one batch -- the phases below cut where a batch-wide sum is needed (fwd_conv_sums | fwd_bn1,
+//   fwd_fcbn_sums | _apply, bwd_fcbn_sums | _apply, bwd_bn1_sums | _apply), five calls with the caller's all-gathers between them, the
+//   ranks' shares added in ascending rank (k_tr_fold_parts).  Every other entry point runs the halves back to back, as one launch list.
 // This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
 // train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
 //   What a call is (StepKind) and which route its scorer takes (ScorerPlan: label form, table-gradient route, dh route, the owned row
@@ -88,6 +92,21 @@ struct StepCarry {
   float* dxin = nullptr;
   const TrainParam* W = nullptr;      // the dense weights: row-major [rc_w * F, d] (generated), [F, d] (static) or the table (looked up)
   bool p3_packed = false;        // the projection's second view (rows f) was packed with its first
+  // ordered rows: the sorted entry indices, and the batch's unique rows with their segment offsets (Step::order_rows; null until it ran)
+  const int32_t *ord_vals = nullptr, *ord_rows = nullptr, *ord_rows_count = nullptr;
+};
+// A step whose batch statistics span several ranks, open between its calls (coper_train_sync_begin | _next): the arguments
+// of the begin call (the caller keeps the batch's buffers as they are until the step is complete or abandoned), what its phases hand on
+// (as the entity-sharded step keeps its StepCarry), and `phase`: 0 no step open, 1..4 the exchange the state waits for.
+struct SyncOpen {
+  int phase = 0;
+  bool rows = false, csr = false;
+  const int64_t *e1 = nullptr, *rel = nullptr, *lab_indptr = nullptr, *lab_idx = nullptr, *lab_row = nullptr;
+  const int32_t* lookup = nullptr;
+  const float* labels = nullptr;
+  int64_t B = 0, L = 0, n_rows = 0, B_global = 0, sample_offset = 0;
+  float* loss_out = nullptr;
+  StepCarry carry;
 };
 
 // the owner of one operand plane set of the split-16 GEMMs; the GEMM helpers take the TgPlanes it hands out
@@ -249,6 +268,10 @@ struct TrainState {
   double sh_labels = 1.0;
   DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
   StepCarry shard_carry;
+  // synchronised batch statistics (coper_train_sync_*): the open step, and [2][2 mx] doubles -- the backward sums of the whole
+  // batch as the last fold left them | this rank's FCBN backward sums (Conv1BN's own stay in their slice of `red`)
+  SyncOpen sync;
+  DevBuf<double> sync_sums;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
       if (t.name == name) return &t;
@@ -870,6 +893,9 @@ struct StepArgs {
   CsrLabels csr;                    // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
   const float* img_rows = nullptr;  // the entity-sharded step: the input images are the rows of img_rows [B, d] (the gathered e1 rows), never the table's
   ScorerPlan plan;                  // plan_scorer of the same call; its dh route once grow_workspaces has run
+  // synchronised batch statistics: the batch is rows [sample_offset, sample_offset + B) of a batch of B_stat samples that
+  // the BN statistics are taken over (0: the batch is its own) -- the dropout masks are drawn by the position in THAT batch
+  int64_t B_stat = 0, sample_offset = 0;
 };
 struct Step : StepArgs, StepCarry {
   coper_handle* const h;
@@ -891,6 +917,10 @@ struct Step : StepArgs, StepCarry {
   const uint32_t thr_h = dropout_threshold24(tc.hidden_dropout), thr_o = dropout_threshold24(tc.output_dropout), thr_c = dropout_threshold24(tc.context_rel_dropout);
   const float ks_h = 1.f / (1.f - tc.hidden_dropout), ks_o = 1.f / (1.f - tc.output_dropout), ks_c = 1.f / (1.f - tc.context_rel_dropout);
   const uint32_t step = T->step;
+  // the dropout counter of element i of a [B, n] tensor is (sample_offset + b) n + j: i plus these (0 outside a synchronised step)
+  uint32_t drop_off(int64_t n) const { return (uint32_t)(sample_offset * n); }
+  const uint32_t off_h = drop_off(dm.F_conv), off_o = drop_off(dm.d);
+  const int64_t Bn = B_stat ? B_stat : B;      // the samples the batch statistics of Conv1BN / FCBN are taken over
   const float inv_BL = (float)(1.0 / ((double)B * (double)L));
   const RedLayout red = T->red_layout();
   float *const mean1 = T->bn_row(BN1_MEAN), *const inv1 = T->bn_row(BN1_INV), *const mean2 = T->bn_row(FCBN_MEAN), *const inv2 = T->bn_row(FCBN_INV);
@@ -902,8 +932,6 @@ struct Step : StepArgs, StepCarry {
   int t_slices = 1, dx_slices = 1;   // K slices the T and dx products left for k_tr_fc_post_slices / k_tr_bn1_bwd_sums to add
   const TrainParam* sumsq_done = nullptr;   // the leaf whose squared gradient norm its own GEMM accumulated
   const int32_t *rows_list = nullptr, *rows_count = nullptr;   // deferred rows: the rows this call claimed (rows_claim_catch_up)
-  // ordered rows: the sorted entry indices, and the batch's unique rows with their segment offsets (order_rows; null until it ran)
-  const int32_t *ord_vals = nullptr, *ord_rows = nullptr, *ord_rows_count = nullptr;
   bool scorer_bwd_on_side() const { return two_streams && plan.dh == DhRoute::Fused && tg_split_k(dm.E, d, B) == 1; }
 
   int grow_workspaces() {
@@ -1137,7 +1165,7 @@ struct Step : StepArgs, StepCarry {
         ga = b.gamma->p;
         be = b.beta->p;
       }
-      hipLaunchKernelGGL(k_tr_chain_act, grid1d(tot), dim3(256), 0, s, ch.u[i], ch.st[i], ga, be, nj, tot, tc.seed, step,
+      hipLaunchKernelGGL(k_tr_chain_act, grid1d(tot), dim3(256), 0, s, ch.u[i], ch.st[i], ga, be, nj, tot, tc.seed, step, drop_off(nj),
                          dropout_stage_chain(g, i), thr_c, ks_c, ch.a[i], ch.v[i + 1]);
     }
   }
@@ -1156,23 +1184,30 @@ struct Step : StepArgs, StepCarry {
     }
   }
   // the conv, Conv1BN, ReLU, dropout -> x [B, F_conv]; concat_rel: [x | c]
-  void fwd_conv_bn1() {
+  void fwd_conv_bn1() { fwd_conv_sums(); fwd_bn1(); }
+  // ... in two halves, cut where a batch-wide sum is needed: the conv and the column sums of this call's rows | the
+  // statistics from the sums (over Bn samples) and what follows.  bn1_fwd_sums(): where the first half leaves the sums.
+  double* bn1_fwd_sums() const { return red.cs_slots(CSS_BN1_FWD); }
+  void fwd_conv_sums() {
     const size_t lds_conv = sizeof(float) * (size_t)(isz + (NT + 1) * C);
     // (sharded: the image of sample b is row b of the gathered rows)
     hipLaunchKernelGGL(k_tr_conv_fwd, dim3((unsigned)B), dim3(256), lds_conv, s, img_rows ? T->sh_iota.get() : e1, rel, img_rows ? img_rows : lv.ent_emb->p,
                        lv.rel_emb ? lv.rel_emb->p : nullptr,
                        dm.gen_conv ? nullptr : lv.conv1_weights->p, dm.gen_conv ? nullptr : lv.conv1_bias->p, img_rows ? B : (int64_t)dm.E, dm.R, d, r, dm.in_h, dm.in_w,
                        dm.stacked ? 1 : 0, C, dm.Ho, dm.Wo, T->img, ((gen || cat) && !genc) ? T->c.get() : nullptr, T->y, K_ps, kb_ps, dm.fh, dm.fw);
-    double* const cs = red.cs_slots(CSS_BN1_FWD);
+    double* const cs = bn1_fwd_sums();
     if (use_batch && det) det_col_sums(T->y, B * (int64_t)P, C, cs, DET_CS_WGS);
     else if (use_batch) {
       hipLaunchKernelGGL(k_tr_col_sums<false>, dim3(1024), dim3(256), 0, s, T->y, B * (int64_t)P, C, cs, TR_CS_SLOTS);
       hipLaunchKernelGGL(k_tr_fold_slots, dim3(1), dim3(256), 0, s, cs, 2 * C, TR_CS_SLOTS);
     }
-    hipLaunchKernelGGL(k_tr_bn_finish, dim3((C + 63) / 64), dim3(64), 0, s, cs, C, (double)B * P, use_batch, tc.batch_norm_momentum, 1 | nomov,
+  }
+  void fwd_bn1() {
+    double* const cs = bn1_fwd_sums();
+    hipLaunchKernelGGL(k_tr_bn_finish, dim3((C + 63) / 64), dim3(64), 0, s, cs, C, (double)Bn * P, use_batch, tc.batch_norm_momentum, 1 | nomov,
                        lv.bn1.mov_mean, lv.bn1.mov_var, mean1, inv1);
     hipLaunchKernelGGL(k_tr_bn1_fwd, grid1d(nBF), dim3(256), 0, s, T->y, mean1, inv1, lv.bn1.gamma->p, lv.bn1.beta->p, C, nBF, tc.seed,
-                       step, thr_h, ks_h, T->x, T->xmax);
+                       step, off_h, thr_h, ks_h, T->x, T->xmax);
     x_slots = cat ? nullptr : T->xmax.get();      // (concat_rel: the dense layer's input is another tensor)
     if (cat) hipLaunchKernelGGL(k_tr_concat, grid1d(B * F), dim3(256), 0, s, T->x, T->c, Fc, r, B * F, T->xc);
     xin = cat ? T->xc : T->x;
@@ -1190,7 +1225,7 @@ struct Step : StepArgs, StepCarry {
       // z0[b] = x[b] W[rel[b]]: one pass over the looked-up rows (B * F * d * 4 bytes), in TR_LK_NSL slices of F (deterministic partial sums)
       hipLaunchKernelGGL(k_tr_lookup_fwd, dim3((unsigned)B, TR_LK_NSL), dim3(256), sizeof(float) * (size_t)((F + TR_LK_NSL - 1) / TR_LK_NSL + 1), s,
                          T->x, W->p, rel, dm.R, F, d, TR_LK_NSL, B, T->dx /* scratch: [NSL][B][d], allocated for it */);
-      hipLaunchKernelGGL(k_tr_lookup_post, grid1d(nBd), dim3(256), 0, s, T->dx, TR_LK_NSL, lv.fc_bias->p, rel, dm.R, d, nBd, tc.seed, step, thr_o,
+      hipLaunchKernelGGL(k_tr_lookup_post, grid1d(nBd), dim3(256), 0, s, T->dx, TR_LK_NSL, lv.fc_bias->p, rel, dm.R, d, nBd, tc.seed, step, off_o, thr_o,
                          ks_o, T->z1);
       return COPER_OK;
     }
@@ -1216,7 +1251,7 @@ struct Step : StepArgs, StepCarry {
 #define COPER_FC_SLICES(NS)                                                                                                                          \
     case NS:                                                                                                                                         \
       hipLaunchKernelGGL(k_tr_fc_post_slices<NS>, grid1d(nBd), dim3(256), 0, s, T->mmP, cw, rc_w, cbv, blast->p, rc_b, d, nBd, tc.seed,              \
-                         step, thr_o, ks_o, Tf, T->z1);                                                                                              \
+                         step, off_o, thr_o, ks_o, Tf, T->z1);                                                                                              \
       break;
       switch (t_slices) {
         COPER_FC_SLICES(2) COPER_FC_SLICES(3) COPER_FC_SLICES(4) COPER_FC_SLICES(5) COPER_FC_SLICES(6) COPER_FC_SLICES(7) COPER_FC_SLICES(8)
@@ -1224,15 +1259,20 @@ struct Step : StepArgs, StepCarry {
 #undef COPER_FC_SLICES
     } else
       hipLaunchKernelGGL(k_tr_fc_post, grid1d(nBd), dim3(256), 0, s, gen ? Tf : T->z0.get(), gen ? nullptr : lv.fc_bias->p, cw, rc_w, cbv,
-                         gen ? blast->p : nullptr, rc_b, d, nBd, tc.seed, step, thr_o, ks_o, T->z1);
+                         gen ? blast->p : nullptr, rc_b, d, nBd, tc.seed, step, off_o, thr_o, ks_o, T->z1);
     return COPER_OK;
   }
 
-  void fwd_fcbn() {
-    double* const cs = red.colsum_slice(CS_FCBN);
+  void fwd_fcbn() { fwd_fcbn_sums(); fwd_fcbn_apply(); }
+  double* fcbn_fwd_sums() const { return red.colsum_slice(CS_FCBN); }
+  void fwd_fcbn_sums() {
+    double* const cs = fcbn_fwd_sums();
     if (use_batch && det) det_col_sums(T->z1, B, d, cs, 64);
     else if (use_batch) hipLaunchKernelGGL(k_tr_col_sums<false>, dim3(64), dim3(256), 0, s, T->z1, B, d, cs, 1);
-    hipLaunchKernelGGL(k_tr_bn_finish, dim3((d + 63) / 64), dim3(64), 0, s, cs, d, (double)B, use_batch, tc.batch_norm_momentum, 0 | nomov,
+  }
+  void fwd_fcbn_apply() {
+    double* const cs = fcbn_fwd_sums();
+    hipLaunchKernelGGL(k_tr_bn_finish, dim3((d + 63) / 64), dim3(64), 0, s, cs, d, (double)Bn, use_batch, tc.batch_norm_momentum, 0 | nomov,
                        lv.fcbn.mov_mean, lv.fcbn.mov_var, mean2, inv2);
     hipLaunchKernelGGL(k_tr_fcbn_fwd, grid1d(nBd), dim3(256), 0, s, T->z1, mean2, inv2, lv.fcbn.gamma->p, lv.fcbn.beta->p, d, nBd, T->hv);
   }
@@ -1442,6 +1482,15 @@ struct Step : StepArgs, StepCarry {
     hipLaunchKernelGGL(k_tr_fcbn_bwd, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d,
                        use_batch, lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
   }
+  // ... in two launches around the exchange of a synchronised step (batch statistics on): this rank's sums into `own` | dz from the sums
+  // of the whole batch, the gamma / beta gradients from `own`
+  void bwd_fcbn_sums(double* own) {
+    hipLaunchKernelGGL(k_tr_fcbn_bwd_sums, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, B, d, own);
+  }
+  void bwd_fcbn_apply(const double* all, const double* own) {
+    hipLaunchKernelGGL(k_tr_fcbn_bwd_apply, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d, (double)Bn,
+                       all, own, lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
+  }
   // dT[rho][b,:] = cw[b,rho] dz[b,:];  dP[rho][f][k] = sum_b x[b][f] dT[rho][b][k]  and
   // dx[b][f] = sum_(rho,k) dT[rho][b][k] P[rho][f][k]: two split-bf16 GEMMs, the [B, r*F] intermediate dz P2^T is never formed
   int bwd_dense_generated() {
@@ -1473,10 +1522,10 @@ struct Step : StepArgs, StepCarry {
     int rc;
     if (lk) {
       if (det) {
-        hipLaunchKernelGGL(k_tr_lookup_post_bwd<true>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o, ks_o, lv.fc_bias->g);
+        hipLaunchKernelGGL(k_tr_lookup_post_bwd<true>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, off_o, thr_o, ks_o, lv.fc_bias->g);
         det_rows_by_key(T->dz, d, 0, d, rel, dm.R, lv.fc_bias->g);
       } else
-      hipLaunchKernelGGL(k_tr_lookup_post_bwd<false>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, thr_o, ks_o, lv.fc_bias->g);
+      hipLaunchKernelGGL(k_tr_lookup_post_bwd<false>, grid1d(nBd), dim3(256), 0, s, T->dz, rel, dm.R, d, nBd, tc.seed, step, off_o, thr_o, ks_o, lv.fc_bias->g);
       const int rows_per_wg = 32;
       hipLaunchKernelGGL(k_tr_lookup_dW, dim3((unsigned)((F + rows_per_wg - 1) / rows_per_wg), (unsigned)dm.R), dim3(256), 0, s, T->x, T->dz, det ? T->det_perm.get() : h->grouping().perm,
                          h->grouping().rel_offset, h->grouping().rel_count, F, d, rows_per_wg, W->g);
@@ -1487,12 +1536,12 @@ struct Step : StepArgs, StepCarry {
     const TrainParam* const blast = gen ? lv.gen[1].proj[nh] : nullptr;
     if (det) {
       hipLaunchKernelGGL(k_tr_fc_post_bwd<true>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, cbv, gen ? blast->p : nullptr, rc_b, d, tc.seed,
-                         step, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
+                         step, off_o, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
                          gen ? T->chain[1].dv[nh].get() : nullptr);
       if (!gen) det_col_sum_f32(T->dz, d, lv.fc_bias->g.get(), s);
     } else
     hipLaunchKernelGGL(k_tr_fc_post_bwd<false>, dim3((unsigned)B), dim3(256), sizeof(float) * d, s, T->dz, cbv, gen ? blast->p : nullptr, rc_b, d, tc.seed,
-                       step, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
+                       step, off_o, thr_o, ks_o, gen ? nullptr : lv.fc_bias->g.get(), gen ? blast->g.get() : nullptr,
                        gen ? T->chain[1].dv[nh].get() : nullptr);
     if (gen) {     // (into the zeroed gradient: 8 atomics per address; deterministic mode: one thread per entry, ascending b)
       if (det) {
@@ -1526,7 +1575,7 @@ struct Step : StepArgs, StepCarry {
       const TrainLeaves::Bn& b = lv.gen[g].bn[i];
       const TrainParam* const proj = lv.gen[g].proj[i];
       const int64_t tot = B * nj;
-      hipLaunchKernelGGL(k_tr_chain_drop_bwd, grid1d(tot), dim3(256), 0, s, ch.dv[i + 1], tot, tc.seed, step, dropout_stage_chain(g, i), thr_c, ks_c,
+      hipLaunchKernelGGL(k_tr_chain_drop_bwd, grid1d(tot), dim3(256), 0, s, ch.dv[i + 1], tot, tc.seed, step, drop_off(nj), dropout_stage_chain(g, i), thr_c, ks_c,
                          ch.du[i]);
       // ReLU (+ BN) backward, in place on du; BN gamma / beta gradients
       const bool cb = dm.ctx_bn;
@@ -1538,18 +1587,20 @@ struct Step : StepArgs, StepCarry {
     }
   }
   // dropout, ReLU and Conv1BN backward on dx (the K slices of the dx product, where it left them, are added on the way)
-  void bwd_bn1() {
-    double* const colsum = red.cs_slots(CSS_BN1_BWD);
+  void bwd_bn1() { bwd_bn1_sums(); bwd_bn1_apply(bn1_bwd_sums()); }
+  double* bn1_bwd_sums() const { return red.cs_slots(CSS_BN1_BWD); }
+  void bwd_bn1_sums() {
+    double* const colsum = bn1_bwd_sums();
     const dim3 g1((unsigned)((nBF + 255) / 256 < 2048 ? (nBF + 255) / 256 : 2048));
     if (det) {      // (dx is whole: the dx product kept no K slices in this mode)
       hipLaunchKernelGGL(k_tr_bn1_bwd_sums_det, dim3(DET_CS_WGS), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, lv.bn1.beta->p, C,
-                         B * (int64_t)P, tc.seed, step, thr_h, ks_h, T->det_slab.get());
+                         B * (int64_t)P, tc.seed, step, off_h, thr_h, ks_h, T->det_slab.get());
       det_fold(2 * C, DET_CS_WGS, colsum, 0);
     } else {
 #define COPER_BN1_SUMS(NS)                                                                                                                           \
     case NS:                                                                                                                                         \
       hipLaunchKernelGGL(k_tr_bn1_bwd_sums<NS>, g1, dim3(256), 0, s, T->dx, NS ? T->mmP : nullptr, T->y, mean1, inv1,                                \
-                         lv.bn1.gamma->p, lv.bn1.beta->p, C, nBF, tc.seed, step, thr_h, ks_h, colsum, TR_CS_SLOTS);                                  \
+                         lv.bn1.gamma->p, lv.bn1.beta->p, C, nBF, tc.seed, step, off_h, thr_h, ks_h, colsum, TR_CS_SLOTS);                                  \
       break;
     switch (dx_slices > 1 ? dx_slices : 0) {
       COPER_BN1_SUMS(0) COPER_BN1_SUMS(2) COPER_BN1_SUMS(3) COPER_BN1_SUMS(4) COPER_BN1_SUMS(5) COPER_BN1_SUMS(6) COPER_BN1_SUMS(7) COPER_BN1_SUMS(8)
@@ -1557,8 +1608,11 @@ struct Step : StepArgs, StepCarry {
 #undef COPER_BN1_SUMS
     hipLaunchKernelGGL(k_tr_fold_slots, dim3(1), dim3(256), 0, s, colsum, 2 * C, TR_CS_SLOTS);
     }
-    hipLaunchKernelGGL(k_tr_bn1_bwd_apply, grid1d(nBF), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, colsum, C, nBF,
-                       (double)B * P, use_batch, lv.bn1.gamma->g, lv.bn1.beta->g);
+  }
+  // all: the sums over the positions the statistics were taken over (this call's own, or the whole batch's of a synchronised step)
+  void bwd_bn1_apply(const double* all) {
+    hipLaunchKernelGGL(k_tr_bn1_bwd_apply, grid1d(nBF), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, all, (const double*)bn1_bwd_sums(), C, nBF,
+                       (double)Bn * P, use_batch, lv.bn1.gamma->g, lv.bn1.beta->g);
   }
   // the conv backward: adds the e1 rows to dE (so the scorer's dE is joined in front of it), leaves per-query filter gradients
   void bwd_conv() {
@@ -1639,12 +1693,57 @@ int coper::train_rows_sync(coper_handle* h, void* stream, bool device_wide) {
   return COPER_OK;
 }
 
+// ---- synchronised batch statistics (include/coper_hip.h, "Synchronised batch statistics")
+namespace {
+// what coper_train_sync_begin / _csr adds to the arguments of coper_train_backward / _rows_backward
+struct SyncReq {
+  int64_t B_global, sample_offset;
+  int32_t rows;
+  double* part_out;
+  int64_t part_cap;
+  int64_t* n_out;
+};
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+// this rank's share of a batch-wide sum, ordered on the caller's stream behind the launches that formed it
+static int sync_hand_out(coper_handle* h, hipStream_t s, const double* sums, int64_t n, double* part_out, int64_t* n_out) {
+  COPER_HIP_TRY(h, hipMemcpyAsync(part_out, sums, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  *n_out = n;
+  return COPER_OK;
+}
+// the refusals of a begin call that the step's own checks do not make
+static int sync_check_begin(coper_handle* h, const TrainState* T, const SyncReq& q, int64_t B) {
+  const Dims& dm = h->dm;
+  if (q.rows != 0 && q.rows != 1) return fail(h, COPER_EINVAL, "coper_train_sync_begin: rows is 0 or 1");
+  if (!q.n_out) return fail(h, COPER_EINVAL, "coper_train_sync_begin: n_out is NULL");
+  if (B <= 0 || q.B_global <= 0 || q.B_global % B != 0)
+    return fail(h, COPER_EINVAL, "coper_train_sync_begin: B_global must be a multiple of B (even shards)");
+  if (q.sample_offset < 0 || q.sample_offset + B > q.B_global)
+    return fail(h, COPER_EINVAL, "coper_train_sync_begin: the shard [sample_offset, sample_offset + B) does not lie in [0, B_global)");
+  if (T->sharded)
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_sync_begin: an entity-sharded state (coper_train_init_sharded) replicates the encoder on the whole "
+                                       "batch: its statistics are the whole batch's already");
+  if (T->cfg.batch_norm_train_stats && dm.ctx_bn && (T->nh > 0 || T->nhc > 0))
+    return fail(h, COPER_EUNSUPPORTED, "coper_train_sync_begin: a generator with hidden layers and context_rel_use_batch_norm: its hidden BN layers take "
+                                       "batch statistics too, and synchronising them is not built");
+  const int64_t n = T->cfg.batch_norm_train_stats ? 2 * (int64_t)dm.C : 0;
+  if (n && (!q.part_out || !aligned8(q.part_out))) return fail(h, COPER_EINVAL, "coper_train_sync_begin: part_out must be an 8-byte aligned device buffer");
+  if (q.part_cap < n) return fail(h, COPER_EINVAL, "coper_train_sync_begin: part_cap is below the 2 * conv_num_channels doubles this call hands out");
+  if ((q.sample_offset + B) * (int64_t)dm.F > 0xffffffffLL)
+    return fail(h, COPER_EINVAL, "coper_train_sync_begin: (sample_offset + B) * features does not fit the dropout counter");
+  return COPER_OK;
+}
+}  // namespace
+
 static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
                            int64_t B, int64_t L, float* loss_out, void* stream, const StepKind kind, float* pred_out, float* h_out,
-                           const CsrLabels csr = CsrLabels()) {
+                           const CsrLabels csr = CsrLabels(), const SyncReq* sync = nullptr) {
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_step: call coper_train_init first");
+  if (sync) {
+    if (int rc = sync_check_begin(h, T, *sync, B)) return rc;
+    *sync->n_out = 0;
+  }
   if (csr.indptr) {      // sparse 1-vs-all labels: L is num_ent, no [B, L] matrix exists and nothing is indexed by B * L in 32 bits
     if (!e1 || !rel || !csr.idx || B <= 0 || csr.n_rows < 0 || (!csr.row && csr.n_rows != B))
       return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_row == NULL needs n_rows == B)");
@@ -1674,6 +1773,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   a.kind = kind; a.s = (hipStream_t)stream; a.e1 = e1; a.rel = rel; a.lookup = lookup; a.labels = labels; a.B = B; a.L = L;
   a.loss_out = loss_out; a.pred_out = pred_out; a.h_out = h_out; a.csr = csr;
   a.plan = plan_scorer(h, T, lookup, csr, B);
+  if (sync) { a.B_stat = sync->B_global; a.sample_offset = sync->sample_offset; }
   if (T->det) {      // what the mode does not put in order is refused, never served unordered
     // (the plan says atomics: no dense S for this B * num_ent.  Ordered rows: the sorted-segment route at every num_ent)
     if (a.plan.table == TableGrad::Atomics)
@@ -1696,6 +1796,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   T->pending = false;      // (the gradient buffers are zeroed next: what a coper_train_backward left in them is gone)
   T->rows_pending_clear();      // (... and what a coper_train_rows_backward or the imports left: rows_rezero below)
+  T->sync = SyncOpen();         // (... and a synchronised step that was open: abandoned, as a pending backward is dropped)
   st.zero_accumulators();
   if (st.rows) {
     rows_rezero_launch(h, T, st.s);
@@ -1703,6 +1804,21 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   if (st.lk && (rc = st.group_for_lookup())) return rc;
 
+  if (sync && st.use_batch) {      // coper_train_sync_begin: up to the first batch-wide sum; the rest of the step is coper_train_sync_next's
+    if ((rc = T->sync_sums.ensure(h, (size_t)4 * T->mx, "synchronised BN sums"))) return rc;
+    st.fwd_conv_filters();
+    st.fwd_conv_sums();
+    if ((rc = sync_hand_out(h, st.s, st.bn1_fwd_sums(), 2 * (int64_t)st.C, sync->part_out, sync->n_out))) return rc;
+    COPER_HIP_TRY(h, hipGetLastError());
+    SyncOpen& o = T->sync;
+    o.rows = kind == StepKind::RowsBackward; o.csr = csr.indptr != nullptr;
+    o.e1 = e1; o.rel = rel; o.lookup = lookup; o.labels = labels; o.B = B; o.L = L; o.loss_out = loss_out;
+    o.lab_indptr = csr.indptr; o.lab_idx = csr.idx; o.lab_row = csr.row; o.n_rows = csr.n_rows;
+    o.B_global = sync->B_global; o.sample_offset = sync->sample_offset;
+    o.carry = st;      // (the StepCarry part)
+    o.phase = 1;
+    return COPER_OK;
+  }
   st.fwd_conv_filters();
   st.fwd_conv_bn1();
   if ((rc = st.fwd_dense())) return rc;
@@ -1816,6 +1932,7 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
+  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_grads_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (T->sharded)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: an entity-sharded state (coper_train_init_sharded): no table gradient leaves its shard");
   if (T->rows_deferred)
@@ -1833,6 +1950,7 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
+  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (T->sharded)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: an entity-sharded state (coper_train_init_sharded): its update is coper_train_shard_apply");
   if (T->rows_deferred)
@@ -1900,6 +2018,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
     if (int rc = rows_sync_launch(h, T, s)) return rc;
     T->rows_deferred = false;
     T->rows_pending_clear();      // (the dense step zeroes the two buffers whole: a pending row gradient is gone)
+    T->sync = SyncOpen();         // (an open synchronised step was the mode's: abandoned)
     return COPER_OK;
   }
   const size_t E = (size_t)rows_held(h, T);      // (a shard: a word and a claim bit per OWNED row)
@@ -1918,6 +2037,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   T->rows_l2b1p = std::log2(T->b1p);      // (log2(0) = -inf: the power is 0 at every gap, as the dense step has it)
   T->rows_l2b2p = std::log2(T->b2p);
   T->pending = false;      // (a pending backward's gradient is gone with the zeroing)
+  T->sync = SyncOpen();    // (... and an open synchronised step)
   T->rows_pending_clear();
   T->rows_deferred = true;
   return COPER_OK;
@@ -1953,6 +2073,7 @@ COPER_API int coper_train_order_rows(coper_handle* h, int32_t enable, void* stre
   T->rows_ordered = enable != 0;
   T->rows_list_unsorted = false;
   T->pending = false;      // (as switching deferred rows: what a split step left pending is dropped, never applied by another route)
+  T->sync = SyncOpen();    // (... and an open synchronised step with it)
   T->rows_pending_clear();
   return COPER_OK;
 }
@@ -2043,6 +2164,7 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_export: call coper_train_init first");
+  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_rows_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_export: the deferred-rows mode is off (coper_train_grads_export is the dense call)");
   if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_export: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
@@ -2113,6 +2235,7 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_apply: call coper_train_init first");
+  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_rows_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_apply: the deferred-rows mode is off (coper_train_apply is the dense call)");
   if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_apply: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
@@ -2210,6 +2333,134 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
   if (beta2_power) *beta2_power = T->b2p;
   if (step) *step = (int64_t)T->step;
   return COPER_OK;
+}
+
+}  // extern "C"
+
+// ---- synchronised batch statistics: the backward in phases (include/coper_hip.h).  coper_train_sync_begin is
+// train_step_impl up to the first batch-wide sum (SyncReq); every coper_train_sync_next folds the ranks' shares of that sum in ascending
+// rank and runs on to the next one.  Between the calls the step is TrainState::sync: its arguments and its StepCarry.
+namespace {
+
+// a Step over the open step's arguments for one of its phases
+static Step sync_step(coper_handle* h, TrainState* T, hipStream_t s) {
+  const SyncOpen& o = T->sync;
+  StepArgs a;
+  a.kind = o.rows ? StepKind::RowsBackward : StepKind::Backward;
+  a.s = s; a.e1 = o.e1; a.rel = o.rel; a.lookup = o.lookup; a.labels = o.labels; a.B = o.B; a.L = o.L; a.loss_out = o.loss_out;
+  if (o.csr) a.csr = CsrLabels{o.lab_indptr, o.lab_idx, o.lab_row, o.n_rows};
+  a.B_stat = o.B_global; a.sample_offset = o.sample_offset;
+  a.plan = plan_scorer(h, T, o.lookup, a.csr, o.B);
+  return Step(h, T, a);
+}
+// the doubles exchange `phase` carries (1, 4: Conv1BN's channels; 2, 3: FCBN's features; 5: the step is complete)
+inline int64_t sync_part_doubles(const Dims& dm, int phase) { return phase > 4 ? 0 : 2 * (int64_t)((phase == 1 || phase == 4) ? dm.C : dm.d); }
+
+}  // namespace
+
+extern "C" {
+
+COPER_API int coper_train_sync_begin(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels, int64_t B,
+                                     int64_t L, int64_t B_global, int64_t sample_offset, int32_t rows, double* part_out, int64_t part_cap,
+                                     int64_t* n_out, float* loss_out, void* stream) {
+  const SyncReq q{B_global, sample_offset, rows, part_out, part_cap, n_out};
+  return train_step_impl(h, e1, rel, lookup, labels, B, L, loss_out, stream, rows == 1 ? StepKind::RowsBackward : StepKind::Backward, nullptr, nullptr,
+                         CsrLabels(), &q);
+}
+
+COPER_API int coper_train_sync_begin_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr, const int64_t* lab_idx,
+                                         const int64_t* lab_row, int64_t n_rows, int64_t B, int64_t B_global, int64_t sample_offset,
+                                         double* part_out, int64_t part_cap, int64_t* n_out, float* loss_out, void* stream) {
+  if (!h) return COPER_EINVAL;
+  if (!lab_indptr) return fail(h, COPER_EINVAL, "coper_train_sync_begin_csr: bad argument (lab_indptr is NULL)");
+  const SyncReq q{B_global, sample_offset, 0, part_out, part_cap, n_out};
+  return train_step_impl(h, e1, rel, nullptr, nullptr, B, h->dm.E, loss_out, stream, StepKind::Backward, nullptr, nullptr,
+                         CsrLabels{lab_indptr, lab_idx, lab_row, n_rows}, &q);
+}
+
+COPER_API int coper_train_sync_next(coper_handle* h, const double* parts_in, int32_t G, double* part_out, int64_t part_cap, int64_t* n_out,
+                                    void* stream) {
+  if (!h) return COPER_EINVAL;
+  TrainState* T = (TrainState*)h->train;
+  if (!T) return fail(h, COPER_ESTATE, "coper_train_sync_next: call coper_train_init first");
+  const int ph = T->sync.phase;
+  if (!ph) return fail(h, COPER_ESTATE, "coper_train_sync_next: no synchronised step is open (coper_train_sync_begin opens one)");
+  if (G < 1) return fail(h, COPER_EINVAL, "coper_train_sync_next: G < 1");
+  if (!parts_in || !aligned8(parts_in) || !n_out) return fail(h, COPER_EINVAL, "coper_train_sync_next: parts_in must be an 8-byte aligned device buffer, n_out not NULL");
+  const Dims& dm = h->dm;
+  const int64_t n_in = sync_part_doubles(dm, ph), n_next = sync_part_doubles(dm, ph + 1);
+  if (n_next && (!part_out || !aligned8(part_out))) return fail(h, COPER_EINVAL, "coper_train_sync_next: part_out must be an 8-byte aligned device buffer");
+  if (part_cap < n_next) return fail(h, COPER_EINVAL, "coper_train_sync_next: part_cap is below the doubles this call hands out (coper_train_sync_part_len holds every call's)");
+  COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
+  hipStream_t const s = (hipStream_t)stream;
+  Step st = sync_step(h, T, s);
+  T->sync.phase = 0;      // (a call that fails leaves no step open: what it left half done is no state to go on from)
+  int rc;
+  if ((rc = st.grow_workspaces())) return rc;      // (nothing grows: the begin call sized them; the pointers a phase reads are set here)
+  static_cast<StepCarry&>(st) = T->sync.carry;
+  double *const all = T->sync_sums.get(), *const own = T->sync_sums + (size_t)2 * T->mx;
+  auto fold = [&](double* out) { hipLaunchKernelGGL(k_tr_fold_parts, grid1d(n_in), dim3(256), 0, s, parts_in, (int)G, (int)n_in, out); };
+  const double* hand = nullptr;
+  switch (ph) {
+  case 1:      // Conv1BN's statistics over B_global P positions, ReLU, dropout, the dense layer; FCBN's column sums of this rank's rows
+    fold(st.bn1_fwd_sums());
+    st.fwd_bn1();
+    if ((rc = st.fwd_dense())) return rc;
+    st.fwd_fcbn_sums();
+    hand = st.fcbn_fwd_sums();
+    break;
+  case 2:      // FCBN over B_global samples, the scorer with the loss and its backward; FCBN's backward sums of this rank's rows
+    fold(st.fcbn_fwd_sums());
+    st.fwd_fcbn_apply();
+    if ((rc = st.csr.indptr ? st.score_csr() : st.fwd_score_loss())) return rc;
+    if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
+    if ((rc = st.bwd_scorer())) return rc;
+    st.bwd_fcbn_sums(own);
+    hand = own;
+    break;
+  case 3:      // dz from the whole batch's sums, the dense layer's backward, the generators' chains; Conv1BN's backward sums of this rank's rows
+    fold(all);
+    st.bwd_fcbn_apply(all, own);
+    if ((rc = st.bwd_dense())) return rc;
+    if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
+    st.bwd_bn1_sums();
+    hand = st.bn1_bwd_sums();
+    break;
+  default:     // Conv1BN's backward from the whole batch's sums, the conv's, the filters'
+    fold(all);
+    st.bwd_bn1_apply(all);
+    st.bwd_conv();
+    st.bwd_conv_filters();
+    break;
+  }
+  // (what a side stream was given in this call is joined before the call returns: the exchange, and the next call, find it done)
+  st.sj.join(SJ_DP);
+  st.sj.join(SJ_SCORER_BWD);
+  if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_sync_next: an event call of the side streams failed");
+  *n_out = 0;
+  if (hand && (rc = sync_hand_out(h, s, hand, n_next, part_out, n_out))) return rc;
+  COPER_HIP_TRY(h, hipGetLastError());
+  T->sync.carry = st;      // (the StepCarry part)
+  if (ph < 4) { T->sync.phase = ph + 1; return COPER_OK; }
+  // complete: the handle is where coper_train_backward / coper_train_rows_backward leaves it
+  T->step += 1;
+  if (T->sync.rows) {
+    T->rows_pending_small = T->rows_pending_table = true;
+    T->rows_bound = std::min<int64_t>(st.B * (st.L + 1), h->dm.E);
+  } else T->pending = true;
+  T->sync = SyncOpen();
+  return COPER_OK;
+}
+
+COPER_API int coper_train_sync_phase(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  const TrainState* T = (const TrainState*)h->train;
+  return T ? T->sync.phase : -COPER_ESTATE;
+}
+
+COPER_API int64_t coper_train_sync_part_len(const coper_handle* h) {
+  if (!h) return -COPER_EINVAL;
+  return 2 * (int64_t)std::max(h->dm.C, h->dm.d);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 namespace coper {
 
 // keep (true) with probability 1 - rate: 24-bit uniform from a counter hash of (seed, step, stage, element)
+// (element: the flat index in the [B, n] tensor the mask is drawn for -- plus, in the kernels, an offset `ioff` = sample_offset * n when
+//  the B samples are rows [sample_offset, sample_offset + B) of a larger batch whose masks they draw; 0 everywhere else)
 __host__ __device__ __forceinline__ bool dropout_keep_u32(uint32_t seed, uint32_t step, uint32_t stage, uint32_t idx,
                                                           uint32_t threshold24) {
   uint32_t x = idx * 0x9E3779B1u + seed * 0x85EBCA77u + step * 0xC2B2AE3Du + stage * 0x27D4EB2Fu;

@@ -212,7 +212,7 @@ __device__ __forceinline__ void tr_block_max_to_slot(float v_abs, unsigned* __re
 __global__ __launch_bounds__(256) void k_tr_bn1_fwd(const float* __restrict__ y, const float* __restrict__ mean,
                                                     const float* __restrict__ inv, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, int C, int64_t total, uint32_t seed,
-                                                    uint32_t step, uint32_t thr, float keep_scale, float* __restrict__ x,
+                                                    uint32_t step, uint32_t ioff, uint32_t thr, float keep_scale, float* __restrict__ x,
                                                     unsigned* __restrict__ max_slots) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   float out = 0.f;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_fwd(const float* __restrict__ y,
     const int c = (int)(i % C);
     float v = (y[i] - mean[c]) * inv[c] * gamma[c] + beta[c];
     v = v > 0.f ? v : 0.f;
-    out = dropout_keep_u32(seed, step, 1u, (uint32_t)i, thr) ? v * keep_scale : 0.f;
+    out = dropout_keep_u32(seed, step, 1u, (uint32_t)i + ioff, thr) ? v * keep_scale : 0.f;
     x[i] = out;
   }
   if (max_slots) tr_block_max_to_slot(out, max_slots);       // (x >= 0)
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_fwd(const float* __restrict__ y,
 __global__ __launch_bounds__(256) void k_tr_fc_post(const float* __restrict__ z0, const float* __restrict__ fc_bias,
                                                     const float* __restrict__ cw, int rw, const float* __restrict__ cb,
                                                     const float* __restrict__ Pb, int rb, int d, int64_t total, uint32_t seed,
-                                                    uint32_t step, uint32_t thr, float keep_scale, float* __restrict__ z1) {
+                                                    uint32_t step, uint32_t ioff, uint32_t thr, float keep_scale, float* __restrict__ z1) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int k = (int)(i % d);
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_tr_fc_post(const float* __restrict__ z0
   } else {
     v = z0[i] + fc_bias[k];
   }
-  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? v * keep_scale : 0.f;
+  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i + ioff, thr) ? v * keep_scale : 0.f;
 }
 
 // the generated dense layer straight from the K slices of its product (tg_gemm_nt: leave_slices): T[rho][b, k] = the slices of
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void k_tr_fc_post(const float* __restrict__ z0
 template <int NS>
 __global__ __launch_bounds__(256) void k_tr_fc_post_slices(const float* __restrict__ part, const float* __restrict__ cw, int rw,
                                                            const float* __restrict__ cb, const float* __restrict__ Pb, int rb, int d,
-                                                           int64_t total, uint32_t seed, uint32_t step, uint32_t thr, float keep_scale,
+                                                           int64_t total, uint32_t seed, uint32_t step, uint32_t ioff, uint32_t thr, float keep_scale,
                                                            float* __restrict__ Tf, float* __restrict__ z1) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void k_tr_fc_post_slices(const float* __restri
     v = fmaf(cw[b * rw + rho], a, v);
   }
   for (int rho = 0; rho < rb; ++rho) v = fmaf(cb[b * rb + rho], Pb[rho * d + k], v);
-  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? v * keep_scale : 0.f;
+  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i + ioff, thr) ? v * keep_scale : 0.f;
 }
 
 __global__ __launch_bounds__(256) void k_tr_fcbn_fwd(const float* __restrict__ z1, const float* __restrict__ mean,
@@ -930,7 +930,7 @@ __global__ __launch_bounds__(256) void k_tr_small_mm_tn(const float* __restrict_
 }
 // a = relu(BN(u)) (or relu(u) when the generator has no BN); v_next = dropout(a)
 __global__ __launch_bounds__(256) void k_tr_chain_act(const float* __restrict__ u, const float* __restrict__ st, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, int n, int64_t total, uint32_t seed, uint32_t step,
+                                                      const float* __restrict__ beta, int n, int64_t total, uint32_t seed, uint32_t step, uint32_t ioff,
                                                       uint32_t stage, uint32_t thr, float keep_scale, float* __restrict__ a,
                                                       float* __restrict__ vnext) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -940,14 +940,14 @@ __global__ __launch_bounds__(256) void k_tr_chain_act(const float* __restrict__ 
   if (gamma) v = (v - st[k]) * st[n + k] * gamma[k] + beta[k];
   v = v > 0.f ? v : 0.f;
   a[i] = v;
-  vnext[i] = dropout_keep_u32(seed, step, stage, (uint32_t)i, thr) ? v * keep_scale : 0.f;
+  vnext[i] = dropout_keep_u32(seed, step, stage, (uint32_t)i + ioff, thr) ? v * keep_scale : 0.f;
 }
 // g = keep * dv_next / (1 - rate)   (dropout backward; the ReLU / BN part is k_tr_fcbn_bwd)
-__global__ __launch_bounds__(256) void k_tr_chain_drop_bwd(const float* __restrict__ dvn, int64_t total, uint32_t seed, uint32_t step,
+__global__ __launch_bounds__(256) void k_tr_chain_drop_bwd(const float* __restrict__ dvn, int64_t total, uint32_t seed, uint32_t step, uint32_t ioff,
                                                            uint32_t stage, uint32_t thr, float keep_scale, float* __restrict__ g) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  g[i] = dropout_keep_u32(seed, step, stage, (uint32_t)i, thr) ? dvn[i] * keep_scale : 0.f;
+  g[i] = dropout_keep_u32(seed, step, stage, (uint32_t)i + ioff, thr) ? dvn[i] * keep_scale : 0.f;
 }
 __global__ __launch_bounds__(256) void k_tr_add(const float* __restrict__ a, int64_t n, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1018,7 +1018,7 @@ __global__ __launch_bounds__(256) void k_tr_lookup_dx(const float* __restrict__ 
 // z1 = keep * (sum of the forward partials + bias_table[rel[b]]) / (1 - rate)
 __global__ __launch_bounds__(256) void k_tr_lookup_post(const float* __restrict__ part, int nsl, const float* __restrict__ bias_t,
                                                         const int64_t* __restrict__ rel, int64_t R, int d, int64_t total,
-                                                        uint32_t seed, uint32_t step, uint32_t thr, float keep_scale,
+                                                        uint32_t seed, uint32_t step, uint32_t ioff, uint32_t thr, float keep_scale,
                                                         float* __restrict__ z1) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -1026,18 +1026,18 @@ __global__ __launch_bounds__(256) void k_tr_lookup_post(const float* __restrict_
   if (rid < 0 || rid >= R) rid = 0;
   float v = bias_t[rid * d + i % d];
   for (int sl = 0; sl < nsl; ++sl) v += part[(int64_t)sl * total + i];
-  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? v * keep_scale : 0.f;
+  z1[i] = dropout_keep_u32(seed, step, 2u, (uint32_t)i + ioff, thr) ? v * keep_scale : 0.f;
 }
 // dz0 = keep * dz1 / (1 - rate) (in place);  dbias_table[rel[b], k] += dz0[b,k]   (DET: the rows are added by k_tr_rows_by_key_det)
 template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_lookup_post_bwd(float* __restrict__ dz, const int64_t* __restrict__ rel, int64_t R, int d,
-                                                            int64_t total, uint32_t seed, uint32_t step, uint32_t thr,
+                                                            int64_t total, uint32_t seed, uint32_t step, uint32_t ioff, uint32_t thr,
                                                             float keep_scale, float* __restrict__ dbias_t) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   int64_t rid = rel[i / d];
   if (rid < 0 || rid >= R) rid = 0;
-  const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? dz[i] * keep_scale : 0.f;
+  const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i + ioff, thr) ? dz[i] * keep_scale : 0.f;
   dz[i] = v;
   if constexpr (!DET) atomicAdd(&dbias_t[rid * d + i % d], v);
 }
@@ -1080,19 +1080,72 @@ __global__ __launch_bounds__(256) void k_tr_fcbn_bwd(const float* __restrict__ z
   }
 }
 
+// The two halves of k_tr_fcbn_bwd for a step whose batch statistics span several ranks (coper_train_sync_*): the sums of
+// this rank's rows leave the kernel, the caller's exchange adds the ranks', the second half applies the formula with the sums of the
+// WHOLE batch.  The same thread-to-row assignment and the same LDS tree as k_tr_fcbn_bwd, so one rank alone reproduces its bits.
+// sums [2 d] doubles: sum of g | sum of g z_hat.
+__global__ __launch_bounds__(256) void k_tr_fcbn_bwd_sums(const float* __restrict__ z1, const float* __restrict__ hv, const float* __restrict__ dh,
+                                                          const float* __restrict__ mean, const float* __restrict__ inv, int64_t B, int d,
+                                                          double* __restrict__ sums) {
+  __shared__ double s1[256], s2[256];
+  const int k = blockIdx.x;
+  const float mu = mean[k], iv = inv[k];
+  double a1 = 0, a2 = 0;
+  for (int64_t b = threadIdx.x; b < B; b += 256) {
+    const float g = hv[b * d + k] > 0.f ? dh[b * d + k] : 0.f;   // through the ReLU
+    const float zh = (z1[b * d + k] - mu) * iv;
+    a1 += g;
+    a2 += (double)g * zh;
+  }
+  s1[threadIdx.x] = a1; s2[threadIdx.x] = a2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { s1[threadIdx.x] += s1[threadIdx.x + o]; s2[threadIdx.x] += s2[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { sums[k] = s1[0]; sums[d + k] = s2[0]; }
+}
+// all: the sums over the whole batch of n samples (the dz1 formula);  own: this rank's (its share of the gamma / beta gradients -- the
+// caller's all-reduce of the gradients adds the ranks' shares, so the whole batch's sums here would count every rank G times)
+// (dh and dz1 may be the same buffer, as in k_tr_fcbn_bwd)
+__global__ __launch_bounds__(256) void k_tr_fcbn_bwd_apply(const float* __restrict__ z1, const float* __restrict__ hv, const float* dh,
+                                                           const float* __restrict__ mean, const float* __restrict__ inv,
+                                                           const float* __restrict__ gamma, int64_t B, int d, double n,
+                                                           const double* __restrict__ all, const double* __restrict__ own,
+                                                           float* __restrict__ dgamma, float* __restrict__ dbeta, float* dz1) {
+  const int k = blockIdx.x;
+  const float mu = mean[k], iv = inv[k], ga = gamma[k];
+  const double S1 = all[k], S2 = all[d + k];
+  if (threadIdx.x == 0) { dbeta[k] = (float)own[k]; dgamma[k] = (float)own[d + k]; }
+  for (int64_t b = threadIdx.x; b < B; b += 256) {
+    const float g = hv[b * d + k] > 0.f ? dh[b * d + k] : 0.f;
+    const float zh = (z1[b * d + k] - mu) * iv;
+    dz1[b * d + k] = (float)((double)ga * iv * ((double)g - S1 / n - (double)zh * S2 / n));
+  }
+}
+// out[j] = parts[0][j] + parts[1][j] + ... in ascending g: the ranks' shares of a batch-wide sum as the caller gathered them, [G][n].
+// Every rank folds the same buffer in the same order, so every rank holds the same bits; one part alone passes through unchanged.
+__global__ __launch_bounds__(256) void k_tr_fold_parts(const double* __restrict__ parts, int G, int n, double* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  double a = parts[j];
+  for (int g = 1; g < G; ++g) a += parts[(size_t)g * n + j];
+  out[j] = a;
+}
+
 // dz0 = keep * dz1 / (1 - rate) (in place); dense-bias gradients: static dfc_bias[k] += dz0; generated
 // dPb[rho,k] += c[b,rho] dz0[b,k], dc[b,rho] = sum_k dz0[b,k] Pb[rho,k]   (DET: dfc_bias is the column sum of dz0, a launch of its own)
 template <bool DET>
 __global__ __launch_bounds__(256) void k_tr_fc_post_bwd(float* __restrict__ dz, const float* __restrict__ c,
                                                         const float* __restrict__ Pb, int r, int d, uint32_t seed,
-                                                        uint32_t step, uint32_t thr, float keep_scale,
+                                                        uint32_t step, uint32_t ioff, uint32_t thr, float keep_scale,
                                                         float* __restrict__ dfc_bias, float* __restrict__ dPb,
                                                         float* __restrict__ dc) {
   extern __shared__ float row[];  // dz0[b, :]
   const int64_t b = blockIdx.x;
   for (int k = threadIdx.x; k < d; k += 256) {
     const int64_t i = b * d + k;
-    const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i, thr) ? dz[i] * keep_scale : 0.f;
+    const float v = dropout_keep_u32(seed, step, 2u, (uint32_t)i + ioff, thr) ? dz[i] * keep_scale : 0.f;
     dz[i] = v;
     row[k] = v;
     if constexpr (!DET)
@@ -1156,7 +1209,7 @@ template <int NS>
 __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums(float* __restrict__ dx, const float* __restrict__ part, const float* __restrict__ y,
                                                          const float* __restrict__ mean, const float* __restrict__ inv,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, int C,
-                                                         int64_t total, uint32_t seed, uint32_t step, uint32_t thr,
+                                                         int64_t total, uint32_t seed, uint32_t step, uint32_t ioff, uint32_t thr,
                                                          float keep_scale, double* __restrict__ sums, int nslots) {
   __shared__ double s1[256], s2[256];
   sums += (size_t)(blockIdx.x % nslots) * 2 * C;      // (TR_CS_SLOTS copies: k_tr_col_sums)
@@ -1182,7 +1235,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums(float* __restrict__ dx,
       const int c = (int)(i % C);
       const float yh = (y[i] - mean[c]) * inv[c];
       const float act = yh * gamma[c] + beta[c];
-      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i, thr) ? dx_in(i) * keep_scale : 0.f;
+      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i + ioff, thr) ? dx_in(i) * keep_scale : 0.f;
       if (!(act > 0.f)) g = 0.f;
       dx[i] = g;
       atomicAdd(&s1[c], (double)g);
@@ -1209,7 +1262,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums(float* __restrict__ dx,
     for (int u = 0; u < 4; ++u) {
       const float yh = (yv[u] - mc) * ic;
       const float act = yh * gc + bc;
-      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)(i + u * st), thr) ? dv[u] * keep_scale : 0.f;
+      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)(i + u * st) + ioff, thr) ? dv[u] * keep_scale : 0.f;
       if (!(act > 0.f)) g = 0.f;
       dx[i + u * st] = g;
       a1 += g;
@@ -1219,7 +1272,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums(float* __restrict__ dx,
   for (; i < total; i += st) {
     const float yh = (y[i] - mc) * ic;
     const float act = yh * gc + bc;
-    float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i, thr) ? dx_in(i) * keep_scale : 0.f;
+    float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i + ioff, thr) ? dx_in(i) * keep_scale : 0.f;
     if (!(act > 0.f)) g = 0.f;
     dx[i] = g;
     a1 += g;
@@ -1240,13 +1293,16 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums(float* __restrict__ dx,
 }
 
 // pass 2: dy = gamma*inv*(g - S1/n - yhat*S2/n) (batch statistics) or gamma*inv*g; in place on dx
+// sums: S1 | S2 over the n positions the statistics were taken over;  own: the sums of this launch's rows, the gamma / beta gradients
+// (one buffer for both but in a step whose statistics span several ranks, DESIGN 6.13: the ranks' gradients are added afterwards)
 __global__ __launch_bounds__(256) void k_tr_bn1_bwd_apply(float* __restrict__ dx, const float* __restrict__ y,
                                                           const float* __restrict__ mean, const float* __restrict__ inv,
-                                                          const float* __restrict__ gamma, const double* __restrict__ sums, int C,
+                                                          const float* __restrict__ gamma, const double* __restrict__ sums,
+                                                          const double* __restrict__ own, int C,
                                                           int64_t total, double n, int use_batch, float* __restrict__ dgamma,
                                                           float* __restrict__ dbeta) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < C) { dbeta[i] = (float)sums[i]; dgamma[i] = (float)sums[C + i]; }
+  if (i < C) { dbeta[i] = (float)own[i]; dgamma[i] = (float)own[C + i]; }
   if (i >= total) return;
   const int c = (int)(i % C);
   const float g = dx[i];
@@ -1720,7 +1776,7 @@ __global__ __launch_bounds__(256) void k_tr_fold_f32_det(const float* __restrict
 // lanes added in lane order -- over the [B P, C] gradient; workgroup w stores its 2 C sums at slab[w]
 __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums_det(float* __restrict__ dx, const float* __restrict__ y, const float* __restrict__ mean,
                                                              const float* __restrict__ inv, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, int C, int64_t rows, uint32_t seed, uint32_t step,
+                                                             const float* __restrict__ beta, int C, int64_t rows, uint32_t seed, uint32_t step, uint32_t ioff,
                                                              uint32_t thr, float keep_scale, double* __restrict__ slab) {
   __shared__ double s1[256], s2[256];
   double* const out = slab + (size_t)blockIdx.x * 2 * C;
@@ -1732,7 +1788,7 @@ __global__ __launch_bounds__(256) void k_tr_bn1_bwd_sums_det(float* __restrict__
       const int64_t i = rr * C + c;
       const float yh = (y[i] - mc) * ic;
       const float act = yh * gc + bc;
-      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i, thr) ? dx[i] * keep_scale : 0.f;
+      float g = dropout_keep_u32(seed, step, 1u, (uint32_t)i + ioff, thr) ? dx[i] * keep_scale : 0.f;
       if (!(act > 0.f)) g = 0.f;
       dx[i] = g;
       a1 += g;

@@ -1133,10 +1133,10 @@ class ConvE(object):
         self._ent_absmax_cache = None
         self._versions = {n: _version(t) for n, t in self._tensors.items()}
 
-    def _train_dispatch(self, batch, dense_fn, csr_fn):
+    def _train_dispatch(self, batch, dense_fn, csr_fn, keep=False):
         """Routes a training batch in any of its three label forms (sampled lookup, dense 1-vs-all, sparse 1-vs-all) to the
         step-shaped call `dense_fn` (the arguments of coper_train_step) or `csr_fn` (those of coper_train_step_csr); the loss lands
-        in self._train_loss."""
+        in self._train_loss.  keep: returns the device tensors whose pointers the call was given."""
         if getattr(self, "_train_loss", None) is None:
             raise _lib.CoperError(5, "call train_init() first")
         e1, rel = self._ids(batch["e1"]), self._ids(batch["rel"])
@@ -1149,7 +1149,7 @@ class ConvE(object):
             with torch.cuda.device(self.device):
                 _lib.check(self._h, csr_fn(self._h, _ptr(e1), _ptr(rel), _ptr(ip), _ptr(ix), _ptr(row), n_rows, B,
                                            _ptr(self._train_loss), self._stream()))
-            return
+            return (e1, rel, ip, ix, row) if keep else None
         lv = batch.get("lookup_values", None)
         one_vs_all = lv is None or (hasattr(lv, "shape") and len(lv.shape) == 2 and lv.shape[1] == 0)   # data.py:322
         lookup = None if one_vs_all else self._ids(lv, torch.int32)
@@ -1163,6 +1163,7 @@ class ConvE(object):
         with torch.cuda.device(self.device):
             _lib.check(self._h, dense_fn(self._h, _ptr(e1), _ptr(rel), _ptr(lookup), _ptr(labels), B, L,
                                          _ptr(self._train_loss), self._stream()))
+        return (e1, rel, lookup, labels) if keep else None
 
     # ---- the step in three calls (include/coper_hip.h: backward | export | apply)
     def train_backward(self, batch):
@@ -1171,6 +1172,63 @@ class ConvE(object):
         changes and the model stays prepared (an evaluation in between folds BN from the moving statistics as the last prepare()
         found them: call prepare() where the one momentum step matters).  Returns the loss as a 1-element device tensor (no synchronisation)."""
         self._train_dispatch(batch, self._lib.coper_train_backward, self._lib.coper_train_backward_csr)
+        return self._train_loss
+
+    # ---- synchronised batch statistics: the backward in phases (include/coper_hip.h: sync_begin | sync_next x 4; DESIGN.md 6.13)
+    def train_sync_begin(self, batch, B_global, sample_offset, rows=False):
+        """coper_train_sync_begin / _csr: opens a backward whose batch statistics span every rank's shard of one batch of `B_global`
+        samples; this rank's batch is samples [sample_offset, sample_offset + B) of it.  Routes the three label forms like train_backward
+        (rows=True: train_rows_backward, deferred-rows mode).  Returns `(part, n)`: a float64 device vector whose first n entries are this
+        rank's share of the first batch-wide sum; gather the ranks' `part[:n]` in rank order into [G, n] and hand it to `train_sync_next`.
+        n == 0 (batch statistics off): the backward is complete.  The loss (train_sync_loss) is the mean over this rank's labels."""
+        if getattr(self, "_sync_part", None) is None:
+            n = int(self._lib.coper_train_sync_part_len(self._h))
+            self._sync_part = torch.zeros(n, device=self.device, dtype=torch.float64)
+        part, cap, n_out = self._sync_part, self._sync_part.numel(), C.c_int64(0)
+        B_global, sample_offset, rows = int(B_global), int(sample_offset), 1 if rows else 0
+
+        def dense_fn(h, e1, rel, lookup, labels, B, L, loss, stream):
+            return self._lib.coper_train_sync_begin(h, e1, rel, lookup, labels, B, L, B_global, sample_offset, rows, _ptr(part), cap,
+                                                    C.byref(n_out), loss, stream)
+
+        def csr_fn(h, e1, rel, ip, ix, row, n_rows, B, loss, stream):
+            if rows:
+                raise _lib.CoperError(7, "train_sync_begin: deferred-rows mode: a 1-vs-all step has a gradient in every row")
+            return self._lib.coper_train_sync_begin_csr(h, e1, rel, ip, ix, row, n_rows, B, B_global, sample_offset, _ptr(part), cap,
+                                                        C.byref(n_out), loss, stream)
+
+        # (later phases read the batch's device buffers: whatever the dispatch made or passed through stays referenced until the step ends)
+        self._sync_keep = self._train_dispatch(batch, dense_fn, csr_fn, keep=True)
+        if rows:
+            self._rows_bound = min(int(len(batch["e1"])) * (int(batch["e2_multi"].shape[1]) + 1), self.num_ent)
+        if n_out.value == 0:
+            self._sync_keep = None
+        return part, n_out.value
+
+    def train_sync_next(self, parts):
+        """coper_train_sync_next: `parts` float64 [G, n], the ranks' shares of the last sum in rank order -> `(part, n)` of the next
+        one; n == 0: the step is complete and the handle is where train_backward (train_rows_backward) leaves it."""
+        if parts.dtype != torch.float64 or parts.dim() != 2 or not parts.is_contiguous() or parts.device != torch.device(self.device):
+            raise ValueError("train_sync_next: parts must be a contiguous float64 [G, n] tensor on the model's device")
+        part, n_out = self._sync_part, C.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._h, self._lib.coper_train_sync_next(self._h, _ptr(parts), parts.shape[0], _ptr(part), part.numel(), C.byref(n_out),
+                                                                self._stream()))
+        if n_out.value == 0:
+            self._sync_keep = None
+        return part, n_out.value
+
+    @property
+    def train_sync_phase(self):
+        """coper_train_sync_phase: 0 no synchronised step open, 1 .. 4 the exchange the handle waits for."""
+        v = self._lib.coper_train_sync_phase(self._h)
+        if v < 0:
+            raise _lib.CoperError(-v, "call train_init() first")
+        return v
+
+    @property
+    def train_sync_loss(self):
+        """The loss of the last synchronised backward (valid behind its second train_sync_next), a 1-element device tensor."""
         return self._train_loss
 
     def train_grads_layout(self):

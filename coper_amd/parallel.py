@@ -4,7 +4,9 @@ coper_train_grads_export | coper_train_apply).
 Every rank holds a full replica of the model (`ConvE` after `train_init`).  An update is: per micro-batch a backward pass and an
 export that ADDS its gradient into one flat vector, ONE all-reduce (sum) of that vector over the ranks, then the optimizer on the sum
 scaled by 1 / (ranks * micro-batches).  The replicas start equal (rank 0's state is broadcast) and stay equal, because every rank
-applies the same bytes.  The all-reduce does not overlap the backward pass, and there is no SyncBN.
+applies the same bytes.  The all-reduce does not overlap the backward pass.  Batch statistics are per rank unless the trainer is built
+with `sync_bn=True`: then every micro-batch's backward is the phased step of include/coper_hip.h, "Synchronised batch statistics"
+(DESIGN.md 6.13), and an update is the reference's update on the whole batch.
 
 Entity-sharded (model-parallel) 1-vs-all training is `EntityShardedTrainer` below: the entity table, its gradients and
 slots split over the ranks, the encoder replicated; sampled labels on a sharded table are not built.
@@ -46,7 +48,7 @@ def shard_batch(batch, rank, world):
 
 
 class DataParallelTrainer(object):
-    """`DataParallelTrainer(model, group=None, micro_batches=1)`: one replica per rank of a `torch.distributed` process group
+    """`DataParallelTrainer(model, group=None, micro_batches=1, sync_bn=False)`: one replica per rank of a `torch.distributed` process group
     (`group=None`: the default group; no initialised process group at all: one process, plain gradient accumulation).
 
     Construction broadcasts rank 0's variables (BN moving statistics included), AMSGrad slots, beta powers and dropout counter.
@@ -58,9 +60,20 @@ class DataParallelTrainer(object):
       * the BN moving statistics, which every rank updated from its own batches, are averaged over the ranks in one small
         all-reduce (the loss rides in it), so the replicas stay equal.
 
-    Batch statistics are per rank and per micro-batch, as in torch's DistributedDataParallel without SyncBN: a rank normalises by
-    the statistics of the micro-batch in front of it, never by the global batch's.  The gradient is therefore the mean of the
-    micro-batch gradients, not the gradient of the concatenated batch, wherever batch statistics are on.
+    Batch statistics are per rank and per micro-batch by default, as in torch's DistributedDataParallel without SyncBN: a rank
+    normalises by the statistics of the micro-batch in front of it, never by the global batch's.  The gradient is therefore the mean of
+    the micro-batch gradients, not the gradient of the concatenated batch, wherever batch statistics are on.
+
+    SYNCHRONISED BATCH STATISTICS.  `sync_bn=True`: every micro-batch's backward is `train_sync_begin` + four `train_sync_next`, the
+    ranks' shares of each batch-wide sum gathered in rank order in between (four small all-gathers of at most
+    2 max(conv_num_channels, ent_emb_size) doubles; over gloo staged through the host).  Rank r's micro-batch i is samples
+    [r B, (r + 1) B) of a batch of world * B samples -- the ranks' i-th micro-batches, `shard_batch`'s slices of one batch -- so Conv1BN
+    and FCBN normalise by that whole batch and the dropout masks are the whole batch's: with micro_batches == 1 the update is ONE step on
+    the concatenated batch.  Micro-batch i is synchronised over the ranks' i-th micro-batches, NOT across micro-batches: with
+    micro_batches > 1 the gradient is the mean of the gradients of M batches of world * B samples.  Every rank must pass the same B.  The
+    moving statistics are equal on every rank by construction and are not averaged; the loss still rides in the small all-reduce.  Both
+    routes take it (the sparse one through `train_sync_begin(rows=True)`).  Refused by the library: a generator with hidden layers and
+    context BN.  One seed on every rank (`train_init(seed=s)`): the masks are already a function of the sample's global position.
 
     Dropout masks are a function of (seed, dropout counter, element): ranks draw DIFFERENT masks only if the caller gave them
     different seeds -- `model.train_init(seed=s + rank)`.  With one seed every rank drops the same positions of its own shard.
@@ -92,7 +105,7 @@ class DataParallelTrainer(object):
     tensors only, the blocks are staged through the host: ranks sharing a GPU are a correctness run, and multi-GPU scaling of this route
     has not been measured.  Sampled batches only (the mode refuses 1-vs-all)."""
 
-    def __init__(self, model, group=None, micro_batches=1):
+    def __init__(self, model, group=None, micro_batches=1, sync_bn=False):
         import torch.distributed as dist
         if getattr(model, "_train_loss", None) is None:
             raise _lib.CoperError(5, "call train_init() first")
@@ -107,6 +120,7 @@ class DataParallelTrainer(object):
         self.world = self._dist.get_world_size(group) if self._dist else 1
         self.rank = self._dist.get_rank(group) if self._dist else 0
         self.sparse = model.train_rows_deferred == 1      # the deferred-rows mode: the sparse route (class docstring)
+        self.sync_bn = bool(sync_bn)
         if self.sparse:
             self.layout, total, self.row_stride = model.train_rows_layout()
             self._ids = self._vals = None                 # [M, cap] / [M, cap, rs]: micro-batch i's row block in slot i
@@ -164,7 +178,7 @@ class DataParallelTrainer(object):
         small = self._small
         loss = small[-1:]
         for i, b in enumerate(batches):
-            li = m.train_backward(b)
+            li = self._backward_sync(b, rows=False) if self.sync_bn else m.train_backward(b)
             m.train_grads_export(self.flat, accumulate=i > 0)
             if i:
                 loss += li
@@ -177,10 +191,23 @@ class DataParallelTrainer(object):
         m.train_apply(self.flat, 1.0 / (self.world * self.micro_batches))
         return loss / float(self.world * self.micro_batches)
 
+    def _backward_sync(self, batch, rows):
+        """One micro-batch's backward with batch statistics over the ranks' shards (class docstring): the phase loop, the ranks' parts
+        gathered in rank order between the calls.  Returns the loss of this rank's shard as a 1-element device tensor."""
+        m, B = self.model, len(batch["e1"])
+        part, n = m.train_sync_begin(batch, B_global=self.world * B, sample_offset=self.rank * B, rows=rows)
+        while n:
+            parts = self._gather(part[:n]) if self.world > 1 else part[:n].unsqueeze(0)
+            part, n = m.train_sync_next(parts)
+        return m.train_sync_loss
+
     def _average_stats(self):
-        """The BN moving statistics averaged over the ranks in one small all-reduce, written back in place; the loss rides in it."""
+        """The BN moving statistics averaged over the ranks in one small all-reduce, written back in place; the loss rides in it.
+        sync_bn: the statistics are equal on every rank already -- the loss alone is summed."""
         m, small = self.model, self._small
-        if self.world > 1:
+        if self.world > 1 and self.sync_bn:
+            self._dist.all_reduce(small[-1:], op=self._dist.ReduceOp.SUM, group=self.group)
+        elif self.world > 1:
             dist = self._dist
             at = 0
             for k in self._stat_names:
@@ -220,7 +247,7 @@ class DataParallelTrainer(object):
             self._ids = torch.full((M, cap), -1, device=m.device, dtype=torch.int32)
             self._vals = torch.zeros((M, cap, rs), device=m.device, dtype=torch.float32)
         for i, b in enumerate(batches):
-            li = m.train_rows_backward(b)
+            li = self._backward_sync(b, rows=True) if self.sync_bn else m.train_rows_backward(b)
             cnt = m.train_rows_export(self.flat, accumulate=i > 0, ids=self._ids[i], vals=self._vals[i])[3]
             self._counts[i:i + 1].copy_(cnt)
             if i:

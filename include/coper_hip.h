@@ -954,7 +954,8 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
  *     whole-table handle, which catches rows up in place: a row caught up in two stages is rounded twice, and a monitoring call on a
  *     shard changes no later bit of training.  (The fused scorer keeps 9 bytes more per entry in LDS there: L <= 8192 still fits.)
  * Not built: entering the deferred-rows mode on a state that has already stepped; the row-block split step (coper_train_rows_*) on a shard; sorting the owned entries alone; the default
- *   (non-deterministic) mode; splitting the encoder's batch over ranks (needs a synchronised BN); dense [B, num_ent]
+ *   (non-deterministic) mode; splitting the encoder's batch over ranks (the phase cuts it needs are those of "Synchronised batch
+ *   statistics" below: not wired into the sharded calls); dense [B, num_ent]
  *   labels; overlap of the exchanges with compute. */
 COPER_API int coper_train_init_sharded(coper_handle* h, const coper_train_config* cfg);
 COPER_API int coper_train_sharded(const coper_handle* h);
@@ -974,6 +975,60 @@ COPER_API int coper_train_shard_forward_lookup(coper_handle* h, const int64_t* e
 COPER_API int coper_train_shard_forward_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const float* e1_rows,
                                             const int64_t* lab_indptr, const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows,
                                             int64_t B, double* loss_part, float* pred_local, float* h_out, void* stream);
+
+/* Synchronised batch statistics: the backward in phases.  G data-parallel ranks each hold B samples of one batch of
+ * B_global = G B samples (even shards; this rank's are samples [sample_offset, sample_offset + B) of it).  With
+ * batch_norm_train_stats on, coper_train_backward normalises every shard by its own statistics; these calls take the statistics of
+ * Conv1BN (over B_global Ho Wo positions) and FCBN (over B_global samples) over the WHOLE batch, in the forward formulas and in both BN
+ * backward formulas.  After the caller's usual sum of the flat gradients over the ranks and coper_train_apply(flat, 1 / G), every rank
+ * has made ONE step on the whole batch: its gradient, and its moving statistics (equal on every rank, nothing to average).
+ *
+ * The step is coper_train_sync_begin (or _csr) and four coper_train_sync_next.  Each call runs launches on the caller's stream up to
+ * the next point where a batch-wide sum is needed, writes this rank's n doubles to part_out (a device buffer of part_cap doubles) and
+ * returns n in *n_out -- a host value computed from the configuration, nothing is read back and no call synchronises the host once the
+ * workspaces hold the shape.  The caller all-gathers the ranks' parts IN RANK ORDER and hands the [G][n] buffer to the next
+ * coper_train_sync_next, which adds them in ascending g: every rank derives the same bits from the same buffer, no all-reduce order
+ * enters.  When a call returns, everything it handed out is ordered on the caller's stream (the state's side streams are joined).
+ *   begin:   zeroing, the conv filters, the conv; the column sums of Conv1BN's input            hands out 2 conv_num_channels
+ *   next 1:  Conv1BN with the batch's statistics, ReLU, dropout, the dense layer; FCBN's column sums      2 ent_emb_size
+ *   next 2:  FCBN, the scorer, the loss, the scorer's backward; FCBN's backward sums                      2 ent_emb_size
+ *   next 3:  FCBN's backward, the dense layer's, the generators' chains; Conv1BN's backward sums          2 conv_num_channels
+ *   next 4:  Conv1BN's backward, the conv's, the filters'                                                 0: the step is complete
+ * *n_out == 0: the handle is exactly where coper_train_backward / _csr (rows = 0) or coper_train_rows_backward (rows = 1; the
+ * deferred-rows mode is required) leaves it: gradients pending for coper_train_grads_export | _apply (coper_train_rows_export | _import |
+ * _apply), the dropout counter moved once, the moving statistics updated.  With batch_norm_train_stats off there is nothing to
+ * exchange: begin runs the whole backward and returns *n_out = 0.  coper_train_sync_part_len: the largest n of a step,
+ * 2 * max(conv_num_channels, ent_emb_size).  coper_train_sync_phase: 0 no step open, 1 .. 4 the exchange the state waits for
+ * (negative: -COPER_EINVAL for a NULL handle, -COPER_ESTATE without a training state).
+ *   - loss_out receives the mean over THIS rank's labels (in next 2), as coper_train_backward's.
+ *   - The gradients of the two layers' gamma and beta are this rank's share (its own sums): the caller's sum over ranks completes them.
+ *   - Dropout masks are a function of the element's position in the WHOLE batch: sample sample_offset + b draws what sample
+ *     sample_offset + b of one handle's B_global-sample step draws, so the G shards draw that step's masks.
+ *   - The batch's buffers (e1, rel, lookup, labels, the label lists) are read by later phases: they stay valid and unchanged until the
+ *     step is complete or abandoned.  A world of one (G = 1, its own part handed back) leaves the bits of coper_train_backward in
+ *     deterministic mode.
+ *   - Any step-shaped call while a step is open (coper_train_step*, _backward*, _forward*, _rows_backward, another begin) abandons it,
+ *     as a pending coper_train_backward is dropped: each zeroes the accumulators first.  coper_train_grads_export / _apply /
+ *     _rows_export / _rows_apply in the middle of a step return COPER_ESTATE.  A coper_train_sync_next that fails leaves no step open.
+ * Refused: no training state, or coper_train_sync_next with no step open: COPER_ESTATE.  rows not 0 or 1; B_global no multiple of B or
+ *   sample_offset + B > B_global; part_cap below the call's n; NULL or misaligned (8 bytes) buffers; G < 1; (sample_offset + B)
+ *   features past the 32-bit dropout counter: COPER_EINVAL.  rows = 1 outside the deferred-rows mode: COPER_ESTATE; rows = 0 inside it,
+ *   and an entity-sharded state: COPER_EUNSUPPORTED.  A generator with hidden layers (context_rel_out / context_rel_conv) AND
+ *   context_rel_use_batch_norm AND batch statistics on: COPER_EUNSUPPORTED -- its hidden BN layers take statistics over the batch as
+ *   well, and synchronising them is deliberately not built (hidden layers without context BN are served).
+ * Left out: a synchronised coper_train_forward; statistics across micro-batches; overlap of the exchanges with compute; graph capture
+ *   of the phase calls. */
+COPER_API int coper_train_sync_begin(coper_handle* h, const int64_t* e1, const int64_t* rel, const int32_t* lookup, const float* labels,
+                                     int64_t B, int64_t L, int64_t B_global, int64_t sample_offset, int32_t rows, double* part_out,
+                                     int64_t part_cap, int64_t* n_out, float* loss_out, void* stream);
+COPER_API int coper_train_sync_begin_csr(coper_handle* h, const int64_t* e1, const int64_t* rel, const int64_t* lab_indptr,
+                                         const int64_t* lab_idx, const int64_t* lab_row, int64_t n_rows, int64_t B, int64_t B_global,
+                                         int64_t sample_offset, double* part_out, int64_t part_cap, int64_t* n_out, float* loss_out,
+                                         void* stream);
+COPER_API int coper_train_sync_next(coper_handle* h, const double* parts_in /* [G][n] of the last n_out */, int32_t G, double* part_out,
+                                    int64_t part_cap, int64_t* n_out, void* stream);
+COPER_API int coper_train_sync_phase(const coper_handle* h);
+COPER_API int64_t coper_train_sync_part_len(const coper_handle* h);
 
 #ifdef __cplusplus
 }
