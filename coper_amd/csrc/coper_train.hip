@@ -19,7 +19,7 @@
 //   d(loss)/d(logits) matrix and one GEMM.  Every GEMM is the split-fp16 MFMA kernel of train_gemm_bf16.hip (no library).
 //   optimiser: tf.clip_by_global_norm + AMSGrad (amsgrad.py:130-159), one launch each over all tensors.
 //   Schedule (round 6): the scorer's backward and the dP product run on two side streams of the training state, forked from and
-//   joined to the caller's stream by events (SideJoin; the forks and joins are in train_step_impl and where a phase begins); K slices of the few-tile products are added by the
+//   joined to the caller's stream by events (SideJoin; the forks are where a stage begins, the joins in Step::join_sides at the end of a call); K slices of the few-tile products are added by the
 //   kernels that consume them (k_tr_fc_post_slices, k_tr_bn1_bwd_sums<NS>), not by a launch of their own.
 //   Deterministic mode (coper_train_config.deterministic): every atomic accumulation above has a second form with one defined
 //   order -- per-workgroup partial sums in TrainState::det_slab folded by k_tr_fold_det, one writer per embedding / relation row
@@ -35,7 +35,7 @@
 //   num_ent; the heads are the deferred-rows mode's row list, in ascending id, and its norm goes through the slab.  Off: nothing changes.
 //   Entity-sharded 1-vs-all (coper_train_init_sharded): the handle holds rows [shard_lo, shard_hi) of the two tables with their
 //   gradients and slots; the step is four calls -- coper_train_shard_forward | _score_csr or _score_lookup (sampled labels, DESIGN 6.8:
-//   the sampled scorer below over the handle's row range) | _backward | _apply -- over the phases below,
+//   the sampled scorer below over the handle's row range) | _backward | _apply -- three ranges of the stage list and the update,
 //   with the caller's exchanges between them (input rows, the shards' shares of dh and the loss, their squared norms).  A deterministic
 //   state only; kernels of its own in train_shard.h.  Every other entry point behaves as it did.
 //   Deferred rows on a shard: coper_train_defer_rows on such a state, between steps; the row state is per LOCAL row.  The
@@ -44,11 +44,18 @@
 //   (k_shard_list_owned) and catches it up, the backward call's squared norm and the apply call's table update run over that list.  With
 //   the mode off a sharded step launches what it launched.
 //   Synchronised batch statistics (coper_train_sync_begin | _next): the backward of a data-parallel rank whose Conv1BN / FCBN
-//   statistics span every rank's shard of one batch -- the phases below cut where a batch-wide sum is needed (fwd_conv_sums | fwd_bn1,
-//   fwd_fcbn_sums | _apply, bwd_fcbn_sums | _apply, bwd_bn1_sums | _apply), five calls with the caller's all-gathers between them, the
-//   ranks' shares added in ascending rank (k_tr_fold_parts).  Every other entry point runs the halves back to back, as one launch list.
-// This file is the host side: the training state, the GEMM helpers, init / destroy, the step as a schedule of phases (struct Step,
-// train_step_impl) and the small entry points.  The kernels are in train_kernels.h.
+//   statistics span every rank's shard of one batch -- the stage list is cut where a batch-wide sum is needed (behind Bn1Sums, FcbnSums,
+//   FcbnBwdSums, Bn1BwdSums: kSyncCuts), five calls with the caller's all-gathers between them, the ranks' shares added in ascending
+//   rank (k_tr_fold_parts).  Every other entry point runs the halves back to back, as one launch list.
+// This file is the host side: the training state, the GEMM helpers, init / destroy, the step and the small entry points.  The kernels
+// are in train_kernels.h.
+//   The schedule is written ONCE: enum class Stage lists the stages of a step in execution order -- ConvFilters, Bn1Sums, Bn1, Dense,
+//   FcbnSums, Fcbn, Score | ScorerBwd, FcbnBwdSums, FcbnBwd, DenseBwd, ChainsBwd, Bn1BwdSums, Bn1Bwd, ConvBwd, ConvFiltersBwd -- and
+//   Step::run(from, to) executes a range of it; nothing else calls a stage.  Every entry point is its preamble (refusals, workspaces,
+//   the zero list, the row lists) and ranges: the fused calls [ConvFilters, End) or, forward only, [ConvFilters, ScorerBwd) in
+//   train_step_impl; the sharded calls [ConvFilters, Score) | [Score, FcbnBwdSums) | [FcbnBwdSums, End); the synchronised step
+//   [ConvFilters, Bn1) and the four rows of kSyncCuts.  A step that stays open between calls is ONE record, TrainState::open (OpenStep:
+//   the arguments, the StepCarry, the phase), resumed by open_resume and suspended by `open.carry = st`.
 //   What a call is (StepKind) and which route its scorer takes (ScorerPlan: label form, table-gradient route, dh route, the owned row
 //   range) are decided ONCE per call -- plan_scorer, and ScorerPlan::resolve_dh behind the workspaces -- and read everywhere else: the
 //   refusals, the workspace sizes and the launches cannot disagree.  Every update ends in the same tail: a tensor table from
@@ -81,8 +88,8 @@ struct TrainParam {
   DevBuf<float> vh;
 };
 
-// What the forward phases of a step hand to its backward phases (a base of struct Step).  The entity-sharded step runs them in
-// different calls and keeps it on the state between them (TrainState::shard_carry): one assignment each way.
+// What the forward stages of a step hand to its backward stages (a base of struct Step).  A step held open between calls keeps it on
+// the state (OpenStep, below struct StepArgs): one assignment each way.
 struct StepCarry {
   const unsigned* w_slots = nullptr;  // the dense weights' maximum as the last step's optimizer pass left it, when it describes them
   const unsigned* x_slots = nullptr;  // the dense input's, as k_tr_bn1_fwd wrote it
@@ -95,18 +102,86 @@ struct StepCarry {
   // ordered rows: the sorted entry indices, and the batch's unique rows with their segment offsets (Step::order_rows; null until it ran)
   const int32_t *ord_vals = nullptr, *ord_rows = nullptr, *ord_rows_count = nullptr;
 };
-// A step whose batch statistics span several ranks, open between its calls (coper_train_sync_begin | _next): the arguments
-// of the begin call (the caller keeps the batch's buffers as they are until the step is complete or abandoned), what its phases hand on
-// (as the entity-sharded step keeps its StepCarry), and `phase`: 0 no step open, 1..4 the exchange the state waits for.
-struct SyncOpen {
-  int phase = 0;
-  bool rows = false, csr = false;
-  const int64_t *e1 = nullptr, *rel = nullptr, *lab_indptr = nullptr, *lab_idx = nullptr, *lab_row = nullptr;
+
+// 1-vs-all labels as id lists (include/coper_hip.h, coper_train_step_csr); indptr == nullptr: the dense-label call
+struct CsrLabels {
+  const int64_t *indptr = nullptr, *idx = nullptr, *row = nullptr;
+  int64_t n_rows = 0;
+};
+
+// What a call of the step is: coper_train_forward; coper_train_step; coper_train_backward (everything but the optimizer);
+// coper_train_rows_backward (the same in the deferred-rows mode)
+enum class StepKind { Forward, Step, Backward, RowsBackward };
+inline bool differentiates(StepKind k) { return k != StepKind::Forward; }
+inline bool runs_optimizer(StepKind k) { return k == StepKind::Step; }
+inline bool keeps_moving_stats(StepKind k) { return k == StepKind::Forward; }      // (k_tr_bn_finish leaves the moving statistics alone)
+
+// ---- the scorer's routes, decided once per call
+// the dense d(loss)/d(logits) matrix S [B, |E|] fits: 1-vs-all trains through it, the sampled scorer's backward is a GEMM on it
+inline bool dense_S_fits(int64_t B, int64_t E) { return (double)B * (double)E * 4.0 <= 512.0 * 1024 * 1024 && E <= 0x7fffffff; }
+enum class LabelForm { Dense, Csr, Sampled };      // labels [B, |E|] (or none: a sharded call that scores nothing); id lists; [B, L] with a lookup
+// d(ent_emb) / d(pred_bias): one GEMM on the S of 1-vs-all; per chunk of entity columns (Step::score_csr); the dense S built from the
+// lookup and one GEMM; sorted segments, one writer per row (ordered rows, a sharded state); float atomics
+enum class TableGrad { OvaGemm, CsrChunks, DenseS, Ordered, Atomics };
+// dh [B, d]: a GEMM on S (1-vs-all); from the pass that formed the scores (k_tr_score_loss_dh); k_tr_dh_gather4; k_tr_score_bwd
+enum class DhRoute { Gemm, Fused, Gather4, ScoreBwd };
+struct ScorerPlan {
+  LabelForm labels = LabelForm::Dense;
+  TableGrad table = TableGrad::OvaGemm;
+  DhRoute dh = DhRoute::Gemm;
+  size_t lds_fused = 0;         // k_tr_score_loss_dh's dynamic LDS (DhRoute::Fused)
+  bool shard = false;           // an entity-sharded state (DESIGN 6.7): the tables are rows [lo, lo + n) of num_ent, the sampled kernels
+  int64_t lo = 0, n = 0;        //   take their SHARD forms; otherwise [0, num_ent)
+  bool current = false;         // (with shard) the forward-only sharded call in the deferred-rows mode (DESIGN 6.12): the sampled kernels take
+                                //   their CURRENT forms -- every owned row as of the current update in registers, nothing written
+  bool sampled() const { return labels == LabelForm::Sampled; }
+  bool ordered() const { return table == TableGrad::Ordered; }
+  // The part that looks at pointers, once the workspaces exist (ent is the caller's: nothing here follows from an allocator).
+  void resolve_dh(int d, int64_t L, const float* ent, const float* dh_ws, const float* hv_ws) {
+    if (!sampled()) return;
+    dh = DhRoute::ScoreBwd;
+    if (table == TableGrad::Atomics) return;      // (k_tr_score_bwd<true>: dh beside its atomics)
+    // the gather: 16-byte rows; fused with the scores: a training step whose dE goes through S or the segments takes scores, loss, ds
+    // and dh from one pass over the rows (coper_train_forward takes the same kernel: its loss is the step's, bit for bit)
+    if (!((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)dh_ws) & 15) == 0)) return;
+    dh = DhRoute::Gather4;
+    if (!(L >= 1 && L <= SF_MAX_L && ((uintptr_t)hv_ws & 15) == 0)) return;
+    dh = DhRoute::Fused;
+    const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
+    // (SHARD: the compacted entries' positions, int [L] more)
+    lds_fused = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + (shard ? 2 : 1) * sizeof(int) * (size_t)L;
+    // (CURRENT: every compacted entry's C and whether it is behind, double [L] and a byte [L] more -- where that passes the 160 KB of a
+    //  workgroup the launch is refused by the caller, never served by another route: the route decides the bits)
+    if (current) lds_fused += (sizeof(double) + 1) * (size_t)L;
+  }
+};
+
+// One call of the step: the arguments, and what they and the configuration decide once (struct Step: the stages over them).
+struct StepArgs {
+  StepKind kind = StepKind::Step;
+  hipStream_t s = nullptr;
+  const int64_t *e1 = nullptr, *rel = nullptr;
   const int32_t* lookup = nullptr;
   const float* labels = nullptr;
-  int64_t B = 0, L = 0, n_rows = 0, B_global = 0, sample_offset = 0;
-  float* loss_out = nullptr;
+  int64_t B = 0, L = 0;
+  float *loss_out = nullptr, *pred_out = nullptr, *h_out = nullptr;
+  CsrLabels csr;                    // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
+  const float* img_rows = nullptr;  // the entity-sharded step (DESIGN 6.7): the input images are the rows of img_rows [B, d] (the gathered e1 rows), never the table's
+  ScorerPlan plan;                  // plan_scorer of the same call; its dh route once grow_workspaces has run
+  // synchronised batch statistics (DESIGN 6.13): the batch is rows [sample_offset, sample_offset + B) of a batch of B_stat samples that
+  // the BN statistics are taken over (0: the batch is its own) -- the dropout masks are drawn by the position in THAT batch
+  int64_t B_stat = 0, sample_offset = 0;
+};
+// A step held open between calls: the synchronised step (coper_train_sync_begin | _next) and the entity-sharded step
+// (coper_train_shard_forward | _score_* | _backward | _apply) -- a state runs one or the other.  `args`: the arguments of the
+// call that opened it (the begin call's: the caller keeps the batch's buffers as they are until the step is complete or abandoned; the
+// sharded forward call's, over the state's own copy of the ids, amended by the score call with its labels).  `carry`: what the stages
+// that ran hand to the ones to come.  `phase`: 0 no step open; a synchronised step: 1..4, the exchange the state waits for; a sharded
+// state: the call expected next (ShardPhase).  Every later call resumes it (open_resume) and suspends it again (`open.carry = st`).
+struct OpenStep {
+  StepArgs args;
   StepCarry carry;
+  int phase = 0;
 };
 
 // the owner of one operand plane set of the split-16 GEMMs; the GEMM helpers take the TgPlanes it hands out
@@ -255,22 +330,18 @@ struct TrainState {
   int64_t ord_cap = 0;
   DevBuf<int32_t> ord_key[2], ord_val[2], ord_seg, ord_hist, ord_scan, ord_list, ord_count;
   bool rows_list_unsorted = false;
-  // entity-sharded 1-vs-all (coper_train_init_sharded).  shard_phase: the call the state machine expects next (ShardPhase).
-  // sh_e1 / sh_rel: the batch's ids as the forward call saw them (the backward call has no id arguments); sh_iota: 0 .. B - 1, the row
-  // numbers of the gathered input rows.  shard_carry: what the forward phases hand to the backward ones across the calls.  sh_labels: the
-  // labels the step's loss is a mean over, as the score call that ran counts them (B num_ent: 1-vs-all; B L: sampled).
-  // Deferred rows on a shard: the row state above is per LOCAL row; sh_L: the L of the sampled score call (the backward call's
-  // bound of the list, min(B (L + 1), n_local)).
+  // entity-sharded 1-vs-all (coper_train_init_sharded).  sh_e1 / sh_rel: the batch's ids as the forward call saw them (the
+  // open step's arguments name them: the later calls have no id arguments); sh_iota: 0 .. B - 1, the row numbers of the gathered input
+  // rows.  Deferred rows on a shard: the row state above is per LOCAL row.
   bool sharded = false;
-  int shard_phase = 0;
-  int64_t sh_B = 0, sh_cap = 0, sh_L = 0;
+  int64_t sh_cap = 0;
   bool sh_stepped = false;     // a sharded step has begun on this state: the deferred-rows mode is no longer ENABLED on it (it is chosen before the first step)
-  double sh_labels = 1.0;
   DevBuf<int64_t> sh_e1, sh_rel, sh_iota;
-  StepCarry shard_carry;
-  // synchronised batch statistics (coper_train_sync_*): the open step, and [2][2 mx] doubles -- the backward sums of the whole
-  // batch as the last fold left them | this rank's FCBN backward sums (Conv1BN's own stay in their slice of `red`)
-  SyncOpen sync;
+  // the step held open between calls: a synchronised step, or on a sharded state the step of the four calls (OpenStep)
+  OpenStep open;
+  int sync_phase() const { return sharded ? 0 : open.phase; }      // the exchange an open synchronised step waits for (0: none is open)
+  // synchronised batch statistics (coper_train_sync_*): [2][2 mx] doubles -- the backward sums of the whole batch as the
+  // last fold left them | this rank's FCBN backward sums (Conv1BN's own stay in their slice of `red`)
   DevBuf<double> sync_sums;
   TrainParam* find(const char* name) {
     for (auto& t : tp)
@@ -539,16 +610,11 @@ namespace {
 
 inline dim3 grid1d(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
-// the entity-sharded step's state machine (TrainState::shard_phase): the call expected next
+// the entity-sharded step's state machine (OpenStep::phase on a sharded state): the call expected next
 enum ShardPhase { SHP_FORWARD = 0, SHP_SCORE = 1, SHP_BACKWARD = 2, SHP_APPLY = 3 };
 const char* const kShardCall[4] = {"coper_train_shard_forward", "coper_train_shard_score_csr or coper_train_shard_score_lookup",
                                    "coper_train_shard_backward", "coper_train_shard_apply"};
 
-// 1-vs-all labels as id lists (include/coper_hip.h, coper_train_step_csr); indptr == nullptr: the dense-label call
-struct CsrLabels {
-  const int64_t *indptr = nullptr, *idx = nullptr, *row = nullptr;
-  int64_t n_rows = 0;
-};
 constexpr int64_t TR_OVA_GRAIN = 128;                            // a chunk of entity columns is rows of a GEMM operand plane: TG_ROW_PAD
 constexpr int64_t TR_OVA_WS_BYTES = 256LL * 1024 * 1024;         // the [B, chunk] logits of the library's own choice (as coper_rank_counts')
 // entity columns per chunk of the sparse-label step: the request rounded up to the grain, or the widest multiple of it within the bound
@@ -558,52 +624,7 @@ inline int64_t ova_chunk(int64_t B, int64_t E, int32_t request) {
   return c < E ? c : E;
 }
 
-// What a call of the step is: coper_train_forward; coper_train_step; coper_train_backward (everything but the optimizer);
-// coper_train_rows_backward (the same in the deferred-rows mode)
-enum class StepKind { Forward, Step, Backward, RowsBackward };
-inline bool differentiates(StepKind k) { return k != StepKind::Forward; }
-inline bool runs_optimizer(StepKind k) { return k == StepKind::Step; }
-inline bool keeps_moving_stats(StepKind k) { return k == StepKind::Forward; }      // (k_tr_bn_finish leaves the moving statistics alone)
-
-// ---- the scorer's routes, decided once per call
-// the dense d(loss)/d(logits) matrix S [B, |E|] fits: 1-vs-all trains through it, the sampled scorer's backward is a GEMM on it
-inline bool dense_S_fits(int64_t B, int64_t E) { return (double)B * (double)E * 4.0 <= 512.0 * 1024 * 1024 && E <= 0x7fffffff; }
-enum class LabelForm { Dense, Csr, Sampled };      // labels [B, |E|] (or none: a sharded call that scores nothing); id lists; [B, L] with a lookup
-// d(ent_emb) / d(pred_bias): one GEMM on the S of 1-vs-all; per chunk of entity columns (Step::score_csr); the dense S built from the
-// lookup and one GEMM; sorted segments, one writer per row (ordered rows, a sharded state); float atomics
-enum class TableGrad { OvaGemm, CsrChunks, DenseS, Ordered, Atomics };
-// dh [B, d]: a GEMM on S (1-vs-all); from the pass that formed the scores (k_tr_score_loss_dh); k_tr_dh_gather4; k_tr_score_bwd
-enum class DhRoute { Gemm, Fused, Gather4, ScoreBwd };
-struct ScorerPlan {
-  LabelForm labels = LabelForm::Dense;
-  TableGrad table = TableGrad::OvaGemm;
-  DhRoute dh = DhRoute::Gemm;
-  size_t lds_fused = 0;         // k_tr_score_loss_dh's dynamic LDS (DhRoute::Fused)
-  bool shard = false;           // an entity-sharded state (DESIGN 6.7): the tables are rows [lo, lo + n) of num_ent, the sampled kernels
-  int64_t lo = 0, n = 0;        //   take their SHARD forms; otherwise [0, num_ent)
-  bool current = false;         // (with shard) the forward-only sharded call in the deferred-rows mode (DESIGN 6.12): the sampled kernels take
-                                //   their CURRENT forms -- every owned row as of the current update in registers, nothing written
-  bool sampled() const { return labels == LabelForm::Sampled; }
-  bool ordered() const { return table == TableGrad::Ordered; }
-  // The part that looks at pointers, once the workspaces exist (ent is the caller's: nothing here follows from an allocator).
-  void resolve_dh(int d, int64_t L, const float* ent, const float* dh_ws, const float* hv_ws) {
-    if (!sampled()) return;
-    dh = DhRoute::ScoreBwd;
-    if (table == TableGrad::Atomics) return;      // (k_tr_score_bwd<true>: dh beside its atomics)
-    // the gather: 16-byte rows; fused with the scores: a training step whose dE goes through S or the segments takes scores, loss, ds
-    // and dh from one pass over the rows (coper_train_forward takes the same kernel: its loss is the step's, bit for bit)
-    if (!((d & 3) == 0 && d >= 16 && d <= 1024 && (((uintptr_t)ent | (uintptr_t)dh_ws) & 15) == 0)) return;
-    dh = DhRoute::Gather4;
-    if (!(L >= 1 && L <= SF_MAX_L && ((uintptr_t)hv_ws & 15) == 0)) return;
-    dh = DhRoute::Fused;
-    const int d4 = d >> 2, slots = 256 / d4 > 256 / SF_U ? 256 / SF_U : 256 / d4, RB = SF_U * slots;
-    // (SHARD: the compacted entries' positions, int [L] more)
-    lds_fused = sizeof(float4) * (size_t)slots * d4 + sizeof(float) * (size_t)RB * (d4 + 2) + (shard ? 2 : 1) * sizeof(int) * (size_t)L;
-    // (CURRENT: every compacted entry's C and whether it is behind, double [L] and a byte [L] more -- where that passes the 160 KB of a
-    //  workgroup the launch is refused by the caller, never served by another route: the route decides the bits)
-    if (current) lds_fused += (sizeof(double) + 1) * (size_t)L;
-  }
-};
+// The plan of a call's scorer (ScorerPlan, above the training state)
 // (deferred rows: the atomic route at every |E| -- the GEMM writes all of dE;  ordered rows: the sorted-segment route at every |E| --
 //  one arithmetic for every table size;  a sharded state's sampled score call, DESIGN 6.8: always that route)
 static ScorerPlan plan_scorer(const coper_handle* h, const TrainState* T, const int32_t* lookup, const CsrLabels& csr, int64_t B) {
@@ -880,23 +901,16 @@ static bool optimizer_launch(coper_handle* h, TrainState* T, hipStream_t s, cons
   return tt.wmax != nullptr;
 }
 
-// One call of the step: the arguments, what they and the configuration decide once, the few values a phase hands to a later one, and
-// the phases themselves in the order of the header comment's schedule (train_step_impl runs them).
-struct StepArgs {
-  StepKind kind = StepKind::Step;
-  hipStream_t s = nullptr;
-  const int64_t *e1 = nullptr, *rel = nullptr;
-  const int32_t* lookup = nullptr;
-  const float* labels = nullptr;
-  int64_t B = 0, L = 0;
-  float *loss_out = nullptr, *pred_out = nullptr, *h_out = nullptr;
-  CsrLabels csr;                    // the sparse-label 1-vs-all step: `labels` is null, the scorer runs in chunks (score_csr)
-  const float* img_rows = nullptr;  // the entity-sharded step (DESIGN 6.7): the input images are the rows of img_rows [B, d] (the gathered e1 rows), never the table's
-  ScorerPlan plan;                  // plan_scorer of the same call; its dh route once grow_workspaces has run
-  // synchronised batch statistics (DESIGN 6.13): the batch is rows [sample_offset, sample_offset + B) of a batch of B_stat samples that
-  // the BN statistics are taken over (0: the batch is its own) -- the dropout masks are drawn by the position in THAT batch
-  int64_t B_stat = 0, sample_offset = 0;
+// The stages of a step in execution order: the one schedule of this file.  Every entry point runs a range of it (Step::run) -- the fused
+// calls [ConvFilters, End) or, forward only, [ConvFilters, ScorerBwd); the calls of a step held open (OpenStep) the ranges between their
+// exchanges.  The *Sums stages end where a batch-wide sum is needed.
+enum class Stage {
+  ConvFilters, Bn1Sums, Bn1, Dense, FcbnSums, Fcbn, Score,
+  ScorerBwd, FcbnBwdSums, FcbnBwd, DenseBwd, ChainsBwd, Bn1BwdSums, Bn1Bwd, ConvBwd, ConvFiltersBwd, End
 };
+
+// One call of the step: its arguments (StepArgs), what they and the configuration decide once, the few values a stage hands to a later
+// one (and StepCarry), the stages themselves and run(), which executes a range of them.
 struct Step : StepArgs, StepCarry {
   coper_handle* const h;
   TrainState* const T;
@@ -932,6 +946,11 @@ struct Step : StepArgs, StepCarry {
   int t_slices = 1, dx_slices = 1;   // K slices the T and dx products left for k_tr_fc_post_slices / k_tr_bn1_bwd_sums to add
   const TrainParam* sumsq_done = nullptr;   // the leaf whose squared gradient norm its own GEMM accumulated
   const int32_t *rows_list = nullptr, *rows_count = nullptr;   // deferred rows: the rows this call claimed (rows_claim_catch_up)
+  // Set by the driver of a step that is open across exchanges (coper_train_sync_next): TrainState::sync_sums, [2][2 mx] doubles.  The
+  // FCBN backward runs as its sums | apply pair around the exchange and the two backward apply stages read the whole batch's sums from
+  // [0] (bwd_all_sums); null (every other call): one k_tr_fcbn_bwd launch, and Conv1BN's backward reads this call's own sums.
+  double* sync_sums = nullptr;
+  double* bwd_all_sums() const { return sync_sums; }
   bool scorer_bwd_on_side() const { return two_streams && plan.dh == DhRoute::Fused && tg_split_k(dm.E, d, B) == 1; }
 
   int grow_workspaces() {
@@ -1184,9 +1203,8 @@ struct Step : StepArgs, StepCarry {
     }
   }
   // the conv, Conv1BN, ReLU, dropout -> x [B, F_conv]; concat_rel: [x | c]
-  void fwd_conv_bn1() { fwd_conv_sums(); fwd_bn1(); }
-  // ... in two halves, cut where a batch-wide sum is needed: the conv and the column sums of this call's rows | the
-  // statistics from the sums (over Bn samples) and what follows.  bn1_fwd_sums(): where the first half leaves the sums.
+  // In two stages, cut where a batch-wide sum is needed: the conv and the column sums of this call's rows | the
+  // statistics from the sums (over Bn samples) and what follows.  bn1_fwd_sums(): where the first stage leaves the sums.
   double* bn1_fwd_sums() const { return red.cs_slots(CSS_BN1_FWD); }
   void fwd_conv_sums() {
     const size_t lds_conv = sizeof(float) * (size_t)(isz + (NT + 1) * C);
@@ -1263,7 +1281,7 @@ struct Step : StepArgs, StepCarry {
     return COPER_OK;
   }
 
-  void fwd_fcbn() { fwd_fcbn_sums(); fwd_fcbn_apply(); }
+  // FCBN -> h [B, d], in two stages as Conv1BN
   double* fcbn_fwd_sums() const { return red.colsum_slice(CS_FCBN); }
   void fwd_fcbn_sums() {
     double* const cs = fcbn_fwd_sums();
@@ -1478,18 +1496,21 @@ struct Step : StepArgs, StepCarry {
     return COPER_OK;
   }
 
-  void bwd_fcbn() {
-    hipLaunchKernelGGL(k_tr_fcbn_bwd, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d,
-                       use_batch, lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
+  // FCBN and ReLU backward -> dz: one launch, all of it in the second stage.  A step open across exchanges (sync_sums) takes two, around
+  // the exchange: this rank's sums into their half of sync_sums | dz from the sums of the whole batch, the gamma / beta gradients from
+  // the rank's own
+  double* fcbn_bwd_sums() const { return sync_sums + (size_t)2 * T->mx; }
+  void bwd_fcbn_sums() {
+    if (!sync_sums) return;
+    hipLaunchKernelGGL(k_tr_fcbn_bwd_sums, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, B, d, fcbn_bwd_sums());
   }
-  // ... in two launches around the exchange of a synchronised step (batch statistics on): this rank's sums into `own` | dz from the sums
-  // of the whole batch, the gamma / beta gradients from `own`
-  void bwd_fcbn_sums(double* own) {
-    hipLaunchKernelGGL(k_tr_fcbn_bwd_sums, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, B, d, own);
-  }
-  void bwd_fcbn_apply(const double* all, const double* own) {
-    hipLaunchKernelGGL(k_tr_fcbn_bwd_apply, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d, (double)Bn,
-                       all, own, lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
+  void bwd_fcbn_apply() {
+    if (!sync_sums)
+      hipLaunchKernelGGL(k_tr_fcbn_bwd, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d,
+                         use_batch, lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
+    else
+      hipLaunchKernelGGL(k_tr_fcbn_bwd_apply, dim3((unsigned)d), dim3(256), 0, s, T->z1, T->hv, T->dh, mean2, inv2, lv.fcbn.gamma->p, B, d, (double)Bn,
+                         (const double*)sync_sums, (const double*)fcbn_bwd_sums(), lv.fcbn.gamma->g, lv.fcbn.beta->g, T->dz);
   }
   // dT[rho][b,:] = cw[b,rho] dz[b,:];  dP[rho][f][k] = sum_b x[b][f] dT[rho][b][k]  and
   // dx[b][f] = sum_(rho,k) dT[rho][b][k] P[rho][f][k]: two split-bf16 GEMMs, the [B, r*F] intermediate dz P2^T is never formed
@@ -1587,7 +1608,7 @@ struct Step : StepArgs, StepCarry {
     }
   }
   // dropout, ReLU and Conv1BN backward on dx (the K slices of the dx product, where it left them, are added on the way)
-  void bwd_bn1() { bwd_bn1_sums(); bwd_bn1_apply(bn1_bwd_sums()); }
+  // In two stages: this call's sums | the apply.
   double* bn1_bwd_sums() const { return red.cs_slots(CSS_BN1_BWD); }
   void bwd_bn1_sums() {
     double* const colsum = bn1_bwd_sums();
@@ -1610,7 +1631,8 @@ struct Step : StepArgs, StepCarry {
     }
   }
   // all: the sums over the positions the statistics were taken over (this call's own, or the whole batch's of a synchronised step)
-  void bwd_bn1_apply(const double* all) {
+  void bwd_bn1_apply() {
+    const double* const all = sync_sums ? sync_sums : bn1_bwd_sums();
     hipLaunchKernelGGL(k_tr_bn1_bwd_apply, grid1d(nBF), dim3(256), 0, s, T->dx, T->y, mean1, inv1, lv.bn1.gamma->p, all, (const double*)bn1_bwd_sums(), C, nBF,
                        (double)Bn * P, use_batch, lv.bn1.gamma->g, lv.bn1.beta->g);
   }
@@ -1671,12 +1693,80 @@ struct Step : StepArgs, StepCarry {
       else
         hipLaunchKernelGGL(k_tr_scatter_rows, grid1d(B * r), dim3(256), 0, s, T->chain[g].dv[0], rel, dm.R, r, B * r, lv.rel_emb->g);
   }
+  // ---- the schedule: stages [from, to) in order, to the first failure.  The only caller of the stage functions above.
+  int run(Stage from, Stage to) {
+    int rc = COPER_OK;
+    for (int i = (int)from; i < (int)to && !rc; ++i) switch ((Stage)i) {
+      case Stage::ConvFilters: fwd_conv_filters(); break;
+      case Stage::Bn1Sums: fwd_conv_sums(); break;
+      case Stage::Bn1: fwd_bn1(); break;
+      case Stage::Dense: rc = fwd_dense(); break;
+      case Stage::FcbnSums: fwd_fcbn_sums(); break;
+      case Stage::Fcbn: fwd_fcbn_apply(); break;
+      case Stage::Score: rc = csr.indptr ? score_csr() : fwd_score_loss(); break;      // (score_csr: the scorer's backward too, chunk by chunk)
+      case Stage::ScorerBwd:      // (nothing left to do behind score_csr; the fork is joined in front of the conv backward, or by the driver)
+        if (scorer_bwd_on_side()) sj.fork(SJ_SCORER_BWD, 0);
+        rc = bwd_scorer();
+        break;
+      case Stage::FcbnBwdSums: bwd_fcbn_sums(); break;
+      case Stage::FcbnBwd: bwd_fcbn_apply(); break;
+      case Stage::DenseBwd: rc = bwd_dense(); break;      // (generated: forks SJ_DP in front of the dP product, bwd_dense_dP)
+      case Stage::ChainsBwd: if (gen) { chain_backward(0, nh); chain_backward(1, nh); } break;
+      case Stage::Bn1BwdSums: bwd_bn1_sums(); break;
+      case Stage::Bn1Bwd: bwd_bn1_apply(); break;
+      case Stage::ConvBwd: bwd_conv(); break;             // (joins SJ_SCORER_BWD in front of its launch)
+      case Stage::ConvFiltersBwd: bwd_conv_filters(); break;
+      case Stage::End: break;
+    }
+    return rc;
+  }
+  // what the side streams were given is joined before a call returns: the optimizer, an exchange and the next call find it done
+  int join_sides(const char* what) {
+    sj.join(SJ_DP);      // (dP and its squared norm)
+    sj.join(SJ_SCORER_BWD);
+    return sj.err == hipSuccess ? COPER_OK : fail(h, COPER_EHIP, std::string(what) + ": an event call of the side streams failed");
+  }
   // ---- clip + AMSGrad
   bool optimizer() {
     return optimizer_launch(h, T, s, nullptr, sumsq_done, lk ? h->grouping().rel_count : nullptr, 1.0, rows_list, rows_count, false,
                             std::min<int64_t>(B * (L + 1), dm.E));
   }
 };
+
+// A step held open (TrainState::open) goes on in this call: a Step over the stored arguments -- `args`: those, or the score call's
+// amended copy -- on this call's stream, its workspace pointers set (nothing grows: the call that opened the step sized them), the
+// carry restored.  The call suspends the step again with `T->open.carry = st`.
+static Step open_resume(coper_handle* h, TrainState* T, StepArgs args, hipStream_t s, int* rc) {
+  args.s = s;
+  Step st(h, T, args);
+  if (!(*rc = st.grow_workspaces())) static_cast<StepCarry&>(st) = T->open.carry;
+  return st;
+}
+
+// The limits a batch meets in every call that runs the forward stages.  grid_rows: the rows the loss kernel of id-list labels sizes
+// its grid by (num_ent on a whole table, the shard's own on a sharded state; 0: the call has no such labels).  `what` names the call;
+// the whole-table step names its id-list entry point in that one refusal.
+static int check_batch_limits(coper_handle* h, const TrainState* T, const std::string& what, int64_t B, int64_t grid_rows) {
+  if (grid_rows && B * ((grid_rows + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff)
+    return fail(h, COPER_EINVAL, what + (T->sharded ? "" : "_csr") + ": batch too large for the loss kernel's grid");
+  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, what + ": batch too large for the dropout counter");
+  // (routes chosen by pointer alignment -- the fused scorer, the 16-byte loss stream of the CSR chunks -- sum in another order)
+  if (T->det && (((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
+    return fail(h, COPER_EUNSUPPORTED, what + ": deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
+  return COPER_OK;
+}
+
+// A backward pass is complete and no update has consumed it: coper_train_backward leaves the gradients where they are for
+// coper_train_grads_export / coper_train_apply; coper_train_rows_backward for coper_train_rows_export / coper_train_rows_apply, the
+// table part being the claimed list
+static void finish_backward(const coper_handle* h, TrainState* T, StepKind kind, int64_t B, int64_t L) {
+  T->step += 1;
+  if (kind == StepKind::Backward) T->pending = true;
+  else {
+    T->rows_pending_small = T->rows_pending_table = true;
+    T->rows_bound = std::min<int64_t>(B * (L + 1), h->dm.E);
+  }
+}
 
 }  // namespace
 
@@ -1747,8 +1837,6 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   if (csr.indptr) {      // sparse 1-vs-all labels: L is num_ent, no [B, L] matrix exists and nothing is indexed by B * L in 32 bits
     if (!e1 || !rel || !csr.idx || B <= 0 || csr.n_rows < 0 || (!csr.row && csr.n_rows != B))
       return fail(h, COPER_EINVAL, "coper_train_step_csr: bad argument (lab_row == NULL needs n_rows == B)");
-    if (B * ((h->dm.E + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff)
-      return fail(h, COPER_EINVAL, "coper_train_step_csr: batch too large for the loss kernel's grid");
   } else {
   if (!e1 || !rel || !labels || B <= 0 || L <= 0 || B * L > 0x7fffffff)
     return fail(h, COPER_EINVAL, "coper_train_step: bad argument");
@@ -1780,15 +1868,12 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
       return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: sampled labels at B*num_ent*4 > 512 MiB take the atomic scorer backward");
     if (lookup && T->rows_ordered && (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff))
       return fail(h, COPER_EINVAL, "coper_train_step: ordered rows: B * (L + 1) ids and num_ent must fit 31 bits");
-    // (routes chosen by pointer alignment -- the fused scorer, the 16-byte loss stream of the CSR chunks -- sum in another order)
-    if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
-      return fail(h, COPER_EUNSUPPORTED, "coper_train_step: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
   }
+  int rc;
+  if ((rc = check_batch_limits(h, T, "coper_train_step", B, csr.indptr ? (int64_t)h->dm.E : 0))) return rc;
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (runs_optimizer(kind)) h->prepared = false;   // the variables change: per-relation caches, fragment images and folded BN go stale
-  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_step: batch too large for the dropout counter");
   Step st(h, T, a);
-  int rc;
   if ((rc = st.grow_workspaces())) return rc;
   if (st.plan.ordered() && (rc = ord_grow(h, T, B * (L + 1), st.s))) return rc;
   if (st.rows) {
@@ -1796,7 +1881,7 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
   }
   T->pending = false;      // (the gradient buffers are zeroed next: what a coper_train_backward left in them is gone)
   T->rows_pending_clear();      // (... and what a coper_train_rows_backward or the imports left: rows_rezero below)
-  T->sync = SyncOpen();         // (... and a synchronised step that was open: abandoned, as a pending backward is dropped)
+  T->open = OpenStep();         // (... and a synchronised step that was open: abandoned, as a pending backward is dropped)
   st.zero_accumulators();
   if (st.rows) {
     rows_rezero_launch(h, T, st.s);
@@ -1806,49 +1891,18 @@ static int train_step_impl(coper_handle* h, const int64_t* e1, const int64_t* re
 
   if (sync && st.use_batch) {      // coper_train_sync_begin: up to the first batch-wide sum; the rest of the step is coper_train_sync_next's
     if ((rc = T->sync_sums.ensure(h, (size_t)4 * T->mx, "synchronised BN sums"))) return rc;
-    st.fwd_conv_filters();
-    st.fwd_conv_sums();
+    if ((rc = st.run(Stage::ConvFilters, Stage::Bn1))) return rc;
     if ((rc = sync_hand_out(h, st.s, st.bn1_fwd_sums(), 2 * (int64_t)st.C, sync->part_out, sync->n_out))) return rc;
     COPER_HIP_TRY(h, hipGetLastError());
-    SyncOpen& o = T->sync;
-    o.rows = kind == StepKind::RowsBackward; o.csr = csr.indptr != nullptr;
-    o.e1 = e1; o.rel = rel; o.lookup = lookup; o.labels = labels; o.B = B; o.L = L; o.loss_out = loss_out;
-    o.lab_indptr = csr.indptr; o.lab_idx = csr.idx; o.lab_row = csr.row; o.n_rows = csr.n_rows;
-    o.B_global = sync->B_global; o.sample_offset = sync->sample_offset;
-    o.carry = st;      // (the StepCarry part)
-    o.phase = 1;
+    T->open = OpenStep{a, st /* the StepCarry part */, 1};
     return COPER_OK;
   }
-  st.fwd_conv_filters();
-  st.fwd_conv_bn1();
-  if ((rc = st.fwd_dense())) return rc;
-  st.fwd_fcbn();
-  if ((rc = csr.indptr ? st.score_csr() : st.fwd_score_loss())) return rc;      // (score_csr: the scorer's backward too, chunk by chunk)
-  if (!differentiates(kind)) {      // coper_train_forward: nothing is differentiated, nothing updated, the step counter (dropout masks) stays
+  // coper_train_forward: nothing is differentiated, nothing updated, the step counter (dropout masks) stays
+  if ((rc = st.run(Stage::ConvFilters, differentiates(kind) ? Stage::End : Stage::ScorerBwd))) return rc;
+  if ((rc = st.join_sides("coper_train_step"))) return rc;
+  if (!runs_optimizer(kind)) {
     COPER_HIP_TRY(h, hipGetLastError());
-    return COPER_OK;
-  }
-
-  if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
-  if ((rc = st.bwd_scorer())) return rc;      // (nothing left to do behind score_csr)
-  st.bwd_fcbn();
-  if ((rc = st.bwd_dense())) return rc;      // (generated: forks SJ_DP in front of the dP product, Step::bwd_dense_dP)
-  if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
-  st.bwd_bn1();
-  st.bwd_conv();                             // (joins SJ_SCORER_BWD in front of its launch)
-  st.bwd_conv_filters();
-
-  st.sj.join(SJ_DP);      // (dP and its squared norm)
-  st.sj.join(SJ_SCORER_BWD);
-  if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_step: an event call of the side streams failed");
-  if (!runs_optimizer(kind)) {      // coper_train_backward: the gradients stay where they are for coper_train_grads_export / coper_train_apply
-    COPER_HIP_TRY(h, hipGetLastError());
-    T->step += 1;
-    if (kind == StepKind::Backward) T->pending = true;
-    else {               // coper_train_rows_backward: ... for coper_train_rows_export / coper_train_rows_apply; the table part is the claimed list
-      T->rows_pending_small = T->rows_pending_table = true;
-      T->rows_bound = std::min<int64_t>(B * (L + 1), h->dm.E);
-    }
+    if (differentiates(kind)) finish_backward(h, T, kind, B, L);
     return COPER_OK;
   }
   const bool wmax_carried = st.optimizer();
@@ -1932,7 +1986,7 @@ COPER_API int coper_train_grads_export(coper_handle* h, float* flat, int64_t cap
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_grads_export: call coper_train_init first");
-  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_grads_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
+  if (T->sync_phase()) return fail(h, COPER_ESTATE, "coper_train_grads_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (T->sharded)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_grads_export: an entity-sharded state (coper_train_init_sharded): no table gradient leaves its shard");
   if (T->rows_deferred)
@@ -1950,7 +2004,7 @@ COPER_API int coper_train_apply(coper_handle* h, const float* flat, int64_t n, d
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_apply: call coper_train_init first");
-  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
+  if (T->sync_phase()) return fail(h, COPER_ESTATE, "coper_train_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (T->sharded)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_apply: an entity-sharded state (coper_train_init_sharded): its update is coper_train_shard_apply");
   if (T->rows_deferred)
@@ -2002,8 +2056,8 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   if (!T) return fail(h, COPER_ESTATE, "coper_train_defer_rows: call coper_train_init first");
   if (enable != 0 && enable != 1) return fail(h, COPER_EINVAL, "coper_train_defer_rows: enable is 0 or 1");
   // (an entity-sharded state, DESIGN 6.11: between steps only -- the list of a step is built, caught up, summed and updated across its calls)
-  if (T->sharded && T->shard_phase != SHP_FORWARD)
-    return fail(h, COPER_ESTATE, std::string("coper_train_defer_rows: inside an entity-sharded step: the next call of this step is ") + kShardCall[T->shard_phase]);
+  if (T->sharded && T->open.phase != SHP_FORWARD)
+    return fail(h, COPER_ESTATE, std::string("coper_train_defer_rows: inside an entity-sharded step: the next call of this step is ") + kShardCall[T->open.phase]);
   if (enable && T->det && !T->rows_ordered && !T->sharded)      // (ordered rows put both in order: coper_train_order_rows; a sharded state's sampled call is always ordered)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_defer_rows: a deterministic state: the unique-row list and the atomic scorer backward are unordered");
   if ((enable != 0) == T->rows_deferred) return COPER_OK;
@@ -2018,7 +2072,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
     if (int rc = rows_sync_launch(h, T, s)) return rc;
     T->rows_deferred = false;
     T->rows_pending_clear();      // (the dense step zeroes the two buffers whole: a pending row gradient is gone)
-    T->sync = SyncOpen();         // (an open synchronised step was the mode's: abandoned)
+    T->open = OpenStep();         // (an open synchronised step was the mode's: abandoned)
     return COPER_OK;
   }
   const size_t E = (size_t)rows_held(h, T);      // (a shard: a word and a claim bit per OWNED row)
@@ -2037,7 +2091,7 @@ COPER_API int coper_train_defer_rows(coper_handle* h, int32_t enable, void* stre
   T->rows_l2b1p = std::log2(T->b1p);      // (log2(0) = -inf: the power is 0 at every gap, as the dense step has it)
   T->rows_l2b2p = std::log2(T->b2p);
   T->pending = false;      // (a pending backward's gradient is gone with the zeroing)
-  T->sync = SyncOpen();    // (... and an open synchronised step)
+  T->open = OpenStep();    // (... and an open synchronised step)
   T->rows_pending_clear();
   T->rows_deferred = true;
   return COPER_OK;
@@ -2073,7 +2127,7 @@ COPER_API int coper_train_order_rows(coper_handle* h, int32_t enable, void* stre
   T->rows_ordered = enable != 0;
   T->rows_list_unsorted = false;
   T->pending = false;      // (as switching deferred rows: what a split step left pending is dropped, never applied by another route)
-  T->sync = SyncOpen();    // (... and an open synchronised step with it)
+  T->open = OpenStep();    // (... and an open synchronised step with it)
   T->rows_pending_clear();
   return COPER_OK;
 }
@@ -2164,7 +2218,7 @@ COPER_API int coper_train_rows_export(coper_handle* h, float* small, int64_t sma
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_export: call coper_train_init first");
-  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_rows_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
+  if (T->sync_phase()) return fail(h, COPER_ESTATE, "coper_train_rows_export: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_export: the deferred-rows mode is off (coper_train_grads_export is the dense call)");
   if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_export: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
@@ -2235,7 +2289,7 @@ COPER_API int coper_train_rows_apply(coper_handle* h, const float* small, int64_
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_rows_apply: call coper_train_init first");
-  if (T->sync.phase) return fail(h, COPER_ESTATE, "coper_train_rows_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
+  if (T->sync_phase()) return fail(h, COPER_ESTATE, "coper_train_rows_apply: a synchronised step is open (coper_train_sync_next completes it; a step-shaped call abandons it)");
   if (!T->rows_deferred) return fail(h, COPER_ESTATE, "coper_train_rows_apply: the deferred-rows mode is off (coper_train_apply is the dense call)");
   if (T->sharded)      // (a shard steps through its four calls in the mode too; the row-block split step is not built there)
     return fail(h, COPER_EUNSUPPORTED, "coper_train_rows_apply: an entity-sharded state (coper_train_init_sharded) steps through coper_train_shard_forward | "
@@ -2339,20 +2393,22 @@ COPER_API int coper_train_powers(coper_handle* h, const double* set_beta1_power,
 
 // ---- synchronised batch statistics: the backward in phases (include/coper_hip.h).  coper_train_sync_begin is
 // train_step_impl up to the first batch-wide sum (SyncReq); every coper_train_sync_next folds the ranks' shares of that sum in ascending
-// rank and runs on to the next one.  Between the calls the step is TrainState::sync: its arguments and its StepCarry.
+// rank and runs on to the next one.  Between the calls the step is TrainState::open: the begin call's arguments and the StepCarry.
 namespace {
 
-// a Step over the open step's arguments for one of its phases
-static Step sync_step(coper_handle* h, TrainState* T, hipStream_t s) {
-  const SyncOpen& o = T->sync;
-  StepArgs a;
-  a.kind = o.rows ? StepKind::RowsBackward : StepKind::Backward;
-  a.s = s; a.e1 = o.e1; a.rel = o.rel; a.lookup = o.lookup; a.labels = o.labels; a.B = o.B; a.L = o.L; a.loss_out = o.loss_out;
-  if (o.csr) a.csr = CsrLabels{o.lab_indptr, o.lab_idx, o.lab_row, o.n_rows};
-  a.B_stat = o.B_global; a.sample_offset = o.sample_offset;
-  a.plan = plan_scorer(h, T, o.lookup, a.csr, o.B);
-  return Step(h, T, a);
-}
+// coper_train_sync_next by the exchange it follows (OpenStep::phase 1..4): the ranks' shares of that exchange's sum are folded into
+// `fold_into`, the stages [from, to) run, this rank's share of the next sum is handed out from `hand_out` (null: the step is complete).
+// (The begin call is [ConvFilters, Bn1) and hands out bn1_fwd_sums.)
+struct SyncCut { Stage from, to; double* (Step::*fold_into)() const; double* (Step::*hand_out)() const; };
+const SyncCut kSyncCuts[4] = {
+    // Conv1BN's statistics over B_global P positions, ReLU, dropout, the dense layer; FCBN's column sums of this rank's rows
+    {Stage::Bn1, Stage::Fcbn, &Step::bn1_fwd_sums, &Step::fcbn_fwd_sums},
+    // FCBN over B_global samples, the scorer with the loss and its backward; FCBN's backward sums of this rank's rows
+    {Stage::Fcbn, Stage::FcbnBwd, &Step::fcbn_fwd_sums, &Step::fcbn_bwd_sums},
+    // dz from the whole batch's sums, the dense layer's backward, the generators' chains; Conv1BN's backward sums of this rank's rows
+    {Stage::FcbnBwd, Stage::Bn1Bwd, &Step::bwd_all_sums, &Step::bn1_bwd_sums},
+    // Conv1BN's backward from the whole batch's sums, the conv's, the filters'
+    {Stage::Bn1Bwd, Stage::End, &Step::bwd_all_sums, nullptr}};
 // the doubles exchange `phase` carries (1, 4: Conv1BN's channels; 2, 3: FCBN's features; 5: the step is complete)
 inline int64_t sync_part_doubles(const Dims& dm, int phase) { return phase > 4 ? 0 : 2 * (int64_t)((phase == 1 || phase == 4) ? dm.C : dm.d); }
 
@@ -2383,7 +2439,7 @@ COPER_API int coper_train_sync_next(coper_handle* h, const double* parts_in, int
   if (!h) return COPER_EINVAL;
   TrainState* T = (TrainState*)h->train;
   if (!T) return fail(h, COPER_ESTATE, "coper_train_sync_next: call coper_train_init first");
-  const int ph = T->sync.phase;
+  const int ph = T->sync_phase();
   if (!ph) return fail(h, COPER_ESTATE, "coper_train_sync_next: no synchronised step is open (coper_train_sync_begin opens one)");
   if (G < 1) return fail(h, COPER_EINVAL, "coper_train_sync_next: G < 1");
   if (!parts_in || !aligned8(parts_in) || !n_out) return fail(h, COPER_EINVAL, "coper_train_sync_next: parts_in must be an 8-byte aligned device buffer, n_out not NULL");
@@ -2393,69 +2449,30 @@ COPER_API int coper_train_sync_next(coper_handle* h, const double* parts_in, int
   if (part_cap < n_next) return fail(h, COPER_EINVAL, "coper_train_sync_next: part_cap is below the doubles this call hands out (coper_train_sync_part_len holds every call's)");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  Step st = sync_step(h, T, s);
-  T->sync.phase = 0;      // (a call that fails leaves no step open: what it left half done is no state to go on from)
+  T->open.phase = 0;      // (a call that fails leaves no step open: what it left half done is no state to go on from)
   int rc;
-  if ((rc = st.grow_workspaces())) return rc;      // (nothing grows: the begin call sized them; the pointers a phase reads are set here)
-  static_cast<StepCarry&>(st) = T->sync.carry;
-  double *const all = T->sync_sums.get(), *const own = T->sync_sums + (size_t)2 * T->mx;
-  auto fold = [&](double* out) { hipLaunchKernelGGL(k_tr_fold_parts, grid1d(n_in), dim3(256), 0, s, parts_in, (int)G, (int)n_in, out); };
-  const double* hand = nullptr;
-  switch (ph) {
-  case 1:      // Conv1BN's statistics over B_global P positions, ReLU, dropout, the dense layer; FCBN's column sums of this rank's rows
-    fold(st.bn1_fwd_sums());
-    st.fwd_bn1();
-    if ((rc = st.fwd_dense())) return rc;
-    st.fwd_fcbn_sums();
-    hand = st.fcbn_fwd_sums();
-    break;
-  case 2:      // FCBN over B_global samples, the scorer with the loss and its backward; FCBN's backward sums of this rank's rows
-    fold(st.fcbn_fwd_sums());
-    st.fwd_fcbn_apply();
-    if ((rc = st.csr.indptr ? st.score_csr() : st.fwd_score_loss())) return rc;
-    if (st.scorer_bwd_on_side()) st.sj.fork(SJ_SCORER_BWD, 0);
-    if ((rc = st.bwd_scorer())) return rc;
-    st.bwd_fcbn_sums(own);
-    hand = own;
-    break;
-  case 3:      // dz from the whole batch's sums, the dense layer's backward, the generators' chains; Conv1BN's backward sums of this rank's rows
-    fold(all);
-    st.bwd_fcbn_apply(all, own);
-    if ((rc = st.bwd_dense())) return rc;
-    if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
-    st.bwd_bn1_sums();
-    hand = st.bn1_bwd_sums();
-    break;
-  default:     // Conv1BN's backward from the whole batch's sums, the conv's, the filters'
-    fold(all);
-    st.bwd_bn1_apply(all);
-    st.bwd_conv();
-    st.bwd_conv_filters();
-    break;
-  }
-  // (what a side stream was given in this call is joined before the call returns: the exchange, and the next call, find it done)
-  st.sj.join(SJ_DP);
-  st.sj.join(SJ_SCORER_BWD);
-  if (st.sj.err != hipSuccess) return fail(h, COPER_EHIP, "coper_train_sync_next: an event call of the side streams failed");
+  Step st = open_resume(h, T, T->open.args, s, &rc);
+  if (rc) return rc;
+  st.sync_sums = T->sync_sums.get();
+  const SyncCut& cut = kSyncCuts[ph - 1];
+  hipLaunchKernelGGL(k_tr_fold_parts, grid1d(n_in), dim3(256), 0, s, parts_in, (int)G, (int)n_in, (st.*cut.fold_into)());
+  if ((rc = st.run(cut.from, cut.to))) return rc;
+  if ((rc = st.join_sides("coper_train_sync_next"))) return rc;
   *n_out = 0;
-  if (hand && (rc = sync_hand_out(h, s, hand, n_next, part_out, n_out))) return rc;
+  if (cut.hand_out && (rc = sync_hand_out(h, s, (st.*cut.hand_out)(), n_next, part_out, n_out))) return rc;
   COPER_HIP_TRY(h, hipGetLastError());
-  T->sync.carry = st;      // (the StepCarry part)
-  if (ph < 4) { T->sync.phase = ph + 1; return COPER_OK; }
+  T->open.carry = st;      // (the StepCarry part)
+  if (ph < 4) { T->open.phase = ph + 1; return COPER_OK; }
   // complete: the handle is where coper_train_backward / coper_train_rows_backward leaves it
-  T->step += 1;
-  if (T->sync.rows) {
-    T->rows_pending_small = T->rows_pending_table = true;
-    T->rows_bound = std::min<int64_t>(st.B * (st.L + 1), h->dm.E);
-  } else T->pending = true;
-  T->sync = SyncOpen();
+  finish_backward(h, T, st.kind, st.B, st.L);
+  T->open = OpenStep();
   return COPER_OK;
 }
 
 COPER_API int coper_train_sync_phase(const coper_handle* h) {
   if (!h) return -COPER_EINVAL;
   const TrainState* T = (const TrainState*)h->train;
-  return T ? T->sync.phase : -COPER_ESTATE;
+  return T ? T->sync_phase() : -COPER_ESTATE;
 }
 
 COPER_API int64_t coper_train_sync_part_len(const coper_handle* h) {
@@ -2473,8 +2490,8 @@ static TrainState* shard_state(coper_handle* h, const char* what, int phase, int
   TrainState* T = (TrainState*)h->train;
   if (!T) { *rc = fail(h, COPER_ESTATE, std::string(what) + ": call coper_train_init_sharded first"); return nullptr; }
   if (!T->sharded) { *rc = fail(h, COPER_ESTATE, std::string(what) + ": not an entity-sharded state (coper_train_init_sharded)"); return nullptr; }
-  if (phase >= 0 && T->shard_phase != phase) {
-    *rc = fail(h, COPER_ESTATE, std::string(what) + ": out of order: the next call of this step is " + kShardCall[T->shard_phase]);
+  if (phase >= 0 && T->open.phase != phase) {
+    *rc = fail(h, COPER_ESTATE, std::string(what) + ": out of order: the next call of this step is " + kShardCall[T->open.phase]);
     return nullptr;
   }
   return T;
@@ -2493,17 +2510,18 @@ static int shard_rows_grow(coper_handle* h, TrainState* T, int64_t need, hipStre
   return COPER_OK;
 }
 
-// a Step over the state's saved batch (sh_e1 / sh_rel) for one phase of the sharded step: a fused step's arguments (StepKind::Step); the
-// plan names the handle's own rows for the tables
-// (lookup / labels [B, L]: the sampled score call; every other phase names no labels and L is num_ent)
-static Step shard_step(coper_handle* h, TrainState* T, hipStream_t s, float* h_out, const CsrLabels& csr, const float* img_rows,
-                       const int32_t* lookup = nullptr, const float* labels = nullptr, int64_t L = 0) {
-  StepArgs a;
-  a.kind = StepKind::Step; a.s = s; a.e1 = T->sh_e1.get(); a.rel = T->sh_rel.get(); a.lookup = lookup; a.labels = labels;
-  a.B = T->sh_B; a.L = lookup ? L : (int64_t)h->dm.E;
-  a.h_out = h_out; a.csr = csr; a.img_rows = img_rows;
-  a.plan = plan_scorer(h, T, lookup, csr, a.B);
-  return Step(h, T, a);
+// sh_e1 / sh_rel / sh_iota at B entries or more; sh_iota is filled where it grows
+static int shard_ids_grow(coper_handle* h, TrainState* T, int64_t B, hipStream_t s) {
+  if (B <= T->sh_cap) return COPER_OK;
+  int rc;
+  COPER_HIP_TRY(h, hipStreamSynchronize(s));
+  T->sh_cap = 0;
+  if ((rc = T->sh_e1.alloc(h, (size_t)B, "sharded step ids")) || (rc = T->sh_rel.alloc(h, (size_t)B, "sharded step ids")) ||
+      (rc = T->sh_iota.alloc(h, (size_t)B, "sharded step ids")))
+    return rc;
+  T->sh_cap = B;
+  hipLaunchKernelGGL(k_shard_iota, grid1d(B), dim3(256), 0, s, T->sh_iota.get(), B);
+  return COPER_OK;
 }
 
 }  // namespace
@@ -2543,42 +2561,31 @@ COPER_API int coper_train_shard_forward(coper_handle* h, const int64_t* e1, cons
   TrainState* T = shard_state(h, "coper_train_shard_forward", SHP_FORWARD, &rc);
   if (!T) return rc;
   if (!e1 || !rel || !e1_rows || B <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_forward: bad argument");
-  if (B * ((h->dm.n_local + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff)
-    return fail(h, COPER_EINVAL, "coper_train_shard_forward: batch too large for the loss kernel's grid");
-  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, "coper_train_shard_forward: batch too large for the dropout counter");
-  // (routes chosen by pointer alignment sum in another order: as the deterministic step)
-  if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
-    return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_forward: deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
+  if ((rc = check_batch_limits(h, T, "coper_train_shard_forward", B, h->dm.n_local))) return rc;
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  if (B > T->sh_cap) {
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    T->sh_cap = 0;
-    if ((rc = T->sh_e1.alloc(h, (size_t)B, "sharded step ids")) || (rc = T->sh_rel.alloc(h, (size_t)B, "sharded step ids")) ||
-        (rc = T->sh_iota.alloc(h, (size_t)B, "sharded step ids")))
-      return rc;
-    T->sh_cap = B;
-    hipLaunchKernelGGL(k_shard_iota, grid1d(B), dim3(256), 0, s, T->sh_iota.get(), B);
-  }
+  if ((rc = shard_ids_grow(h, T, B, s))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(T->sh_e1, e1, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(T->sh_rel, rel, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToDevice, s));
-  T->sh_B = B;
-  Step st = shard_step(h, T, s, h_out, CsrLabels(), e1_rows);
+  // the step's arguments, over the state's copy of the ids: a fused step's (StepKind::Step); the plan names the handle's own rows for the
+  // tables.  No labels yet and L is num_ent: the score call amends them.
+  StepArgs a;
+  a.kind = StepKind::Step; a.s = s; a.e1 = T->sh_e1.get(); a.rel = T->sh_rel.get(); a.B = B; a.L = (int64_t)h->dm.E;
+  a.img_rows = e1_rows;
+  a.plan = plan_scorer(h, T, nullptr, CsrLabels(), B);
+  Step st(h, T, a);
   if ((rc = st.grow_workspaces())) return rc;
   if (st.rows && (rc = rows_wrap_guard(h, T, s))) return rc;
   T->pending = false;
   st.zero_accumulators();      // (deferred rows: the two tables' gradients are left out ...)
   if (st.rows && T->rows_cap) rows_rezero_launch(h, T, s);      // (... the rows the step before listed are zeroed, their claim bits cleared)
   if (st.lk && (rc = st.group_for_lookup())) return rc;
-  st.fwd_conv_filters();
-  st.fwd_conv_bn1();
-  if ((rc = st.fwd_dense())) return rc;
-  st.fwd_fcbn();
+  if ((rc = st.run(Stage::ConvFilters, Stage::Score))) return rc;
   if (h_out) COPER_HIP_TRY(h, hipMemcpyAsync(h_out, T->hv, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
-  T->shard_carry = st;      // (the StepCarry part)
+  a.img_rows = nullptr;      // (the caller's until this call returns; no later stage reads the input rows)
+  T->open = OpenStep{a, st /* the StepCarry part */, SHP_SCORE};
   T->sh_stepped = true;
-  T->shard_phase = SHP_SCORE;
   return COPER_OK;
 }
 
@@ -2592,19 +2599,22 @@ COPER_API int coper_train_shard_score_csr(coper_handle* h, const int64_t* lab_in
     return fail(h, COPER_EUNSUPPORTED, "coper_train_shard_score_csr: deferred-rows mode (coper_train_defer_rows): a 1-vs-all step has a gradient in every row");
   if (!lab_indptr || !lab_idx || !dh_part || !loss_part || B <= 0 || n_rows < 0 || (!lab_row && n_rows != B))
     return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: bad argument (lab_row == NULL needs n_rows == B)");
-  if (B != T->sh_B) return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: B is not the forward call's");
+  if (B != T->open.args.B) return fail(h, COPER_EINVAL, "coper_train_shard_score_csr: B is not the forward call's");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  Step st = shard_step(h, T, s, nullptr, CsrLabels{lab_indptr, lab_idx, lab_row, n_rows}, nullptr);
-  if ((rc = st.grow_workspaces())) return rc;
-  static_cast<StepCarry&>(st) = T->shard_carry;
-  // the chunk loop over the own rows: d(pred_bias), d(ent_emb), the chunk shares of dh in ascending chunk order, the loss shares onto the zeroed sum
-  if ((rc = st.score_csr())) return rc;
+  StepArgs a = T->open.args;      // (amended on a copy: a call that fails leaves the open step as the forward call left it)
+  a.lookup = nullptr; a.labels = nullptr; a.L = (int64_t)h->dm.E;
+  a.csr = CsrLabels{lab_indptr, lab_idx, lab_row, n_rows};
+  a.plan = plan_scorer(h, T, nullptr, a.csr, B);
+  Step st = open_resume(h, T, a, s, &rc);
+  if (rc) return rc;
+  // the chunk loop over the own rows: d(pred_bias), d(ent_emb), the chunk shares of dh in ascending chunk order, the loss shares onto the
+  // zeroed sum (Stage::ScorerBwd has nothing left to do behind it)
+  if ((rc = st.run(Stage::Score, Stage::FcbnBwdSums))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
-  T->sh_labels = (double)B * (double)h->dm.E;
-  T->shard_phase = SHP_BACKWARD;
+  T->open = OpenStep{a, st /* the StepCarry part */, SHP_BACKWARD};
   return COPER_OK;
 }
 
@@ -2615,7 +2625,7 @@ COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* loo
   TrainState* T = shard_state(h, "coper_train_shard_score_lookup", SHP_SCORE, &rc);
   if (!T) return rc;
   if (!lookup || !labels || !dh_part || !loss_part || B <= 0 || L <= 0) return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: bad argument");
-  if (B != T->sh_B) return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: B is not the forward call's");
+  if (B != T->open.args.B) return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: B is not the forward call's");
   if (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff)
     return fail(h, COPER_EINVAL, "coper_train_shard_score_lookup: ordered rows: B * (L + 1) ids and num_ent must fit 31 bits");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -2626,20 +2636,20 @@ COPER_API int coper_train_shard_score_lookup(coper_handle* h, const int32_t* loo
     if ((rc = T->ds.alloc(h, (size_t)T->capB * (size_t)L, "training workspace"))) return rc;
   }
   if (L > T->capL) T->capL = L;
-  Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr, lookup, labels, L);
-  if ((rc = st.grow_workspaces()) || (rc = ord_grow(h, T, B * (L + 1), s))) return rc;
+  StepArgs a = T->open.args;      // (amended on a copy, as the CSR score call)
+  a.lookup = lookup; a.labels = labels; a.L = L; a.csr = CsrLabels();
+  a.plan = plan_scorer(h, T, lookup, a.csr, B);
+  Step st = open_resume(h, T, a, s, &rc);
+  if (rc || (rc = ord_grow(h, T, B * (L + 1), s))) return rc;
   if (st.rows && (rc = shard_rows_grow(h, T, B * (L + 1), s))) return rc;
-  static_cast<StepCarry&>(st) = T->shard_carry;
   // (deferred rows: the sort and the heads first -- the owned rows of the list are what is caught up, in front of the scorer that reads them)
   if (st.rows) st.shard_rows_list_catch_up();
   // the owned entries' scores, loss shares and ds, then d(pred_bias), d(ent_emb) by sorted segments over the own rows, and this shard's share of dh
-  if ((rc = st.fwd_score_loss()) || (rc = st.bwd_scorer())) return rc;
-  T->sh_L = L;
+  if ((rc = st.run(Stage::Score, Stage::FcbnBwdSums))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(dh_part, T->dh, sizeof(float) * (size_t)st.nBd, hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
-  T->sh_labels = (double)B * (double)L;
-  T->shard_phase = SHP_BACKWARD;
+  T->open = OpenStep{a, st /* the StepCarry part */, SHP_BACKWARD};
   return COPER_OK;
 }
 
@@ -2652,28 +2662,23 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   if (!dh_parts || !loss_parts || !sumsq_part || G < 1) return fail(h, COPER_EINVAL, "coper_train_shard_backward: bad argument");
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  Step st = shard_step(h, T, s, nullptr, CsrLabels(), nullptr);
-  if ((rc = st.grow_workspaces())) return rc;
-  static_cast<StepCarry&>(st) = T->shard_carry;
+  Step st = open_resume(h, T, T->open.args, s, &rc);      // (with the score call's labels: L is what its loss is a mean over)
+  if (rc) return rc;
   // dh and the loss: the ranks' shares in ascending rank
   const int64_t nBd = st.nBd;
   const int vec = (nBd & 3) == 0 && (((uintptr_t)dh_parts | (uintptr_t)T->dh.get()) & 15) == 0;
   hipLaunchKernelGGL(k_shard_fold_parts, dim3((unsigned)std::min<int64_t>(((vec ? nBd / 4 : nBd) + 255) / 256, 2048)), dim3(256), 0, s, dh_parts, (int)G, nBd,
                      vec, T->dh.get(), loss_parts, st.red.loss());
   // (the mean is over the labels of the score call that ran: B num_ent of a 1-vs-all step, B L of a sampled one)
-  if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, st.red.loss(), 1.0 / T->sh_labels, loss_out);
-  st.bwd_fcbn();
-  if ((rc = st.bwd_dense())) return rc;
-  if (st.gen) { st.chain_backward(0, st.nh); st.chain_backward(1, st.nh); }
-  st.bwd_bn1();
-  st.bwd_conv();      // (the owned e1 rows onto what the score call stored in d(ent_emb))
-  st.bwd_conv_filters();
+  if (loss_out) hipLaunchKernelGGL(k_tr_store_loss, dim3(1), dim3(1), 0, s, st.red.loss(), 1.0 / ((double)st.B * (double)st.L), loss_out);
+  // (the conv backward: the owned e1 rows onto what the score call stored in d(ent_emb))
+  if ((rc = st.run(Stage::FcbnBwdSums, Stage::End))) return rc;
   // the squared norm of this shard's table gradients, in the fixed order of the slab's fold, into its own double
   if (st.rows) {
     // deferred rows: every row off the step's list has a zero gradient -- the listed rows' squares in partial sums of ORD_SUMSQ_ROWS list
     // positions (exact zeros behind the list's end), folded in the slab's fixed order (the slab holds them: the score call sized it)
     const int pv = T->rows_prev;
-    const int64_t parts = std::max<int64_t>((std::min<int64_t>(st.B * (T->sh_L + 1), rows_held(h, T)) + ORD_SUMSQ_ROWS - 1) / ORD_SUMSQ_ROWS, 1);
+    const int64_t parts = std::max<int64_t>((std::min<int64_t>(st.B * (st.L + 1), rows_held(h, T)) + ORD_SUMSQ_ROWS - 1) / ORD_SUMSQ_ROWS, 1);
     hipLaunchKernelGGL(k_rows_sumsq_ord, dim3((unsigned)parts), dim3(256), 0, s, row_tables(h, T), (const int32_t*)T->rows_list[pv].get(),
                        (const int32_t*)(T->rows_count + pv), T->det_slab.get());
     hipLaunchKernelGGL(k_tr_fold_det, dim3(1), dim3(256), 0, s, T->det_slab.get(), 1, parts, sumsq_part, 0);
@@ -2684,8 +2689,9 @@ COPER_API int coper_train_shard_backward(coper_handle* h, const float* dh_parts,
   sumsq_det_launch(T, s, tt, np, sumsq_part);
   }
   COPER_HIP_TRY(h, hipGetLastError());
+  T->open.carry = st;      // (the StepCarry part)
   T->step += 1;
-  T->shard_phase = SHP_APPLY;
+  T->open.phase = SHP_APPLY;
   return COPER_OK;
 }
 
@@ -2723,7 +2729,7 @@ COPER_API int coper_train_shard_apply(coper_handle* h, const double* sumsq_parts
   }
   COPER_HIP_TRY(h, hipGetLastError());
   finish_update(T, tt.wmax != nullptr);
-  T->shard_phase = SHP_FORWARD;
+  T->open.phase = SHP_FORWARD;
   return COPER_OK;
 }
 
@@ -2746,21 +2752,10 @@ static int shard_forward_only(coper_handle* h, const char* what, const bool samp
     if (B * (L + 1) > 0x7fffffff || h->dm.E > 0x7fffffff) return fail(h, COPER_EINVAL, w + ": B * (L + 1) ids and num_ent must fit 31 bits");
   } else if (!csr.indptr || !csr.idx || csr.n_rows < 0 || (!csr.row && csr.n_rows != B))
     return fail(h, COPER_EINVAL, w + ": bad argument (lab_row == NULL needs n_rows == B)");
-  if (B * ((h->dm.n_local + TR_CSR_STRETCH - 1) / TR_CSR_STRETCH) > 0x7fffffff) return fail(h, COPER_EINVAL, w + ": batch too large for the loss kernel's grid");
-  if ((int64_t)B * h->dm.F > 0xffffffffLL) return fail(h, COPER_EINVAL, w + ": batch too large for the dropout counter");
-  if ((((uintptr_t)T->lv.ent_emb->p | (uintptr_t)T->lv.pred_bias->p) & 15) != 0)
-    return fail(h, COPER_EUNSUPPORTED, w + ": deterministic mode: ent_emb and pred_bias must be 16-byte aligned");
+  if ((rc = check_batch_limits(h, T, w, B, h->dm.n_local))) return rc;
   COPER_HIP_TRY(h, hipSetDevice(h->cfg.device));
   hipStream_t const s = (hipStream_t)stream;
-  if (B > T->sh_cap) {      // (the row numbers of the gathered input rows: as coper_train_shard_forward grows them)
-    COPER_HIP_TRY(h, hipStreamSynchronize(s));
-    T->sh_cap = 0;
-    if ((rc = T->sh_e1.alloc(h, (size_t)B, "sharded step ids")) || (rc = T->sh_rel.alloc(h, (size_t)B, "sharded step ids")) ||
-        (rc = T->sh_iota.alloc(h, (size_t)B, "sharded step ids")))
-      return rc;
-    T->sh_cap = B;
-    hipLaunchKernelGGL(k_shard_iota, grid1d(B), dim3(256), 0, s, T->sh_iota.get(), B);
-  }
+  if ((rc = shard_ids_grow(h, T, B, s))) return rc;      // (the row numbers of the gathered input rows)
   StepArgs a;
   a.kind = StepKind::Forward; a.s = s; a.e1 = e1; a.rel = rel; a.lookup = lookup; a.labels = labels;
   a.B = B; a.L = sampled ? L : (int64_t)h->dm.E;
@@ -2773,12 +2768,8 @@ static int shard_forward_only(coper_handle* h, const char* what, const bool samp
     return fail(h, COPER_EUNSUPPORTED, w + ": deferred-rows mode: L is too large for the fused scorer's LDS with the rows' catch-up scalars");
   st.zero_forward_scratch();
   if (st.lk && (rc = st.group_for_lookup())) return rc;
-  st.fwd_conv_filters();
-  st.fwd_conv_bn1();
-  if ((rc = st.fwd_dense())) return rc;
-  st.fwd_fcbn();
   // (deferred rows: no sort, no list, no catch-up launch -- the CURRENT row loads; the list of the step before keeps its re-zero owed)
-  if ((rc = sampled ? st.fwd_score_loss() : st.score_csr())) return rc;
+  if ((rc = st.run(Stage::ConvFilters, Stage::ScorerBwd))) return rc;
   COPER_HIP_TRY(h, hipMemcpyAsync(loss_part, st.red.loss(), sizeof(double), hipMemcpyDeviceToDevice, s));
   COPER_HIP_TRY(h, hipGetLastError());
   return COPER_OK;
